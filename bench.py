@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: FK + cost + gradient rollouts/sec (batch x horizon) -- every BASELINE config as a driver-runnable workload.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write the last step's outputs
+(`--dump-outputs DIR`: DIR/<name>.npy, float32; the inputs are seeded, so two builds compare output for output) and print the line.
+`--full` adds every secondary measurement and check (see its help): the CPU baseline, the beyond-the-Infinity-Cache figure, the
+dominant kernel of a multi-launch step timed alone (`roofline`, null without it for such a step), the closing check of the outputs,
+and the N > 1 comparisons in `multi_gpu`.
 
 N > 1 without a launcher: this script starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
 127.0.0.1 --master-port P bench.py ...` itself as a CHILD process, before anything in this process has touched the GPU, and
@@ -63,6 +69,7 @@ VALU_PEAK_WAVE_INSTS_PER_S = 256 * 4 * 2.4e9 / 2
 PMC_FILES = ("r06_pmc.json", "r05_pmc.json", "r04_pmc.json", "r03_pmc.json", "r02_hbm_traffic.json")
 DEFAULT_SHAPE = {"c2": (4096, 64), "c3": (4096, 64), "c4": (4096, 64), "c5": (2048, 128)}     # per-GPU batch x horizon
 SIGMA_GP, T_GP = 0.1, 5.0        # config 5's GP prior: sigma_gp of the reference's planner parameters (env_spheres_3d.py:57), 5 s trajectories
+DUMP_BUDGET = 60 << 20           # --dump-outputs: bytes of arrays at most (whole trajectories; a seeded sample of them beyond this)
 
 
 def algorithmic_bytes_per_sample(D, L, n_grid_links=0, esz=4):
@@ -113,6 +120,13 @@ def parse_args(argv):
     ap.add_argument("--force-dist", action="store_true",
                     help="debug: run the N > 1 code path (process group, side-stream all-reduce, in-stream barriers, multi_gpu section) "
                          "even with ONE rank -- the only way to put the RCCL calls on hardware on a 1-GPU box")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: the CPU baseline, the beyond-the-Infinity-Cache "
+                         "run, the dominant kernel timed alone (multi-launch steps), the closing output check, and at N > 1 the loop "
+                         "without / with every-step exchanges, config 3's stack, the exchange's own cost and the all-reduce check")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (the arrays a caller of the step receives) as "
+                         "DIR/<name>.npy in float32 (rank 0; a fixed seeded sample of whole trajectories beyond %d MiB)" % (DUMP_BUDGET >> 20))
     args = ap.parse_args(argv)
     b, h = DEFAULT_SHAPE[args.config]
     args.batch = b if args.batch is None else args.batch
@@ -441,6 +455,51 @@ def exchange_schedule(count, cadence, graph_steps, mailbox, n_slots):
     return items
 
 
+def step_outputs(wl, block_sums):
+    """What a caller of the timed step receives after it: {name: tensor}, the per-trajectory ones with the batch axis first."""
+    plan = wl.plan
+    per_traj = {"cost": plan.cost, "gq": plan.gq}
+    if plan.link_pos is not None:
+        per_traj["link_pos"] = plan.link_pos
+    jac = getattr(wl, "jac", None)
+    if jac is not None:                                          # c4: the Jacobian of ee_link, one launch or two
+        for k in ("pos", "quat", "lin_jac", "ang_jac"):
+            t = getattr(jac, k)
+            per_traj[k] = t.reshape(wl.B, wl.H, *t.shape[1:]) if t.shape[0] != wl.B else t
+    if wl.cfg == "c5":
+        per_traj["gqd"] = wl.gqd
+    if wl.traj_cost is not None:                                 # c5 two-launch: the GP prior's cost per trajectory
+        per_traj["gp_cost"] = wl.traj_cost
+    return per_traj, {"cost_block_sums": block_sums}
+
+
+def dump_rows(n_rows, bytes_per_row, fixed_bytes=0, budget=DUMP_BUDGET, seed=0):
+    """The trajectories --dump-outputs writes: None = all of them when they fit the budget, else the sorted indices of a fixed, seeded
+    sample that does."""
+    import numpy as np
+    if n_rows * bytes_per_row + fixed_bytes <= budget:
+        return None
+    k = max(1, min(n_rows, (budget - fixed_bytes) // bytes_per_row))
+    return np.sort(np.random.default_rng(seed).choice(n_rows, size=k, replace=False))
+
+
+def dump_outputs(wl, block_sums, out_dir, torch):
+    """--dump-outputs: the last step's outputs as out_dir/<name>.npy (float32; fp16 outputs widened exactly)."""
+    import numpy as np
+    per_traj, whole = step_outputs(wl, block_sums)
+    row_bytes = sum(4 * t.numel() // t.shape[0] for t in per_traj.values())
+    rows = dump_rows(wl.B, row_bytes, sum(4 * t.numel() for t in whole.values()))
+    if rows is not None:
+        idx = torch.as_tensor(rows, device=wl.plan.cost.device)
+        per_traj = {k: t.index_select(0, idx) for k, t in per_traj.items()}
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, t in {**per_traj, **whole}.items():
+        np.save(out_dir / f"{name}.npy", t.detach().float().cpu().numpy())
+    what = f"all {wl.B}" if rows is None else f"a seeded sample of {len(rows)} of the {wl.B}"
+    print(f"[bench] outputs of the last step ({what} trajectories) written to {out_dir}", file=sys.stderr)
+
+
 def main():
     argv = sys.argv[1:]
     args = parse_args(argv)
@@ -753,13 +812,16 @@ def main():
         elapsed, ev_ms = measure(plan, cadence)
     n_coll_value = n_coll[0]
     per_rank_value = per_rank[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, block_sums, args.dump_outputs, torch)
 
     samples_per_step = B * H * world
     value = samples_per_step * args.steps / elapsed
     bps = wl.bps
     bytes_per_launch = bps * B * H
     step_s = ev_ms * 1e-3 / args.steps
-    if wl.extras:
+    launch_s = None                 # the dominant kernel's duration; a multi-launch step needs a run of its own for it (--full)
+    if wl.extras and args.full:
         # the step has more launches than the dominant kernel: time that kernel alone, same stream, same brackets
         def only_rollout(n):
             for _ in range(n):
@@ -772,17 +834,18 @@ def main():
         launch_s = e0.elapsed_time(e1) * 1e-3 / args.steps
         wl.step(bs_ptr, stream.cuda_stream)                     # leave the buffers as a whole step leaves them
         torch.cuda.synchronize(dev)
-    else:
+    elif not wl.extras:
         launch_s = step_s
-    achieved = bytes_per_launch / launch_s / 1e9
+    achieved = None if launch_s is None else bytes_per_launch / launch_s / 1e9
 
-    # sanity: the outputs of the last step are finite and the cost sums agree with the per-sample costs
-    assert torch.isfinite(plan.cost).all() and torch.isfinite(plan.gq.float()).all()
-    if plan.gq.dtype == torch.float16:          # nothing saturated either: the loss scale holds
-        assert float(plan.gq.float().abs().max()) < 65504.0 and float(wl.gqd.float().abs().max()) < 65504.0
-    last = ops.reduce_sum(block_sums).item()
-    ref = plan.cost.double().sum().item()
-    assert abs(last - ref) <= 1e-4 * abs(ref) + 1e-3, (last, ref)
+    if args.full:
+        # sanity: the outputs of the last step are finite and the cost sums agree with the per-sample costs
+        assert torch.isfinite(plan.cost).all() and torch.isfinite(plan.gq.float()).all()
+        if plan.gq.dtype == torch.float16:          # nothing saturated either: the loss scale holds
+            assert float(plan.gq.float().abs().max()) < 65504.0 and float(wl.gqd.float().abs().max()) < 65504.0
+        last = ops.reduce_sum(block_sums).item()
+        ref = plan.cost.double().sum().item()
+        assert abs(last - ref) <= 1e-4 * abs(ref) + 1e-3, (last, ref)
 
     # PMC figures of this workload recorded under profiles/ (separate rocprofv3 --pmc passes of this very command)
     kind = "specialized" if model.specialized else "table-driven"
@@ -792,7 +855,7 @@ def main():
         pmc, pmc_src = pmc_record(f"{args.config}:{B}x{H}:{kind}")                  # round-2 key format
     traffic = pmc.get("traffic_bytes_per_launch") if pmc else None
     valu_per_wave = pmc.get("valu_insts_per_wave") if pmc else None
-    valu_frac = None if valu_per_wave is None else valu_per_wave * nb / launch_s / VALU_PEAK_WAVE_INSTS_PER_S
+    valu_frac = None if (valu_per_wave is None or launch_s is None) else valu_per_wave * nb / launch_s / VALU_PEAK_WAVE_INSTS_PER_S
 
     out = {
         "metric": wl.metric,
@@ -811,7 +874,7 @@ def main():
                    **({"grad_scale": wl.grad_scale} if args.config == "c5" else {}),
                    **({"experiment_weights": list(wl.weights)} if args.weights else {}),
                    **({"experiment_no_pos": True} if args.no_pos else {})},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "roofline": None if launch_s is None else {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": pmc_src if traffic else None,
                      "kernel": ("fused rollout + GP prior (trk_rollout_gp_cost_grad)" if isinstance(plan, ops.RolloutGpPlan) else
                                 "fused rollout + geometric Jacobian (trk_rollout_jacobian_cost_grad)" if isinstance(plan, ops.RolloutJacobianPlan) else
@@ -826,12 +889,12 @@ def main():
                      # absorbed by it (61 - 62 % of the same peak at 400 - 600 MB per launch)
                      "working_set_MB": round(bytes_per_launch / 1e6, 1), "infinity_cache_MB": 256},
     }
-    if wl.extras:
+    if wl.extras and out["roofline"] is not None:
         out["roofline"]["step"] = {"bytes_per_sample": wl.bps_step, "step_us": step_s * 1e6,
                                    "achieved": wl.bps_step * B * H / step_s / 1e9, "frac": wl.bps_step * B * H / step_s / 1e9 / HBM_PEAK_GBS,
                                    "launches": ["fused rollout"] + [lbl for lbl, _, _ in wl.extras]}
 
-    if (rank == 0 and not distributed and args.config == "c2" and not args.no_out_of_cache and wl.random_q is not None
+    if (args.full and rank == 0 and not distributed and args.config == "c2" and not args.no_out_of_cache and wl.random_q is not None
             and bytes_per_launch < 256e6):
         # Secondary figure: the same kernel on a batch whose working set exceeds the 256 MB Infinity Cache (8 x the trajectories:
         # 403 MB per launch at the default size), i.e. what the DRAM itself sustains for this read / write mix.
@@ -872,7 +935,7 @@ def main():
                                                      if bps * B_big * H > 256 * 1024 * 1024 else "write-through"}
         del g_big, big, q_big, sums_big
 
-    if distributed:
+    if distributed and args.full:
         # (1) the same loop without the collectives; (2) with one exchange per step; (3) c2 / c3: configs[2]'s objective stack on the
         # same shards, with collectives; (4) a check of the exchange itself: all-reduced packed sums == the sum of the ranks' local ones
         ko_elapsed, _ = measure(plan, 0)
@@ -928,24 +991,18 @@ def main():
             rccl_cmp = {"value": samples_per_step * args.steps / rc_elapsed, "ms_per_step": rc_elapsed * 1e3 / args.steps,
                         "collectives_in_timed_region": n_coll[0],
                         "via": "librccl ncclAllReduce (ctypes)" if native is not None else "torch.distributed.all_reduce"}
+    if distributed:
         mb_status = mailbox.status() if mailbox is not None else None
         out["multi_gpu"] = {
             "backend": dist.get_backend(), "ranks": dist.get_world_size(), "reduce_every": args.reduce_every, "reduce_every_effective": R,
             "exchange_via": ("peer-to-peer mailbox (trk_mailbox_exchange: stores into every peer's device memory, rows added in rank order"
                              + ("; captured into the step graphs)" if S_live[0] else "; eager, on the launch stream)")) if mailbox is not None else
                             "librccl ncclAllReduce (ctypes)" if native is not None else "torch.distributed.all_reduce",
-            **({"mailbox": {"exchanges": mb_status[0], "timeouts": mb_status[1], "memory": mb_status[2], "sums_bit_identical_to_rank_order": bitwise}}
+            **({"mailbox": {"exchanges": mb_status[0], "timeouts": mb_status[1], "memory": mb_status[2]}}
                if mailbox is not None else {"mailbox": None, "mailbox_note": mailbox_note}),
-            **({"rccl_allreduce": rccl_cmp} if rccl_cmp else {}),
-            "collectives_in_timed_region": n_coll_value, "exchange_us": exchange_us,
-            "allreduce_floats": int(local.numel()),
+            "collectives_in_timed_region": n_coll_value,
+            "allreduce_floats": 1 + H + H * D,
             "with_allreduce": {"value": value, "ms_per_step": elapsed * 1e3 / args.steps, "per_rank": per_rank_value},
-            "kernel_only": {"value": samples_per_step * args.steps / ko_elapsed, "ms_per_step": ko_elapsed * 1e3 / args.steps},
-            "every_step": {"value": samples_per_step * args.steps / es_elapsed, "ms_per_step": es_elapsed * 1e3 / args.steps,
-                           "collectives_in_timed_region": n_coll_every},
-            **({"full_stack_c3": c3} if c3 else {}),
-            "allreduce_check": {"ok": bool(err < 1e-5), "max_rel_err": err,
-                                "sum_cost_all_ranks": float(check_out[0].item()), "sum_cost_rank0": float(gathered[0][0].item())},
         }
         mg = out["multi_gpu"]
         # north_star: "HBM GB/s vs peak at 1/2/4/8 GPUs" -- every rank's own figure: the step's algorithmic bytes x the timed steps over
@@ -957,12 +1014,25 @@ def main():
                                "frac": step_bytes * args.steps / (t_us * 1e-6) / 1e9 / HBM_PEAK_GBS}
                               for r, t_us in enumerate(per_rank_value["launch_stream_us"])]
             mg["per_rank_bytes_per_step"] = step_bytes
+        if mb_status is not None and mb_status[1] != 0:
+            print(f"[bench] WARNING: {mb_status[1]} mailbox exchanges timed out after the headline measurement (secondary figures may be polluted)", file=sys.stderr)
+    if distributed and args.full:
+        if mailbox is not None:
+            mg["mailbox"]["sums_bit_identical_to_rank_order"] = bitwise
+        if rccl_cmp:
+            mg["rccl_allreduce"] = rccl_cmp
+        mg["exchange_us"] = exchange_us
+        mg["kernel_only"] = {"value": samples_per_step * args.steps / ko_elapsed, "ms_per_step": ko_elapsed * 1e3 / args.steps}
+        mg["every_step"] = {"value": samples_per_step * args.steps / es_elapsed, "ms_per_step": es_elapsed * 1e3 / args.steps,
+                            "collectives_in_timed_region": n_coll_every}
+        if c3:
+            mg["full_stack_c3"] = c3
+        mg["allreduce_check"] = {"ok": bool(err < 1e-5), "max_rel_err": err,
+                                 "sum_cost_all_ranks": float(check_out[0].item()), "sum_cost_rank0": float(gathered[0][0].item())}
         # what the exchange leaves of ideal weak scaling: N x (a step without any exchange) / (a step of the timed region with its exchange)
         mg["scaling_bound"] = world * mg["kernel_only"]["ms_per_step"] / mg["with_allreduce"]["ms_per_step"]
         mg["exchange_overhead_us_per_step"] = 1e3 * (mg["with_allreduce"]["ms_per_step"] - mg["kernel_only"]["ms_per_step"])
         assert err < 1e-5, f"all-reduced sums differ from the sum of the ranks' sums: {err}"
-        if mb_status is not None and mb_status[1] != 0:
-            print(f"[bench] WARNING: {mb_status[1]} mailbox exchanges timed out after the headline measurement (secondary figures may be polluted)", file=sys.stderr)
         assert bitwise is not False, "the mailbox sums differ from the rows added in rank order"
 
     if rank == 0 and not distributed and args.independent_streams > 1 and wl.random_q is not None:
@@ -990,7 +1060,7 @@ def main():
                                       "note": f"secondary: unrelated batches round-robin over {ns} streams (launches overlap); "
                                               "the headline value above is one stream, launch after launch"}
 
-    if rank == 0 and not distributed and args.cpu_seconds > 0:       # CPU baseline at N = 1: here; at N > 1: below, once the ranks are done
+    if args.full and rank == 0 and not distributed and args.cpu_seconds > 0:       # CPU baseline at N = 1: here; at N > 1: below, once the ranks are done
         out["cpu_baseline"] = cpu_baseline(wl, args, torch, args.cpu_seconds)
     elif rank == 0:
         out["cpu_baseline"] = None
@@ -1005,7 +1075,7 @@ def main():
             native.close()
         dist.barrier()
         dist.destroy_process_group()
-        if rank == 0 and args.cpu_seconds > 0:
+        if args.full and rank == 0 and args.cpu_seconds > 0:
             # N > 1: rank 0's host threads are free only now -- the other ranks have left their last barrier and are exiting (they do
             # no CPU arithmetic).  A shorter sample than at N = 1: the line must not wait long for a baseline that N = 1 already carries.
             from oracle import oracle as orc_

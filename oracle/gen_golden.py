@@ -147,6 +147,21 @@ ROBOTS = {
     "hab_stretch": "habitat_stretch/urdf/hab_stretch.urdf",
 }
 AUTHORED = {"ur10_allegro": author_ur10_allegro, "dual_panda": author_dual_panda}
+MODEL_TABLES = ("parent", "joint_type", "dof_idx", "R_fixed", "trans", "axis", "lower", "upper", "order")
+
+
+def originals_golden():
+    """urdf_originals.npz: the tables this package's model compiler builds from the reference's ORIGINAL files (meshes, inertia,
+    visuals and all), so that the stripped files shipped here are checked against them without the reference."""
+    sys.path.insert(0, str(REPO))
+    from torch_robotics_amd.kinmodel import KinModel
+    out = {}
+    for name, rel in ROBOTS.items():
+        m = KinModel.from_urdf(str(REF_URDF / rel))
+        out[f"{name}__link_names"] = np.asarray(m.link_names)
+        for f in MODEL_TABLES:
+            out[f"{name}__{f}"] = np.asarray(getattr(m, f))
+    np.savez_compressed(GOLD / "urdf_originals.npz", **out)
 
 
 # ----------------------------------------------------------------------------
@@ -1047,6 +1062,9 @@ def main():
     if sys.argv[1:] == ["builddef"]:
         builddef_goldens()
         return
+    if sys.argv[1:] == ["originals"]:
+        originals_golden()
+        return
     if sys.argv[1:] == ["treecost"]:
         tree_cost_goldens({n: quiet(DifferentiableTree, str(URDF_OUT / f"{n}.urdf"), n) for n in ("ur10_allegro", "dual_panda")})
         return
@@ -1085,6 +1103,7 @@ def main():
     interp_goldens()
     tree_cost_goldens(trees)
     builddef_goldens(trees)
+    originals_golden()
     total = sum(p.stat().st_size for p in GOLD.glob("*.npz"))
     print(f"golden dir: {len(list(GOLD.glob('*.npz')))} files, {total/1024:.0f} kB")
 

@@ -46,7 +46,7 @@ def test_launcher_rejects_world_size_mismatch():
 @pytest.mark.gpu
 def test_two_rank_bench_on_one_gpu_gloo():
     p = _run(["--gpus", "2", "--dist-backend", "gloo", "--single-device", "--same-q", "--steps", "20", "--warmup", "5",
-              "--reduce-every", "8", "--cpu-seconds", "0"], 600)
+              "--reduce-every", "8", "--cpu-seconds", "0", "--full"], 600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -73,7 +73,7 @@ def test_two_rank_config5_on_one_gpu_gloo():
     fp16 gradient (unscaled, fp32) and the GP cost.  Two ranks share cuda:0 over gloo; the driver's 5 + 20 steps at the DEFAULT cadence
     still contain exchanges."""
     p = _run(["--config", "c5", "--gpus", "2", "--dist-backend", "gloo", "--single-device", "--same-q", "--steps", "20", "--warmup", "5",
-              "--batch", "256", "--cpu-seconds", "0"], 600)
+              "--batch", "256", "--cpu-seconds", "0", "--full"], 600)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["dtype"] == "f16" and out["config"]["objectives"] == "c5" and out["config"]["horizon"] == 128
@@ -94,7 +94,7 @@ def test_two_rank_config5_on_one_gpu_gloo():
 def test_bench_configs_4_and_5_one_gpu(cfg, dtype, launches, extra):
     """`bench.py --config c4|c5` on one GPU: a driver-parsable line with the config's own bytes, the dominant kernel's roofline,
     the step's, and a CPU baseline from the oracle (incl. the Jacobian / the GP term)."""
-    p = _run(["--config", cfg, "--steps", "20", "--warmup", "5", "--cpu-seconds", "1.5", "--batch", "512"] + extra, 900)
+    p = _run(["--config", cfg, "--steps", "20", "--warmup", "5", "--cpu-seconds", "1.5", "--batch", "512", "--full"] + extra, 900)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["dtype"] == dtype and out["config"]["launches_per_step"] == launches and out["config"]["kernel"] == "specialized"
@@ -126,7 +126,7 @@ def test_bench_scene_variants(scene, bps):
 def test_rccl_code_path_on_one_rank():
     """`--force-dist`: the N > 1 code path with ONE rank and the real backend ("nccl" = RCCL on ROCm): process-group creation on
     the device, the side-stream all-reduce of the packed sums, the in-stream barriers, the MAX over ranks, all_gather -- on hardware."""
-    p = _run(["--force-dist", "--exchange", "rccl", "--steps", "40", "--warmup", "5", "--reduce-every", "8", "--cpu-seconds", "0"], 600)
+    p = _run(["--force-dist", "--exchange", "rccl", "--steps", "40", "--warmup", "5", "--reduce-every", "8", "--cpu-seconds", "0", "--full"], 600)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     mg = out["multi_gpu"]
@@ -135,7 +135,7 @@ def test_rccl_code_path_on_one_rank():
     assert mg["allreduce_check"]["sum_cost_all_ranks"] == pytest.approx(mg["allreduce_check"]["sum_cost_rank0"], rel=1e-6)
     # the driver's settings (20 steps after 5) at the default cadence (64): the interval shrinks to the run, the region contains
     # an exchange -- `value` is never a kernel-only figure
-    p = _run(["--force-dist", "--exchange", "rccl", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0"], 600)
+    p = _run(["--force-dist", "--exchange", "rccl", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0", "--full"], 600)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["multi_gpu"]["collectives_in_timed_region"] == 1 and out["config"]["reduce_every"] == 64
@@ -145,7 +145,8 @@ def test_rccl_code_path_on_one_rank():
 @pytest.mark.gpu
 def test_native_rccl_exchange_on_one_rank():
     """`--native-rccl`: the exchange issued straight on librccl (ncclAllReduce through ctypes on the side stream)."""
-    p = _run(["--force-dist", "--exchange", "rccl", "--native-rccl", "--steps", "40", "--warmup", "5", "--reduce-every", "8", "--cpu-seconds", "0"], 600)
+    p = _run(["--force-dist", "--exchange", "rccl", "--native-rccl", "--steps", "40", "--warmup", "5", "--reduce-every", "8", "--cpu-seconds", "0",
+              "--full"], 600)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     mg = out["multi_gpu"]
@@ -160,7 +161,7 @@ def test_launch_modes_graph_by_default_eager_on_request():
     outputs behind (bench.py's own closing check compares the cost sums with the per-sample costs)."""
     seen = {}
     for mode, extra in (("graph", []), ("eager", ["--graph", "0"]), ("small graphs", ["--graph", "4"])):
-        p = _run(["--steps", "23", "--warmup", "7", "--cpu-seconds", "0", "--batch", "512", "--no-out-of-cache"] + extra, 600)
+        p = _run(["--steps", "23", "--warmup", "7", "--cpu-seconds", "0", "--batch", "512", "--no-out-of-cache", "--full"] + extra, 600)
         assert p.returncode == 0, p.stderr[-3000:]
         out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
         assert out["steps"] == 23 and out["warmup"] == 7 and out["value"] > 0 and "capture failed" not in p.stderr
@@ -174,7 +175,7 @@ def test_launch_modes_graph_by_default_eager_on_request():
     assert p.returncode == 0, p.stderr[-3000:]
     assert json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])["config"]["launch"].startswith("hipGraph")
     # N > 1 code path (one rank, RCCL) in graph mode: the exchange sits between two replays inside the timed region
-    p = _run(["--force-dist", "--exchange", "rccl", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0", "--batch", "512"], 600)
+    p = _run(["--force-dist", "--exchange", "rccl", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0", "--batch", "512", "--full"], 600)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["config"]["launch"].startswith("hipGraph") and out["multi_gpu"]["collectives_in_timed_region"] == 1
@@ -185,7 +186,7 @@ def test_launch_modes_graph_by_default_eager_on_request():
 def test_mailbox_exchange_is_the_default_and_rides_in_the_graph():
     """`--exchange auto` (default): the peer-to-peer mailbox passes its known-answer validation and carries the exchange; at the
     driver's settings the 20 timed steps AND their exchange are one captured graph; the all-reduce path is measured next to it."""
-    p = _run(["--force-dist", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0"], 600)
+    p = _run(["--force-dist", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0", "--full"], 600)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     mg = out["multi_gpu"]
@@ -196,7 +197,7 @@ def test_mailbox_exchange_is_the_default_and_rides_in_the_graph():
     assert 0 < mg["scaling_bound"] <= 1.05 and mg["exchange_overhead_us_per_step"] < 3.0
     # eager loop: the same exchange on a side stream
     p = _run(["--force-dist", "--exchange", "p2p", "--graph", "0", "--steps", "24", "--warmup", "4", "--reduce-every", "8", "--cpu-seconds", "0",
-              "--batch", "512"], 600)
+              "--batch", "512", "--full"], 600)
     assert p.returncode == 0, p.stderr[-3000:]
     mg = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])["multi_gpu"]
     assert "eager" in mg["exchange_via"] and mg["collectives_in_timed_region"] == 3 and mg["mailbox"]["timeouts"] == 0
@@ -208,7 +209,7 @@ def test_two_rank_mailbox_exchange_on_one_gpu(cfg, extra):
     """Two processes share cuda:0 and exchange through each other's mailboxes (hipIpc handles): the sums every rank reads equal the
     rows added in rank order bit for bit, equal gloo's all-reduce of the same rows, nothing times out -- eager and captured."""
     p = _run(["--config", cfg, "--gpus", "2", "--dist-backend", "gloo", "--single-device", "--exchange", "p2p", "--steps", "20", "--warmup", "5",
-              "--reduce-every", "8", "--cpu-seconds", "0"] + extra, 600)
+              "--reduce-every", "8", "--cpu-seconds", "0", "--full"] + extra, 600)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     mg = out["multi_gpu"]
@@ -224,7 +225,7 @@ def test_many_rank_dress_rehearsal_on_one_gpu(cfg, ranks, extra):
     world-N mailbox (hipIpc handles, the N-rank argument struct, slot reuse), captured into the step graphs; the line carries what a
     SCALE line must carry -- `roofline`, `cpu_baseline` (rank 0, after the process group is gone), per-rank bandwidth fractions."""
     p = _run(["--config", cfg, "--gpus", str(ranks), "--single-device", "--dist-backend", "gloo", "--exchange", "p2p", "--graph", "20",
-              "--steps", "20", "--warmup", "5", "--cpu-seconds", "1.5"] + extra, 1500)
+              "--steps", "20", "--warmup", "5", "--cpu-seconds", "1.5", "--full"] + extra, 1500)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     mg = out["multi_gpu"]
@@ -272,3 +273,63 @@ def test_exchange_schedule_is_exact():
                                 assert sum(it[1]) <= S and len(it[1]) - 1 <= n_slots and (sum(it[1]) > 0 or len(it[1]) > 1)
                                 assert mailbox or len(it[1]) == 1          # all-reduce mode: graphs hold plain steps only
                             assert S or it[0] != "graph"
+
+
+def test_dump_sample_is_fixed_and_within_budget():
+    """bench.dump_rows (pure): every trajectory while the arrays fit --dump-outputs' budget, else the same seeded sample of whole
+    trajectories on every call, sorted, without repeats, filling the budget."""
+    sys.path.insert(0, str(ROOT))
+    import importlib
+    bench = importlib.import_module("bench")
+    row = 64 * (11 * 3 + 1 + 7) * 4                                # c2 at horizon 64: positions, cost, gradient
+    assert bench.dump_rows(4096, row, 4096 * 4) is None
+    row4 = 64 * (30 * 3 + 1 + 22 + 3 + 4 + 2 * 3 * 22) * 4          # c4: + pos, quat, both Jacobians
+    a, b = bench.dump_rows(4096, row4, 4096 * 4), bench.dump_rows(4096, row4, 4096 * 4)
+    assert a is not None and list(a) == list(b) and list(a) == sorted(set(a.tolist())) and 0 <= a[0] and a[-1] < 4096
+    assert len(a) * row4 + 4096 * 4 <= bench.DUMP_BUDGET < (len(a) + 1) * row4 + 4096 * 4
+    assert bench.DUMP_BUDGET <= 64 * 10 ** 6
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps, prints the headline fields and nothing measured beside them, and with
+    --dump-outputs leaves the last step's outputs as float32 .npy files: identical from run to run, consistent with each other."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        p = _run(["--gpus", "1", "--steps", "17", "--warmup", "3", "--batch", "512", "--dump-outputs", str(d)], 600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 17 and out["warmup"] == 3 and out["unit"] == "rollouts/s" and out["higher_is_better"] is True
+        assert out["dtype"] == "f32" and out["metric"].startswith("FK+cost+grad rollouts/sec") and out["value"] > 0
+        assert out["ms_per_step"] > 0 and out["value"] == pytest.approx(512 * 64 / (out["ms_per_step"] * 1e-3), rel=1e-9)
+        assert out["cpu_baseline"] is None and "out_of_cache" not in out["roofline"] and "multi_gpu" not in out
+        dumps.append({f.stem: np.load(f) for f in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert sorted(a) == ["cost", "cost_block_sums", "gq", "link_pos"]
+    assert a["cost"].shape == (512, 64) and a["gq"].shape == (512, 64, 7) and a["link_pos"].shape == (512, 64, 11, 3)
+    for name in a:
+        assert a[name].dtype == np.float32 and np.isfinite(a[name]).all() and np.array_equal(a[name], b[name]), name
+    assert abs(a["cost_block_sums"].astype(np.float64).sum() - a["cost"].astype(np.float64).sum()) <= 1e-4 * abs(a["cost"].sum()) + 1e-3
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_a_large_step_is_a_seeded_sample(tmp_path):
+    """c4's one-launch step at 1024 x 64 returns more than the dump budget: a fixed sample of whole trajectories is written, the same
+    one as bench.dump_rows picks, with the Jacobian outputs next to the rollout's."""
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    import importlib
+    bench = importlib.import_module("bench")
+    p = _run(["--config", "c4", "--steps", "5", "--warmup", "2", "--batch", "1024", "--dump-outputs", str(tmp_path)], 600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    got = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+    assert sorted(got) == ["ang_jac", "cost", "cost_block_sums", "gq", "lin_jac", "link_pos", "pos", "quat"]
+    assert sum(v.nbytes for v in got.values()) <= bench.DUMP_BUDGET
+    rows = bench.dump_rows(1024, sum(v.nbytes // v.shape[0] for k, v in got.items() if k != "cost_block_sums"),
+                           got["cost_block_sums"].nbytes)
+    assert rows is not None and got["cost"].shape == (len(rows), 64) and got["lin_jac"].shape == (len(rows), 64, 3, 22)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in got.values())

@@ -146,7 +146,7 @@ def test_concurrent_jit_builds_do_not_corrupt_each_other(tmp_path):
     assert not list(jit.JIT_DIR.glob("*.tmp*"))
 
 
-def test_unit_with_another_struct_layout_is_refused():
+def test_unit_with_another_struct_layout_is_refused(tmp_path, monkeypatch):
     """A stale on-disk unit (compiled before a change to SpecArgs / SpecEntry / trk.h) must never be dispatched: the entry's
     layout stamp is checked by `trk_spec_register` and the run-time compiler's cache key covers every header and the flags."""
     import ctypes as C
@@ -166,13 +166,14 @@ def test_unit_with_another_struct_layout_is_refused():
     stamp = jit._generator_stamp()
     cmd = " ".join(jit._compile_cmd("<src>", "<out>"))
     assert "-fno-honor-nans" in cmd and "max-ilp" in cmd
-    real = jit._REPO_INCLUDE / "trk.h"
-    orig = real.read_bytes()
-    try:
-        real.write_bytes(orig + b"\n/* layout change */\n")
-        assert jit._generator_stamp() != stamp
-    finally:
-        real.write_bytes(orig)
+    # (a changed COPY of the header: the committed one is never written)
+    orig = (jit._REPO_INCLUDE / "trk.h").read_bytes()
+    (tmp_path / "trk.h").write_bytes(orig)
+    monkeypatch.setattr(jit, "_REPO_INCLUDE", tmp_path)
+    assert jit._generator_stamp() == stamp
+    (tmp_path / "trk.h").write_bytes(orig + b"\n/* layout change */\n")
+    assert jit._generator_stamp() != stamp
+    monkeypatch.undo()
     assert jit._generator_stamp() == stamp
 
 

@@ -40,18 +40,17 @@ def test_model_compiler_matches_reference_build(robot):
 
 def test_reference_originals_give_the_same_model():
     """The kinematics-only URDFs shipped here compile to the same tables as the reference's own files
-    (only checked where /root/reference exists, i.e. in the development container)."""
-    from pathlib import Path
-    ref = Path("/root/reference/torch_robotics/data/urdf/robots")
-    if not ref.exists():
-        pytest.skip("reference not present")
-    pairs = {"panda_arm_no_gripper": "franka_description/robots/panda_arm_no_gripper.urdf",
-             "ur10": "ur10/urdf/ur10.urdf", "allegro_hand": "allegro_hand/allegro_hand.urdf",
-             "hab_stretch": "habitat_stretch/urdf/hab_stretch.urdf"}
-    for name, rel in pairs.items():
-        a, b = model(name), KinModel.from_urdf(str(ref / rel))
+    (tests/golden/urdf_originals.npz: what the model compiler built from those originals, oracle/gen_golden.py)."""
+    g = gold("urdf_originals")
+    names = sorted({k.split("__")[0] for k in g.files})
+    assert set(names) >= {"panda_arm_no_gripper", "ur10", "allegro_hand", "hab_stretch"}
+    for name in names:
+        a = model(name)
+        assert a.link_names == list(g[f"{name}__link_names"]), name
         for f in ("parent", "joint_type", "dof_idx", "R_fixed", "trans", "axis", "lower", "upper", "order"):
-            np.testing.assert_array_equal(getattr(a, f), getattr(b, f))
+            b = g[f"{name}__{f}"]
+            assert getattr(a, f).dtype == b.dtype, (name, f)
+            np.testing.assert_array_equal(getattr(a, f), b, err_msg=f"{name}.{f}")
 
 
 def test_urdf_error_cases(tmp_path):
@@ -132,17 +131,19 @@ def test_planning_task_cost_spec_matches_reference(env):
     assert task.get_collision_fields() == [task.df_collision_self, task.df_collision_objects, task.df_collision_ws_boundaries]
 
 
-def test_cpu_tensors_are_rejected_not_computed():
+def test_cpu_tensors_are_rejected_not_computed(monkeypatch):
+    """The no-GPU behaviour, wherever it runs (with a GPU, host tensors take the round trip through it)."""
     robot = tra.RobotPanda(tensor_args=TA)
-    if torch.cuda.is_available():
-        pytest.skip("no-GPU behaviour")
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     with pytest.raises(Exception):
         robot.fk_map_collision(torch.zeros(3, 7))
 
 
-def test_trajectory_plumbing_has_no_cpu_path():
-    """A17 (finite differences, path length, smoothness) runs in HIP kernels: CPU tensors are rejected, not computed."""
+def test_trajectory_plumbing_has_no_cpu_path(monkeypatch):
+    """A17 (finite differences, path length, smoothness) runs in HIP kernels: CPU tensors are rejected, not computed.
+    Checked as on a machine without a GPU, wherever it runs (with one, host tensors take the round trip through it)."""
     from torch_robotics_amd.robots import compute_path_length, finite_difference_vector
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     x = torch.as_tensor(gold("traj")["x"])
     with pytest.raises((ValueError, RuntimeError)):
         finite_difference_vector(x, dt=0.25, method="central")

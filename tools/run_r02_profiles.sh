@@ -6,9 +6,9 @@ O=$R/gpurun_out/r02
 mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; tail -2 $O/pytest.log
-timeout 300 python bench.py --steps 2000 --warmup 200 > $O/bench_c2.json 2> $O/bench_c2.err
-timeout 300 python bench.py --steps 2000 --warmup 200 --config c3 --cpu-seconds 0 > $O/bench_c3.json 2>> $O/bench_c2.err
-for b in 2048 8192 16384; do timeout 200 python bench.py --steps 1000 --warmup 100 --cpu-seconds 0 --batch $b; done > $O/bench_batches.jsonl 2>/dev/null
+timeout 300 python bench.py --full --steps 2000 --warmup 200 > $O/bench_c2.json 2> $O/bench_c2.err
+timeout 300 python bench.py --full --steps 2000 --warmup 200 --config c3 --cpu-seconds 0 > $O/bench_c3.json 2>> $O/bench_c2.err
+for b in 2048 8192 16384; do timeout 200 python bench.py --full --steps 1000 --warmup 100 --cpu-seconds 0 --batch $b; done > $O/bench_batches.jsonl 2>/dev/null
 cd /tmp; export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o r02 -- python3 $R/bench.py --steps 2000 --warmup 200 --cpu-seconds 0 > $O/prof_bench.json 2> $O/prof.err
 timeout 300 python3 $R/bench.py --steps 2000 --warmup 200 --cpu-seconds 0 > $O/bench_after_prof.json 2>/dev/null

@@ -6,11 +6,11 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r03
 mkdir -p $O
 cd $R
-timeout 300 python bench.py --steps 2000 --warmup 200 > $O/bench_c2.json 2> $O/bench.err
-timeout 300 python bench.py --steps 2000 --warmup 200 --config c3 --cpu-seconds 0 > $O/bench_c3.json 2>> $O/bench.err
-for s in grid shelf maze; do timeout 300 python bench.py --steps 1000 --warmup 100 --scene $s --cpu-seconds 6 > $O/bench_c2_$s.json 2>> $O/bench.err; done
-timeout 300 python bench.py --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_c2_driver_settings.json 2>> $O/bench.err
-timeout 600 python bench.py --gpus 2 --dist-backend gloo --single-device --steps 2000 --warmup 200 > $O/bench_2rank_gloo_one_gpu.json 2>> $O/bench.err
+timeout 300 python bench.py --full --steps 2000 --warmup 200 > $O/bench_c2.json 2> $O/bench.err
+timeout 300 python bench.py --full --steps 2000 --warmup 200 --config c3 --cpu-seconds 0 > $O/bench_c3.json 2>> $O/bench.err
+for s in grid shelf maze; do timeout 300 python bench.py --full --steps 1000 --warmup 100 --scene $s --cpu-seconds 6 > $O/bench_c2_$s.json 2>> $O/bench.err; done
+timeout 300 python bench.py --full --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_c2_driver_settings.json 2>> $O/bench.err
+timeout 600 python bench.py --full --gpus 2 --dist-backend gloo --single-device --steps 2000 --warmup 200 > $O/bench_2rank_gloo_one_gpu.json 2>> $O/bench.err
 cd /tmp; export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c2 -o r03 -- python3 $R/bench.py --steps 2000 --warmup 200 --cpu-seconds 0 > $O/bench_c2_under_rocprof.json 2> $O/prof.err
 for s in grid shelf maze; do

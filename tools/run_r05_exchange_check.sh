@@ -8,11 +8,11 @@ cd $R
 timeout 1500 python -m pytest tests/test_gpu_exchange.py tests/test_gpu_api.py tests/test_gpu_parity.py tests/test_gpu_fullsize.py -q -k "mailbox or packed or reassigned or no_bundled or build_defined or dual_panda_fp16" > $O/pytest_exchange.txt 2>&1
 tail -15 $O/pytest_exchange.txt
 for cfg in c2 c5; do
-  timeout 300 python bench.py --force-dist --config $cfg --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_${cfg}_force_dist.json 2>> $O/bench.err
-  timeout 300 python bench.py --force-dist --exchange rccl --config $cfg --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_${cfg}_force_dist_rccl.json 2>> $O/bench.err
+  timeout 300 python bench.py --full --force-dist --config $cfg --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_${cfg}_force_dist.json 2>> $O/bench.err
+  timeout 300 python bench.py --full --force-dist --exchange rccl --config $cfg --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_${cfg}_force_dist_rccl.json 2>> $O/bench.err
 done
-timeout 300 python bench.py --force-dist --steps 2000 --warmup 200 --cpu-seconds 0 > $O/bench_c2_force_dist_2000.json 2>> $O/bench.err
-timeout 600 python bench.py --gpus 2 --dist-backend gloo --single-device --exchange p2p --graph 20 --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_c2_2rank_p2p.json 2>> $O/bench.err
+timeout 300 python bench.py --full --force-dist --steps 2000 --warmup 200 --cpu-seconds 0 > $O/bench_c2_force_dist_2000.json 2>> $O/bench.err
+timeout 600 python bench.py --full --gpus 2 --dist-backend gloo --single-device --exchange p2p --graph 20 --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_c2_2rank_p2p.json 2>> $O/bench.err
 timeout 900 python -m pytest tests/test_bench_launch.py -q > $O/pytest_bench_launch.txt 2>&1
 tail -15 $O/pytest_bench_launch.txt
 cd /tmp; export TMPDIR=/tmp

@@ -6,8 +6,8 @@ O=$R/gpurun_out/r05x
 rm -rf $O; mkdir -p $O
 cd $R
 for cfg in c2 c5; do
-  timeout 300 python bench.py --force-dist --config $cfg --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_${cfg}_force_dist.json 2>> $O/bench.err
-  timeout 300 python bench.py --config $cfg --steps 20 --warmup 5 --cpu-seconds 0 --no-out-of-cache > $O/bench_${cfg}_plain.json 2>> $O/bench.err
+  timeout 300 python bench.py --full --force-dist --config $cfg --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_${cfg}_force_dist.json 2>> $O/bench.err
+  timeout 300 python bench.py --full --config $cfg --steps 20 --warmup 5 --cpu-seconds 0 --no-out-of-cache > $O/bench_${cfg}_plain.json 2>> $O/bench.err
 done
 cd /tmp; export TMPDIR=/tmp
 for cfg in c2 c5; do

@@ -21,7 +21,7 @@ unset TRK_STREAM_STORES
 echo "launch's own choice (threshold 256 MiB)"
 for B in 16384 20480 24576 32768; do b --batch $B --steps 200 --warmup 20; done
 } 2>&1 | tee $O/stream_store_sweep.txt
-timeout 300 python bench.py --steps 2000 --warmup 200 > $O/bench_c2.json 2>> $O/bench.err
-timeout 300 python bench.py --config c3 --batch 32768 --steps 100 --warmup 10 --cpu-seconds 0 > $O/bench_c3_32768.json 2>> $O/bench.err
+timeout 300 python bench.py --full --steps 2000 --warmup 200 > $O/bench_c2.json 2>> $O/bench.err
+timeout 300 python bench.py --full --config c3 --batch 32768 --steps 100 --warmup 10 --cpu-seconds 0 > $O/bench_c3_32768.json 2>> $O/bench.err
 for mib in 32 64 128 512 4096; do timeout 120 $R/tools/gather_calib.bin $mib 8 20 >> $O/gather_rates.txt 2>&1; done
 cat $O/gather_rates.txt

@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r05
 rm -rf $O; mkdir -p $O
 cd $R
-B="timeout 400 python bench.py"
+B="timeout 400 python bench.py --full"
 $B --steps 2000 --warmup 200 > $O/bench_c2.json 2> $O/bench.err
 $B --steps 2000 --warmup 200 --config c3 --cpu-seconds 6 > $O/bench_c3.json 2>> $O/bench.err
 $B --steps 1000 --warmup 100 --config c4 --cpu-seconds 6 > $O/bench_c4.json 2>> $O/bench.err
@@ -19,16 +19,16 @@ $B --steps 1000 --warmup 100 --scene grid --q smooth --cpu-seconds 0 > $O/bench_
 $B --steps 1000 --warmup 100 --q smooth --cpu-seconds 0 > $O/bench_c2_smooth.json 2>> $O/bench.err
 $B --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_c2_driver_settings.json 2>> $O/bench.err
 $B --steps 20 --warmup 5 --cpu-seconds 0 --config c5 > $O/bench_c5_driver_settings.json 2>> $O/bench.err
-timeout 600 python bench.py --gpus 2 --dist-backend gloo --single-device --steps 2000 --warmup 200 > $O/bench_2rank_gloo_one_gpu.json 2>> $O/bench.err
-timeout 600 python bench.py --gpus 2 --dist-backend gloo --single-device --config c5 --steps 1000 --warmup 100 > $O/bench_c5_2rank_gloo_one_gpu.json 2>> $O/bench.err
-timeout 600 python bench.py --force-dist --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_one_rank_driver_settings.json 2>> $O/bench.err
-timeout 600 python bench.py --force-dist --exchange rccl --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_one_rank_rccl_driver_settings.json 2>> $O/bench.err
-timeout 600 python bench.py --force-dist --steps 2000 --warmup 200 --cpu-seconds 0 > $O/bench_one_rank.json 2>> $O/bench.err
-timeout 600 python bench.py --force-dist --config c5 --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_c5_one_rank_driver_settings.json 2>> $O/bench.err
-timeout 600 python bench.py --force-dist --config c3 --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_c3_one_rank_driver_settings.json 2>> $O/bench.err
-timeout 600 python bench.py --gpus 2 --dist-backend gloo --single-device --exchange p2p --graph 20 --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_2rank_p2p_one_gpu.json 2>> $O/bench.err
+timeout 600 python bench.py --full --gpus 2 --dist-backend gloo --single-device --steps 2000 --warmup 200 > $O/bench_2rank_gloo_one_gpu.json 2>> $O/bench.err
+timeout 600 python bench.py --full --gpus 2 --dist-backend gloo --single-device --config c5 --steps 1000 --warmup 100 > $O/bench_c5_2rank_gloo_one_gpu.json 2>> $O/bench.err
+timeout 600 python bench.py --full --force-dist --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_one_rank_driver_settings.json 2>> $O/bench.err
+timeout 600 python bench.py --full --force-dist --exchange rccl --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_one_rank_rccl_driver_settings.json 2>> $O/bench.err
+timeout 600 python bench.py --full --force-dist --steps 2000 --warmup 200 --cpu-seconds 0 > $O/bench_one_rank.json 2>> $O/bench.err
+timeout 600 python bench.py --full --force-dist --config c5 --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_c5_one_rank_driver_settings.json 2>> $O/bench.err
+timeout 600 python bench.py --full --force-dist --config c3 --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_c3_one_rank_driver_settings.json 2>> $O/bench.err
+timeout 600 python bench.py --full --gpus 2 --dist-backend gloo --single-device --exchange p2p --graph 20 --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_2rank_p2p_one_gpu.json 2>> $O/bench.err
 for s in shelf maze; do $B --steps 1000 --warmup 100 --scene $s --q smooth --cpu-seconds 0 --no-out-of-cache > $O/bench_c2_${s}_smooth.json 2>> $O/bench.err; done
-for b in 2048 8192 16384 32768 49152; do timeout 300 python bench.py --steps 300 --warmup 30 --batch $b --cpu-seconds 0 --no-out-of-cache >> $O/bench_batches.jsonl 2>> $O/bench.err; done
+for b in 2048 8192 16384 32768 49152; do timeout 300 python bench.py --full --steps 300 --warmup 30 --batch $b --cpu-seconds 0 --no-out-of-cache >> $O/bench_batches.jsonl 2>> $O/bench.err; done
 cd /tmp; export TMPDIR=/tmp
 P="timeout 400 rocprofv3 --kernel-trace --stats --output-format csv"
 $P -d $O/prof_c2 -o r05 -- python3 $R/bench.py --steps 2000 --warmup 200 --cpu-seconds 0 --no-out-of-cache > $O/bench_c2_under_rocprof.json 2> $O/prof.err
