@@ -638,6 +638,29 @@ __host__ __device__ inline bool scene_is_fast(const DevCostHdr& C) {
 // without any box / grid text 118 + 0 and 9.45 us (configuration 3: 10.5 -> 9.95 us).
 __host__ __device__ inline bool scene_is_general(const DevCostHdr& C) { return C.n_box_objects > 0 || C.has_grid; }
 
+// The equal-radius sphere path's winner: exact distance and unit gradient of point p to the winning centre c (one rsq per point).
+__device__ __forceinline__ void scene_sphere_winner(const DevCostHdr& C, float px, float py, float pz, float cx, float cy, float cz,
+                                                    float& s, float& gx, float& gy, float& gz) {
+    const float dx = px - cx, dy = py - cy, dz = pz - cz;
+    const float n2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+    // torch.norm backward is 0 at p == c: with n2 floored, d * inv = 0 * 1.8e19 = 0 there (and n2 * inv = 0)
+    const float inv = trk_rsq(__builtin_fmaxf(n2, 1.17549435e-38f));     // one transcendental per point
+    s = fmaf(n2, inv, -C.sphere_r); gx = dx * inv; gy = dy * inv; gz = dz * inv;
+}
+template <int NL>
+__device__ __forceinline__ void scene_sphere_winners_global(const DevCostHdr& C, const float (&px)[NL], const float (&py)[NL],
+                                                            const float (&pz)[NL], const int (&bi)[NL], float (&s)[NL],
+                                                            float (&gx)[NL], float (&gy)[NL], float (&gz)[NL]) {
+    float4 Sv[NL];
+#pragma unroll
+    for (int l = 0; l < NL; ++l) Sv[l] = C.spheres[bi[l]];
+#pragma unroll
+    for (int l = 0; l < NL; ++l) scene_sphere_winner(C, px[l], py[l], pz[l], Sv[l].x, Sv[l].y, Sv[l].z, s[l], gx[l], gy[l], gz[l]);
+    // ends this path: the arithmetic above is textually the LDS path's, and without a barrier the compiler sinks the common tail
+    // into the join of the two -- a global load consumed at the join puts its `vmcnt` wait on the LDS path again
+    __builtin_amdgcn_sched_barrier(0);
+}
+
 template <int NL, class Tick = NoTick, bool FAST = false, bool GENERAL = true>
 __device__ __forceinline__ void scene_min_sdf(const DevCostHdr& C, const float (&px)[NL], const float (&py)[NL],
                                               const float (&pz)[NL], float (&s)[NL], float (&gx)[NL], float (&gy)[NL],
@@ -701,6 +724,21 @@ __device__ __forceinline__ void scene_min_sdf(const DevCostHdr& C, const float (
                 }
 #pragma unroll
                 for (int l = 0; l < NL; ++l) bi[l] = (int)(__float_as_uint(bk[l]) & 15u);
+                // per-lane gather of the winning centre, each source with its OWN use.  On this ISA loads and stores share
+                // `vmcnt`: a global gather whose destination registers or join block the LDS path shares makes the waitcnt pass
+                // put the global path's `vmcnt` waits on the LDS path too, and every wave then stops there until HBM has
+                // acknowledged every position chunk the tick slots issued.  The fused kernels always hand the table in LDS here
+                // (n_spheres <= 16 = TRK_LDS_SPHERES): a ds_read (~100 cycles), nothing global in flight when the arithmetic starts.
+                if (lds_spheres) {
+                    // an explicit LDS pointer: as a generic pointer the compiler may turn the read into a FLAT load (vmcnt again)
+                    typedef __attribute__((address_space(3))) const float lds_cfloat;
+                    lds_cfloat* lp = (lds_cfloat*)reinterpret_cast<const float*>(lds_spheres);
+#pragma unroll
+                    for (int l = 0; l < NL; ++l)
+                        scene_sphere_winner(C, px[l], py[l], pz[l], lp[4 * bi[l]], lp[4 * bi[l] + 1], lp[4 * bi[l] + 2], s[l], gx[l], gy[l], gz[l]);
+                } else {
+                    scene_sphere_winners_global<NL>(C, px, py, pz, bi, s, gx, gy, gz);
+                }
             } else {
                 float bn[NL];
 #pragma unroll
@@ -715,31 +753,8 @@ __device__ __forceinline__ void scene_min_sdf(const DevCostHdr& C, const float (
                         bn[l] = lt ? t : bn[l];
                     }
                 }
-            }
-            // per-lane gather of the winning centre: from the wave's LDS copy when there is one (~100 cycles), else from global
-            // memory (L2 hit, ~700 cycles with every wave of the chip asking at once).  Two separate loops, NOT
-            // `cond ? lds[i] : global[i]`: that is one load through a selected pointer, i.e. a FLAT load, whose
-            // `s_waitcnt vmcnt(0)` also waits for every output store the wave has in flight -- the position stream then
-            // stops at the gather until HBM has taken all of it.
-            float4 Sv[NL];
-            if (lds_spheres && (FAST || C.n_spheres <= TRK_LDS_SPHERES)) {
-                // an explicit LDS pointer: as two generic pointers the compiler sinks both loops' loads into one flat load again
-                typedef __attribute__((address_space(3))) const float lds_cfloat;
-                lds_cfloat* lp = (lds_cfloat*)reinterpret_cast<const float*>(lds_spheres);
-#pragma unroll
-                for (int l = 0; l < NL; ++l) Sv[l] = make_float4(lp[4 * bi[l]], lp[4 * bi[l] + 1], lp[4 * bi[l] + 2], 0.0f);
-            } else {
-#pragma unroll
-                for (int l = 0; l < NL; ++l) Sv[l] = C.spheres[bi[l]];
-            }
-#pragma unroll
-            for (int l = 0; l < NL; ++l) {
-                const float4 S = Sv[l];
-                const float dx = px[l] - S.x, dy = py[l] - S.y, dz = pz[l] - S.z;
-                const float n2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
-                // torch.norm backward is 0 at p == c: with n2 floored, d * inv = 0 * 1.8e19 = 0 there (and n2 * inv = 0)
-                const float inv = trk_rsq(__builtin_fmaxf(n2, 1.17549435e-38f));     // one transcendental per point
-                s[l] = fmaf(n2, inv, -C.sphere_r); gx[l] = dx * inv; gy[l] = dy * inv; gz[l] = dz * inv;
+                // more spheres than the LDS copy holds: the winner comes from global memory (L2 hit, ~700 cycles)
+                scene_sphere_winners_global<NL>(C, px, py, pz, bi, s, gx, gy, gz);
             }
         } else {
             for (int k = 0; k < C.n_spheres; ++k) {
