@@ -237,3 +237,45 @@ def test_fused_jacobian_is_generated_where_the_two_walks_coincide():
         assert ("bool JAC = false" in src) == have[ident]
     assert have["panda"] and have["ur10_allegro"] and have["dual_panda"] and have["ur10"] and have["iiwa7"]
     assert not have["tiago"] and not have["hab_stretch"]          # prismatic joints / continuous wheels: the stateful walk differs
+
+
+def _defined_kernels(src):
+    """{kernel name: (template parameters, of which without a default)} of every __global__ function in a generated unit"""
+    found = {}
+    lines = src.splitlines()
+    for k, line in enumerate(lines):
+        m = re.match(r"__global__ void __launch_bounds__\(.*?\) (\w+)\(", line)
+        if m:
+            t = re.match(r"template <(.*)>", lines[k - 1])
+            params = [p.strip() for p in t.group(1).split(",")] if t else []
+            found[m.group(1)] = (len(params), sum("=" not in p for p in params))
+    return found
+
+
+@__import__("pytest").mark.parametrize("ident,schedule", [(i, "tree") for i in codegen.SPEC_ROBOTS] + [("dual_panda", "segments")])
+def test_unit_kernel_list_and_registry_entry_name_what_the_unit_defines(ident, schedule, monkeypatch):
+    """meta["kernels"] (the name expressions jit.py hands to hipRTC) and the SpecEntry's launchers are derived from the same plan as the
+    kernels themselves: every listed kernel is defined where a code-object build sees it (outside the host-only sections) and takes
+    that many template arguments; every launcher in the entry is defined, and every kernel a launcher starts exists."""
+    if schedule != "tree":
+        monkeypatch.setenv("TRK_GP_SCHEDULE", schedule)
+    kin, tmpl = codegen.template_for(ident)
+    meta = {}
+    src = codegen.generate_rollout_source(kin, tmpl, ident, meta=meta)
+    rtc_src = re.sub(r"#ifndef __HIPCC_RTC__.*?#endif", "", src, flags=re.S)       # what a code-object build compiles
+    rtc_kernels, all_kernels = _defined_kernels(rtc_src), _defined_kernels(src)
+    assert meta["kernels"] and len(set(meta["kernels"])) == len(meta["kernels"])
+    for name in meta["kernels"]:
+        m = re.fullmatch(rf"spec_{ident}::(\w+)(?:<(.*)>)?", name)
+        assert m and m.group(1) in rtc_kernels, name
+        n_args = len(m.group(2).split(",")) if m.group(2) else 0
+        n_params, n_required = rtc_kernels[m.group(1)]
+        assert n_required <= n_args <= n_params, name
+    entry = re.search(r"static const SpecEntry kEntry = \{(.*)\};", src).group(1)
+    launchers = re.findall(r"\blaunch\w*", entry)
+    assert "launch" in launchers and "launch_posbwd" in launchers
+    for name in launchers:
+        assert re.search(rf"^static (?:void|int) {name}\(", src, re.M), name
+    for name in re.findall(r"hipLaunchKernelGGL\(\(?(\w+)", src):
+        assert name in all_kernels, name
+    assert ("launch_gp" in launchers) == any(k.startswith("k_rollout_gp") for k in all_kernels)

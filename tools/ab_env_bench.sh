@@ -1,5 +1,5 @@
 # Same-box A/B of a bench.py configuration under GENERATION-time knobs (environment variables read by codegen.py): one tree per setting, built
-# on the box, alternated.   usage (gpurun): bash tools/ab_env_bench.sh "--config c5 --steps 1000 --warmup 100" "TRK_EXP_GP_PRIOR=lds" "TRK_EXP_GP_PRIOR=dpp"
+# on the box, alternated.   usage (on the GPU box): bash tools/ab_env_bench.sh "--config c5 --steps 1000 --warmup 100" "TRK_GP_SCHEDULE=tree" "TRK_GP_SCHEDULE=segments"
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r05envb; mkdir -p $O
 ARGS=$1; shift

@@ -502,15 +502,7 @@ def _arm_lane_kernel_lines(kin: KinModel, tmpl: CollisionTemplate, plan: ArmLane
         E.raw("    }")
         E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
         # ---------------- what differs between the arms: per-lane selects ----------------
-        R: Dict[int, List[List[S]]] = {}
-        t: Dict[int, List[S]] = {}
-        passv: Dict[int, S] = {}
-        if base_identity:
-            R[0] = [[ONE if r == c else ZERO for c in range(3)] for r in range(3)]
-            t[0] = [ZERO, ZERO, ZERO]
-        else:
-            R[0] = [[S(1.0, f"A.base_R[{3 * r + c}]") for c in range(3)] for r in range(3)]
-            t[0] = [S(1.0, f"A.base_t[{r}]") for r in range(3)]
+        R, t, passv = _root_pose(base_identity)
         Rf = [[S(snap_const(arm.R_fixed[1][r][c], snap)) for c in range(3)] for r in range(3)]
         tlv = [S(snap_const(arm.trans[1][k], 0.0)) for k in range(3)]
         for kind, r, c, a, b in plan.differ:
@@ -537,31 +529,20 @@ def _arm_lane_kernel_lines(kin: KinModel, tmpl: CollisionTemplate, plan: ArmLane
         E.raw(f"    constexpr int PPT = (Img::NP + {n_slots - 1}) / {n_slots};")
         E.raw("    const ImgTicks<Img, PPT> flush{pimg};")
         E.raw("    if (!A.gq) { flush.template rest<0>(); return; }      // positions only: wave-uniform exit (the whole grid takes it: no barrier is missed)")
-        next_chunk = [0]
-
-        def tick_line(indent="    "):
-            c = next_chunk[0]
-            next_chunk[0] += 1
-            return f"{indent}flush.template chunk<{c}>();"
+        ticks = _Ticks()
         # ---------------- objectives of this lane's arm ----------------
         adj = sorted(set(plan.obj) | ({plan.ee} if plan.ee >= 0 else set()))
         E.raw("    float cost = 0.0f;")
         for i in adj:
             E.raw(f"    float tb{i}_0 = 0.0f, tb{i}_1 = 0.0f, tb{i}_2 = 0.0f;")
         if NLA:
-            for k, nm in enumerate("xyz"):
-                E.raw(f"    const float p{nm}[NLA] = {{{', '.join(E.expr(t[i][k]) for i in plan.obj)}}};")
-            E.raw("    float gx[NLA], gy[NLA], gz[NLA];")
-            E.raw("#pragma unroll")
-            E.raw("    for (int l = 0; l < NLA; ++l) { gx[l] = 0.0f; gy[l] = 0.0f; gz[l] = 0.0f; }")
-            c0 = next_chunk[0]
-            next_chunk[0] += OBJ_TICK_SLOTS
+            _emit_obj_inputs(E, t, plan.obj, "NLA", "    ")
+            c0 = ticks.take(OBJ_TICK_SLOTS)
             E.raw(f"    const TickFrom<decltype(flush), {c0}> ticks{{flush}};")
             E.raw("    if (A.w.w_obj != 0.0f) cost += spec_objects_cost_arm<NLA, decltype(ticks), true, false>(A.C, A.w.w_obj, px, py, pz, gx, gy, gz, ticks, lds_sph, odd);")
-            E.raw(f"    else flush.template range<{c0}, {next_chunk[0]}>();")
+            E.raw(f"    else flush.template range<{c0}, {c0 + OBJ_TICK_SLOTS}>();")
             E.raw("    if (A.w.w_ws != 0.0f && A.C.has_ws) cost += spec_ws_cost_arm<NLA>(A.C, A.w.w_ws, px, py, pz, gx, gy, gz, odd);")
-            for j, i in enumerate(plan.obj):
-                E.raw(f"    tb{i}_0 += gx[{j}]; tb{i}_1 += gy[{j}]; tb{i}_2 += gz[{j}];")
+            _emit_obj_adjoints(E, plan.obj, "    ")
         if plan.ee >= 0:
             ee = plan.ee
             E.raw("    float eeRb[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};")
@@ -579,7 +560,7 @@ def _arm_lane_kernel_lines(kin: KinModel, tmpl: CollisionTemplate, plan: ArmLane
             E.raw("        for (int k = 0; k < 9; ++k) eeRb[k] = A.w.w_ee * gR[k];")
             E.raw(f"        tb{ee}_0 = fmaf(A.w.w_ee, gt[0], tb{ee}_0); tb{ee}_1 = fmaf(A.w.w_ee, gt[1], tb{ee}_1); tb{ee}_2 = fmaf(A.w.w_ee, gt[2], tb{ee}_2);")
             E.raw("    }")
-        E.raw(tick_line())
+        E.raw(ticks())
         # ---------------- cost: the sample's cost is the sum over its two lanes; a 64-sample block sum is two wavefronts' ----------------
         E.raw("    cost += cost_gp;           // the prior's factor t -> t + 1 (this arm's joints), attributed to this sample")
         E.raw("    const float cs = cost + trk_dpp_partner(cost);      // both lanes of a sample hold its cost (a + b == b + a: the same bits)")
@@ -590,9 +571,9 @@ def _arm_lane_kernel_lines(kin: KinModel, tmpl: CollisionTemplate, plan: ArmLane
         E.raw("    }")
         # ---------------- reverse ----------------
         gq_expr = _emit_reverse_links(E, arm, R, t, {i: [f"tb{i}_{k}" for k in range(3)] for i in adj},
-                                      ({plan.ee: "eeRb"} if plan.ee >= 0 else {}), masked, tick=tick_line, order=list(range(LA)))
-        assert next_chunk[0] <= n_slots, (next_chunk[0], n_slots)
-        E.raw(f"    flush.template rest<{next_chunk[0]}>();")
+                                      ({plan.ee: "eeRb"} if plan.ee >= 0 else {}), masked, tick=ticks, order=list(range(LA)))
+        assert ticks.n <= n_slots, (ticks.n, n_slots)
+        E.raw(f"    flush.template rest<{ticks.n}>();")
         E.raw(f"    const float gv[DA] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) + f' + gpv[{d}]' for d in range(DA))}}};")
         E.raw("    spec_store_gq<DA, IOG, IoTraits<IO>::kScaled>(static_cast<IOG*>(A.gq), base_h, rows, lane, lds, gv, A.grad_scale);")
         E.raw("    if (A.cost_sum) {          // wave-uniform for the whole workgroup")
@@ -607,1599 +588,1406 @@ def _arm_lane_kernel_lines(kin: KinModel, tmpl: CollisionTemplate, plan: ArmLane
 
 TRK_WAVE_ = 64
 JAC_DIRECT_MAX_DOFS = 16    # k_jac: robots up to this many DOF write their columns straight into the output tiles (Panda 17.0 -> 13.1 us, dual Panda 34.6 -> 27.3)
-# tick slots handed to one scene evaluation (csrc/trk_device.h: TRK_OBJ_TICK_SLOTS must agree)
+# tick slots handed to one scene evaluation (csrc/trk_device.h: TRK_OBJ_TICK_SLOTS must agree; the tick schedule is open for re-tuning)
 OBJ_TICK_SLOTS = int(os.environ.get("TRK_EXP_OBJ_SLOTS", "5"))
 
 
-def generate_rollout_source(kin: KinModel, tmpl: CollisionTemplate, ident: str, snap: float = SNAP, meta: Optional[dict] = None) -> str:
-    """meta (optional): receives what a loader of the unit's DEVICE code alone needs (jit.py's hipRTC fall-back: the host half of the
-    unit -- launchers, registry entry -- is then played by libtrk.so's generic launchers): the kernels' name expressions and the
-    unit's traits."""
-    L, D = kin.n_links, kin.n_dofs
-    NL = len(tmpl.obj_links)
-    masked = _masked_factory(kin)
-    tracked = [(l, tgt, rb) for l, tgt, rb in ((tmpl.ee_link, "A.C.ee_target", "eeRb"), (tmpl.ee2_link, "A.C.ee2_target", "ee2Rb"))
-               if l >= 0]
-    virt = {L + v: row for v, row in enumerate(tmpl.virtual)}          # virtual column -> (src0, src1, w0, w1)
-    used = set(tmpl.obj_links) | {a for p in tmpl.self_pairs for a in p}
-    assert all(i < L + len(virt) for i in used), "collision column out of range"
-    used_virt = sorted(i for i in used if i >= L)
-    # every column that can receive a position adjoint: the real links among them go to the reverse pass, the virtual ones
-    # hand theirs to their two source links first
-    adj_links = sorted(used | {l for l, _, _ in tracked} | {src for i in used_virt for src in virt[i][:2]})
-    real_adj = [i for i in adj_links if i < L]
+def _ancestry(kin: KinModel, leaves) -> set:
+    """the given links and all their ancestors, link 0 excluded"""
+    need = set()
+    for a in leaves:
+        while a > 0 and a not in need:
+            need.add(a); a = int(kin.parent[a])
+    return need
 
-    def with_virtual(E, t):
-        """t extended by the interpolated points this template uses (named temporaries: w0 * p_src0 + w1 * p_src1)"""
-        if not used_virt:
-            return t
-        t = dict(t)
-        for i in used_virt:
-            s0, s1, w0, w1 = virt[i]
-            t[i] = [E.named(E.lincomb([(t[s0][k], S(float(np.float32(w0)))), (t[s1][k], S(float(np.float32(w1))))])) for k in range(3)]
-        return t
 
-    def scatter_virtual(E, indent="    "):
-        """adjoint of an interpolated point -> its two source links, with its weights"""
-        for i in used_virt:
-            s0, s1, w0, w1 = virt[i]
-            for src, w in ((s0, w0), (s1, w1)):
-                if float(np.float32(w)) != 0.0:
-                    E.raw(f"{indent}tb{src}_0 = fmaf({flit(float(np.float32(w)))}, tb{i}_0, tb{src}_0); tb{src}_1 = fmaf({flit(float(np.float32(w)))}, tb{i}_1, tb{src}_1); "
-                          f"tb{src}_2 = fmaf({flit(float(np.float32(w)))}, tb{i}_2, tb{src}_2);")
-    out: List[str] = []
-    out.append(f"// GENERATED by torch_robotics_amd/codegen.py for model '{kin.name}' ({L} links, {D} DOF) -- do not edit.")
-    # Value-changing-but-bounded FP freedoms for this unit (NOT finite-math-only): reassociation + contraction turn
-    # mul/add chains into FMAs, 1/x may use v_rcp.  Same-box A/B on the headline kernel: 11.55 -> 11.06 us; deviation from
-    # the fp64 oracle on 65 536 samples unchanged for positions (2.5e-7) and 6.4e-7 -> 1.0e-6 of max for the gradient
-    # (tools/accuracy_check.py).  The attached-point generator does not use it (its kernels got slower: register pressure).
-    out.append("#pragma clang fp reassociate(on) contract(fast) reciprocal(on)")
-    out.append('#include "trk_spec_common.h"')
-    out.append(f"namespace spec_{ident} {{")
-    out.append(f"constexpr int L = {L}, D = {D}, NL = {NL};")
-    out.append(f'static_assert(TRK_OBJ_TICK_SLOTS == {OBJ_TICK_SLOTS}, "chunk numbering of this unit assumes another TRK_OBJ_TICK_SLOTS");')
-    # the walk: file order when that puts every parent before its children (then a link's floats are staged where they sit in
-    # the output row, which is what the ring staging needs), else the model's DFS pre-order
-    walk = list(range(L)) if all(int(kin.parent[i]) < i for i in range(1, L)) else [int(v) for v in kin.order]
-    chunked = 3 * L > CHUNKED_STAGING_MIN_FLOATS and walk == list(range(L))
-    if chunked:
+def _jacobian_columns(kin: KinModel, link: int) -> List[int]:
+    """links whose joints get a column of `link`'s geometric Jacobian: the reference's rule (idx - 1) <= joint_list_idx
+    (robot_tree.py:239-240); none without a tracked link"""
+    if link < 0:
+        return []
+    return [i for i in range(1, kin.n_links) if int(kin.dof_idx[i]) >= 0 and int(kin.jac_axis[i]) >= 0 and
+            (i - 1) <= int(kin.joint_list_idx[link])]
+
+
+def _gp_segments(kin: KinModel, tmpl: CollisionTemplate, tracked) -> Tuple[List[dict], bool]:
+    """(segments of k_rollout_gp, whether a self pair crosses two of them): the subtrees hanging off the root, in file order, when
+    each is a contiguous run of links and of the template's object-collision links; else the whole tree as one segment"""
+    L = kin.n_links
+    par_ = [int(v) for v in kin.parent]
+    top = {}
+    for i in range(1, L):
+        a = i
+        while par_[a] != 0:
+            a = par_[a]
+        top[i] = a
+    roots = [i for i in range(1, L) if par_[i] == 0]
+    cand = [[i for i in range(1, L) if top[i] == c] for c in roots]
+    contiguous = all(ls == list(range(ls[0], ls[-1] + 1)) for ls in cand) and [l for ls in cand for l in ls] == list(range(1, L))
+    # each segment's object-collision links must be one consecutive run of the template (their margins are addressed by a base)
+    runs_ok = contiguous
+    if contiguous:
+        pos_in = 0
+        for ls in cand:
+            mine = [i for i in tmpl.obj_links if i in ls or (i == 0 and ls is cand[0])]
+            if tmpl.obj_links[pos_in:pos_in + len(mine)] != mine:
+                runs_ok = False
+            pos_in += len(mine)
+    if not (contiguous and runs_ok and len(cand) > 1):
+        cand = [list(range(1, L))]
+    cross_pairs = any(a != 0 and b != 0 and top[a] != top[b] for a, b in tmpl.self_pairs) if len(cand) > 1 else False
+    segs: List[dict] = []
+    obj_at = 0
+    for k, ls in enumerate(cand):
+        own = set(ls) | ({0} if k == 0 else set())
+        objs = [i for i in tmpl.obj_links if i in own]
+        cols = ([0] if k == 0 else []) + ls                        # links whose positions this segment writes
+        segs.append(dict(links=ls, cols=cols, obj=objs, obj_base=obj_at,
+                         pairs=[(pi, a, b) for pi, (a, b) in enumerate(tmpl.self_pairs)
+                                if (a in own or a == 0) and (b in own or b == 0) and (a in ls or b in ls)],
+                         tracked=[(l, tgt, rb) for l, tgt, rb in tracked if l in own],
+                         dofs=[int(kin.dof_idx[i]) for i in ls if int(kin.dof_idx[i]) >= 0]))
+        obj_at += len(objs)
+    return segs, cross_pairs
+
+
+class _LinkUnit:
+    """Everything generate_rollout_source decides about one unit, decided once: the walk and the staging of its positions, the columns
+    that receive adjoints, and which kernel families (and launchers) the unit carries.  The emitters below only read it."""
+
+    def __init__(self, kin: KinModel, tmpl: CollisionTemplate, ident: str, snap: float):
+        self.kin, self.tmpl, self.ident, self.snap = kin, tmpl, ident, snap
+        L, D = self.L, self.D = kin.n_links, kin.n_dofs
+        self.NL = len(tmpl.obj_links)
+        self.masked = _masked_factory(kin)
+        file_walk = [int(v) for v in kin.order] == list(range(L))         # the file order is the model's DFS pre-order
+        self.tracked = [(l, tgt, rb) for l, tgt, rb in ((tmpl.ee_link, "A.C.ee_target", "eeRb"), (tmpl.ee2_link, "A.C.ee2_target", "ee2Rb"))
+                        if l >= 0]
+        self.virt = {L + v: row for v, row in enumerate(tmpl.virtual)}          # virtual column -> (src0, src1, w0, w1)
+        used = set(tmpl.obj_links) | {a for p in tmpl.self_pairs for a in p}
+        assert all(i < L + len(self.virt) for i in used), "collision column out of range"
+        self.used_virt = sorted(i for i in used if i >= L)
+        # every column that can receive a position adjoint: the real links among them go to the reverse pass, the virtual ones
+        # hand theirs to their two source links first
+        self.adj_links = sorted(used | {l for l, _, _ in self.tracked} | {src for i in self.used_virt for src in self.virt[i][:2]})
+        self.real_adj = [i for i in self.adj_links if i < L]
+        # the walk: file order when that puts every parent before its children (then a link's floats are staged where they sit in
+        # the output row, which is what the ring staging needs), else the model's DFS pre-order
+        self.walk = list(range(L)) if all(int(kin.parent[i]) < i for i in range(1, L)) else [int(v) for v in kin.order]
+        self.chunked = 3 * L > CHUNKED_STAGING_MIN_FLOATS and self.walk == list(range(L))
         # ring staging: the pieces of the whole chunks leave between the links that follow them; the tail chunk's pieces are what
         # the objectives' tick slots issue (flush.chunk<CH>() -> RingTail)
-        rp = ring_plan(3 * L)
-        ring_t = f"RingFlusher<{rp.W}, {rp.V}, {'true' if rp.aligned else 'false'}, IOQ>"
-        out.append("template <class R> struct RingTail {      // tick slot CH of the objectives -> store piece CH of the tail chunk")
-        out.append("    const R& r;")
-        out.append("    template <int CH> __device__ __forceinline__ void chunk() const { r.template piece<R::NFULL, CH>(); }")
-        out.append("    template <int A, int B> __device__ __forceinline__ void range() const { if constexpr (A < B && A < R::NP) { chunk<A>(); range<A + 1, B>(); } }")
-        out.append("    template <int A> __device__ __forceinline__ void rest() const { range<A, R::NP>(); }")
-        out.append("};")
+        self.rp = ring_plan(3 * L) if self.chunked else None
+        # FAST (two-wavefront kernels, D > 8) or BOX (the 128-register kernels): the scene switch of the fused rollouts, decided at the
+        # launch (see _rollout_kernel)
+        self.fast_switch = D > 8
+        self.scene_switch = "scene_is_fast(a.C)" if self.fast_switch else "scene_is_general(a.C)"
 
-    # Fused rollout + geometric Jacobian of the tracked link (round 6; BASELINE config 4: "FK + Jacobian + cost" in ONE launch).  The
-    # Jacobian's stateful walk (robot_tree.py:136-248: clamp wherever limits exist, rotation about sf_rot_axis with the axis sign ignored)
-    # must coincide with the rollout's stateless one on every link the columns need -- then the columns z_j x (p_ee - p_j) | z_j are read
-    # out of the poses this kernel already holds.  Columns: the reference's rule (idx - 1) <= joint_list_idx (robot_tree.py:239-240).
-    jacf_cols: List[int] = []
-    jacf_ok = False
-    if tmpl.ee_link >= 0 and not tmpl.virtual and os.environ.get("TRK_EXP_NO_JAC_FUSE", "0") != "1":
-        ee_ = tmpl.ee_link
-        jacf_cols = [i for i in range(1, L) if int(kin.dof_idx[i]) >= 0 and int(kin.jac_axis[i]) >= 0 and (i - 1) <= int(kin.joint_list_idx[ee_])]
-        need_ = set()
-        for leaf in [ee_] + jacf_cols:
-            a = leaf
-            while a > 0 and a not in need_:
-                need_.add(a); a = int(kin.parent[a])
-        same_ = all(int(kin.joint_type[i]) == JOINT_FIXED or
-                    (int(kin.joint_type[i]) in (JOINT_REVOLUTE, JOINT_CONTINUOUS) and int(kin.clamp[i]) == int(kin.sf_clamp[i]) and
-                     int(kin.rot_axis[i]) == int(kin.sf_rot_axis[i]) and float(kin.rot_sign[i]) == 1.0) for i in need_)
-        jacf_ok = bool(jacf_cols) and same_
+        # Fused rollout + geometric Jacobian of the tracked link (round 6; BASELINE config 4: "FK + Jacobian + cost" in ONE launch).  The
+        # Jacobian's stateful walk (robot_tree.py:136-248: clamp wherever limits exist, rotation about sf_rot_axis with the axis sign ignored)
+        # must coincide with the rollout's stateless one on every link the columns need -- then the columns z_j x (p_ee - p_j) | z_j are read
+        # out of the poses this kernel already holds.  The same columns make k_ikgn's Newton step.
+        self.ee_jac_cols = _jacobian_columns(kin, tmpl.ee_link)
+        same = all(int(kin.joint_type[i]) == JOINT_FIXED or
+                   (int(kin.joint_type[i]) in (JOINT_REVOLUTE, JOINT_CONTINUOUS) and int(kin.clamp[i]) == int(kin.sf_clamp[i]) and
+                    int(kin.rot_axis[i]) == int(kin.sf_rot_axis[i]) and float(kin.rot_sign[i]) == 1.0)
+                   for i in _ancestry(kin, [tmpl.ee_link] + self.ee_jac_cols))
+        self.jacf_ok = bool(self.ee_jac_cols) and not tmpl.virtual and same
 
-    def emit_collision_objectives(E, t, next_chunk, fast_arg="", prims_ptr=""):
-        """cost + position adjoints (tb<i>_k) of the three collision fields on link positions t[i][k]; the scene evaluation owns
-        OBJ_TICK_SLOTS tick slots of `flush` per group.  Shared by the fused rollout and the positions-in field kernel."""
-        E.raw("    float cost = 0.0f;")
-        for i in adj_links:
-            E.raw(f"    float tb{i}_0 = 0.0f, tb{i}_1 = 0.0f, tb{i}_2 = 0.0f;")
-        t = with_virtual(E, t)
-        # leading collision links whose position is a CONSTANT of the model (identity base: the Panda's first link origin): in the
-        # GENERAL-scene instantiation (boxes / grid: scene_is_general) their object cost is evaluated once per wavefront, cooperatively
-        # (scene_min_sdf_uniform_point), instead of 64 times through the primitive loop; they get no gradient (no joint moves them).
-        # The spheres-only instantiation keeps its text (its register allocation is the headline's).
-        n_const = 0
-        if prims_ptr and os.environ.get("TRK_EXP_NO_UNIFORM_POINT", "0") != "1":
-            for i in tmpl.obj_links:
-                if all(t[i][k].is_const for k in range(3)) and i not in used_virt:
-                    n_const += 1
-                else:
-                    break
-        if 0 < n_const < NL <= LINK_OBJ_GROUP_MAX:
-            rest = list(tmpl.obj_links[n_const:])
-            nr = len(rest)
-            c0 = next_chunk[0]
-            next_chunk[0] += OBJ_TICK_SLOTS
-            E.raw(f"    const TickFrom<decltype(flush), {c0}> ticks{{flush}};")
-            # (a voxel-grid scene keeps all links in one batch: its cost is the gathers' latency, and a separate gather for the constant
-            # link in front of the others only adds a second exposed latency: 22.8 -> 23.8 us measured)
-            # (TRK_EXP_UNIFORM_SPHERES=1 at generation time: the spheres-only instantiation too -- an experiment knob, see DESIGN 6e)
-            cond = "!A.C.has_grid" if os.environ.get("TRK_EXP_UNIFORM_SPHERES", "0") == "1" else "BOX && !A.C.has_grid"
-            E.raw(f"    if ({cond}) {{")
-            for k, nm in enumerate("xyz"):
-                E.raw(f"        const float p{nm}[{nr}] = {{{', '.join(E.expr(t[i][k]) for i in rest)}}};")
-            E.raw(f"        float gx[{nr}], gy[{nr}], gz[{nr}];")
-            E.raw("#pragma unroll")
-            E.raw(f"        for (int l = 0; l < {nr}; ++l) {{ gx[l] = 0.0f; gy[l] = 0.0f; gz[l] = 0.0f; }}")
-            fa = fast_arg.replace("NL", str(nr))
-            E.raw(f"        if (A.w.w_obj != 0.0f) {{")
-            for j in range(n_const):      # first: its table reads (LDS) / grid gather are issued before this phase's position ticks
-                i = tmpl.obj_links[j]
-                E.raw(f"            cost += spec_object_cost_uniform_point(A.C, A.w.w_obj, {', '.join(E.expr(t[i][k]) for k in range(3))}, {j}, lane, {prims_ptr});")
-            E.raw(f"            cost += spec_objects_cost<{nr}{fa}>(A.C, A.w.w_obj, px, py, pz, gx, gy, gz, ticks, lds_sph, {n_const}, {prims_ptr});")
-            E.raw("        }")
-            E.raw(f"        else flush.template range<{c0}, {next_chunk[0]}>();")
-            E.raw(f"        if (A.w.w_ws != 0.0f && A.C.has_ws) {{")
-            E.raw(f"            cost += spec_ws_cost<{nr}>(A.C, A.w.w_ws, px, py, pz, gx, gy, gz, {n_const});")
-            for j in range(n_const):
-                i = tmpl.obj_links[j]
-                E.raw(f"            {{ float ux_ = 0.0f, uy_ = 0.0f, uz_ = 0.0f; cost += A.w.w_ws * ws_cost_point(A.C, cptr(A.C.obj_link_margin)[{j}], "
-                      f"{', '.join(E.expr(t[i][k]) for k in range(3))}, A.w.w_ws, ux_, uy_, uz_); }}")
-            E.raw("        }")
-            for j, i in enumerate(rest):
-                E.raw(f"        tb{i}_0 += gx[{j}]; tb{i}_1 += gy[{j}]; tb{i}_2 += gz[{j}];")
-            E.raw("    } else {")
-            for k, nm in enumerate("xyz"):
-                E.raw(f"        const float p{nm}[NL] = {{{', '.join(E.expr(t[i][k]) for i in tmpl.obj_links)}}};")
-            E.raw("        float gx[NL], gy[NL], gz[NL];")
-            E.raw("#pragma unroll")
-            E.raw("        for (int l = 0; l < NL; ++l) { gx[l] = 0.0f; gy[l] = 0.0f; gz[l] = 0.0f; }")
-            E.raw(f"        if (A.w.w_obj != 0.0f) cost += spec_objects_cost<NL{fast_arg}>(A.C, A.w.w_obj, px, py, pz, gx, gy, gz, ticks, lds_sph, 0, {prims_ptr});")
-            E.raw(f"        else flush.template range<{c0}, {next_chunk[0]}>();")
-            E.raw("        if (A.w.w_ws != 0.0f && A.C.has_ws) cost += spec_ws_cost<NL>(A.C, A.w.w_ws, px, py, pz, gx, gy, gz);")
-            for j, i in enumerate(tmpl.obj_links):
-                E.raw(f"        tb{i}_0 += gx[{j}]; tb{i}_1 += gy[{j}]; tb{i}_2 += gz[{j}];")
-            E.raw("    }")
-        elif 0 < NL <= LINK_OBJ_GROUP_MAX:
-            for k, nm in enumerate("xyz"):
-                E.raw(f"    const float p{nm}[NL] = {{{', '.join(E.expr(t[i][k]) for i in tmpl.obj_links)}}};")
-            E.raw("    float gx[NL], gy[NL], gz[NL];")
-            E.raw("#pragma unroll")
-            E.raw("    for (int l = 0; l < NL; ++l) { gx[l] = 0.0f; gy[l] = 0.0f; gz[l] = 0.0f; }")
-            c0 = next_chunk[0]
-            next_chunk[0] += OBJ_TICK_SLOTS     # the scene evaluation owns these tick slots, used or flushed on every path
-            E.raw(f"    const TickFrom<decltype(flush), {c0}> ticks{{flush}};")
-            E.raw(f"    if (A.w.w_obj != 0.0f) cost += spec_objects_cost<NL{fast_arg}>(A.C, A.w.w_obj, px, py, pz, gx, gy, gz, ticks, lds_sph{', 0, ' + prims_ptr if prims_ptr else ''});")
-            E.raw(f"    else flush.template range<{c0}, {next_chunk[0]}>();")
-            E.raw("    if (A.w.w_ws != 0.0f && A.C.has_ws) cost += spec_ws_cost<NL>(A.C, A.w.w_ws, px, py, pz, gx, gy, gz);")
-            for j, i in enumerate(tmpl.obj_links):
-                E.raw(f"    tb{i}_0 += gx[{j}]; tb{i}_1 += gy[{j}]; tb{i}_2 += gz[{j}];")
-        elif NL > 0:
-            # many collision links (tree robots): score them in groups so the working set of one scene evaluation
-            # (positions, keys, gradients: ~10 registers per link) does not sit on top of everything the reverse pass keeps
-            n_groups = -(-NL // LINK_OBJ_GROUP)
-            size = -(-NL // n_groups)
-            for g0 in range(0, NL, size):
-                grp = list(tmpl.obj_links[g0:g0 + size])
-                n = len(grp)
-                E.raw("    {")
-                for k, nm in enumerate("xyz"):
-                    E.raw(f"        const float p{nm}[{n}] = {{{', '.join(E.expr(t[i][k]) for i in grp)}}};")
-                E.raw(f"        float gx[{n}], gy[{n}], gz[{n}];")
-                E.raw("#pragma unroll")
-                E.raw(f"        for (int l = 0; l < {n}; ++l) {{ gx[l] = 0.0f; gy[l] = 0.0f; gz[l] = 0.0f; }}")
-                c0 = next_chunk[0]
-                next_chunk[0] += OBJ_TICK_SLOTS
-                E.raw(f"        const TickFrom<decltype(flush), {c0}> ticks{{flush}};")
-                E.raw(f"        if (A.w.w_obj != 0.0f) cost += spec_objects_cost<{n}{fast_arg}>(A.C, A.w.w_obj, px, py, pz, gx, gy, gz, ticks, lds_sph, {g0}{', ' + prims_ptr if prims_ptr else ''});")
-                E.raw(f"        else flush.template range<{c0}, {c0 + OBJ_TICK_SLOTS}>();")
-                E.raw(f"        if (A.w.w_ws != 0.0f && A.C.has_ws) cost += spec_ws_cost<{n}>(A.C, A.w.w_ws, px, py, pz, gx, gy, gz, {g0});")
-                for j, i in enumerate(grp):
-                    E.raw(f"        tb{i}_0 += gx[{j}]; tb{i}_1 += gy[{j}]; tb{i}_2 += gz[{j}];")
-                E.raw("    }")
-        if tmpl.self_pairs:
-            E.raw("    if (A.w.w_self != 0.0f) {")
-            for pi, (a, b) in enumerate(tmpl.self_pairs):
-                pa = ", ".join(E.expr(t[a][k]) for k in range(3))
-                pb = ", ".join(E.expr(t[b][k]) for k in range(3))
-                E.raw(f"        cost += spec_self_pair(A.w.w_self, cptr(A.C.self_margin)[{pi}], {pa}, {pb}, "
-                      f"tb{a}_0, tb{a}_1, tb{a}_2, tb{b}_0, tb{b}_1, tb{b}_2, (A.C.clamp_fields & TRK_FIELD_SELF) != 0);")
-            E.raw("    }")
-        scatter_virtual(E)
+        # GPT: the fused rollout with the GP prior fused in ("tree" schedule of trk_rollout_gp_cost_grad: the whole tree at once, like
+        # k_rollout -- see _gp_segments_kernel for the segment schedule and for what the prior adds).  launch_gp exists exactly when it does.
+        self.gpt_ok = (not self.chunked) and not tmpl.virtual and D <= 32
+        # the same objective with one ARM per lane (two isomorphic arms on one base: the dual Panda of BASELINE config 5)
+        self.arm_plan = arm_lane_plan(kin, tmpl) if (self.gpt_ok and os.environ.get("TRK_EXP_NO_ARM_LANES", "0") != "1") else None
+        # The segment schedule is compiled only on request (TRK_GP_SCHEDULE=segments at generation time): measured on the dual Panda it
+        # is slower than the tree schedule (DESIGN.md 6d) -- its wavefronts are VALU-bound either way, and what one resident
+        # generation gains the serial arms lose in instruction-level parallelism.
+        self.gp_ok = self.gpt_ok and self.walk == list(range(L)) and L >= 2
+        self.segs, self.gp_cross_pairs = _gp_segments(kin, tmpl, self.tracked) if self.gp_ok else ([], False)
+        self.use_seg = self.gp_ok and os.environ.get("TRK_GP_SCHEDULE", "tree") == "segments"
 
-    def emit_boolean_fields(E, t):
-        """`hit` = OR of the selected fields' "signed distance < margin" tests on link positions t[i][k] (k_coll after its FK walk,
-        k_collf on the caller's positions)"""
-        E.raw("    bool hit = false;")
-        t = with_virtual(E, t)
-        if NL > 0:
-            grp_size = NL if NL <= LINK_OBJ_GROUP_MAX else -(-NL // (-(-NL // LINK_OBJ_GROUP)))
-            E.raw("    if (A.coll_fields & (TRK_FIELD_OBJECTS | TRK_FIELD_WS)) {")
-            for g0 in range(0, NL, grp_size):
-                grp = list(tmpl.obj_links[g0:g0 + grp_size])
-                n = len(grp)
-                E.raw("        {")
-                for k, nm in enumerate("xyz"):
-                    E.raw(f"            const float p{nm}[{n}] = {{{', '.join(E.expr(t[i][k]) for i in grp)}}};")
-                E.raw(f"            hit |= spec_collision_links<{n}>(A.C, A.coll_fields, A.coll_margin, A.coll_use_default, px, py, pz, lds_sph, {g0});")
-                E.raw("        }")
-            E.raw("    }")
-        if tmpl.self_pairs:
-            E.raw("    if (A.coll_fields & TRK_FIELD_SELF) {")
-            for pi, (a_, b_) in enumerate(tmpl.self_pairs):
-                pa = ", ".join(E.expr(t[a_][k]) for k in range(3))
-                pb = ", ".join(E.expr(t[b_][k]) for k in range(3))
-                E.raw(f"        hit |= spec_self_hit(A.coll_use_default ? cptr(A.C.self_margin)[{pi}] : A.coll_margin, {pa}, {pb});")
-            E.raw("    }")
+        # Explicit reverse mode of the link positions.  Many links (the ring-staged units): the whole-row tile is 92 KB per workgroup for
+        # 30 links -- one wavefront per SIMD -- and 3L adjoint registers per lane.  Those units take the attached-point generator's kernel
+        # instead (columns = the links, chunked loads, prefix-sum gradients; needs the file order to be the pre-order walk): UR10 + Allegro
+        # 34.1 -> 29.8 us, iiwa7 + Allegro 33.4 -> 30.9, Shadow hand 32.6 -> 30.4 (profiles/r05_bench_positions.txt).
+        self.posbwd_chunked = self.chunked and file_walk
+        # FK matrices of all links: two links per flush (128 bytes per sample) when rows are whole 128-byte lines (L even) and the walk is
+        # the file order: full-line writes matter once the output exceeds the 256 MB Infinity Cache (UR10+Allegro, 526 MB: 122 - 154 ->
+        # 101 us); with odd L every other row starts mid-line and the pairs straddle lines anyway (Panda, dual Panda: no difference).
+        self.fkh_pair = L % 2 == 0 and file_walk
+        # the collision fields on given positions: whole rows through the LDS transpose
+        self.fields_ok = 3 * L <= 96 and (self.NL > 0 or bool(tmpl.self_pairs))
+        # every link's rotation stays live until the reverse walk has consumed it: beyond ~24 links the kernel spills (UR10+Allegro:
+        # 252 registers, 347 us against the table-driven kernel's 253) -- such robots keep the table-driven reverse mode
+        self.fkhbwd_ok = L <= 24
+        # Adam IK: q, m and v of every DOF stay in registers across the loop: beyond ~9 DOF the kernel spills (dual Panda, 14 DOF: 10
+        # registers; UR10+Allegro, 22 DOF: 377) and those robots keep the table-driven kernel
+        self.ik_ok = tmpl.ee_link >= 0 and D <= 9
+        self.ikgn_ok = tmpl.ee_link >= 0 and D <= 9 and len(self.ee_jac_cols) > 0
+        # k_jac.  Small arms: the lane writes its columns straight into two [64][3D] output tiles (static offsets; non-ancestor columns
+        # stay zero), finishes z x (p_link - p_joint) in place, and the read-out is a contiguous 16-byte copy.  The record scheme
+        # needs less LDS when the target link has few ancestors among many joints (a finger tip of UR10+Allegro: 10 of 22), but its
+        # read-out maps every output element through the slot table at run time -- half of the Panda kernel's time.
+        self.jac_joints = [i for i in range(1, L) if int(kin.dof_idx[i]) >= 0 and int(kin.jac_axis[i]) >= 0]
+        self.jac_direct = D <= JAC_DIRECT_MAX_DOFS
+        jac_lds = 6 * D if self.jac_direct else max((6 * len(self.jac_joints) + 3) | 1, D)
+        self.jac_ok = (TRK_WAVE_ * jac_lds + 32) * 4 <= 64 * 1024            # default dynamic-LDS limit of a launch
+        # the analytic Jacobian of every link, staged through a ring like the big units' positions
+        self.ajac_ok = D <= 16 and L <= 24 and 7 * D * L >= RING_FLOATS
+        self.arp = ring_plan(7 * D * L) if self.ajac_ok else None
 
-    # GPT: the same kernel with the GP prior fused in ("tree" schedule of trk_rollout_gp_cost_grad: the whole tree at once, like
-    # k_rollout -- see k_rollout_gp below for the segment schedule and for what the prior adds)
-    gpt_ok = (not chunked) and not tmpl.virtual and D <= 32
-    for base_identity, GPT in ((True, False), (False, False)) + (((True, True), (False, True)) if gpt_ok else ()):
-        E = Emitter()
-        kname = ("k_rollout_gpt_" if GPT else "k_rollout_") + ("bi" if base_identity else "bg")
-        # small arms fit 128 VGPRs (4 waves/SIMD: the whole 4096 x 64 batch resident); big trees get 256 VGPRs
-        # FAST (two-wavefront kernels only): scene_is_fast(A.C) -- a few equal spheres and nothing else -- is decided at the launch and
-        # only that scene path is compiled into the instantiation (5-rep same-box A/B: dual Panda 19.5 -> 18.6 us, UR10 + Allegro
-        # 31.0 -> 30.7; the 128-register Panda kernel measured no gain and keeps the run-time branches)
-        fast_t = D > 8
-        # BOX: the scene has boxes and its primitive table fits TRK_LDS_PRIMS -- the instantiation keeps a copy of the table in LDS
-        # and scene_min_sdf carries only (value, index) through its primitive loop (shelf 23.2 -> 22.0 us, maze 24.6 -> 22.2).  The
-        # 128-register kernels get it as a switch of its own, decided at the launch: compiled into the one kernel the sphere scene
-        # runs as well, the headline measured 9.17 -> 9.37 us (register allocation again).  Two-wavefront kernels: BOX = !FAST.
-        # The BOX instantiation is the GENERAL scene kernel: launches choose it with scene_is_general (any box object, or a voxel grid),
-        # and only it carries the box and grid text of scene_min_sdf (GENERAL = BOX there).  Behind run-time branches in the
-        # sphere-scene kernel the brick-tiled cell index alone cost the headline 9.2 -> 9.55 us (same-box A/B,
-        # profiles/r04_ab_headline_*.txt).
-        box_t = D <= 8
-        if chunked:
-            # POS: the launch wants the link positions.  A compile-time switch, because the ring staging costs the launches that
-            # only want cost + gradient (the planners' inner loop) 2-4 us even with every store masked off.
-            # JAC (units with jacf_ok): the same launch also writes the geometric Jacobian of the tracked link (launch_rjac).
-            E.raw(f"template <class IO, bool POS{', bool FAST' if fast_t else ''}{', bool BOX' if box_t else ''}{', bool JAC = false' if (jacf_ok and not GPT) else ''}>      // IO: HBM-side type of q / link_pos / gq (float or _Float16)")
-        else:
-            E.raw(f"template <class IO{', bool FAST' if fast_t else ''}{', bool BOX' if box_t else ''}{', bool JAC = false' if (jacf_ok and not GPT) else ''}>      // HBM-side type of q / link_pos / gq: float or _Float16")
-        if GPT and box_t:
-            # the prior's gradient (D registers) lives across the whole kernel: the box-scene instantiation of a small arm would spill
-            # 26 registers at four wavefronts per SIMD -- it runs at three
-            E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, BOX ? 3 : 4) {kname}(SpecArgs A) {{")
-        else:
-            E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, {4 if D <= 8 else 2}) {kname}(SpecArgs A) {{")
-        if not box_t:
-            E.raw("    constexpr bool BOX = !FAST;")
-        if chunked:
-            if jacf_ok and not GPT:
-                E.raw(f"    constexpr int LDS_LANE = JAC ? {max(rp.stride, D, 3 * D)} : (POS ? {max(rp.stride, D)} : {D});      // JAC: the [64][3D] Jacobian tiles reuse the region")
-                E.raw('    static_assert(!JAC || TrkSame<IO, float>::value, "the fused Jacobian is an fp32 output");')
-            else:
-                E.raw(f"    constexpr int LDS_LANE = POS ? {max(rp.stride, D)} : {D};")
-            lds_lane = "LDS_LANE"
-        else:
-            lds_lane = max(3 * L, D)      # (>= 3 D: the [64][3D] Jacobian tiles of a JAC instantiation fit the staging tile, L > D)
-            if jacf_ok and not GPT:
-                assert 3 * D <= lds_lane
-                E.raw('    static_assert(!JAC || TrkSame<IO, float>::value, "the fused Jacobian is an fp32 output");')
-            if GPT:     # the raw q / qd tiles (fp32 at worst) and the factor tile of the prior phase must fit the staging tile
-                pad = -(-D // 4) * 4
-                need = 2 * (-(-((pad + 65 * D) * 4) // 16) * 16) + (65 * (2 * D + 1) + 2) * 4
-                lds_lane = max(lds_lane, -(-need // 256))
-        E.raw(f"    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * {lds_lane} + SPEC_WAVES * (TRK_LDS_SPHERES * 4 + (BOX ? TRK_LDS_PRIMS * 8 : 0))];")
-        E.raw("    typedef typename IoTraits<IO>::Q IOQ;      // q, link_pos in HBM")
-        E.raw("    typedef typename IoTraits<IO>::G IOG;      // gq in HBM (fp16 q: scaled by A.grad_scale, fp16 stores saturate)")
-        E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
-        E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);   // wave-uniform -> SGPR")
-        E.raw(f"    float* lds = lds_all + wave * (TRK_WAVE * {lds_lane});")
-        E.raw(f"    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * {lds_lane}) + wave * (TRK_LDS_SPHERES + (BOX ? 2 * TRK_LDS_PRIMS : 0));")
-        E.raw("    float4* lds_prm = BOX ? lds_sph + TRK_LDS_SPHERES : nullptr;        // box scenes: the primitive records, for the winning box's gather")
-        E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);   // waited for together with the rows below")
-        E.raw("    SpheresInFlight prm{};")
-        E.raw("    if constexpr (BOX) prm = spec_load_prims_issue(A.C, lane);")
-        E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;     // index of this wave's 64-sample block")
-        E.raw("    const int64_t base = wblock * TRK_WAVE;")
-        E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
-        E.raw("    spec_stamp(A.stamps, wblock, 0, lane);")
-        E.raw("    spec_stamp_real(A.stamps, wblock, 2, lane);      // 100 MHz chip-wide clock: aligns the per-CU s_memtime domains")
-        E.raw("    float q[D];")
-        if not GPT:
-            E.raw("    spec_load_q<D>(static_cast<const IOQ*>(A.q), base, rows, lane, lds, q);")
-        else:
-            E.raw("    typedef RawRowsInFlight<D, IOQ> Raw;")
-            E.raw("    constexpr int RS = 2 * D + 1;         // floats per row of the factor tile (odd: conflict-free)")
-            E.raw(f"    static_assert(2 * Raw::BYTES + ((TRK_WAVE + 1) * RS + 2) * 4 <= TRK_WAVE * {lds_lane} * 4 && TRK_WAVE * D * 4 <= TRK_WAVE * {lds_lane} * 4, \"the raw q / qd tiles and the factor tile share the staging tile\");")
-            E.raw("    const unsigned Hh = (unsigned)A.gp_H;")
-            E.raw("    const unsigned t0 = (unsigned)(base % (int64_t)A.gp_H);")
-            E.raw("    const unsigned tl = (t0 + (unsigned)lane) % Hh, t_last = (t0 + (unsigned)(TRK_WAVE - 1)) % Hh;")
-            E.raw("    const bool edge_prev = rows > 0 && t0 > 0u, edge_next = rows == TRK_WAVE && t_last + 1u < Hh && base + TRK_WAVE < A.n;")
-            E.raw("    const Raw rq = spec_raw_rows_issue<D, IOQ>(static_cast<const IOQ*>(A.q), base, rows, lane, edge_prev, edge_next);")
-            E.raw("    const Raw rv = spec_raw_rows_issue<D, IOQ>(static_cast<const IOQ*>(A.qd), base, rows, lane, edge_prev, edge_next);")
-            E.raw("    const IOQ* qb = spec_raw_rows_finish<D, IOQ>(rq, static_cast<const IOQ*>(A.q), base, rows, lane, reinterpret_cast<IOQ*>(lds));")
-            E.raw("    const IOQ* vb = spec_raw_rows_finish<D, IOQ>(rv, static_cast<const IOQ*>(A.qd), base, rows, lane, reinterpret_cast<IOQ*>(reinterpret_cast<unsigned char*>(lds) + Raw::BYTES));")
-            E.raw("    float* rt = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(lds) + 2 * Raw::BYTES);     // [65][RS]: row l + 1 = lane l's factor")
-            E.raw("    spec_wave_sync();")
-            if os.environ.get("TRK_EXP_GP_PRIOR", "dpp") == "lds":
-                E.raw("    float gpv[D], cost_gp;")
-                E.raw("    {")
-                E.raw("        // ---- the prior.  A lane computes ONLY the factor it starts: e_t = (p_t + dt v_t - p_t+1, v_t - v_t+1), r_t = w Q^-1 e_t (zero")
-                E.raw("        // when the trajectory ends here); the factor that ends at this sample is the previous lane's, fetched through LDS (the one in")
-                E.raw("        // front of the block: lanes 0 .. D-1, one joint each).  d/dq_t = r_t.p - r_t-1.p,  d/dqd_t = dt r_t.p + r_t.v - r_t-1.v.")
-                E.raw("        const float wm = (lane < rows && tl + 1u < Hh) ? A.gp_w : 0.0f;")
-                E.raw("        const float dt = A.gp_dt, ga = A.gp_a, gb = A.gp_b, gc = A.gp_c;")
-                E.raw("        float gvv[D], accg = 0.0f;")
-                E.raw("#pragma unroll")
-                E.raw("        for (int d = 0; d < D; ++d) {")
-                E.raw("            const float p0 = (float)qb[lane * D + d], v0 = (float)vb[lane * D + d];")
-                E.raw("            const float pn = (float)qb[(lane + 1) * D + d], vn = (float)vb[(lane + 1) * D + d];")
-                E.raw("            const float ep = fmaf(dt, v0, p0) - pn, ev = v0 - vn;")
-                E.raw("            const float rp = wm * fmaf(ga, ep, gb * ev), rv_ = wm * fmaf(gb, ep, gc * ev);")
-                E.raw("            accg = fmaf(0.5f, fmaf(ep, rp, ev * rv_), accg);")
-                E.raw("            rt[(lane + 1) * RS + 2 * d] = rp; rt[(lane + 1) * RS + 2 * d + 1] = rv_;")
-                E.raw("            q[d] = p0;")
-                E.raw("            if (d % 4 == 3) __builtin_amdgcn_sched_barrier(0);      // four joints in flight: the max-ILP scheduler would hoist all 4 D tile reads (and spill)")
-                E.raw("        }")
-                E.raw("        {       // the factor between the sample in front of the block and its first sample: lanes 0 .. D-1, joint `lane`.  Branch-free")
-                E.raw("                // (the other lanes compute joint 0 again and write a scratch slot behind the tile): as a divergent branch this")
-                E.raw("                // block cost the whole kernel 38 registers (217 -> 255, spills in the box-scene instantiation)")
-                E.raw("            const int dj = lane < D ? lane : 0;")
-                E.raw("            const float pm = (float)qb[dj - D], vm = (float)vb[dj - D], pf = (float)qb[dj], vf = (float)vb[dj];")
-                E.raw("            const float wp = edge_prev ? A.gp_w : 0.0f;")
-                E.raw("            const float ep = fmaf(dt, vm, pm) - pf, ev = vm - vf;")
-                E.raw("            float* slot = rt + (lane < D ? 2 * lane : (TRK_WAVE + 1) * RS);")
-                E.raw("            slot[0] = wp * fmaf(ga, ep, gb * ev); slot[1] = wp * fmaf(gb, ep, gc * ev);")
-                E.raw("        }")
-                E.raw("        spec_wave_sync();")
-                E.raw("#pragma unroll")
-                E.raw("        for (int d = 0; d < D; ++d) {")
-                E.raw("            const float rp = rt[(lane + 1) * RS + 2 * d], rv_ = rt[(lane + 1) * RS + 2 * d + 1];      // re-read: 2 D registers less across the sync")
-                E.raw("            gpv[d] = rp - rt[lane * RS + 2 * d];")
-                E.raw("            gvv[d] = fmaf(dt, rp, rv_) - rt[lane * RS + 2 * d + 1];")
-                E.raw("            if (d % 4 == 3) __builtin_amdgcn_sched_barrier(0);")
-                E.raw("        }")
-                E.raw("        cost_gp = accg;")
-                E.raw("        // d cost / d qd is final: out through the staging tile (its first line waits for every lane's reads of the tiles)")
-                E.raw("        spec_store_gq<D, IOG, IoTraits<IO>::kScaled>(static_cast<IOG*>(A.gqd), base, rows, lane, lds, gvv, A.grad_scale);")
-                E.raw("        spec_wave_sync();")
-                E.raw("    }")
-            else:
-                # Round 5: the neighbours come through DPP wave shifts instead of LDS.  The phase stamps put "rows in + prior + gqd out" at 36 - 42 %
-                # of a config-5 wavefront's life (7300 - 8200 of 20 000 ticks): per joint the LDS form cost four reads, two writes and four
-                # more reads behind a second sync -- ten dependent round trips' worth of instructions at two wavefronts per SIMD.  Now a lane
-                # reads its own row, the next sample's (p, v) arrive by `wave_shl:1` (lane 63: the row behind the block, handed to the
-                # shift as its `old` operand, which a lane without a source keeps), the finished factor (rp, rv) goes to the next lane by
-                # `wave_shr:1` (lane 0: the factor in front of the block, computed by lanes 0 .. D-1 as before and read back broadcast).
-                # Same expressions on the same values as the LDS form: bit-identical results.
-                E.raw("    float gpv[D], cost_gp;")
-                E.raw("    {")
-                E.raw("        const float wm = (lane < rows && tl + 1u < Hh) ? A.gp_w : 0.0f;")
-                E.raw("        const float dt = A.gp_dt, ga = A.gp_a, gb = A.gp_b, gc = A.gp_c;")
-                E.raw("        {       // the factor between the sample in front of the block and its first sample: lanes 0 .. D-1, joint `lane`.  Branch-free")
-                E.raw("                // (the other lanes compute joint 0 again and write a scratch slot behind the records)")
-                E.raw("            const int dj = lane < D ? lane : 0;")
-                E.raw("            const float pm = (float)qb[dj - D], vm = (float)vb[dj - D], pf = (float)qb[dj], vf = (float)vb[dj];")
-                E.raw("            const float wp = edge_prev ? A.gp_w : 0.0f;")
-                E.raw("            const float ep = fmaf(dt, vm, pm) - pf, ev = vm - vf;")
-                E.raw("            float* slot = rt + (lane < D ? 2 * lane : 2 * D);")
-                E.raw("            slot[0] = wp * fmaf(ga, ep, gb * ev); slot[1] = wp * fmaf(gb, ep, gc * ev);")
-                E.raw("        }")
-                E.raw("        spec_wave_sync();")
-                E.raw("        float gvv[D], accg = 0.0f;")
-                E.raw("        const float gaw = wm * ga, gbw = wm * gb, gcw = wm * gc;")
-                E.raw("#pragma unroll")
-                E.raw("        for (int d = 0; d < D; ++d) {")
-                E.raw("            const float p0 = (float)qb[lane * D + d], v0 = (float)vb[lane * D + d];")
-                E.raw("            const float pn = trk_dpp_from_next((float)qb[TRK_WAVE * D + d], p0), vn = trk_dpp_from_next((float)vb[TRK_WAVE * D + d], v0);")
-                E.raw("            const float ep = fmaf(dt, v0, p0) - pn, ev = v0 - vn;")
-                E.raw("            const float rp = fmaf(gaw, ep, gbw * ev), rv_ = fmaf(gbw, ep, gcw * ev);      // w Q^-1 e with the weight folded into Q^-1 once per lane")
-                E.raw("            accg = fmaf(ep, rp, fmaf(ev, rv_, accg));                                      // 2 x the factor's cost: halved once, below")
-                E.raw("            gpv[d] = rp - trk_dpp_from_prev(rt[2 * d], rp);")
-                E.raw("            gvv[d] = fmaf(dt, rp, rv_) - trk_dpp_from_prev(rt[2 * d + 1], rv_);")
-                E.raw("            q[d] = p0;")
-                E.raw("        }")
-                E.raw("        cost_gp = 0.5f * accg;")
-                E.raw("        // d cost / d qd is final: out through the staging tile (its first line waits for every lane's reads of the tiles)")
-                E.raw("        spec_store_gq<D, IOG, IoTraits<IO>::kScaled>(static_cast<IOG*>(A.gqd), base, rows, lane, lds, gvv, A.grad_scale);")
-                E.raw("        spec_wave_sync();")
-                E.raw("    }")
-        E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
-        E.raw("    if constexpr (BOX) spec_load_spheres_finish(lds_prm, lane, prm);")
-        E.raw("    spec_stamp(A.stamps, wblock, 1, lane);")
-        # ---------------- forward ----------------
-        R: Dict[int, List[List[S]]] = {}
-        t: Dict[int, List[S]] = {}
-        passv: Dict[int, S] = {}
-        if base_identity:
-            R[0] = [[ONE if r == c else ZERO for c in range(3)] for r in range(3)]
-            t[0] = [ZERO, ZERO, ZERO]
-        else:
-            R[0] = [[S(1.0, f"A.base_R[{3 * r + c}]") for c in range(3)] for r in range(3)]
-            t[0] = [S(1.0, f"A.base_t[{r}]") for r in range(3)]
-        _emit_angles(E, kin)
-        if chunked:
-            # Many links: a full [64][3L] staging tile per wavefront (92 KB per workgroup for 30 links) leaves ONE workgroup per
-            # CU.  The positions go through a 64-float ring per lane instead (RingFlusher): each link is staged as it exists, a
-            # complete 32-float chunk leaves piece by piece between the links that fill the other half of the ring.
-            W = 3 * L
-            E.raw(f"    static_assert({ring_t}::LS == {rp.stride} && {ring_t}::HX == {rp.hx} && {ring_t}::NFULL == {rp.n_full} && {ring_t}::NP == {rp.pieces}, "
-                  '"generator and RingFlusher disagree on the ring geometry");')
-            E.raw(f"    const {ring_t} ring = spec_make_ring<{rp.W}, {rp.V}, {'true' if rp.aligned else 'false'}, IOQ>("
-                  "static_cast<IOQ*>(A.link_pos), base, rows, lane, lds);")
-            E.raw("    float* const prow = ring.row();        // this lane's ring; prow_a: the same, shifted by the lane's head")
-            E.raw("    float* const prow_a = ring.row_a();")
-            E.raw("    spec_wave_sync();")
-            ready_at: Dict[int, List[int]] = {}
-            for c in range(rp.n_full + 1):
-                ready_at.setdefault(rp.ready_float(c), []).append(c)
-            pending: List[Tuple[int, int]] = []       # (chunk, piece) not yet issued, oldest first
 
-            def stage_link(i):
-                for k in range(3):
-                    f = 3 * i + k
-                    assert all(rp.reuse_float(c) > f for c, _ in pending), "ring half reused before its pieces were issued"
-                    x = E.expr(t[i][k])
-                    if rp.regular(f):
-                        E.raw(f"    if constexpr (POS) prow_a[{f & 63}] = {x};")
-                    else:
-                        E.raw(f"    if constexpr (POS) prow[ring.slot({f})] = {x};")
-                    if f < rp.hx:
-                        E.raw(f"    if constexpr (POS) prow[{64 + f}] = {x};")
-                    for c in ready_at.get(f, []):
-                        E.raw(f"    if constexpr (POS) ring.template done<{c}>();")
-                        if c < rp.n_full:
-                            pending.extend((c, kk) for kk in range(rp.pieces))
+class _Ticks:
+    """The compile-time chunk numbers of a kernel's position flusher (flush.chunk<CH>()), handed out in program order."""
 
-            def issue_pieces(i):
-                """slot after link i: the pending pieces (of one chunk) are spread evenly over the slots that remain until the
-                link whose staging re-uses their half of the ring (or the end of the walk)"""
-                if not pending:
-                    return
-                c = pending[0][0]
-                last_slot = min(L - 1, rp.reuse_float(c) // 3 - 1)
-                slots = max(1, last_slot - i + 1)
-                n = -(-sum(1 for cc, _ in pending if cc == c) // slots)
-                for _ in range(n):
-                    cc, kk = pending.pop(0)
-                    E.raw(f"    if constexpr (POS) ring.template piece<{cc}, {kk}>();")
-            stage_link(0)
-            issue_pieces(0)
-        for p in range(1, L):
-            i = walk[p]
-            _emit_fk_link(E, kin, i, R, t, passv, snap)
-            if chunked:
-                stage_link(i)
-                issue_pieces(i)
-        # ---------------- outputs that depend only on FK ----------------
-        if chunked:
-            assert not pending
-            E.raw("    const typename TrkIf<POS, RingTail<decltype(ring)>, NoFlushOf<decltype(ring)>>::type flush{ring};")
-        else:
-            E.raw(f"    PosFlusher<{3 * L}, IOQ> flush{{reinterpret_cast<const float4*>(lds) + lane, 0u, 0ull, 0ull, lane, make_float4(0.0f, 0.0f, 0.0f, 0.0f)}};")
-            pos_list = ", ".join(E.expr(t[i][k]) for i in range(L) for k in range(3))
-            E.raw("    if (A.link_pos) {")
-            E.raw(f"        const float pv[{3 * L}] = {{{pos_list}}};")
-            E.raw(f"        flush = spec_stage_rows<{3 * L}>(static_cast<IOQ*>(A.link_pos), base, rows, lane, lds, pv);")
-            E.raw("    }")
-        E.raw("    if (!A.gq) { flush.template rest<0>(); return; }      // positions only (trk_fk_positions): wave-uniform exit")
-        # position chunks leave at tick points with COMPILE-TIME chunk numbers (PosFlusher::chunk<CH>); `next_chunk` counts them
-        next_chunk = [0]
+    def __init__(self):
+        self.n = 0
 
-        def tick_line(indent="    "):
-            c = next_chunk[0]
-            next_chunk[0] += 1
-            return f"{indent}flush.template chunk<{c}>();"
-        # experiment knob: TRK_EXP_FIRST_BURST=n issues the first n chunks right after staging (default none: +0.35 us with 2)
-        first = int(os.environ.get("TRK_EXP_FIRST_BURST", "0"))
-        for _ in range(first):
-            E.raw(tick_line())
-        E.raw("    spec_stamp(A.stamps, wblock, 3, lane);")
-        # ---------------- objectives ----------------
-        emit_collision_objectives(E, t, next_chunk, fast_arg=f", decltype(ticks), {'FAST' if fast_t else 'false'}, BOX", prims_ptr="lds_prm")
-        E.raw("    spec_stamp(A.stamps, wblock, 4, lane);")
-        for ee, tgt, rb in tracked:
-            E.raw(f"    float {rb}[9] = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}};")
-        if tracked:
-            E.raw("    if (A.w.w_ee != 0.0f) {")
-            for ee, tgt, rb in tracked:
-                E.raw("      {")
-                E.raw(f"        const float eR[9] = {{{', '.join(E.expr(R[ee][r][c]) for r in range(3) for c in range(3))}}};")
-                E.raw(f"        const float et[3] = {{{', '.join(E.expr(t[ee][k]) for k in range(3))}}};")
-                E.raw("        float gR[9], gt[3];")
-                E.raw(f"        const float ce = ee_cost_eval(eR, et, {tgt}, A.C.ee_w_pos, A.C.ee_w_rot, A.C.ee_square, gR, gt);")
-                E.raw("        cost = fmaf(A.w.w_ee, ce, cost);")
-                E.raw("#pragma unroll")
-                E.raw(f"        for (int k = 0; k < 9; ++k) {rb}[k] = A.w.w_ee * gR[k];")
-                E.raw(f"        tb{ee}_0 = fmaf(A.w.w_ee, gt[0], tb{ee}_0); tb{ee}_1 = fmaf(A.w.w_ee, gt[1], tb{ee}_1); "
-                      f"tb{ee}_2 = fmaf(A.w.w_ee, gt[2], tb{ee}_2);")
-                E.raw("      }")
-            E.raw("    }")
-        E.raw(tick_line())
-        E.raw("    spec_stamp(A.stamps, wblock, 5, lane);")
-        if GPT:
-            E.raw("    cost += cost_gp;           // the prior's factor t -> t + 1, attributed to this sample")
-        E.raw("    if (lane < rows) store_wt_f1(A.cost + base + lane, cost);")
-        E.raw("    if (A.cost_sum) {")
-        E.raw("        const float tot = spec_wave_sum(lane < rows ? cost : 0.0f);")
-        # write-through like every other output: the plain 4-byte store left 4096 dirty partial lines for the end-of-kernel
-        # write-back (same-box A/B 9.94 -> 9.77 us)
-        E.raw("        if (lane == 0 && rows > 0) store_wt_f1(A.cost_sum + wblock, tot);")
-        E.raw("    }")
-        # ---------------- reverse: wrench accumulators towards the root ----------------
-        # (A second FK walk with prefix-sum gradients instead of this reverse pass -- so that the joints' axes / origins need not
-        # stay alive -- was measured on UR10+Allegro: 41.3 vs 37.5 us.  These kernels are bound by VALU issue, not by occupancy.)
-        gq_expr = _emit_reverse_links(E, kin, R, t, {i: [f"tb{i}_{k}" for k in range(3)] for i in real_adj},
-                                      {l: rb for l, _, rb in tracked}, masked, tick=tick_line, order=walk)
-        E.raw("    spec_stamp(A.stamps, wblock, 6, lane);")
-        E.raw(f"    flush.template rest<{next_chunk[0]}>();")
-        if GPT:
-            E.raw(f"    const float gv[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) + f' + gpv[{d}]' for d in range(D))}}};")
-        else:
-            E.raw(f"    const float gv[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
-        E.raw("    spec_store_gq<D, IOG, IoTraits<IO>::kScaled>(static_cast<IOG*>(A.gq), base, rows, lane, lds, gv, A.grad_scale);")
-        E.raw("    spec_stamp(A.stamps, wblock, 7, lane);")
-        if jacf_ok and not GPT:
-            ee = tmpl.ee_link
-            E.raw("    if constexpr (JAC) {")
-            E.raw(f"        // ---- geometric Jacobian of link {ee} '{kin.link_names[ee]}' (robot_tree.py:218-248) from the poses of this walk: column d of a")
-            E.raw("        // joint with a column = [z x (p_link - p_joint) ; z], every other column zero; lin_jac / ang_jac [N, 3, D] leave as the")
-            E.raw("        // wavefront's contiguous 64 x 3D floats through one LDS tile each (16-byte write-through stores, like k_jac's)")
-            pe = [E.named(t[ee][k]) for k in range(3)]
-            colz: Dict[int, List[S]] = {}
-            coll: Dict[int, List[S]] = {}
-            for i in jacf_cols:
-                d, ax = int(kin.dof_idx[i]), int(kin.jac_axis[i])
-                z = [E.named(R[i][r][ax]) for r in range(3)]
-                rel = [E.named(E.lincomb([(pe[k], ONE), (t[i][k], S(-1.0))])) for k in range(3)]
-                colz[d] = z
-                coll[d] = [E.named(v) for v in E.cross(z, rel)]
-            E.raw(f"        float* jrow = lds + lane * {3 * D};")
-            for nm, cols, dst in (("lin", coll, "A.jac_lin"), ("ang", colz, "A.jac_ang")):
-                E.raw(f"        spec_wave_sync();          // the region's previous readers are done ({nm}_jac)")
-                vals = []
-                for r in range(3):
-                    for d in range(D):
-                        vals.append(E.expr(cols[d][r]) if d in cols else "0.0f")
-                E.raw("        " + " ".join(f"jrow[{k}] = {v};" for k, v in enumerate(vals)))
-                E.raw("        spec_wave_sync();")
-                # beyond the Infinity Cache the contiguous tiles are faster as non-temporal stores (UR10 + Allegro, 287 MB per launch, same box,
-                # three alternations: 46.4 - 47.7 -> 45.3 - 45.4 us; inside the cache write-through wins, as for the headline's chunks): the launch decides
-                E.raw(f"        if (A.jac_stream) spec_store_tile<{3 * D}, true>({dst}, base, rows, lane, lds);")
-                E.raw(f"        else spec_store_tile<{3 * D}>({dst}, base, rows, lane, lds);")
-            E.raw("        if (lane < rows) {")
-            E.raw("            const int64_t s_ = base + lane;")
-            E.raw(f"            const float jR[9] = {{{', '.join(E.expr(R[ee][r][c]) for r in range(3) for c in range(3))}}};")
-            E.raw("            " + " ".join(f"A.jac_pos[s_ * 3 + {k}] = {E.expr(pe[k])};" for k in range(3)))
-            E.raw("            float qo[4];")
-            E.raw("            frame_quat_wxyz(jR, qo);")
-            E.raw("            *reinterpret_cast<float4*>(A.jac_quat + s_ * 4) = make_float4(qo[0], qo[1], qo[2], qo[3]);")
-            E.raw("        }")
-            E.raw("    }")
-        E.raw("}")
-        out.extend(E.lines)
-        out.append("")
+    def __call__(self) -> str:
+        """one tick slot"""
+        self.n += 1
+        return f"    flush.template chunk<{self.n - 1}>();"
 
-    # ---- the same objective with one ARM per lane (two isomorphic arms on one base: the dual Panda of BASELINE config 5)
-    arm_plan = arm_lane_plan(kin, tmpl) if (gpt_ok and os.environ.get("TRK_EXP_NO_ARM_LANES", "0") != "1") else None
-    if arm_plan is not None:
-        out.extend(_arm_lane_kernel_lines(kin, tmpl, arm_plan, snap))
+    def take(self, k: int) -> int:
+        """k consecutive slots (a scene evaluation owns them, used or flushed on every path); returns the first"""
+        self.n += k
+        return self.n - k
 
-    # ---- the fused rollout with the GP prior fused in (trk_rollout_gp_cost_grad; BASELINE config 5's objective in ONE launch, gq and
-    # gqd written once).  BUILD-DEFINED like the prior itself.  Two things differ from k_rollout:
-    # (1) SEGMENTS.  The subtrees hanging off the root that share no objective (the two arms of the dual Panda when no self pair
-    #     crosses them) are evaluated one after the other -- FK, scene, EE, reverse pass, positions -- so that only ONE arm's poses
-    #     are live at a time: the dual Panda fits the 128 registers and ~10 KB of LDS per wavefront that let all 4096 wavefronts of
-    #     its 2048 x 128 share be resident at once (k_rollout: 189 registers, two generations of workgroups).  Per-lane state that
-    #     must survive a segment lives in LDS: the raw q rows (HBM element type), the gradient accumulator [64][D].
-    # (2) The prior.  A lane is one (trajectory, time step); its neighbours' q / qd rows sit next to its own in the raw tiles (the
-    #     two rows beyond the wavefront's block are fetched with the block), so the prior's gradient is a few FMAs per joint at the
-    #     top of the kernel: d/dqd leaves at once, d/dq seeds the accumulator the segments add their gradients to.
-    # The factor between t and t + 1 is attributed to sample t: cost[b, t] += w/2 e_t^T Q^-1 e_t.
-    par_ = [int(v) for v in kin.parent]
-    gp_ok = (not chunked) and not tmpl.virtual and walk == list(range(L)) and D <= 32 and L >= 2
-    segs: List[dict] = []
-    gp_cross_pairs = False
-    if gp_ok:
-        top = {}
-        for i in range(1, L):
-            a = i
-            while par_[a] != 0:
-                a = par_[a]
-            top[i] = a
-        roots = [i for i in range(1, L) if par_[i] == 0]
-        cand = [[i for i in range(1, L) if top[i] == c] for c in roots]
-        contiguous = all(ls == list(range(ls[0], ls[-1] + 1)) for ls in cand) and [l for ls in cand for l in ls] == list(range(1, L))
-        # each segment's object-collision links must be one consecutive run of the template (their margins are addressed by a base)
-        runs_ok = contiguous
-        if contiguous:
-            pos_in = 0
-            for ls in cand:
-                mine = [i for i in tmpl.obj_links if i in ls or (i == 0 and ls is cand[0])]
-                if tmpl.obj_links[pos_in:pos_in + len(mine)] != mine:
-                    runs_ok = False
-                pos_in += len(mine)
-        if not (contiguous and runs_ok and len(cand) > 1):
-            cand = [list(range(1, L))]
-        gp_cross_pairs = any(a != 0 and b != 0 and top[a] != top[b] for a, b in tmpl.self_pairs) if len(cand) > 1 else False
-        obj_at = 0
-        for k, ls in enumerate(cand):
-            own = set(ls) | ({0} if k == 0 else set())
-            objs = [i for i in tmpl.obj_links if i in own]
-            cols = ([0] if k == 0 else []) + ls                        # links whose positions this segment writes
-            seg = dict(links=ls, cols=cols, col0=3 * cols[0], ncol=3 * len(cols), obj=objs, obj_base=obj_at,
-                       pairs=[(pi, a, b) for pi, (a, b) in enumerate(tmpl.self_pairs)
-                              if (a in own or a == 0) and (b in own or b == 0) and (a in ls or b in ls)],
-                       tracked=[(l, tgt, rb) for l, tgt, rb in tracked if l in own],
-                       dofs=[int(kin.dof_idx[i]) for i in ls if int(kin.dof_idx[i]) >= 0])
-            obj_at += len(objs)
-            segs.append(seg)
-        if len(segs) > 1 and gp_cross_pairs:
-            pass            # served with w_self == 0 only (launch_gp returns 1 otherwise)
-    # The segment schedule is compiled only on request (TRK_GP_SCHEDULE=segments at generation time): measured on the dual Panda it
-    # is slower than the tree schedule above (DESIGN.md 6d) -- its wavefronts are VALU-bound either way, and what one resident
-    # generation gains the serial arms lose in instruction-level parallelism.
-    use_seg = gp_ok and (os.environ.get("TRK_GP_SCHEDULE", "tree") == "segments" or not gpt_ok)
-    for base_identity in ((True, False) if use_seg else ()):
-        E = Emitter()
-        kname = "k_rollout_gp_bi" if base_identity else "k_rollout_gp_bg"
-        fast_t = D > 8
-        box_t = D <= 8
-        occ = 4 if max(len(sg["dofs"]) for sg in segs) <= 8 else 2
-        E.raw(f"template <class IO{', bool FAST' if fast_t else ''}{', bool BOX' if box_t else ''}>")
-        E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, {occ}) {kname}(SpecArgs A) {{")
-        if not box_t:
-            E.raw("    constexpr bool BOX = !FAST;")
-        E.raw("    typedef typename IoTraits<IO>::Q IOQ;")
-        E.raw("    typedef typename IoTraits<IO>::G IOG;")
-        E.raw("    typedef RawRowsInFlight<D, IOQ> Raw;")
-        # LDS per wavefront: accumulator [64][D] fp32 | raw q of the later segments [64][DL] | image: first the raw q and qd tiles, then
-        # the gqd staging tile, then the positions as they will lie in HBM
-        later_dofs = [d for sg in segs[1:] for d in sg["dofs"]]
-        DL = len(later_dofs)
-        E.raw(f"    constexpr int DL = {DL};            // joints of the segments after the first: their raw q waits in LDS")
-        E.raw("    constexpr int ACC_B = TRK_WAVE * D * 4, QL_B = (TRK_WAVE * DL * (int)sizeof(IOQ) + 15) / 16 * 16;")
-        E.raw(f"    constexpr int IMG_B0 = TRK_WAVE * {3 * L} * (int)sizeof(IOQ);")
-        E.raw("    constexpr int IMG_B1 = IMG_B0 > 2 * Raw::BYTES ? IMG_B0 : 2 * Raw::BYTES;")
-        E.raw("    constexpr int IMG_B = ((IMG_B1 > ACC_B ? IMG_B1 : ACC_B) + 15) / 16 * 16;")
-        E.raw("    constexpr int WAVE_B = ACC_B + QL_B + IMG_B;")
-        E.raw("    // the sphere (and primitive) tables are shared by the workgroup's wavefronts here: one barrier at the top, 192 bytes of LDS per wavefront saved")
-        E.raw("    __shared__ __attribute__((aligned(16))) unsigned char lds_all[SPEC_WAVES * WAVE_B + TRK_LDS_SPHERES * 16 + (BOX ? TRK_LDS_PRIMS * 32 : 0)];")
-        E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
-        E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);")
-        E.raw("    unsigned char* wl = lds_all + wave * WAVE_B;")
-        E.raw("    float* acc = reinterpret_cast<float*>(wl);                      // [64][D] fp32: d cost / d q, prior first, then the segments")
-        E.raw("    IOQ* qlater = reinterpret_cast<IOQ*>(wl + ACC_B);              // [64][DL]: raw q of the later segments' joints")
-        E.raw("    IOQ* img = reinterpret_cast<IOQ*>(wl + ACC_B + QL_B);          // the output image; before that: scratch")
-        E.raw("    IOQ* qtile = img;                                               // raw q rows of the block (+ the neighbouring rows)")
-        E.raw("    float* scr = reinterpret_cast<float*>(wl + ACC_B + QL_B);")
-        E.raw("    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_WAVES * WAVE_B);")
-        E.raw("    float4* lds_prm = BOX ? lds_sph + TRK_LDS_SPHERES : nullptr;")
-        E.raw("    {")
-        E.raw("        const int tid = threadIdx.x;")
-        E.raw("        if (tid < TRK_LDS_SPHERES && tid < 2 * A.C.n_sphere_pairs) lds_sph[tid] = A.C.spheres[tid];")
-        E.raw("        if constexpr (BOX) { if (A.C.n_box_objects > 0 && A.C.n_prims <= TRK_LDS_PRIMS && tid < 2 * A.C.n_prims) lds_prm[tid] = reinterpret_cast<const float4*>(A.C.prims)[tid]; }")
-        E.raw("    }")
-        E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;")
-        E.raw("    const int64_t base = wblock * TRK_WAVE;")
-        E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
-        E.raw("    // time steps: the block starts at step t0 of its trajectory (wave-uniform), a lane sits at (t0 + lane) mod H")
-        E.raw("    const unsigned Hh = (unsigned)A.gp_H;")
-        E.raw("    const unsigned t0 = (unsigned)(base % (int64_t)A.gp_H);")
-        E.raw("    const unsigned tl = (t0 + (unsigned)lane) % Hh, t_last = (t0 + (unsigned)(TRK_WAVE - 1)) % Hh;")
-        E.raw("    const bool edge_prev = rows > 0 && t0 > 0u, edge_next = rows == TRK_WAVE && t_last + 1u < Hh && base + TRK_WAVE < A.n;")
-        E.raw("    const Raw rq = spec_raw_rows_issue<D, IOQ>(static_cast<const IOQ*>(A.q), base, rows, lane, edge_prev, edge_next);")
-        E.raw("    const Raw rv = spec_raw_rows_issue<D, IOQ>(static_cast<const IOQ*>(A.qd), base, rows, lane, edge_prev, edge_next);")
-        E.raw("    const IOQ* qb = spec_raw_rows_finish<D, IOQ>(rq, static_cast<const IOQ*>(A.q), base, rows, lane, qtile);")
-        E.raw("    const IOQ* vb = spec_raw_rows_finish<D, IOQ>(rv, static_cast<const IOQ*>(A.qd), base, rows, lane, reinterpret_cast<IOQ*>(wl + ACC_B + QL_B + Raw::BYTES));")
-        E.raw("    __syncthreads();            // the shared scene tables (and, wave-locally, the tiles) are in LDS")
-        E.raw("    float cost;")
-        E.raw("    float " + ", ".join(f"q0_{d}" for d in segs[0]["dofs"]) + ";")
-        E.raw("    {")
-        E.raw("        // ---- the prior: e_t = (p_t + dt v_t - p_t+1, v_t - v_t+1), r = Q^-1 e; this sample takes part in factors t-1 and t")
-        E.raw("        const bool on = lane < rows;")
-        E.raw("        const float mn = (on && tl + 1u < Hh) ? 1.0f : 0.0f, mp = (on && tl > 0u) ? 1.0f : 0.0f;")
-        E.raw("        const float dt = A.gp_dt, ga = A.gp_a, gb = A.gp_b, gc = A.gp_c;")
-        E.raw("        float gpv[D], gvv[D], accg = 0.0f;")
-        E.raw("#pragma unroll")
-        E.raw("        for (int d = 0; d < D; ++d) {")
-        E.raw("            const float p0 = (float)qb[lane * D + d], v0 = (float)vb[lane * D + d];")
-        E.raw("            const float pm = (float)qb[(lane - 1) * D + d], vm = (float)vb[(lane - 1) * D + d];")
-        E.raw("            const float pn = (float)qb[(lane + 1) * D + d], vn = (float)vb[(lane + 1) * D + d];")
-        E.raw("            const float ep = fmaf(dt, v0, p0) - pn, ev = v0 - vn;")
-        E.raw("            const float rp = fmaf(ga, ep, gb * ev), rv_ = fmaf(gb, ep, gc * ev);")
-        E.raw("            accg = fmaf(0.5f * mn, fmaf(ep, rp, ev * rv_), accg);")
-        E.raw("            const float em = fmaf(dt, vm, pm) - p0, fm = vm - v0;")
-        E.raw("            gpv[d] = A.gp_w * (mn * rp - mp * fmaf(ga, em, gb * fm));")
-        E.raw("            gvv[d] = A.gp_w * (mn * fmaf(dt, rp, rv_) - mp * fmaf(gb, em, gc * fm));")
-        E.raw("        }")
-        E.raw("        cost = A.gp_w * accg;")
-        E.raw("#pragma unroll")
-        E.raw("        for (int d = 0; d < D; ++d) acc[lane * D + d] = gpv[d];")
-        E.raw("        // the raw q tile is about to be overwritten: the first segment's joints go to registers, the others' wait in LDS")
-        for d in segs[0]["dofs"]:
-            E.raw(f"        q0_{d} = (float)qb[lane * D + {d}];")
-        for k_, d in enumerate(later_dofs):
-            E.raw(f"        qlater[lane * DL + {k_}] = qb[lane * D + {d}];")
-        E.raw("        // d cost / d qd is final: out through the scratch tile (its first line waits for every lane's reads of the qd rows)")
-        E.raw("        spec_store_gq<D, IOG, IoTraits<IO>::kScaled>(static_cast<IOG*>(A.gqd), base, rows, lane, scr, gvv, A.grad_scale);")
-        E.raw("    }")
-        E.raw("    unsigned passbits = 0u;")
-        E.raw(f"    const ImgFlusher<{3 * L}, IOQ> pimg = spec_make_img<{3 * L}, IOQ>(static_cast<IOQ*>(A.link_pos), base, rows, lane, img);")
-        E.raw("    spec_wave_sync();          // the gqd staging tile has been read out: the image may be written")
-        R: Dict[int, List[List[S]]] = {}
-        t: Dict[int, List[S]] = {}
-        passv: Dict[int, S] = {}
-        if base_identity:
-            R[0] = [[ONE if r == c else ZERO for c in range(3)] for r in range(3)]
-            t[0] = [ZERO, ZERO, ZERO]
-        else:
-            R[0] = [[S(1.0, f"A.base_R[{3 * r + c}]") for c in range(3)] for r in range(3)]
-            t[0] = [S(1.0, f"A.base_t[{r}]") for r in range(3)]
-        for k, sg in enumerate(segs):
-            E.raw(f"    // ================= segment {k}: links {sg['links'][0]} .. {sg['links'][-1]} =================")
-            E.raw("    {")
-            if k == 0:
-                _emit_angles(E, kin, links=sg["links"], declare_passbits=False, qexpr=lambda d: f"q0_{d}")
-            else:
-                _emit_angles(E, kin, links=sg["links"], declare_passbits=False,
-                             qexpr=lambda d: f"(float)qlater[lane * DL + {later_dofs.index(d)}]")
-            for i in sg["links"]:
-                _emit_fk_link(E, kin, i, R, t, passv, snap)
-            E.raw("    if (A.link_pos) {")
-            for i in sg["cols"]:
-                E.raw("        " + " ".join(f"pimg.put({3 * i + kk}, {E.expr(t[i][kk])});" for kk in range(3)))
-            E.raw("    }")
-            last = k == len(segs) - 1
-            # tick slots of this segment: the scene evaluation's, one after the EE term, one per two links of the reverse pass
-            n_obj = len(sg["obj"])
-            if 0 < n_obj <= LINK_OBJ_GROUP_MAX:
-                groups = [sg["obj"]]
-            elif n_obj > 0:
-                n_groups = -(-n_obj // LINK_OBJ_GROUP)
-                size = -(-n_obj // n_groups)
-                groups = [sg["obj"][g0:g0 + size] for g0 in range(0, n_obj, size)]
-            else:
-                groups = []
-            n_slots = OBJ_TICK_SLOTS * len(groups) + 1 + sum(1 for p in range(len(sg["links"]), 0, -1) if p % 2 == 0)
-            if last:
-                E.raw("    spec_wave_sync();          // the image is complete")
-                E.raw("    spec_img_copy_slow(pimg, static_cast<IOQ*>(A.link_pos), base, rows);       // ragged last wavefront / unaligned view only")
-                E.raw(f"    constexpr int PPT = (decltype(pimg)::NP + {n_slots - 1}) / {n_slots};")
-            else:
-                E.raw("    constexpr int PPT = 0;     // the image is not complete before the last segment has staged its links")
-            E.raw("    const ImgTicks<decltype(pimg), PPT> flush{pimg};")
-            next_chunk = [0]
 
-            def tick_line(indent="    "):
-                c = next_chunk[0]
-                next_chunk[0] += 1
-                return f"{indent}flush.template chunk<{c}>();"
-            own = set(sg["links"]) | ({0} if k == 0 else set())
-            adj = sorted(set(sg["obj"]) | {a for _, a, b in sg["pairs"]} | {b for _, a, b in sg["pairs"]} | {l for l, _, _ in sg["tracked"]})
-            for i in adj:
-                E.raw(f"    float tb{i}_0 = 0.0f, tb{i}_1 = 0.0f, tb{i}_2 = 0.0f;")
-            fast_arg = f", decltype(ticks), {'FAST' if fast_t else 'false'}, BOX"
-            g_at = 0
-            for grp in groups:
-                n = len(grp)
-                E.raw("    {")
-                for kk, nm in enumerate("xyz"):
-                    E.raw(f"        const float p{nm}[{n}] = {{{', '.join(E.expr(t[i][kk]) for i in grp)}}};")
-                E.raw(f"        float gx[{n}], gy[{n}], gz[{n}];")
-                E.raw("#pragma unroll")
-                E.raw(f"        for (int l = 0; l < {n}; ++l) {{ gx[l] = 0.0f; gy[l] = 0.0f; gz[l] = 0.0f; }}")
-                c0 = next_chunk[0]
-                next_chunk[0] += OBJ_TICK_SLOTS
-                E.raw(f"        const TickFrom<decltype(flush), {c0}> ticks{{flush}};")
-                E.raw(f"        if (A.w.w_obj != 0.0f) cost += spec_objects_cost<{n}{fast_arg}>(A.C, A.w.w_obj, px, py, pz, gx, gy, gz, ticks, lds_sph, {sg['obj_base'] + g_at}, lds_prm);")
-                E.raw(f"        else flush.template range<{c0}, {c0 + OBJ_TICK_SLOTS}>();")
-                E.raw(f"        if (A.w.w_ws != 0.0f && A.C.has_ws) cost += spec_ws_cost<{n}>(A.C, A.w.w_ws, px, py, pz, gx, gy, gz, {sg['obj_base'] + g_at});")
-                for j, i in enumerate(grp):
-                    E.raw(f"        tb{i}_0 += gx[{j}]; tb{i}_1 += gy[{j}]; tb{i}_2 += gz[{j}];")
-                E.raw("    }")
-                g_at += n
-            if sg["pairs"]:
-                E.raw("    if (A.w.w_self != 0.0f) {")
-                for pi, a, b in sg["pairs"]:
-                    pa = ", ".join(E.expr(t[a][kk]) for kk in range(3))
-                    pb = ", ".join(E.expr(t[b][kk]) for kk in range(3))
-                    E.raw(f"        cost += spec_self_pair(A.w.w_self, cptr(A.C.self_margin)[{pi}], {pa}, {pb}, "
-                          f"tb{a}_0, tb{a}_1, tb{a}_2, tb{b}_0, tb{b}_1, tb{b}_2, (A.C.clamp_fields & TRK_FIELD_SELF) != 0);")
-                E.raw("    }")
-            for ee, tgt, rb in sg["tracked"]:
-                E.raw(f"    float {rb}[9] = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}};")
-            if sg["tracked"]:
-                E.raw("    if (A.w.w_ee != 0.0f) {")
-                for ee, tgt, rb in sg["tracked"]:
-                    E.raw("      {")
-                    E.raw(f"        const float eR[9] = {{{', '.join(E.expr(R[ee][r][c]) for r in range(3) for c in range(3))}}};")
-                    E.raw(f"        const float et[3] = {{{', '.join(E.expr(t[ee][kk]) for kk in range(3))}}};")
-                    E.raw("        float gR[9], gt[3];")
-                    E.raw(f"        const float ce = ee_cost_eval(eR, et, {tgt}, A.C.ee_w_pos, A.C.ee_w_rot, A.C.ee_square, gR, gt);")
-                    E.raw("        cost = fmaf(A.w.w_ee, ce, cost);")
-                    E.raw("#pragma unroll")
-                    E.raw(f"        for (int k = 0; k < 9; ++k) {rb}[k] = A.w.w_ee * gR[k];")
-                    E.raw(f"        tb{ee}_0 = fmaf(A.w.w_ee, gt[0], tb{ee}_0); tb{ee}_1 = fmaf(A.w.w_ee, gt[1], tb{ee}_1); "
-                          f"tb{ee}_2 = fmaf(A.w.w_ee, gt[2], tb{ee}_2);")
-                    E.raw("      }")
-                E.raw("    }")
-            E.raw(tick_line())
-            real = [i for i in adj if i != 0]
-            gq_expr = _emit_reverse_links(E, kin, R, t, {i: [f"tb{i}_{kk}" for kk in range(3)] for i in real},
-                                          {l: rb for l, _, rb in sg["tracked"]}, masked, tick=tick_line, order=[0] + sg["links"],
-                                          n_links=len(sg["links"]) + 1)
-            assert next_chunk[0] <= n_slots, (next_chunk[0], n_slots)
-            E.raw(f"    flush.template rest<{next_chunk[0]}>();")
-            for d in sg["dofs"]:
-                ex = E.expr(gq_expr.get(d, ZERO))
-                if ex != "0.0f":
-                    E.raw(f"    acc[lane * D + {d}] += {ex};")
-            E.raw("    }")
-            # poses of this segment are dead from here on: drop them so that nothing downstream can reference them by accident
-            for i in sg["links"]:
-                R.pop(i, None); t.pop(i, None)
-        E.raw("    if (lane < rows) store_wt_f1(A.cost + base + lane, cost);")
-        E.raw("    if (A.cost_sum) {")
-        E.raw("        const float tot = spec_wave_sum(lane < rows ? cost : 0.0f);")
-        E.raw("        if (lane == 0 && rows > 0) store_wt_f1(A.cost_sum + wblock, tot);")
-        E.raw("    }")
-        E.raw("    spec_store_acc_tile<D, IOG, IoTraits<IO>::kScaled>(static_cast<IOG*>(A.gq), base, rows, lane, acc, A.grad_scale);")
-        E.raw("}")
-        out.extend(E.lines)
-        out.append("")
-
-    # ---- explicit reverse mode of the link positions (trk_fk_positions_backward with all links selected):
-    # FK again (cheaper than storing poses), the adjoint rows [64][3L] come in through the LDS transpose, reverse pass.
-    # Many links (the ring-staged units): the whole-row tile is 92 KB per workgroup for 30 links -- one wavefront per SIMD -- and 3L adjoint
-    # registers per lane.  Those units take the attached-point generator's kernel instead (columns = the links, chunked loads, prefix-sum
-    # gradients; needs the file order to be the pre-order walk): UR10 + Allegro 34.1 -> 29.8 us, iiwa7 + Allegro 33.4 -> 30.9, Shadow hand 32.6 -> 30.4
-    # (profiles/r05_bench_positions.txt).
-    posbwd_chunked = chunked and [int(v) for v in kin.order] == list(range(L)) and os.environ.get("TRK_EXP_POSBWD_TILE", "0") == "0"
-    if posbwd_chunked:
-        out.extend(_chunked_posbwd_lines(kin, list(range(L)), np.zeros((L, 3), np.float32), snap, w_expr=str(3 * L)))
-    for base_identity in (() if posbwd_chunked else (True, False)):
-        E = Emitter()
-        kname = "k_posbwd_bi" if base_identity else "k_posbwd_bg"
-        E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, {4 if D <= 8 else 2}) {kname}(SpecArgs A) {{")
-        E.raw(f"    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * {max(3 * L, D)}];")
-        E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
-        E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);")
-        E.raw(f"    float* lds = lds_all + wave * (TRK_WAVE * {max(3 * L, D)});")
-        E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;")
-        E.raw("    const int64_t base = wblock * TRK_WAVE;")
-        E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
-        E.raw("    float q[D];")
-        E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
-        early = 3 * L <= 48        # the loads in flight cost 3L/4 registers per lane: only for the small arms
-        if early:
-            E.raw(f"    // the position adjoints are needed only by the reverse pass: their loads are in flight during the forward pass")
-            E.raw(f"    const RowsInFlight<{3 * L}> gp_rows = spec_load_rows_issue<{3 * L}>(static_cast<const float*>(A.link_pos), base, rows, lane);")
-        R = {}; t = {}; passv = {}
-        if base_identity:
-            R[0] = [[ONE if r == c else ZERO for c in range(3)] for r in range(3)]
-            t[0] = [ZERO, ZERO, ZERO]
-        else:
-            R[0] = [[S(1.0, f"A.base_R[{3 * r + c}]") for c in range(3)] for r in range(3)]
-            t[0] = [S(1.0, f"A.base_t[{r}]") for r in range(3)]
-        _emit_angles(E, kin)
-        for p in range(1, L):
-            _emit_fk_link(E, kin, int(kin.order[p]), R, t, passv, snap)
-        E.raw(f"    float gp[{3 * L}];                       // this sample's position adjoints, link-major")
-        if early:
-            E.raw(f"    spec_load_rows_finish<{3 * L}>(gp_rows, static_cast<const float*>(A.link_pos), base, rows, lane, lds, gp);")
-        else:
-            E.raw(f"    spec_load_q<{3 * L}>(static_cast<const float*>(A.link_pos), base, rows, lane, lds, gp);")
-        gq_expr = _emit_reverse_links(E, kin, R, t, {i: [f"gp[{3 * i + k}]" for k in range(3)] for i in range(1, L)}, {}, masked)
-        E.raw(f"    const float gv[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
-        E.raw("    spec_store_gq<D>(static_cast<float*>(A.gq), base, rows, lane, lds, gv);")
-        E.raw("}")
-        out.extend(E.lines)
-        out.append("")
-
-    # ---- boolean mode (trk_rollout_collision): FK + the OR of the selected fields' "signed distance < margin" tests, one byte
-    # per sample out.  Its own kernel: inside k_rollout the extra SpecArgs fields and the cold path cost the hot path
-    # ~100 SGPR spill moves (v_writelane / v_readlane) per wavefront.
-    for base_identity in (True, False):
-        E = Emitter()
-        kname = "k_coll_bi" if base_identity else "k_coll_bg"
-        E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, {4 if D <= 8 else 2}) {kname}(SpecArgs A) {{")
-        E.raw(f"    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * D + SPEC_WAVES * TRK_LDS_SPHERES * 4];")
-        E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
-        E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);")
-        E.raw("    float* lds = lds_all + wave * (TRK_WAVE * D);")
-        E.raw("    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * D) + wave * TRK_LDS_SPHERES;")
-        E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);   // waited for together with the rows below")
-        E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;")
-        E.raw("    const int64_t base = wblock * TRK_WAVE;")
-        E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
-        E.raw("    float q[D];")
-        E.raw("    unsigned via_slot = 0u;")
-        E.raw("    int64_t via_traj0 = 0;")
-        E.raw("    bool via_outside = false;")
-        E.raw("    if (A.via_n > 0) spec_load_q_via<D>(A, base, rows, lane, q, via_slot, via_traj0, via_outside);     // trajectory validation: interpolate the via points here")
-        E.raw("    else spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
-        E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
-        R = {}; t = {}; passv = {}
-        if base_identity:
-            R[0] = [[ONE if r == c else ZERO for c in range(3)] for r in range(3)]
-            t[0] = [ZERO, ZERO, ZERO]
-        else:
-            R[0] = [[S(1.0, f"A.base_R[{3 * r + c}]") for c in range(3)] for r in range(3)]
-            t[0] = [S(1.0, f"A.base_t[{r}]") for r in range(3)]
-        _emit_angles(E, kin)
-        for p in range(1, L):
-            _emit_fk_link(E, kin, int(kin.order[p]), R, t, passv, snap)
-        emit_boolean_fields(E, t)
-        E.raw("    if (lane < rows) A.coll_out[base + lane] = hit ? 1 : 0;")
-        E.raw("    if (A.via_n > 0 && A.via_partial) spec_via_partial_flags(A, wblock, via_traj0, via_slot, hit, via_outside, lane < rows, lane);     // wave-uniform")
-        E.raw("}")
-        out.extend(E.lines)
-        out.append("")
-
-    # ---- FK matrices of ALL links (trk_fk_forward with every link selected = compute_forward_kinematics_all_links,
-    # robot_tree.py:267-301): the same stateless walk as the fused rollout; a link's 4x4 leaves as soon as it exists -- each lane
-    # puts its 16 floats into a [64][17] LDS tile, the wave writes them as 8-byte write-through vectors, eight consecutive lanes
-    # completing one sample's 64 bytes (two whole sectors).  The kernel is a pure write stream (704 B per sample for Panda).
-    # Two links per flush (128 bytes per sample) when rows are whole 128-byte lines (L even) and the walk is the file order:
-    # full-line writes matter once the output exceeds the 256 MB Infinity Cache (UR10+Allegro, 526 MB: 122 - 154 -> 101 us);
-    # with odd L every other row starts mid-line and the pairs straddle lines anyway (Panda, dual Panda: no difference).
-    FKH_PAIR = L % 2 == 0 and [int(v) for v in kin.order] == list(range(L))
-    FKH_LS = 33 if FKH_PAIR else 17
-    for base_identity in (True, False):
-        E = Emitter()
-        kname = "k_fkh_bi" if base_identity else "k_fkh_bg"
-        E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, {4 if D <= 16 else 2}) {kname}(SpecArgs A) {{")
-        E.raw(f"    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * {max(FKH_LS, D)}];")
-        E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
-        E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);")
-        E.raw(f"    float* lds = lds_all + wave * (TRK_WAVE * {max(FKH_LS, D)});")
-        E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;")
-        E.raw("    const int64_t base = wblock * TRK_WAVE;")
-        E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
-        E.raw("    float q[D];")
-        E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
-        R = {}; t = {}; passv = {}
-        if base_identity:
-            R[0] = [[ONE if r == c else ZERO for c in range(3)] for r in range(3)]
-            t[0] = [ZERO, ZERO, ZERO]
-        else:
-            R[0] = [[S(1.0, f"A.base_R[{3 * r + c}]") for c in range(3)] for r in range(3)]
-            t[0] = [S(1.0, f"A.base_t[{r}]") for r in range(3)]
-        _emit_angles(E, kin)
-        E.raw(f"    float* hrow = lds + lane * {FKH_LS};")
-
-        def emit_h(i, p):
-            vals = []
-            for r in range(3):
-                vals += [E.expr(R[i][r][c]) for c in range(3)] + [E.expr(t[i][r])]
-            vals += ["0.0f", "0.0f", "0.0f", "1.0f"]
-            if FKH_PAIR:
-                off = 16 * (p % 2)
-                E.raw("    " + " ".join(f"hrow[{off + k}] = {v};" for k, v in enumerate(vals)))
-                if p % 2 == 1:
-                    E.raw(f"    spec_flush_chunk<{16 * L}, 32, {FKH_LS}, 2>(A.fk_H, base, {16 * (i - 1)}, rows, lane, lds);")
-                elif p == L - 1:
-                    E.raw(f"    spec_flush_chunk<{16 * L}, 16, {FKH_LS}, 2>(A.fk_H, base, {16 * i}, rows, lane, lds);")
-            else:
-                E.raw("    " + " ".join(f"hrow[{k}] = {v};" for k, v in enumerate(vals)))
-                E.raw(f"    spec_flush_chunk<{16 * L}, 16, {FKH_LS}, 2>(A.fk_H, base, {16 * i}, rows, lane, lds);")
-        emit_h(int(kin.order[0]), 0)
-        for p in range(1, L):
-            i = int(kin.order[p])
-            _emit_fk_link(E, kin, i, R, t, passv, snap)
-            emit_h(i, p)
-        E.raw("}")
-        out.extend(E.lines)
-        out.append("")
-        # (Round 5: a copy of this kernel with NON-TEMPORAL stores for outputs beyond the Infinity Cache -- what pays for the fused rollout's
-        # contiguous 1 KiB chunks, trk_spec_common.h F32Stream -- was built and measured: SLOWER for these 8-byte pieces, dual Panda 90.3 ->
-        # 116.1 us, UR10 + Allegro 96.9 -> 101.5 us, Panda (in cache) 27.4 -> 47.2 us; profiles/r05_bench_fkh_stream.txt.  Dropped.)
-
-    # ---- the collision fields on GIVEN link positions (trk_cost_fields: EmbodimentDistanceFieldBase.compute_embodiment_cost,
-    # distance_fields.py:107-124, for the fields selected by the caller): positions in through the LDS transpose, the fused
-    # kernel's objective code on them, cost + position gradient out.  No kinematics: the unit is found by its collision
-    # template (columns = all links of the robot), so the reference-style call `field.compute_cost(q, link_pos)` runs the same
-    # arithmetic as the fused rollout.
-    fields_ok = 3 * L <= 96 and (NL > 0 or bool(tmpl.self_pairs))
-    if fields_ok:
-        E = Emitter()
-        E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, {4 if 3 * L <= 48 else 2}) k_fields(SpecArgs A) {{")
-        E.raw(f"    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * {3 * L} + SPEC_WAVES * TRK_LDS_SPHERES * 4];")
-        E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
-        E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);")
-        E.raw(f"    float* lds = lds_all + wave * (TRK_WAVE * {3 * L});")
-        E.raw(f"    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * {3 * L}) + wave * TRK_LDS_SPHERES;")
-        E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);   // waited for together with the rows below")
-        E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;")
-        E.raw("    const int64_t base = wblock * TRK_WAVE;")
-        E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
-        E.raw(f"    float p[{3 * L}];")
-        E.raw(f"    spec_load_q<{3 * L}>(A.fld_pos, base, rows, lane, lds, p);")
-        E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
-        E.raw("    const NoFlush flush;")
-        tp = {i: [S(1.0, f"p[{3 * i + k}]") for k in range(3)] for i in range(L)}
-        emit_collision_objectives(E, tp, [0])
-        E.raw("    if (lane < rows) store_wt_f1(A.cost + base + lane, cost);")
-        E.raw("    if (A.fld_g) {")
-        E.raw("        const float sc = (A.fld_gcost && lane < rows) ? A.fld_gcost[base + lane] : 1.0f;")
-        gl = []
-        for i in range(L):
-            gl += [f"sc * tb{i}_{k}" if i in real_adj else "0.0f" for k in range(3)]
-        E.raw(f"        const float gv[{3 * L}] = {{{', '.join(gl)}}};")
-        E.raw(f"        spec_store_gq<{3 * L}>(A.fld_g, base, rows, lane, lds, gv);")
-        E.raw("    }")
-        E.raw("}")
-        out.extend(E.lines)
-        out.append("")
-
-    # ---- the same for the boolean fields (trk_collision_fields; distance_fields.py:210-215, 283-291)
-    if fields_ok:
-        E = Emitter()
-        E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, {4 if 3 * L <= 48 else 2}) k_collf(SpecArgs A) {{")
-        E.raw(f"    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * {3 * L} + SPEC_WAVES * TRK_LDS_SPHERES * 4];")
-        E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
-        E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);")
-        E.raw(f"    float* lds = lds_all + wave * (TRK_WAVE * {3 * L});")
-        E.raw(f"    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * {3 * L}) + wave * TRK_LDS_SPHERES;")
-        E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);   // waited for together with the rows below")
-        E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;")
-        E.raw("    const int64_t base = wblock * TRK_WAVE;")
-        E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
-        E.raw(f"    float p[{3 * L}];")
-        E.raw(f"    spec_load_q<{3 * L}>(A.fld_pos, base, rows, lane, lds, p);")
-        E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
-        emit_boolean_fields(E, {i: [S(1.0, f"p[{3 * i + k}]") for k in range(3)] for i in range(L)})
-        E.raw("    if (lane < rows) A.coll_out[base + lane] = hit ? 1 : 0;")
-        E.raw("}")
-        out.extend(E.lines)
-        out.append("")
-
-    # ---- FK matrix of ONE link (trk_fk_forward with a single link selected: compute_forward_kinematics(..., state_less=True)
-    # robot_tree.py:192-216, RobotPanda.get_EE_pose robot_panda.py:172-184): the stateless walk with a wave-uniform early exit
-    # after the target (a run-time argument, captured by a wave-uniform switch), 64 bytes per sample out through the LDS transpose.
-    for base_identity in (True, False):
-        E = Emitter()
-        kname = "k_fk1_bi" if base_identity else "k_fk1_bg"
-        E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, {4 if D <= 16 else 2}) {kname}(SpecArgs A) {{")
-        E.raw(f"    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * {max(16, D)}];")
-        E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
-        E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);")
-        E.raw(f"    float* lds = lds_all + wave * (TRK_WAVE * {max(16, D)});")
-        E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;")
-        E.raw("    const int64_t base = wblock * TRK_WAVE;")
-        E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
-        E.raw("    float q[D];")
-        E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
-        R = {}; t = {}; passv = {}
-        if base_identity:
-            R[0] = [[ONE if r == c else ZERO for c in range(3)] for r in range(3)]
-            t[0] = [ZERO, ZERO, ZERO]
-        else:
-            R[0] = [[S(1.0, f"A.base_R[{3 * r + c}]") for c in range(3)] for r in range(3)]
-            t[0] = [S(1.0, f"A.base_t[{r}]") for r in range(3)]
-        _emit_angles(E, kin)
-        E.raw("    float hv[16] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f};")
-
-        def capture_h(i):
-            body = "; ".join(f"hv[{4 * r + c}] = {E.expr(R[i][r][c])}" for r in range(3) for c in range(3))
-            body += "; " + "; ".join(f"hv[{4 * r + 3}] = {E.expr(t[i][r])}" for r in range(3))
-            E.raw(f"    if (A.jac_link == {i}) {{ {body}; }}       // wave-uniform")
-        capture_h(int(kin.order[0]))
-        E.raw("    do {                               // the walk stops after the target's pre-order position")
-        for p in range(1, L):
-            i = int(kin.order[p])
-            E.raw(f"    if (A.jac_p_end <= {p}) break;")
-            _emit_fk_link(E, kin, i, R, t, passv, snap)
-            capture_h(i)
-        E.raw("    } while (0);")
-        E.raw("    spec_store_gq<16>(A.fk_H, base, rows, lane, lds, hv);")
-        E.raw("}")
-        out.extend(E.lines)
-        out.append("")
-
-    # ---- reverse mode of the all-links FK matrices (trk_fk_backward with every link selected): FK again, then the reverse
-    # walk; a link's adjoint (its 4x4 block of gH, bottom row ignored) comes in through an LDS transpose right before the walk
-    # consumes it, so only one block per lane is live.
-    FKB_LS = 18
-    # every link's rotation stays live until the reverse walk has consumed it: beyond ~24 links the kernel spills (UR10+Allegro:
-    # 252 registers, 347 us against the table-driven kernel's 253) -- such robots keep the table-driven reverse mode
-    fkhbwd_ok = L <= 24
-    for base_identity in ((True, False) if fkhbwd_ok else ()):
-        E = Emitter()
-        kname = "k_fkhbwd_bi" if base_identity else "k_fkhbwd_bg"
-        # two wavefronts per SIMD: the rotation adjoint of EVERY link needs that link's rotation, so all of them stay live (Panda
-        # at four per SIMD: 63 registers spilled, and on this ISA a spill reload waits for every outstanding load)
-        E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, 2) {kname}(SpecArgs A) {{")
-        E.raw(f"    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * {max(FKB_LS, D)}];")
-        E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
-        E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);")
-        E.raw(f"    float* lds = lds_all + wave * (TRK_WAVE * {max(FKB_LS, D)});")
-        E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;")
-        E.raw("    const int64_t base = wblock * TRK_WAVE;")
-        E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
-        E.raw("    float q[D];")
-        E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
-        R = {}; t = {}; passv = {}
-        if base_identity:
-            R[0] = [[ONE if r == c else ZERO for c in range(3)] for r in range(3)]
-            t[0] = [ZERO, ZERO, ZERO]
-        else:
-            R[0] = [[S(1.0, f"A.base_R[{3 * r + c}]") for c in range(3)] for r in range(3)]
-            t[0] = [S(1.0, f"A.base_t[{r}]") for r in range(3)]
-        _emit_angles(E, kin)
-        for p in range(1, L):
-            _emit_fk_link(E, kin, int(kin.order[p]), R, t, passv, snap)
-        E.raw(f"    const float* gh = lds + lane * {FKB_LS};")
-
-        def fetch_adjoint(i):
-            E.raw(f"    spec_load_chunk<{16 * L}, 16, {FKB_LS}, 2>(A.fk_H, base, {16 * i}, rows, lane, lds);")
-            E.raw(f"    const float gR{i}[9] = {{gh[0], gh[1], gh[2], gh[4], gh[5], gh[6], gh[8], gh[9], gh[10]}};")
-            E.raw(f"    const float gt{i}_0 = gh[3], gt{i}_1 = gh[7], gt{i}_2 = gh[11];")
-        gq_expr = _emit_reverse_links(E, kin, R, t, {i: [f"gt{i}_{k}" for k in range(3)] for i in range(1, L)},
-                                      {i: f"gR{i}" for i in range(1, L)}, masked, pre_link=fetch_adjoint)
-        E.raw(f"    const float gv[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
-        E.raw("    spec_store_gq<D>(static_cast<float*>(A.gq), base, rows, lane, lds, gv);")
-        E.raw("}")
-        out.extend(E.lines)
-        out.append("")
-
-    # ---- Adam IK on the unit's tracked link (trk_ik_steps; robot_tree.py:345-442): the configurations AND the optimiser state
-    # live in registers for all iterations of a launch -- FK, SE3 distance, reverse pass, joint-limit hinge, termination test and
-    # the Adam update per lane, nothing but the result goes back to memory.  (The table-driven kernel keeps them in LDS and walks
-    # the tree from tables: ~9 us per iteration whatever the batch.)
-    # q, m and v of every DOF stay in registers across the loop: beyond ~9 DOF the kernel spills (dual Panda, 14 DOF: 10 registers;
-    # UR10+Allegro, 22 DOF: 377) and those robots keep the table-driven kernel
-    ik_ok = tmpl.ee_link >= 0 and D <= 9
-    for base_identity in ((True, False) if ik_ok else ()):
-        E = Emitter()
-        kname = "k_ik_bi" if base_identity else "k_ik_bg"
-        E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, {4 if D <= 8 else 2}) {kname}(IkArgs A) {{")
-        E.raw("    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * D];")
-        E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
-        E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);")
-        E.raw("    float* lds = lds_all + wave * (TRK_WAVE * D);")
-        E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;")
-        E.raw("    const int64_t base = wblock * TRK_WAVE;")
-        E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
-        E.raw("    float q[D], am[D], av[D];")
-        E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
-        E.raw("    if (A.lr > 0.0f) {")
-        E.raw("        spec_load_q<D>(static_cast<const float*>(A.adam_m), base, rows, lane, lds, am);")
-        E.raw("        spec_load_q<D>(static_cast<const float*>(A.adam_v), base, rows, lane, lds, av);")
-        E.raw("    } else {")
-        E.raw("#pragma unroll")
-        E.raw("        for (int d = 0; d < D; ++d) { am[d] = 0.0f; av[d] = 0.0f; }")
-        E.raw("    }")
-        E.raw("    float Ht[16];")
-        E.raw("    {")
-        E.raw("        const float* tp = A.H_target + (A.per_sample ? min(base + lane, A.n - 1) * 16 : 0);")
-        E.raw("#pragma unroll")
-        E.raw("        for (int k = 0; k < 12; ++k) Ht[k] = tp[k];")
-        E.raw("    }")
-        E.raw("    float loss0 = 0.0f;")
-        E.raw("    bool ok0 = false;")
-        E.raw("    for (int it = 0; it < A.n_steps; ++it) {")
-        R = {}; t = {}; passv = {}
-        if base_identity:
-            R[0] = [[ONE if r == c else ZERO for c in range(3)] for r in range(3)]
-            t[0] = [ZERO, ZERO, ZERO]
-        else:
-            R[0] = [[S(1.0, f"A.base_R[{3 * r + c}]") for c in range(3)] for r in range(3)]
-            t[0] = [S(1.0, f"A.base_t[{r}]") for r in range(3)]
-        _emit_angles(E, kin)
-        # only the chain of the tracked link matters: the other branches' poses would be dead code
-        chain, a = set(), tmpl.ee_link
-        while a >= 0:
-            chain.add(a); a = int(kin.parent[a])
-        for p in range(1, L):
-            i = int(kin.order[p])
-            if i in chain:
-                _emit_fk_link(E, kin, i, R, t, passv, snap)
-        ee = tmpl.ee_link
-        E.raw(f"    const float eR[9] = {{{', '.join(E.expr(R[ee][r][c]) for r in range(3) for c in range(3))}}};")
-        E.raw(f"    const float et[3] = {{{', '.join(E.expr(t[ee][k]) for k in range(3))}}};")
-        E.raw("    float gR[9], gt[3];")
-        E.raw("    const float err = ee_cost_eval(eR, et, Ht, 1.0f, 1.0f, 0, gR, gt);      // SE3_distance, w_pos = w_rot = 1 (robot_tree.py:386-417)")
-        order_chain = [int(kin.order[0])] + [int(kin.order[p]) for p in range(1, L) if int(kin.order[p]) in chain]
-        gq_expr = _emit_reverse_links(E, kin, R, t, {ee: ["gt[0]", "gt[1]", "gt[2]"]}, {ee: "gR"}, masked, order=order_chain,
-                                      n_links=len(order_chain))
-        E.raw(f"    const float g_[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
-        E.raw("    bool ok = err < A.se3_eps;")
-        E.raw("    float jl = 0.0f;")
-        E.raw("    const float bc1 = A.sched.bc1[it], rsqrt_bc2 = A.sched.rsqrt_bc2[it];")
-        E.raw("#pragma unroll")
-        E.raw("    for (int d = 0; d < D; ++d) {      // hinge on the (shrunk) limits, validity, torch.optim.Adam's update")
-        E.raw("        const float qv = q[d], lo = cptr(A.lower)[d], hi = cptr(A.upper)[d];")
-        E.raw("        float g = g_[d];")
-        E.raw("        if (qv < lo) { const float e = lo - qv; jl = fmaf(e, e, jl); g = fmaf(-2.0f * A.w_jl, e, g); }")
-        E.raw("        if (qv > hi) { const float e = hi - qv; jl = fmaf(e, e, jl); g = fmaf(-2.0f * A.w_jl, e, g); }")
-        E.raw("        ok = ok && (qv >= lo) && (qv <= hi);")
-        E.raw("        if (A.lr > 0.0f) {")
-        E.raw("            const float m1 = fmaf(0.9f, am[d], 0.1f * g);")
-        E.raw("            const float v1 = fmaf(0.999f, av[d], 0.001f * g * g);")
-        E.raw("            am[d] = m1; av[d] = v1;")
-        E.raw("            const float denom = fmaf(sqrtf(v1), rsqrt_bc2, 1e-8f);")
-        E.raw("            q[d] = qv - (A.lr / bc1) * (m1 / denom);")
-        E.raw("        }")
-        E.raw("    }")
-        E.raw("    if (it == 0) { loss0 = fmaf(A.w_jl, jl, err); ok0 = ok; }")
-        E.raw("    }")
-        E.raw("    if (lane < rows) {")
-        E.raw("        if (A.loss) A.loss[base + lane] = loss0;")
-        E.raw("        if (A.valid) A.valid[base + lane] = ok0 ? 1 : 0;")
-        E.raw("    }")
-        E.raw("    if (A.lr > 0.0f) {")
-        E.raw("        spec_store_gq<D>(A.q, base, rows, lane, lds, q);")
-        E.raw("        spec_store_gq<D>(A.adam_m, base, rows, lane, lds, am);")
-        E.raw("        spec_store_gq<D>(A.adam_v, base, rows, lane, lds, av);")
-        E.raw("    }")
-        E.raw("}")
-        out.extend(E.lines)
-        out.append("")
-
-    # ---- Gauss-Newton / Levenberg-Marquardt IK on the unit's tracked link (trk_ik_gn_steps; BUILD-DEFINED: the reference's loop is
-    # Adam, robot_tree.py:303-384, its geometric Jacobian :218-248 is what a Newton step is made of; oracle: orc_ik_gn_step).  Per
-    # iteration and lane: stateful FK of the links that matter, the Jacobian columns of the reference's rule, the pose residual,
-    # J^T J + lambda I and J^T r as straight-line FMAs on the symbolic columns (structural zeros fold away), a Cholesky solve in
-    # registers, the clamped step.  The Jacobian never leaves the registers -- the two-launch form (trk_fk_jacobian + trk_jtj)
-    # writes and re-reads 416 bytes per sample and iteration.
-    ikgn_cols = [i for i in range(1, L) if int(kin.dof_idx[i]) >= 0 and int(kin.jac_axis[i]) >= 0 and tmpl.ee_link >= 0 and
-                 (i - 1) <= int(kin.joint_list_idx[tmpl.ee_link])]
-    ikgn_ok = tmpl.ee_link >= 0 and D <= 9 and len(ikgn_cols) > 0
-    for base_identity in ((True, False) if ikgn_ok else ()):
-        E = Emitter()
-        kname = "k_ikgn_bi" if base_identity else "k_ikgn_bg"
-        E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, {4 if D <= 8 else 2}) {kname}(IkGnArgs A) {{")
-        E.raw("    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * D];")
-        E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
-        E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);")
-        E.raw("    float* lds = lds_all + wave * (TRK_WAVE * D);")
-        E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;")
-        E.raw("    const int64_t base = wblock * TRK_WAVE;")
-        E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
-        E.raw("    float q[D];")
-        E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
-        E.raw("    float Ht[12];")
-        E.raw("    {")
-        E.raw("        const float* tp = A.H_target + (A.per_sample ? min(base + lane, A.n - 1) * 16 : 0);")
-        E.raw("#pragma unroll")
-        E.raw("        for (int k = 0; k < 12; ++k) Ht[k] = tp[k];")
-        E.raw("    }")
-        E.raw("    float lo[D], hi[D];")
-        E.raw("#pragma unroll")
-        E.raw("    for (int d = 0; d < D; ++d) { lo[d] = cptr(A.lower)[d]; hi[d] = cptr(A.upper)[d]; }")
-        E.raw("    float err0 = 0.0f;")
-        E.raw("    bool ok0 = false;")
-        E.raw("    for (int it = 0; it < A.n_steps; ++it) {")
-        R = {}; t = {}; passv = {}
-        if base_identity:
-            R[0] = [[ONE if r == c else ZERO for c in range(3)] for r in range(3)]
-            t[0] = [ZERO, ZERO, ZERO]
-        else:
-            R[0] = [[S(1.0, f"A.base_R[{3 * r + c}]") for c in range(3)] for r in range(3)]
-            t[0] = [S(1.0, f"A.base_t[{r}]") for r in range(3)]
-        need = set()
-        for leaf in [tmpl.ee_link] + ikgn_cols:
-            a = leaf
-            while a >= 0 and a not in need:
-                need.add(a); a = int(kin.parent[a])
-        rot_dofs = []
-        for i in range(1, L):
-            jt, d = int(kin.joint_type[i]), int(kin.dof_idx[i])
-            if jt == JOINT_FIXED or i not in need:
-                continue
-            if kin.sf_clamp[i]:                  # rigid_body.py:218-224: the stateful path clamps whenever limits exist
-                E.raw(f"    const float qh{d} = __builtin_amdgcn_fmed3f(q[{d}], {flit(kin.lower[i])}, {flit(kin.upper[i])});")
-            else:
-                E.raw(f"    const float qh{d} = q[{d}];")
-            if jt in (JOINT_REVOLUTE, JOINT_CONTINUOUS):
-                rot_dofs.append(d)
-        for d in rot_dofs:
-            E.raw(f"    float sn{d}, cs{d};")
-        for a, b in zip(rot_dofs[0::2], rot_dofs[1::2]):
-            E.raw(f"    trk_sincos2(qh{a}, qh{b}, &sn{a}, &cs{a}, &sn{b}, &cs{b});")
-        if len(rot_dofs) % 2:
-            d = rot_dofs[-1]
-            E.raw(f"    trk_sincos(qh{d}, &sn{d}, &cs{d});")
-        for p in range(1, L):
-            i = int(kin.order[p])
-            if i in need:
-                _emit_fk_link(E, kin, i, R, t, passv, snap, stateful=True)
-        ee = tmpl.ee_link
-        E.raw(f"    const float eR[9] = {{{', '.join(E.expr(R[ee][r][c]) for r in range(3) for c in range(3))}}};")
-        E.raw(f"    const float et[3] = {{{', '.join(E.expr(t[ee][k]) for k in range(3))}}};")
-        # residual r = [p* - p ; rotvec(R* R^T)]
-        E.raw("    float Re[9];")
-        E.raw("#pragma unroll")
-        E.raw("    for (int a = 0; a < 3; ++a)")
-        E.raw("#pragma unroll")
-        E.raw("        for (int b = 0; b < 3; ++b) Re[3 * a + b] = fmaf(Ht[4 * a], eR[3 * b], fmaf(Ht[4 * a + 1], eR[3 * b + 1], Ht[4 * a + 2] * eR[3 * b + 2]));")
-        E.raw("    float r6[6] = {Ht[3] - et[0], Ht[7] - et[1], Ht[11] - et[2], 0.0f, 0.0f, 0.0f};")
-        E.raw("    trk_rotvec(Re, r6 + 3);")
-        E.raw("    if (it == 0) {          // what the caller learns about q as passed in: the metric of ik_termination (robot_tree.py:419-442)")
-        E.raw("        float gR_[9], gt_[3];")
-        E.raw("        err0 = ee_cost_eval(eR, et, Ht, 1.0f, 1.0f, 0, gR_, gt_);")
-        E.raw("        ok0 = err0 < A.se3_eps;")
-        E.raw("#pragma unroll")
-        E.raw("        for (int d = 0; d < D; ++d) ok0 = ok0 && (q[d] >= lo[d]) && (q[d] <= hi[d]);")
-        E.raw("    }")
-        E.raw("    const float lam = fmaf(A.lm_gain, fmaf(r6[0], r6[0], fmaf(r6[1], r6[1], fmaf(r6[2], r6[2], fmaf(r6[3], r6[3], fmaf(r6[4], r6[4], r6[5] * r6[5]))))), A.damping);")
-        # symbolic Jacobian columns: rows 0-2 linear z x (p_ee - p_joint), rows 3-5 angular z
-        col: Dict[int, List[S]] = {}
-        pe = [S(1.0, f"et[{k}]") for k in range(3)]
-        for i in ikgn_cols:
-            d, ax = int(kin.dof_idx[i]), int(kin.jac_axis[i])
-            z = [E.named(R[i][r][ax]) for r in range(3)]
-            rel = [E.named(E.lincomb([(pe[k], ONE), (t[i][k], S(-1.0))])) for k in range(3)]
-            lin = [E.named(v) for v in E.cross(z, rel)]
-            col[d] = lin + z
-        rr = [S(1.0, f"r6[{k}]") for k in range(6)]
-        for d in range(D):
-            if d in col:
-                E.raw(f"    const float g{d}_ = {E.expr(E.lincomb([(col[d][k], rr[k]) for k in range(6)]))};")
-        E.raw(f"    float An[{D * (D + 1) // 2}], gn[D];")
-        for i in range(D):
-            E.raw(f"    gn[{i}] = {f'g{i}_' if i in col else '0.0f'};")
-            for j in range(i + 1):
-                idx = i * (i + 1) // 2 + j
-                if i in col and j in col:
-                    a = E.lincomb([(col[i][k], col[j][k]) for k in range(6)])
-                    E.raw(f"    An[{idx}] = {E.expr(a)}{' + lam' if i == j else ''};")
-                else:
-                    E.raw(f"    An[{idx}] = {'lam' if i == j else '0.0f'};")
-        E.raw("    trk_chol_solve<D>(An, gn);")
-        E.raw("#pragma unroll")
-        E.raw("    for (int d = 0; d < D; ++d) q[d] = __builtin_amdgcn_fmed3f(fmaf(A.step_scale, gn[d], q[d]), lo[d], hi[d]);")
-        E.raw("    }")
-        E.raw("    if (lane < rows) {")
-        E.raw("        if (A.err) A.err[base + lane] = err0;")
-        E.raw("        if (A.valid) A.valid[base + lane] = ok0 ? 1 : 0;")
-        E.raw("    }")
-        E.raw("    spec_store_gq<D>(A.q, base, rows, lane, lds, q);")
-        E.raw("}")
-        out.extend(E.lines)
-        out.append("")
-
-    # ---- stateful FK + geometric Jacobian of ONE link (trk_fk_jacobian; robot_tree.py:136-190, 218-248): the walk unrolled
-    # with the stateful path's quirks (clamp wherever limits exist, rotation about the axis with its sign ignored); every
-    # joint that can receive a column leaves a record (z, p) in LDS, the target link (a run-time argument) is picked by a
-    # wave-uniform switch, and the read-out is the table-driven kernel's (trk_jac_readout).  One wavefront per workgroup.
-    jac_joints = [i for i in range(1, L) if int(kin.dof_idx[i]) >= 0 and int(kin.jac_axis[i]) >= 0]
-    NJ = len(jac_joints)
-    RS = (6 * NJ + 3) | 1
-    # Small arms: the lane writes its columns straight into two [64][3D] output tiles (static offsets; non-ancestor columns stay
-    # zero), finishes z x (p_link - p_joint) in place, and the read-out is a contiguous 16-byte copy.  The record scheme below
-    # needs less LDS when the target link has few ancestors among many joints (a finger tip of UR10+Allegro: 10 of 22), but its
-    # read-out maps every output element through the slot table at run time -- half of the Panda kernel's time.
-    direct = D <= JAC_DIRECT_MAX_DOFS
-    JAC_LDS = 6 * D if direct else max(RS, D)
-    for base_identity in (True, False):
-        E = Emitter()
-        kname = "k_jac_bi" if base_identity else "k_jac_bg"
-        E.raw(f"__global__ void __launch_bounds__(TRK_WAVE) {kname}(SpecArgs A) {{")
-        E.raw("    extern __shared__ __attribute__((aligned(16))) float lds[];     // 64 x max(record stride, D) floats + the slot table")
-        if not direct:
-            E.raw("    const int rstride = (6 * A.jac_n_cols + 3) | 1;       // records only for the joints that get a column")
-        E.raw("    const int lane = threadIdx.x;")
-        E.raw("    const int64_t base = (int64_t)blockIdx.x * TRK_WAVE;")
-        E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
-        E.raw("    float q[D];")
-        E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
-        R = {}; t = {}; passv = {}
-        if base_identity:
-            R[0] = [[ONE if r == c else ZERO for c in range(3)] for r in range(3)]
-            t[0] = [ZERO, ZERO, ZERO]
-        else:
-            R[0] = [[S(1.0, f"A.base_R[{3 * r + c}]") for c in range(3)] for r in range(3)]
-            t[0] = [S(1.0, f"A.base_t[{r}]") for r in range(3)]
-        rot_dofs = []
-        for i in range(1, L):
-            jt, d = int(kin.joint_type[i]), int(kin.dof_idx[i])
-            if jt == JOINT_FIXED:
-                continue
-            if kin.sf_clamp[i]:                  # rigid_body.py:218-224: clamp whenever limits exist, continuous joints too
-                E.raw(f"    const float qh{d} = __builtin_amdgcn_fmed3f(q[{d}], {flit(kin.lower[i])}, {flit(kin.upper[i])});")
-            else:
-                E.raw(f"    const float qh{d} = q[{d}];")
-            if jt in (JOINT_REVOLUTE, JOINT_CONTINUOUS):
-                rot_dofs.append(d)
-        for d in rot_dofs:
-            E.raw(f"    float sn{d}, cs{d};")
-        for a, b in zip(rot_dofs[0::2], rot_dofs[1::2]):
-            E.raw(f"    trk_sincos2(qh{a}, qh{b}, &sn{a}, &cs{a}, &sn{b}, &cs{b});")
-        if len(rot_dofs) % 2:
-            d = rot_dofs[-1]
-            E.raw(f"    trk_sincos(qh{d}, &sn{d}, &cs{d});")
-        if direct:
-            E.raw(f"    float* lin_row = lds + lane * {3 * D};                       // this sample's row of the two [64][3D] output tiles")
-            E.raw(f"    float* ang_row = lds + TRK_WAVE * {3 * D} + lane * {3 * D};")
-            E.raw("    spec_wave_sync();                  // the q transpose is done with this LDS")
-            E.raw("#pragma unroll")
-            E.raw(f"    for (int k = 0; k < {3 * D}; ++k) {{ lin_row[k] = 0.0f; ang_row[k] = 0.0f; }}")
-        else:
-            E.raw("    float* rec = lds + lane * rstride;")
-            E.raw("    spec_wave_sync();                  // the q transpose is done with this LDS")
-        E.raw("    float eR[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f}, et[3] = {0.0f, 0.0f, 0.0f};")
-
-        def capture(i):
-            rl = "; ".join(f"eR[{3 * r + c}] = {E.expr(R[i][r][c])}" for r in range(3) for c in range(3))
-            tl = "; ".join(f"et[{r}] = {E.expr(t[i][r])}" for r in range(3))
-            E.raw(f"    if (A.jac_link == {i}) {{ {rl}; {tl}; }}       // wave-uniform")
-        capture(int(kin.order[0]))
-        E.raw("    do {                               // the walk stops after the last pre-order position that matters")
-        for p in range(1, L):
-            i = int(kin.order[p])
-            E.raw(f"    if (A.jac_p_end <= {p}) break;")
-            _emit_fk_link(E, kin, i, R, t, passv, snap, stateful=True)
-            if i in jac_joints:
-                d, ax = int(kin.dof_idx[i]), int(kin.jac_axis[i])
-                vals = [E.expr(R[i][r][ax]) for r in range(3)] + [E.expr(t[i][r]) for r in range(3)]
-                if direct:      # the axis is final (angular rows); the joint origin waits in the linear rows for the link's position
-                    body = " ".join([f"ang_row[{r * D + d}] = {vals[r]};" for r in range(3)] +
-                                    [f"lin_row[{r * D + d}] = {vals[3 + r]};" for r in range(3)])
-                    E.raw(f"    if (A.jac_slot[{d}] >= 0) {{ {body} }}      // wave-uniform")
-                else:
-                    body = " ".join(f"j[{r}] = {v};" for r, v in enumerate(vals))
-                    E.raw(f"    if (A.jac_slot[{d}] >= 0) {{ float* j = rec + 6 * A.jac_slot[{d}]; {body} }}      // wave-uniform")
-            capture(i)
-        E.raw("    } while (0);")
-        if direct:
-            for i in jac_joints:
-                d = int(kin.dof_idx[i])
-                E.raw(f"    if (A.jac_slot[{d}] >= 0) {{      // wave-uniform: lin = z x (p_link - p_joint)")
-                E.raw(f"        const float z0 = ang_row[{d}], z1 = ang_row[{D + d}], z2 = ang_row[{2 * D + d}];")
-                E.raw(f"        const float r0 = et[0] - lin_row[{d}], r1 = et[1] - lin_row[{D + d}], r2 = et[2] - lin_row[{2 * D + d}];")
-                E.raw(f"        lin_row[{d}] = z1 * r2 - z2 * r1; lin_row[{D + d}] = z2 * r0 - z0 * r2; lin_row[{2 * D + d}] = z0 * r1 - z1 * r0;")
-                E.raw("    }")
-            E.raw("    spec_wave_sync();")
-            E.raw(f"    spec_store_tile<{3 * D}>(A.jac_lin, base, rows, lane, lds);")
-            E.raw(f"    spec_store_tile<{3 * D}>(A.jac_ang, base, rows, lane, lds + TRK_WAVE * {3 * D});")
-        else:
-            E.raw("    rec[6 * A.jac_n_cols] = et[0]; rec[6 * A.jac_n_cols + 1] = et[1]; rec[6 * A.jac_n_cols + 2] = et[2];")
-            E.raw(f"    int* slot = reinterpret_cast<int*>(lds + TRK_WAVE * max(rstride, {D}));")
-            for d in range(D):
-                E.raw(f"    if (lane == {d}) slot[{d}] = A.jac_slot[{d}];")
-            E.raw("    spec_wave_sync();")
-            E.raw("    trk_jac_readout(lds, slot, rstride, A.jac_n_cols, D, rows, A.jac_lin + base * 3 * D, A.jac_ang + base * 3 * D, lane);")
-        E.raw("    if (lane >= rows) return;")
-        E.raw("    const int64_t s = base + lane;")
-        E.raw("    A.jac_pos[s * 3] = et[0]; A.jac_pos[s * 3 + 1] = et[1]; A.jac_pos[s * 3 + 2] = et[2];")
-        E.raw("    float qo[4];")
-        E.raw("    frame_quat_wxyz(eR, qo);")
-        E.raw("    *reinterpret_cast<float4*>(A.jac_quat + s * 4) = make_float4(qo[0], qo[1], qo[2], qo[3]);")
-        E.raw("}")
-        out.extend(E.lines)
-        out.append("")
-
-    # ---- analytic Jacobian of EVERY link (trk_fk_analytic_jacobian; robot_tree.py:250-265): d [pos, quat_wxyz] / d q, [N, L, 7, D].  The
-    # stateless walk unrolled; a joint leaves (omega = pass * sign * its axis in the world, its origin) in registers, every link combines the
-    # joints of its chain into its 7 x D block in an LDS tile (off-chain columns are literal zeros), and the block leaves as the sample's
-    # contiguous run of 7 D floats (spec_store_link_block).  One wavefront per workgroup.  The table-driven kernel walks the same
-    # tables at one instruction per ~25 cycles (Panda 4096 x 64: 340 us for 572 MB).
-    ajac_ok = D <= 16 and L <= 24 and 7 * D * L >= RING_FLOATS and os.environ.get("TRK_EXP_NO_AJAC", "0") != "1"
-    AJ_W = 7 * D * L                        # floats of a sample's output row
-    arp = ring_plan(AJ_W) if ajac_ok else None
-    if ajac_ok:
-        out.append("#ifndef __HIPCC_RTC__          // (linked / dlopen-ed units only: a code-object unit keeps the table-driven kernel)")
-        dof_link = {int(kin.dof_idx[i]): i for i in range(1, L) if int(kin.dof_idx[i]) >= 0}
-        chain: Dict[int, set] = {}
-        for i in range(L):
-            c_, a_ = set(), i
-            while a_ > 0:
-                c_.add(a_); a_ = int(kin.parent[a_])
-            chain[i] = c_
-        aring_t = f"RingFlusher<{arp.W}, {arp.V}, {'true' if arp.aligned else 'false'}, float>"
-        for base_identity in (True, False):
-            E = Emitter()
-            kname = "k_ajac_bi" if base_identity else "k_ajac_bg"
-            E.raw(f"__global__ void __launch_bounds__(TRK_WAVE) {kname}(SpecArgs A) {{")
-            E.raw(f"    extern __shared__ __attribute__((aligned(16))) float lds[];     // the wavefront's ring [64][{arp.stride}] (first: the q transpose)")
-            E.raw("    const int lane = threadIdx.x;")
-            E.raw("    const int64_t base = (int64_t)blockIdx.x * TRK_WAVE;")
-            E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
-            E.raw("    float q[D];")
-            E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
-            _emit_angles(E, kin)
-            E.raw(f"    static_assert({aring_t}::LS == {arp.stride} && {aring_t}::HX == {arp.hx} && {aring_t}::NFULL == {arp.n_full} && {aring_t}::NP == {arp.pieces}, "
-                  '"generator and RingFlusher disagree on the ring geometry");')
-            E.raw("    spec_wave_sync();                  // the q transpose is done with this LDS")
-            # (write-through pieces.  Non-temporal ones were measured for outputs beyond the Infinity Cache: 2.4 -> 1.8 TB/s -- an 8-byte piece
-            # is not the 1 KiB contiguous store that policy pays for)
-            E.raw(f"    const {aring_t} ring = spec_make_ring<{arp.W}, {arp.V}, {'true' if arp.aligned else 'false'}, float>(A.jac_lin, base, rows, lane, lds);")
-            E.raw("    float* const prow = ring.row();        // this lane's ring; prow_a: the same, shifted by the lane's head")
-            E.raw("    float* const prow_a = ring.row_a();")
-            R = {}; t = {}; passv = {}
-            if base_identity:
-                R[0] = [[ONE if r == c else ZERO for c in range(3)] for r in range(3)]
-                t[0] = [ZERO, ZERO, ZERO]
-            else:
-                R[0] = [[S(1.0, f"A.base_R[{3 * r + c}]") for c in range(3)] for r in range(3)]
-                t[0] = [S(1.0, f"A.base_t[{r}]") for r in range(3)]
-            ready_at: Dict[int, List[int]] = {}
-            for c in range(arp.n_full + 1):
-                ready_at.setdefault(arp.ready_float(c), []).append(c)
-
-            def stage_float(f, x):
-                """float f of the sample's row into the ring; a chunk that is complete leaves at once (its 16 pieces back to back: the next
-                floats overwrite the OTHER half of the ring, nothing waits for these stores)"""
-                if arp.regular(f):
-                    E.raw(f"        prow_a[{f & 63}] = {x};")
-                else:
-                    E.raw(f"        prow[ring.slot({f})] = {x};")
-                if f < arp.hx:
-                    E.raw(f"        prow[{64 + f}] = {x};")
-                for c in ready_at.get(f, []):
-                    E.raw(f"        ring.template done<{c}>();")
-                    for kk in range(arp.pieces):
-                        E.raw(f"        ring.template piece<{c}, {kk}>();")
-
-            def emit_block(i):
-                E.raw(f"    {{   // link {i}: its 7 x D block of the Jacobian")
-                on = []
-                for d in range(D):
-                    jd = dof_link[d]
-                    if jd in chain[i] and (int(kin.joint_type[jd]) == JOINT_PRISMATIC or float(kin.rot_sign[jd]) != 0.0):
-                        on.append(d)
-                if any(int(kin.joint_type[dof_link[d]]) != JOINT_PRISMATIC for d in on):
-                    E.raw("        const float Ri[9] = {" + ", ".join(E.expr(R[i][r][c]) for r in range(3) for c in range(3)) + "};")
-                    E.raw("        const QuatSel qs = quat_sel(Ri);")
-                tt = ", ".join(E.expr(t[i][r]) for r in range(3))
-                for d in on:
-                    if int(kin.joint_type[dof_link[d]]) == JOINT_PRISMATIC:
-                        E.raw(f"        const float c{d}[7] = {{aw{d}_0, aw{d}_1, aw{d}_2, 0.0f, 0.0f, 0.0f, 0.0f}};")
-                    else:
-                        E.raw(f"        float c{d}[7];")
-                        E.raw(f"        spec_ajac_col_revolute(c{d}, Ri, qs, {tt}, aw{d}_0, aw{d}_1, aw{d}_2, ap{d}_0, ap{d}_1, ap{d}_2);")
-                for k in range(7):
-                    for d in range(D):
-                        stage_float(7 * D * i + k * D + d, f"c{d}[{k}]" if d in on else "0.0f")
-                E.raw("    }")
-            # the row is staged in MEMORY order (link index), the walk visits the links in pre-order: a link's block is emitted when every
-            # link in front of it (by index) has been walked
-            walked = {int(kin.order[0])}
-            next_block = [0]
-
-            def flush_blocks():
-                while next_block[0] < L and next_block[0] in walked:
-                    emit_block(next_block[0])
-                    next_block[0] += 1
-            flush_blocks()
-            for p in range(1, L):
-                i = int(kin.order[p])
-                _emit_fk_link(E, kin, i, R, t, passv, snap)
-                jt, d = int(kin.joint_type[i]), int(kin.dof_idx[i])
-                if jt != JOINT_FIXED and d >= 0:
-                    mask = (lambda e, d=d: f"((passbits & {1 << d}u) ? {e} : 0.0f)") if kin.clamp[i] else (lambda e: e)
-                    if jt == JOINT_PRISMATIC:
-                        par = int(kin.parent[i])
-                        dirw = [E.lincomb([(R[par][r][k], S(float(kin.axis[i][k]))) for k in range(3)]) for r in range(3)]
-                        for k in range(3):
-                            E.raw(f"    const float aw{d}_{k} = {mask(E.expr(dirw[k]))};")
-                    elif float(kin.rot_sign[i]) != 0.0:
-                        sg, ax = float(kin.rot_sign[i]), int(kin.rot_axis[i])
-                        for k in range(3):
-                            z = R[i][k][ax]
-                            E.raw(f"    const float aw{d}_{k} = {mask(E.expr(S(z.c * sg, z.n)))};")
-                            E.raw(f"    const float ap{d}_{k} = {E.expr(t[i][k])};")
-                walked.add(i)
-                flush_blocks()
-            assert next_block[0] == L
-            E.raw("}")                      # (the tail chunk -- what is left of every row and the head of the next one -- left with the last float)
-            out.extend(E.lines)
-            out.append("")
-        out.append("#endif      // !__HIPCC_RTC__")
-
-    out.append("#ifndef __HIPCC_RTC__          // the unit's host half: launchers and its registry entry")
-    obj = ", ".join(str(i) for i in tmpl.obj_links) or "0"
-    pairs = ", ".join(f"{a}, {b}" for a, b in tmpl.self_pairs) or "0"
-    out.append(f"static const int32_t kObjLinks[] = {{{obj}}};")
-    out.append(f"static const int32_t kSelfPairs[] = {{{pairs}}};")
-    vsrc = ", ".join(f"{r[0]}, {r[1]}" for r in tmpl.virtual) or "0"
-    vw = ", ".join(f"{flit(float(np.float32(r[2])))}, {flit(float(np.float32(r[3])))}" for r in tmpl.virtual) or "0.0f"
-    out.append(f"static const int32_t kVirtualSrc[] = {{{vsrc}}};")
-    out.append(f"static const float kVirtualW[] = {{{vw}}};")
-    out.append("static void launch(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {")
-    out.append("    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);")
-    # every (IO, [POS,] [FAST,] [BOX,] base) instantiation: one generic lambda per compile-time switch, in template-parameter order
-    switches = []
-    if chunked:
-        switches.append("a.link_pos != nullptr")
-    if D > 8:
-        switches.append("scene_is_fast(a.C)")
+def _root_pose(base_identity: bool):
+    """(R, t, passv) of a walk that starts at link 0: the identity, or the run-time base pose"""
+    if base_identity:
+        R = {0: [[ONE if r == c else ZERO for c in range(3)] for r in range(3)]}
+        t = {0: [ZERO, ZERO, ZERO]}
     else:
-        switches.append("scene_is_general(a.C)")     # BOX: box objects ((value, index) primitive loop over the LDS table) and / or a voxel grid
+        R = {0: [[S(1.0, f"A.base_R[{3 * r + c}]") for c in range(3)] for r in range(3)]}
+        t = {0: [S(1.0, f"A.base_t[{r}]") for r in range(3)]}
+    return R, t, {}
+
+
+def _kernel_head(E: Emitter, kname: str, occupancy, lds_lane, args: str = "SpecArgs", spheres: bool = False) -> None:
+    """signature, the static LDS (lds_lane floats per lane; spheres: plus the wavefronts' sphere tables) and the wavefront's rows"""
+    E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, {occupancy}) {kname}({args} A) {{")
+    E.raw(f"    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * {lds_lane}{' + SPEC_WAVES * TRK_LDS_SPHERES * 4' if spheres else ''}];")
+    E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
+    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);")
+    E.raw(f"    float* lds = lds_all + wave * (TRK_WAVE * {lds_lane});")
+    if spheres:
+        E.raw(f"    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * {lds_lane}) + wave * TRK_LDS_SPHERES;")
+        E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);   // waited for together with the rows below")
+    E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;")
+    E.raw("    const int64_t base = wblock * TRK_WAVE;")
+    E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
+
+
+def _emit_stateful_angles(E: Emitter, kin: KinModel, links=None) -> None:
+    """joint angles of the stateful walk (rigid_body.py:218-224: clamp whenever limits exist, continuous joints too), all sines /
+    cosines; links: only the joints of these links"""
+    rot_dofs = []
+    for i in range(1, kin.n_links):
+        jt, d = int(kin.joint_type[i]), int(kin.dof_idx[i])
+        if jt == JOINT_FIXED or (links is not None and i not in links):
+            continue
+        if kin.sf_clamp[i]:
+            E.raw(f"    const float qh{d} = __builtin_amdgcn_fmed3f(q[{d}], {flit(kin.lower[i])}, {flit(kin.upper[i])});")
+        else:
+            E.raw(f"    const float qh{d} = q[{d}];")
+        if jt in (JOINT_REVOLUTE, JOINT_CONTINUOUS):
+            rot_dofs.append(d)
+    for d in rot_dofs:
+        E.raw(f"    float sn{d}, cs{d};")
+    for a, b in zip(rot_dofs[0::2], rot_dofs[1::2]):
+        E.raw(f"    trk_sincos2(qh{a}, qh{b}, &sn{a}, &cs{a}, &sn{b}, &cs{b});")
+    if len(rot_dofs) % 2:
+        d = rot_dofs[-1]
+        E.raw(f"    trk_sincos(qh{d}, &sn{d}, &cs{d});")
+
+
+def _with_virtual(u: _LinkUnit, E: Emitter, t):
+    """t extended by the interpolated points this template uses (named temporaries: w0 * p_src0 + w1 * p_src1)"""
+    if not u.used_virt:
+        return t
+    t = dict(t)
+    for i in u.used_virt:
+        s0, s1, w0, w1 = u.virt[i]
+        t[i] = [E.named(E.lincomb([(t[s0][k], S(float(np.float32(w0)))), (t[s1][k], S(float(np.float32(w1))))])) for k in range(3)]
+    return t
+
+
+def _scatter_virtual(u: _LinkUnit, E: Emitter, indent: str = "    ") -> None:
+    """adjoint of an interpolated point -> its two source links, with its weights"""
+    for i in u.used_virt:
+        s0, s1, w0, w1 = u.virt[i]
+        for src, w in ((s0, w0), (s1, w1)):
+            if float(np.float32(w)) != 0.0:
+                E.raw(f"{indent}tb{src}_0 = fmaf({flit(float(np.float32(w)))}, tb{i}_0, tb{src}_0); tb{src}_1 = fmaf({flit(float(np.float32(w)))}, tb{i}_1, tb{src}_1); "
+                      f"tb{src}_2 = fmaf({flit(float(np.float32(w)))}, tb{i}_2, tb{src}_2);")
+
+
+def _obj_groups(links: Sequence[int]) -> List[List[int]]:
+    """collision links in scene evaluations: all in one up to LINK_OBJ_GROUP_MAX, else groups of about LINK_OBJ_GROUP"""
+    n = len(links)
+    if n <= LINK_OBJ_GROUP_MAX:
+        return [list(links)] if n else []
+    size = -(-n // -(-n // LINK_OBJ_GROUP))
+    return [list(links[g0:g0 + size]) for g0 in range(0, n, size)]
+
+
+def _emit_obj_inputs(E: Emitter, t, links, n, ind: str) -> None:
+    """the position arrays px / py / pz of one scene evaluation (n: their C size) and its zeroed gradients"""
+    for k, nm in enumerate("xyz"):
+        E.raw(f"{ind}const float p{nm}[{n}] = {{{', '.join(E.expr(t[i][k]) for i in links)}}};")
+    E.raw(f"{ind}float gx[{n}], gy[{n}], gz[{n}];")
+    E.raw("#pragma unroll")
+    E.raw(f"{ind}for (int l = 0; l < {n}; ++l) {{ gx[l] = 0.0f; gy[l] = 0.0f; gz[l] = 0.0f; }}")
+
+
+def _emit_obj_adjoints(E: Emitter, links, ind: str) -> None:
+    for j, i in enumerate(links):
+        E.raw(f"{ind}tb{i}_0 += gx[{j}]; tb{i}_1 += gy[{j}]; tb{i}_2 += gz[{j}];")
+
+
+def _emit_obj_group(E: Emitter, t, grp, first: int, ticks: _Ticks, fast_arg: str, prims_ptr: str) -> None:
+    """one braced scene evaluation of the collision links `grp`, whose margins start at `first`"""
+    n = len(grp)
+    E.raw("    {")
+    _emit_obj_inputs(E, t, grp, n, "        ")
+    c0 = ticks.take(OBJ_TICK_SLOTS)
+    E.raw(f"        const TickFrom<decltype(flush), {c0}> ticks{{flush}};")
+    E.raw(f"        if (A.w.w_obj != 0.0f) cost += spec_objects_cost<{n}{fast_arg}>(A.C, A.w.w_obj, px, py, pz, gx, gy, gz, ticks, lds_sph, {first}{', ' + prims_ptr if prims_ptr else ''});")
+    E.raw(f"        else flush.template range<{c0}, {c0 + OBJ_TICK_SLOTS}>();")
+    E.raw(f"        if (A.w.w_ws != 0.0f && A.C.has_ws) cost += spec_ws_cost<{n}>(A.C, A.w.w_ws, px, py, pz, gx, gy, gz, {first});")
+    _emit_obj_adjoints(E, grp, "        ")
+    E.raw("    }")
+
+
+def _emit_self_pairs(E: Emitter, t, pairs) -> None:
+    """pairs: [(index in the template, link a, link b)]"""
+    E.raw("    if (A.w.w_self != 0.0f) {")
+    for pi, a, b in pairs:
+        pa = ", ".join(E.expr(t[a][k]) for k in range(3))
+        pb = ", ".join(E.expr(t[b][k]) for k in range(3))
+        E.raw(f"        cost += spec_self_pair(A.w.w_self, cptr(A.C.self_margin)[{pi}], {pa}, {pb}, "
+              f"tb{a}_0, tb{a}_1, tb{a}_2, tb{b}_0, tb{b}_1, tb{b}_2, (A.C.clamp_fields & TRK_FIELD_SELF) != 0);")
+    E.raw("    }")
+
+
+def _emit_ee_terms(E: Emitter, tracked, R, t) -> None:
+    """the tracked links' SE3 costs: position adjoints into tb<i>, rotation adjoints into the 9-float arrays they name"""
+    for ee, tgt, rb in tracked:
+        E.raw(f"    float {rb}[9] = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}};")
+    if not tracked:
+        return
+    E.raw("    if (A.w.w_ee != 0.0f) {")
+    for ee, tgt, rb in tracked:
+        E.raw("      {")
+        E.raw(f"        const float eR[9] = {{{', '.join(E.expr(R[ee][r][c]) for r in range(3) for c in range(3))}}};")
+        E.raw(f"        const float et[3] = {{{', '.join(E.expr(t[ee][k]) for k in range(3))}}};")
+        E.raw("        float gR[9], gt[3];")
+        E.raw(f"        const float ce = ee_cost_eval(eR, et, {tgt}, A.C.ee_w_pos, A.C.ee_w_rot, A.C.ee_square, gR, gt);")
+        E.raw("        cost = fmaf(A.w.w_ee, ce, cost);")
+        E.raw("#pragma unroll")
+        E.raw(f"        for (int k = 0; k < 9; ++k) {rb}[k] = A.w.w_ee * gR[k];")
+        E.raw(f"        tb{ee}_0 = fmaf(A.w.w_ee, gt[0], tb{ee}_0); tb{ee}_1 = fmaf(A.w.w_ee, gt[1], tb{ee}_1); "
+              f"tb{ee}_2 = fmaf(A.w.w_ee, gt[2], tb{ee}_2);")
+        E.raw("      }")
+    E.raw("    }")
+
+
+def _emit_collision_objectives(u: _LinkUnit, E: Emitter, t, ticks: _Ticks, fast_arg: str = "", prims_ptr: str = "") -> None:
+    """cost + position adjoints (tb<i>_k) of the three collision fields on link positions t[i][k]; the scene evaluation owns
+    OBJ_TICK_SLOTS tick slots of `flush` per group.  Shared by the fused rollout and the positions-in field kernel."""
+    obj, NL = list(u.tmpl.obj_links), u.NL
+    E.raw("    float cost = 0.0f;")
+    for i in u.adj_links:
+        E.raw(f"    float tb{i}_0 = 0.0f, tb{i}_1 = 0.0f, tb{i}_2 = 0.0f;")
+    t = _with_virtual(u, E, t)
+    # leading collision links whose position is a CONSTANT of the model (identity base: the Panda's first link origin): in the
+    # GENERAL-scene instantiation (boxes / grid: scene_is_general) their object cost is evaluated once per wavefront, cooperatively
+    # (scene_min_sdf_uniform_point), instead of 64 times through the primitive loop; they get no gradient (no joint moves them).
+    # The spheres-only instantiation keeps its text (its register allocation is the headline's; compiled in there too, the headline
+    # measured 9.09 - 9.17 -> 9.35 - 9.43 us: r05_ab_uniform_spheres.txt).
+    n_const = 0
+    if prims_ptr:
+        for i in obj:
+            if all(t[i][k].is_const for k in range(3)) and i not in u.used_virt:
+                n_const += 1
+            else:
+                break
+    if 0 < n_const < NL <= LINK_OBJ_GROUP_MAX:
+        rest = obj[n_const:]
+        nr = len(rest)
+        c0 = ticks.take(OBJ_TICK_SLOTS)
+        E.raw(f"    const TickFrom<decltype(flush), {c0}> ticks{{flush}};")
+        # (a voxel-grid scene keeps all links in one batch: its cost is the gathers' latency, and a separate gather for the constant
+        # link in front of the others only adds a second exposed latency: 22.8 -> 23.8 us measured)
+        E.raw("    if (BOX && !A.C.has_grid) {")
+        _emit_obj_inputs(E, t, rest, nr, "        ")
+        fa = fast_arg.replace("NL", str(nr))
+        E.raw("        if (A.w.w_obj != 0.0f) {")
+        for j in range(n_const):      # first: its table reads (LDS) / grid gather are issued before this phase's position ticks
+            i = obj[j]
+            E.raw(f"            cost += spec_object_cost_uniform_point(A.C, A.w.w_obj, {', '.join(E.expr(t[i][k]) for k in range(3))}, {j}, lane, {prims_ptr});")
+        E.raw(f"            cost += spec_objects_cost<{nr}{fa}>(A.C, A.w.w_obj, px, py, pz, gx, gy, gz, ticks, lds_sph, {n_const}, {prims_ptr});")
+        E.raw("        }")
+        E.raw(f"        else flush.template range<{c0}, {c0 + OBJ_TICK_SLOTS}>();")
+        E.raw("        if (A.w.w_ws != 0.0f && A.C.has_ws) {")
+        E.raw(f"            cost += spec_ws_cost<{nr}>(A.C, A.w.w_ws, px, py, pz, gx, gy, gz, {n_const});")
+        for j in range(n_const):
+            i = obj[j]
+            E.raw(f"            {{ float ux_ = 0.0f, uy_ = 0.0f, uz_ = 0.0f; cost += A.w.w_ws * ws_cost_point(A.C, cptr(A.C.obj_link_margin)[{j}], "
+                  f"{', '.join(E.expr(t[i][k]) for k in range(3))}, A.w.w_ws, ux_, uy_, uz_); }}")
+        E.raw("        }")
+        _emit_obj_adjoints(E, rest, "        ")
+        E.raw("    } else {")
+        _emit_obj_inputs(E, t, obj, "NL", "        ")
+        E.raw(f"        if (A.w.w_obj != 0.0f) cost += spec_objects_cost<NL{fast_arg}>(A.C, A.w.w_obj, px, py, pz, gx, gy, gz, ticks, lds_sph, 0, {prims_ptr});")
+        E.raw(f"        else flush.template range<{c0}, {c0 + OBJ_TICK_SLOTS}>();")
+        E.raw("        if (A.w.w_ws != 0.0f && A.C.has_ws) cost += spec_ws_cost<NL>(A.C, A.w.w_ws, px, py, pz, gx, gy, gz);")
+        _emit_obj_adjoints(E, obj, "        ")
+        E.raw("    }")
+    elif 0 < NL <= LINK_OBJ_GROUP_MAX:
+        _emit_obj_inputs(E, t, obj, "NL", "    ")
+        c0 = ticks.take(OBJ_TICK_SLOTS)
+        E.raw(f"    const TickFrom<decltype(flush), {c0}> ticks{{flush}};")
+        E.raw(f"    if (A.w.w_obj != 0.0f) cost += spec_objects_cost<NL{fast_arg}>(A.C, A.w.w_obj, px, py, pz, gx, gy, gz, ticks, lds_sph{', 0, ' + prims_ptr if prims_ptr else ''});")
+        E.raw(f"    else flush.template range<{c0}, {c0 + OBJ_TICK_SLOTS}>();")
+        E.raw("    if (A.w.w_ws != 0.0f && A.C.has_ws) cost += spec_ws_cost<NL>(A.C, A.w.w_ws, px, py, pz, gx, gy, gz);")
+        _emit_obj_adjoints(E, obj, "    ")
+    else:
+        # many collision links (tree robots): score them in groups so the working set of one scene evaluation
+        # (positions, keys, gradients: ~10 registers per link) does not sit on top of everything the reverse pass keeps
+        g0 = 0
+        for grp in _obj_groups(obj):
+            _emit_obj_group(E, t, grp, g0, ticks, fast_arg, prims_ptr)
+            g0 += len(grp)
+    if u.tmpl.self_pairs:
+        _emit_self_pairs(E, t, [(pi, a, b) for pi, (a, b) in enumerate(u.tmpl.self_pairs)])
+    _scatter_virtual(u, E)
+
+
+def _emit_boolean_fields(u: _LinkUnit, E: Emitter, t) -> None:
+    """`hit` = OR of the selected fields' "signed distance < margin" tests on link positions t[i][k] (k_coll after its FK walk,
+    k_collf on the caller's positions)"""
+    E.raw("    bool hit = false;")
+    t = _with_virtual(u, E, t)
+    if u.NL > 0:
+        E.raw("    if (A.coll_fields & (TRK_FIELD_OBJECTS | TRK_FIELD_WS)) {")
+        g0 = 0
+        for grp in _obj_groups(u.tmpl.obj_links):
+            n = len(grp)
+            E.raw("        {")
+            for k, nm in enumerate("xyz"):
+                E.raw(f"            const float p{nm}[{n}] = {{{', '.join(E.expr(t[i][k]) for i in grp)}}};")
+            E.raw(f"            hit |= spec_collision_links<{n}>(A.C, A.coll_fields, A.coll_margin, A.coll_use_default, px, py, pz, lds_sph, {g0});")
+            E.raw("        }")
+            g0 += n
+        E.raw("    }")
+    if u.tmpl.self_pairs:
+        E.raw("    if (A.coll_fields & TRK_FIELD_SELF) {")
+        for pi, (a_, b_) in enumerate(u.tmpl.self_pairs):
+            pa = ", ".join(E.expr(t[a_][k]) for k in range(3))
+            pb = ", ".join(E.expr(t[b_][k]) for k in range(3))
+            E.raw(f"        hit |= spec_self_hit(A.coll_use_default ? cptr(A.C.self_margin)[{pi}] : A.coll_margin, {pa}, {pb});")
+        E.raw("    }")
+
+
+class _RingStager:
+    """k_rollout's ring staging (RingFlusher): each link is staged as it exists, a complete 32-float chunk leaves piece by piece
+    between the links that fill the other half of the ring"""
+
+    def __init__(self, E: Emitter, rp: RingPlan, t, L: int):
+        self.E, self.rp, self.t, self.L = E, rp, t, L
+        self.ready_at: Dict[int, List[int]] = {}
+        for c in range(rp.n_full + 1):
+            self.ready_at.setdefault(rp.ready_float(c), []).append(c)
+        self.pending: List[Tuple[int, int]] = []       # (chunk, piece) not yet issued, oldest first
+
+    def link(self, i: int) -> None:
+        """stage link i's three floats, then issue pending pieces in the slot after it"""
+        E, rp = self.E, self.rp
+        for k in range(3):
+            f = 3 * i + k
+            assert all(rp.reuse_float(c) > f for c, _ in self.pending), "ring half reused before its pieces were issued"
+            x = E.expr(self.t[i][k])
+            if rp.regular(f):
+                E.raw(f"    if constexpr (POS) prow_a[{f & 63}] = {x};")
+            else:
+                E.raw(f"    if constexpr (POS) prow[ring.slot({f})] = {x};")
+            if f < rp.hx:
+                E.raw(f"    if constexpr (POS) prow[{64 + f}] = {x};")
+            for c in self.ready_at.get(f, []):
+                E.raw(f"    if constexpr (POS) ring.template done<{c}>();")
+                if c < rp.n_full:
+                    self.pending.extend((c, kk) for kk in range(rp.pieces))
+        # the pending pieces (of one chunk) are spread evenly over the slots that remain until the link whose staging re-uses their
+        # half of the ring (or the end of the walk)
+        if not self.pending:
+            return
+        c = self.pending[0][0]
+        last_slot = min(self.L - 1, rp.reuse_float(c) // 3 - 1)
+        slots = max(1, last_slot - i + 1)
+        n = -(-sum(1 for cc, _ in self.pending if cc == c) // slots)
+        for _ in range(n):
+            cc, kk = self.pending.pop(0)
+            E.raw(f"    if constexpr (POS) ring.template piece<{cc}, {kk}>();")
+
+
+def _emit_gpt_prior(E: Emitter, lds_lane) -> None:
+    """k_rollout_gpt's top: the raw q / qd rows of the block and its neighbours, the prior's cost and gradient (gpv, cost_gp), d/dqd out.
+    Round 5: the neighbours come through DPP wave shifts instead of LDS.  The phase stamps put "rows in + prior + gqd out" at 36 - 42 %
+    of a config-5 wavefront's life (7300 - 8200 of 20 000 ticks): per joint the LDS form cost four reads, two writes and four
+    more reads behind a second sync -- ten dependent round trips' worth of instructions at two wavefronts per SIMD.  Now a lane
+    reads its own row, the next sample's (p, v) arrive by `wave_shl:1` (lane 63: the row behind the block, handed to the
+    shift as its `old` operand, which a lane without a source keeps), the finished factor (rp, rv) goes to the next lane by
+    `wave_shr:1` (lane 0: the factor in front of the block, computed by lanes 0 .. D-1 as before and read back broadcast).
+    Same expressions on the same values as the LDS form: bit-identical results."""
+    E.raw("    typedef RawRowsInFlight<D, IOQ> Raw;")
+    E.raw("    constexpr int RS = 2 * D + 1;         // floats per row of the factor tile (odd: conflict-free)")
+    E.raw(f"    static_assert(2 * Raw::BYTES + ((TRK_WAVE + 1) * RS + 2) * 4 <= TRK_WAVE * {lds_lane} * 4 && TRK_WAVE * D * 4 <= TRK_WAVE * {lds_lane} * 4, \"the raw q / qd tiles and the factor tile share the staging tile\");")
+    E.raw("    const unsigned Hh = (unsigned)A.gp_H;")
+    E.raw("    const unsigned t0 = (unsigned)(base % (int64_t)A.gp_H);")
+    E.raw("    const unsigned tl = (t0 + (unsigned)lane) % Hh, t_last = (t0 + (unsigned)(TRK_WAVE - 1)) % Hh;")
+    E.raw("    const bool edge_prev = rows > 0 && t0 > 0u, edge_next = rows == TRK_WAVE && t_last + 1u < Hh && base + TRK_WAVE < A.n;")
+    E.raw("    const Raw rq = spec_raw_rows_issue<D, IOQ>(static_cast<const IOQ*>(A.q), base, rows, lane, edge_prev, edge_next);")
+    E.raw("    const Raw rv = spec_raw_rows_issue<D, IOQ>(static_cast<const IOQ*>(A.qd), base, rows, lane, edge_prev, edge_next);")
+    E.raw("    const IOQ* qb = spec_raw_rows_finish<D, IOQ>(rq, static_cast<const IOQ*>(A.q), base, rows, lane, reinterpret_cast<IOQ*>(lds));")
+    E.raw("    const IOQ* vb = spec_raw_rows_finish<D, IOQ>(rv, static_cast<const IOQ*>(A.qd), base, rows, lane, reinterpret_cast<IOQ*>(reinterpret_cast<unsigned char*>(lds) + Raw::BYTES));")
+    E.raw("    float* rt = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(lds) + 2 * Raw::BYTES);     // [65][RS]: row l + 1 = lane l's factor")
+    E.raw("    spec_wave_sync();")
+    E.raw("    float gpv[D], cost_gp;")
+    E.raw("    {")
+    E.raw("        const float wm = (lane < rows && tl + 1u < Hh) ? A.gp_w : 0.0f;")
+    E.raw("        const float dt = A.gp_dt, ga = A.gp_a, gb = A.gp_b, gc = A.gp_c;")
+    E.raw("        {       // the factor between the sample in front of the block and its first sample: lanes 0 .. D-1, joint `lane`.  Branch-free")
+    E.raw("                // (the other lanes compute joint 0 again and write a scratch slot behind the records)")
+    E.raw("            const int dj = lane < D ? lane : 0;")
+    E.raw("            const float pm = (float)qb[dj - D], vm = (float)vb[dj - D], pf = (float)qb[dj], vf = (float)vb[dj];")
+    E.raw("            const float wp = edge_prev ? A.gp_w : 0.0f;")
+    E.raw("            const float ep = fmaf(dt, vm, pm) - pf, ev = vm - vf;")
+    E.raw("            float* slot = rt + (lane < D ? 2 * lane : 2 * D);")
+    E.raw("            slot[0] = wp * fmaf(ga, ep, gb * ev); slot[1] = wp * fmaf(gb, ep, gc * ev);")
+    E.raw("        }")
+    E.raw("        spec_wave_sync();")
+    E.raw("        float gvv[D], accg = 0.0f;")
+    E.raw("        const float gaw = wm * ga, gbw = wm * gb, gcw = wm * gc;")
+    E.raw("#pragma unroll")
+    E.raw("        for (int d = 0; d < D; ++d) {")
+    E.raw("            const float p0 = (float)qb[lane * D + d], v0 = (float)vb[lane * D + d];")
+    E.raw("            const float pn = trk_dpp_from_next((float)qb[TRK_WAVE * D + d], p0), vn = trk_dpp_from_next((float)vb[TRK_WAVE * D + d], v0);")
+    E.raw("            const float ep = fmaf(dt, v0, p0) - pn, ev = v0 - vn;")
+    E.raw("            const float rp = fmaf(gaw, ep, gbw * ev), rv_ = fmaf(gbw, ep, gcw * ev);      // w Q^-1 e with the weight folded into Q^-1 once per lane")
+    E.raw("            accg = fmaf(ep, rp, fmaf(ev, rv_, accg));                                      // 2 x the factor's cost: halved once, below")
+    E.raw("            gpv[d] = rp - trk_dpp_from_prev(rt[2 * d], rp);")
+    E.raw("            gvv[d] = fmaf(dt, rp, rv_) - trk_dpp_from_prev(rt[2 * d + 1], rv_);")
+    E.raw("            q[d] = p0;")
+    E.raw("        }")
+    E.raw("        cost_gp = 0.5f * accg;")
+    E.raw("        // d cost / d qd is final: out through the staging tile (its first line waits for every lane's reads of the tiles)")
+    E.raw("        spec_store_gq<D, IOG, IoTraits<IO>::kScaled>(static_cast<IOG*>(A.gqd), base, rows, lane, lds, gvv, A.grad_scale);")
+    E.raw("        spec_wave_sync();")
+    E.raw("    }")
+
+
+def _emit_fused_jacobian(u: _LinkUnit, E: Emitter, R, t) -> None:
+    """the JAC instantiation's tail: the geometric Jacobian of the tracked link (launch_rjac) out of the poses of the rollout's walk"""
+    kin, D, ee = u.kin, u.D, u.tmpl.ee_link
+    E.raw("    if constexpr (JAC) {")
+    E.raw(f"        // ---- geometric Jacobian of link {ee} '{kin.link_names[ee]}' (robot_tree.py:218-248) from the poses of this walk: column d of a")
+    E.raw("        // joint with a column = [z x (p_link - p_joint) ; z], every other column zero; lin_jac / ang_jac [N, 3, D] leave as the")
+    E.raw("        // wavefront's contiguous 64 x 3D floats through one LDS tile each (16-byte write-through stores, like k_jac's)")
+    pe = [E.named(t[ee][k]) for k in range(3)]
+    colz: Dict[int, List[S]] = {}
+    coll: Dict[int, List[S]] = {}
+    for i in u.ee_jac_cols:
+        d, ax = int(kin.dof_idx[i]), int(kin.jac_axis[i])
+        z = [E.named(R[i][r][ax]) for r in range(3)]
+        rel = [E.named(E.lincomb([(pe[k], ONE), (t[i][k], S(-1.0))])) for k in range(3)]
+        colz[d] = z
+        coll[d] = [E.named(v) for v in E.cross(z, rel)]
+    E.raw(f"        float* jrow = lds + lane * {3 * D};")
+    for nm, cols, dst in (("lin", coll, "A.jac_lin"), ("ang", colz, "A.jac_ang")):
+        E.raw(f"        spec_wave_sync();          // the region's previous readers are done ({nm}_jac)")
+        vals = []
+        for r in range(3):
+            for d in range(D):
+                vals.append(E.expr(cols[d][r]) if d in cols else "0.0f")
+        E.raw("        " + " ".join(f"jrow[{k}] = {v};" for k, v in enumerate(vals)))
+        E.raw("        spec_wave_sync();")
+        # beyond the Infinity Cache the contiguous tiles are faster as non-temporal stores (UR10 + Allegro, 287 MB per launch, same box,
+        # three alternations: 46.4 - 47.7 -> 45.3 - 45.4 us; inside the cache write-through wins, as for the headline's chunks): the launch decides
+        E.raw(f"        if (A.jac_stream) spec_store_tile<{3 * D}, true>({dst}, base, rows, lane, lds);")
+        E.raw(f"        else spec_store_tile<{3 * D}>({dst}, base, rows, lane, lds);")
+    E.raw("        if (lane < rows) {")
+    E.raw("            const int64_t s_ = base + lane;")
+    E.raw(f"            const float jR[9] = {{{', '.join(E.expr(R[ee][r][c]) for r in range(3) for c in range(3))}}};")
+    E.raw("            " + " ".join(f"A.jac_pos[s_ * 3 + {k}] = {E.expr(pe[k])};" for k in range(3)))
+    E.raw("            float qo[4];")
+    E.raw("            frame_quat_wxyz(jR, qo);")
+    E.raw("            *reinterpret_cast<float4*>(A.jac_quat + s_ * 4) = make_float4(qo[0], qo[1], qo[2], qo[3]);")
+    E.raw("        }")
+    E.raw("    }")
+
+
+def _rollout_kernel(u: _LinkUnit, base_identity: bool, GPT: bool) -> List[str]:
+    """k_rollout_bi / _bg (GPT: k_rollout_gpt_bi / _bg, the GP prior fused in): FK + objectives + reverse pass in one launch, the
+    positions staged for output as they exist; the JAC instantiation adds the tracked link's geometric Jacobian"""
+    kin, tmpl, L, D, rp = u.kin, u.tmpl, u.L, u.D, u.rp
+    E = Emitter()
+    kname = ("k_rollout_gpt_" if GPT else "k_rollout_") + ("bi" if base_identity else "bg")
+    jac = u.jacf_ok and not GPT
+    # small arms fit 128 VGPRs (4 waves/SIMD: the whole 4096 x 64 batch resident); big trees get 256 VGPRs
+    # FAST (two-wavefront kernels only): scene_is_fast(A.C) -- a few equal spheres and nothing else -- is decided at the launch and
+    # only that scene path is compiled into the instantiation (5-rep same-box A/B: dual Panda 19.5 -> 18.6 us, UR10 + Allegro
+    # 31.0 -> 30.7; the 128-register Panda kernel measured no gain and keeps the run-time branches)
+    fast_t = u.fast_switch
+    # BOX: the scene has boxes and its primitive table fits TRK_LDS_PRIMS -- the instantiation keeps a copy of the table in LDS
+    # and scene_min_sdf carries only (value, index) through its primitive loop (shelf 23.2 -> 22.0 us, maze 24.6 -> 22.2).  The
+    # 128-register kernels get it as a switch of its own, decided at the launch: compiled into the one kernel the sphere scene
+    # runs as well, the headline measured 9.17 -> 9.37 us (register allocation again).  Two-wavefront kernels: BOX = !FAST.
+    # The BOX instantiation is the GENERAL scene kernel: launches choose it with scene_is_general (any box object, or a voxel grid),
+    # and only it carries the box and grid text of scene_min_sdf (GENERAL = BOX there).  Behind run-time branches in the
+    # sphere-scene kernel the brick-tiled cell index alone cost the headline 9.2 -> 9.55 us (same-box A/B,
+    # profiles/r04_ab_headline_*.txt).
+    box_t = not fast_t
+    switches = f"{', bool FAST' if fast_t else ''}{', bool BOX' if box_t else ''}{', bool JAC = false' if jac else ''}"
+    if u.chunked:
+        # POS: the launch wants the link positions.  A compile-time switch, because the ring staging costs the launches that
+        # only want cost + gradient (the planners' inner loop) 2-4 us even with every store masked off.
+        # JAC (units with jacf_ok): the same launch also writes the geometric Jacobian of the tracked link (launch_rjac).
+        E.raw(f"template <class IO, bool POS{switches}>      // IO: HBM-side type of q / link_pos / gq (float or _Float16)")
+    else:
+        E.raw(f"template <class IO{switches}>      // HBM-side type of q / link_pos / gq: float or _Float16")
+    if GPT and box_t:
+        # the prior's gradient (D registers) lives across the whole kernel: the box-scene instantiation of a small arm would spill
+        # 26 registers at four wavefronts per SIMD -- it runs at three
+        E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, BOX ? 3 : 4) {kname}(SpecArgs A) {{")
+    else:
+        E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, {4 if D <= 8 else 2}) {kname}(SpecArgs A) {{")
+    if not box_t:
+        E.raw("    constexpr bool BOX = !FAST;")
+    if u.chunked:
+        if jac:
+            E.raw(f"    constexpr int LDS_LANE = JAC ? {max(rp.stride, D, 3 * D)} : (POS ? {max(rp.stride, D)} : {D});      // JAC: the [64][3D] Jacobian tiles reuse the region")
+            E.raw('    static_assert(!JAC || TrkSame<IO, float>::value, "the fused Jacobian is an fp32 output");')
+        else:
+            E.raw(f"    constexpr int LDS_LANE = POS ? {max(rp.stride, D)} : {D};")
+        lds_lane = "LDS_LANE"
+    else:
+        lds_lane = max(3 * L, D)      # (>= 3 D: the [64][3D] Jacobian tiles of a JAC instantiation fit the staging tile, L > D)
+        if jac:
+            assert 3 * D <= lds_lane
+            E.raw('    static_assert(!JAC || TrkSame<IO, float>::value, "the fused Jacobian is an fp32 output");')
+        if GPT:     # the raw q / qd tiles (fp32 at worst) and the factor tile of the prior phase must fit the staging tile
+            pad = -(-D // 4) * 4
+            need = 2 * (-(-((pad + 65 * D) * 4) // 16) * 16) + (65 * (2 * D + 1) + 2) * 4
+            lds_lane = max(lds_lane, -(-need // 256))
+    E.raw(f"    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * {lds_lane} + SPEC_WAVES * (TRK_LDS_SPHERES * 4 + (BOX ? TRK_LDS_PRIMS * 8 : 0))];")
+    E.raw("    typedef typename IoTraits<IO>::Q IOQ;      // q, link_pos in HBM")
+    E.raw("    typedef typename IoTraits<IO>::G IOG;      // gq in HBM (fp16 q: scaled by A.grad_scale, fp16 stores saturate)")
+    E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
+    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);   // wave-uniform -> SGPR")
+    E.raw(f"    float* lds = lds_all + wave * (TRK_WAVE * {lds_lane});")
+    E.raw(f"    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * {lds_lane}) + wave * (TRK_LDS_SPHERES + (BOX ? 2 * TRK_LDS_PRIMS : 0));")
+    E.raw("    float4* lds_prm = BOX ? lds_sph + TRK_LDS_SPHERES : nullptr;        // box scenes: the primitive records, for the winning box's gather")
+    E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);   // waited for together with the rows below")
+    E.raw("    SpheresInFlight prm{};")
+    E.raw("    if constexpr (BOX) prm = spec_load_prims_issue(A.C, lane);")
+    E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;     // index of this wave's 64-sample block")
+    E.raw("    const int64_t base = wblock * TRK_WAVE;")
+    E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
+    E.raw("    spec_stamp(A.stamps, wblock, 0, lane);")
+    E.raw("    spec_stamp_real(A.stamps, wblock, 2, lane);      // 100 MHz chip-wide clock: aligns the per-CU s_memtime domains")
+    E.raw("    float q[D];")
+    if GPT:
+        _emit_gpt_prior(E, lds_lane)
+    else:
+        E.raw("    spec_load_q<D>(static_cast<const IOQ*>(A.q), base, rows, lane, lds, q);")
+    E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
+    E.raw("    if constexpr (BOX) spec_load_spheres_finish(lds_prm, lane, prm);")
+    E.raw("    spec_stamp(A.stamps, wblock, 1, lane);")
+    # ---------------- forward ----------------
+    R, t, passv = _root_pose(base_identity)
+    _emit_angles(E, kin)
+    ring = None
+    if u.chunked:
+        # Many links: a full [64][3L] staging tile per wavefront (92 KB per workgroup for 30 links) leaves ONE workgroup per
+        # CU.  The positions go through a 64-float ring per lane instead (RingFlusher).
+        ring_t = f"RingFlusher<{rp.W}, {rp.V}, {'true' if rp.aligned else 'false'}, IOQ>"
+        E.raw(f"    static_assert({ring_t}::LS == {rp.stride} && {ring_t}::HX == {rp.hx} && {ring_t}::NFULL == {rp.n_full} && {ring_t}::NP == {rp.pieces}, "
+              '"generator and RingFlusher disagree on the ring geometry");')
+        E.raw(f"    const {ring_t} ring = spec_make_ring<{rp.W}, {rp.V}, {'true' if rp.aligned else 'false'}, IOQ>("
+              "static_cast<IOQ*>(A.link_pos), base, rows, lane, lds);")
+        E.raw("    float* const prow = ring.row();        // this lane's ring; prow_a: the same, shifted by the lane's head")
+        E.raw("    float* const prow_a = ring.row_a();")
+        E.raw("    spec_wave_sync();")
+        ring = _RingStager(E, rp, t, L)
+        ring.link(0)
+    for p in range(1, L):
+        i = u.walk[p]
+        _emit_fk_link(E, kin, i, R, t, passv, u.snap)
+        if ring is not None:
+            ring.link(i)
+    # ---------------- outputs that depend only on FK ----------------
+    if ring is not None:
+        assert not ring.pending
+        E.raw("    const typename TrkIf<POS, RingTail<decltype(ring)>, NoFlushOf<decltype(ring)>>::type flush{ring};")
+    else:
+        E.raw(f"    PosFlusher<{3 * L}, IOQ> flush{{reinterpret_cast<const float4*>(lds) + lane, 0u, 0ull, 0ull, lane, make_float4(0.0f, 0.0f, 0.0f, 0.0f)}};")
+        pos_list = ", ".join(E.expr(t[i][k]) for i in range(L) for k in range(3))
+        E.raw("    if (A.link_pos) {")
+        E.raw(f"        const float pv[{3 * L}] = {{{pos_list}}};")
+        E.raw(f"        flush = spec_stage_rows<{3 * L}>(static_cast<IOQ*>(A.link_pos), base, rows, lane, lds, pv);")
+        E.raw("    }")
+    E.raw("    if (!A.gq) { flush.template rest<0>(); return; }      // positions only (trk_fk_positions): wave-uniform exit")
+    # position chunks leave at tick points with COMPILE-TIME chunk numbers (PosFlusher::chunk<CH>); none right after staging
+    # (issuing the first two there measured +0.35 us)
+    ticks = _Ticks()
+    E.raw("    spec_stamp(A.stamps, wblock, 3, lane);")
+    # ---------------- objectives ----------------
+    _emit_collision_objectives(u, E, t, ticks, fast_arg=f", decltype(ticks), {'FAST' if fast_t else 'false'}, BOX", prims_ptr="lds_prm")
+    E.raw("    spec_stamp(A.stamps, wblock, 4, lane);")
+    _emit_ee_terms(E, u.tracked, R, t)
+    E.raw(ticks())
+    E.raw("    spec_stamp(A.stamps, wblock, 5, lane);")
+    if GPT:
+        E.raw("    cost += cost_gp;           // the prior's factor t -> t + 1, attributed to this sample")
+    E.raw("    if (lane < rows) store_wt_f1(A.cost + base + lane, cost);")
+    E.raw("    if (A.cost_sum) {")
+    E.raw("        const float tot = spec_wave_sum(lane < rows ? cost : 0.0f);")
+    # write-through like every other output: the plain 4-byte store left 4096 dirty partial lines for the end-of-kernel
+    # write-back (same-box A/B 9.94 -> 9.77 us)
+    E.raw("        if (lane == 0 && rows > 0) store_wt_f1(A.cost_sum + wblock, tot);")
+    E.raw("    }")
+    # ---------------- reverse: wrench accumulators towards the root ----------------
+    # (A second FK walk with prefix-sum gradients instead of this reverse pass -- so that the joints' axes / origins need not
+    # stay alive -- was measured on UR10+Allegro: 41.3 vs 37.5 us.  These kernels are bound by VALU issue, not by occupancy.)
+    gq_expr = _emit_reverse_links(E, kin, R, t, {i: [f"tb{i}_{k}" for k in range(3)] for i in u.real_adj},
+                                  {l: rb for l, _, rb in u.tracked}, u.masked, tick=ticks, order=u.walk)
+    E.raw("    spec_stamp(A.stamps, wblock, 6, lane);")
+    E.raw(f"    flush.template rest<{ticks.n}>();")
+    prior = (lambda d: f" + gpv[{d}]") if GPT else (lambda d: "")
+    E.raw(f"    const float gv[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) + prior(d) for d in range(D))}}};")
+    E.raw("    spec_store_gq<D, IOG, IoTraits<IO>::kScaled>(static_cast<IOG*>(A.gq), base, rows, lane, lds, gv, A.grad_scale);")
+    E.raw("    spec_stamp(A.stamps, wblock, 7, lane);")
+    if jac:
+        _emit_fused_jacobian(u, E, R, t)
+    E.raw("}")
+    return E.lines
+
+
+def _gp_segments_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
+    """k_rollout_gp_bi / _bg: the fused rollout with the GP prior fused in, segment schedule (trk_rollout_gp_cost_grad; BASELINE
+    config 5's objective in ONE launch, gq and gqd written once).  BUILD-DEFINED like the prior itself.  Two things differ from k_rollout:
+    (1) SEGMENTS.  The subtrees hanging off the root that share no objective (the two arms of the dual Panda when no self pair
+        crosses them) are evaluated one after the other -- FK, scene, EE, reverse pass, positions -- so that only ONE arm's poses
+        are live at a time: the dual Panda fits the 128 registers and ~10 KB of LDS per wavefront that let all 4096 wavefronts of
+        its 2048 x 128 share be resident at once (k_rollout: 189 registers, two generations of workgroups).  Per-lane state that
+        must survive a segment lives in LDS: the raw q rows (HBM element type), the gradient accumulator [64][D].
+    (2) The prior.  A lane is one (trajectory, time step); its neighbours' q / qd rows sit next to its own in the raw tiles (the
+        two rows beyond the wavefront's block are fetched with the block), so the prior's gradient is a few FMAs per joint at the
+        top of the kernel: d/dqd leaves at once, d/dq seeds the accumulator the segments add their gradients to.
+    The factor between t and t + 1 is attributed to sample t: cost[b, t] += w/2 e_t^T Q^-1 e_t."""
+    kin, L, D, segs = u.kin, u.L, u.D, u.segs
+    E = Emitter()
+    kname = "k_rollout_gp_bi" if base_identity else "k_rollout_gp_bg"
+    fast_t = u.fast_switch
+    box_t = not fast_t
+    occ = 4 if max(len(sg["dofs"]) for sg in segs) <= 8 else 2
+    E.raw(f"template <class IO{', bool FAST' if fast_t else ''}{', bool BOX' if box_t else ''}>")
+    E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, {occ}) {kname}(SpecArgs A) {{")
+    if not box_t:
+        E.raw("    constexpr bool BOX = !FAST;")
+    E.raw("    typedef typename IoTraits<IO>::Q IOQ;")
+    E.raw("    typedef typename IoTraits<IO>::G IOG;")
+    E.raw("    typedef RawRowsInFlight<D, IOQ> Raw;")
+    # LDS per wavefront: accumulator [64][D] fp32 | raw q of the later segments [64][DL] | image: first the raw q and qd tiles, then
+    # the gqd staging tile, then the positions as they will lie in HBM
+    later_dofs = [d for sg in segs[1:] for d in sg["dofs"]]
+    DL = len(later_dofs)
+    E.raw(f"    constexpr int DL = {DL};            // joints of the segments after the first: their raw q waits in LDS")
+    E.raw("    constexpr int ACC_B = TRK_WAVE * D * 4, QL_B = (TRK_WAVE * DL * (int)sizeof(IOQ) + 15) / 16 * 16;")
+    E.raw(f"    constexpr int IMG_B0 = TRK_WAVE * {3 * L} * (int)sizeof(IOQ);")
+    E.raw("    constexpr int IMG_B1 = IMG_B0 > 2 * Raw::BYTES ? IMG_B0 : 2 * Raw::BYTES;")
+    E.raw("    constexpr int IMG_B = ((IMG_B1 > ACC_B ? IMG_B1 : ACC_B) + 15) / 16 * 16;")
+    E.raw("    constexpr int WAVE_B = ACC_B + QL_B + IMG_B;")
+    E.raw("    // the sphere (and primitive) tables are shared by the workgroup's wavefronts here: one barrier at the top, 192 bytes of LDS per wavefront saved")
+    E.raw("    __shared__ __attribute__((aligned(16))) unsigned char lds_all[SPEC_WAVES * WAVE_B + TRK_LDS_SPHERES * 16 + (BOX ? TRK_LDS_PRIMS * 32 : 0)];")
+    E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
+    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);")
+    E.raw("    unsigned char* wl = lds_all + wave * WAVE_B;")
+    E.raw("    float* acc = reinterpret_cast<float*>(wl);                      // [64][D] fp32: d cost / d q, prior first, then the segments")
+    E.raw("    IOQ* qlater = reinterpret_cast<IOQ*>(wl + ACC_B);              // [64][DL]: raw q of the later segments' joints")
+    E.raw("    IOQ* img = reinterpret_cast<IOQ*>(wl + ACC_B + QL_B);          // the output image; before that: scratch")
+    E.raw("    IOQ* qtile = img;                                               // raw q rows of the block (+ the neighbouring rows)")
+    E.raw("    float* scr = reinterpret_cast<float*>(wl + ACC_B + QL_B);")
+    E.raw("    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_WAVES * WAVE_B);")
+    E.raw("    float4* lds_prm = BOX ? lds_sph + TRK_LDS_SPHERES : nullptr;")
+    E.raw("    {")
+    E.raw("        const int tid = threadIdx.x;")
+    E.raw("        if (tid < TRK_LDS_SPHERES && tid < 2 * A.C.n_sphere_pairs) lds_sph[tid] = A.C.spheres[tid];")
+    E.raw("        if constexpr (BOX) { if (A.C.n_box_objects > 0 && A.C.n_prims <= TRK_LDS_PRIMS && tid < 2 * A.C.n_prims) lds_prm[tid] = reinterpret_cast<const float4*>(A.C.prims)[tid]; }")
+    E.raw("    }")
+    E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;")
+    E.raw("    const int64_t base = wblock * TRK_WAVE;")
+    E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
+    E.raw("    // time steps: the block starts at step t0 of its trajectory (wave-uniform), a lane sits at (t0 + lane) mod H")
+    E.raw("    const unsigned Hh = (unsigned)A.gp_H;")
+    E.raw("    const unsigned t0 = (unsigned)(base % (int64_t)A.gp_H);")
+    E.raw("    const unsigned tl = (t0 + (unsigned)lane) % Hh, t_last = (t0 + (unsigned)(TRK_WAVE - 1)) % Hh;")
+    E.raw("    const bool edge_prev = rows > 0 && t0 > 0u, edge_next = rows == TRK_WAVE && t_last + 1u < Hh && base + TRK_WAVE < A.n;")
+    E.raw("    const Raw rq = spec_raw_rows_issue<D, IOQ>(static_cast<const IOQ*>(A.q), base, rows, lane, edge_prev, edge_next);")
+    E.raw("    const Raw rv = spec_raw_rows_issue<D, IOQ>(static_cast<const IOQ*>(A.qd), base, rows, lane, edge_prev, edge_next);")
+    E.raw("    const IOQ* qb = spec_raw_rows_finish<D, IOQ>(rq, static_cast<const IOQ*>(A.q), base, rows, lane, qtile);")
+    E.raw("    const IOQ* vb = spec_raw_rows_finish<D, IOQ>(rv, static_cast<const IOQ*>(A.qd), base, rows, lane, reinterpret_cast<IOQ*>(wl + ACC_B + QL_B + Raw::BYTES));")
+    E.raw("    __syncthreads();            // the shared scene tables (and, wave-locally, the tiles) are in LDS")
+    E.raw("    float cost;")
+    E.raw("    float " + ", ".join(f"q0_{d}" for d in segs[0]["dofs"]) + ";")
+    E.raw("    {")
+    E.raw("        // ---- the prior: e_t = (p_t + dt v_t - p_t+1, v_t - v_t+1), r = Q^-1 e; this sample takes part in factors t-1 and t")
+    E.raw("        const bool on = lane < rows;")
+    E.raw("        const float mn = (on && tl + 1u < Hh) ? 1.0f : 0.0f, mp = (on && tl > 0u) ? 1.0f : 0.0f;")
+    E.raw("        const float dt = A.gp_dt, ga = A.gp_a, gb = A.gp_b, gc = A.gp_c;")
+    E.raw("        float gpv[D], gvv[D], accg = 0.0f;")
+    E.raw("#pragma unroll")
+    E.raw("        for (int d = 0; d < D; ++d) {")
+    E.raw("            const float p0 = (float)qb[lane * D + d], v0 = (float)vb[lane * D + d];")
+    E.raw("            const float pm = (float)qb[(lane - 1) * D + d], vm = (float)vb[(lane - 1) * D + d];")
+    E.raw("            const float pn = (float)qb[(lane + 1) * D + d], vn = (float)vb[(lane + 1) * D + d];")
+    E.raw("            const float ep = fmaf(dt, v0, p0) - pn, ev = v0 - vn;")
+    E.raw("            const float rp = fmaf(ga, ep, gb * ev), rv_ = fmaf(gb, ep, gc * ev);")
+    E.raw("            accg = fmaf(0.5f * mn, fmaf(ep, rp, ev * rv_), accg);")
+    E.raw("            const float em = fmaf(dt, vm, pm) - p0, fm = vm - v0;")
+    E.raw("            gpv[d] = A.gp_w * (mn * rp - mp * fmaf(ga, em, gb * fm));")
+    E.raw("            gvv[d] = A.gp_w * (mn * fmaf(dt, rp, rv_) - mp * fmaf(gb, em, gc * fm));")
+    E.raw("        }")
+    E.raw("        cost = A.gp_w * accg;")
+    E.raw("#pragma unroll")
+    E.raw("        for (int d = 0; d < D; ++d) acc[lane * D + d] = gpv[d];")
+    E.raw("        // the raw q tile is about to be overwritten: the first segment's joints go to registers, the others' wait in LDS")
+    for d in segs[0]["dofs"]:
+        E.raw(f"        q0_{d} = (float)qb[lane * D + {d}];")
+    for k_, d in enumerate(later_dofs):
+        E.raw(f"        qlater[lane * DL + {k_}] = qb[lane * D + {d}];")
+    E.raw("        // d cost / d qd is final: out through the scratch tile (its first line waits for every lane's reads of the qd rows)")
+    E.raw("        spec_store_gq<D, IOG, IoTraits<IO>::kScaled>(static_cast<IOG*>(A.gqd), base, rows, lane, scr, gvv, A.grad_scale);")
+    E.raw("    }")
+    E.raw("    unsigned passbits = 0u;")
+    E.raw(f"    const ImgFlusher<{3 * L}, IOQ> pimg = spec_make_img<{3 * L}, IOQ>(static_cast<IOQ*>(A.link_pos), base, rows, lane, img);")
+    E.raw("    spec_wave_sync();          // the gqd staging tile has been read out: the image may be written")
+    R, t, passv = _root_pose(base_identity)
+    fast_arg = f", decltype(ticks), {'FAST' if fast_t else 'false'}, BOX"
+    for k, sg in enumerate(segs):
+        E.raw(f"    // ================= segment {k}: links {sg['links'][0]} .. {sg['links'][-1]} =================")
+        E.raw("    {")
+        if k == 0:
+            _emit_angles(E, kin, links=sg["links"], declare_passbits=False, qexpr=lambda d: f"q0_{d}")
+        else:
+            _emit_angles(E, kin, links=sg["links"], declare_passbits=False,
+                         qexpr=lambda d: f"(float)qlater[lane * DL + {later_dofs.index(d)}]")
+        for i in sg["links"]:
+            _emit_fk_link(E, kin, i, R, t, passv, u.snap)
+        E.raw("    if (A.link_pos) {")
+        for i in sg["cols"]:
+            E.raw("        " + " ".join(f"pimg.put({3 * i + kk}, {E.expr(t[i][kk])});" for kk in range(3)))
+        E.raw("    }")
+        # tick slots of this segment: the scene evaluation's, one after the EE term, one per two links of the reverse pass
+        groups = _obj_groups(sg["obj"])
+        n_slots = OBJ_TICK_SLOTS * len(groups) + 1 + sum(1 for p in range(len(sg["links"]), 0, -1) if p % 2 == 0)
+        if k == len(segs) - 1:
+            E.raw("    spec_wave_sync();          // the image is complete")
+            E.raw("    spec_img_copy_slow(pimg, static_cast<IOQ*>(A.link_pos), base, rows);       // ragged last wavefront / unaligned view only")
+            E.raw(f"    constexpr int PPT = (decltype(pimg)::NP + {n_slots - 1}) / {n_slots};")
+        else:
+            E.raw("    constexpr int PPT = 0;     // the image is not complete before the last segment has staged its links")
+        E.raw("    const ImgTicks<decltype(pimg), PPT> flush{pimg};")
+        ticks = _Ticks()
+        adj = sorted(set(sg["obj"]) | {a for _, a, b in sg["pairs"]} | {b for _, a, b in sg["pairs"]} | {l for l, _, _ in sg["tracked"]})
+        for i in adj:
+            E.raw(f"    float tb{i}_0 = 0.0f, tb{i}_1 = 0.0f, tb{i}_2 = 0.0f;")
+        g_at = sg["obj_base"]
+        for grp in groups:
+            _emit_obj_group(E, t, grp, g_at, ticks, fast_arg, "lds_prm")
+            g_at += len(grp)
+        if sg["pairs"]:
+            _emit_self_pairs(E, t, sg["pairs"])
+        _emit_ee_terms(E, sg["tracked"], R, t)
+        E.raw(ticks())
+        gq_expr = _emit_reverse_links(E, kin, R, t, {i: [f"tb{i}_{kk}" for kk in range(3)] for i in adj if i != 0},
+                                      {l: rb for l, _, rb in sg["tracked"]}, u.masked, tick=ticks, order=[0] + sg["links"],
+                                      n_links=len(sg["links"]) + 1)
+        assert ticks.n <= n_slots, (ticks.n, n_slots)
+        E.raw(f"    flush.template rest<{ticks.n}>();")
+        for d in sg["dofs"]:
+            ex = E.expr(gq_expr.get(d, ZERO))
+            if ex != "0.0f":
+                E.raw(f"    acc[lane * D + {d}] += {ex};")
+        E.raw("    }")
+        # poses of this segment are dead from here on: drop them so that nothing downstream can reference them by accident
+        for i in sg["links"]:
+            R.pop(i, None); t.pop(i, None)
+    E.raw("    if (lane < rows) store_wt_f1(A.cost + base + lane, cost);")
+    E.raw("    if (A.cost_sum) {")
+    E.raw("        const float tot = spec_wave_sum(lane < rows ? cost : 0.0f);")
+    E.raw("        if (lane == 0 && rows > 0) store_wt_f1(A.cost_sum + wblock, tot);")
+    E.raw("    }")
+    E.raw("    spec_store_acc_tile<D, IOG, IoTraits<IO>::kScaled>(static_cast<IOG*>(A.gq), base, rows, lane, acc, A.grad_scale);")
+    E.raw("}")
+    return E.lines
+
+
+def _posbwd_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
+    """k_posbwd_bi / _bg: explicit reverse mode of the link positions (trk_fk_positions_backward with all links selected): FK again
+    (cheaper than storing poses), the adjoint rows [64][3L] come in through the LDS transpose, reverse pass"""
+    kin, L, D = u.kin, u.L, u.D
+    E = Emitter()
+    _kernel_head(E, "k_posbwd_bi" if base_identity else "k_posbwd_bg", 4 if D <= 8 else 2, max(3 * L, D))
+    E.raw("    float q[D];")
+    E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
+    early = 3 * L <= 48        # the loads in flight cost 3L/4 registers per lane: only for the small arms
+    if early:
+        E.raw("    // the position adjoints are needed only by the reverse pass: their loads are in flight during the forward pass")
+        E.raw(f"    const RowsInFlight<{3 * L}> gp_rows = spec_load_rows_issue<{3 * L}>(static_cast<const float*>(A.link_pos), base, rows, lane);")
+    R, t, passv = _root_pose(base_identity)
+    _emit_angles(E, kin)
+    for p in range(1, L):
+        _emit_fk_link(E, kin, int(kin.order[p]), R, t, passv, u.snap)
+    E.raw(f"    float gp[{3 * L}];                       // this sample's position adjoints, link-major")
+    if early:
+        E.raw(f"    spec_load_rows_finish<{3 * L}>(gp_rows, static_cast<const float*>(A.link_pos), base, rows, lane, lds, gp);")
+    else:
+        E.raw(f"    spec_load_q<{3 * L}>(static_cast<const float*>(A.link_pos), base, rows, lane, lds, gp);")
+    gq_expr = _emit_reverse_links(E, kin, R, t, {i: [f"gp[{3 * i + k}]" for k in range(3)] for i in range(1, L)}, {}, u.masked)
+    E.raw(f"    const float gv[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
+    E.raw("    spec_store_gq<D>(static_cast<float*>(A.gq), base, rows, lane, lds, gv);")
+    E.raw("}")
+    return E.lines
+
+
+def _coll_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
+    """k_coll_bi / _bg: boolean mode (trk_rollout_collision): FK + the OR of the selected fields' "signed distance < margin" tests, one
+    byte per sample out.  Its own kernel: inside k_rollout the extra SpecArgs fields and the cold path cost the hot path ~100 SGPR spill
+    moves (v_writelane / v_readlane) per wavefront."""
+    kin, L, D = u.kin, u.L, u.D
+    E = Emitter()
+    _kernel_head(E, "k_coll_bi" if base_identity else "k_coll_bg", 4 if D <= 8 else 2, "D", spheres=True)
+    E.raw("    float q[D];")
+    E.raw("    unsigned via_slot = 0u;")
+    E.raw("    int64_t via_traj0 = 0;")
+    E.raw("    bool via_outside = false;")
+    E.raw("    if (A.via_n > 0) spec_load_q_via<D>(A, base, rows, lane, q, via_slot, via_traj0, via_outside);     // trajectory validation: interpolate the via points here")
+    E.raw("    else spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
+    E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
+    R, t, passv = _root_pose(base_identity)
+    _emit_angles(E, kin)
+    for p in range(1, L):
+        _emit_fk_link(E, kin, int(kin.order[p]), R, t, passv, u.snap)
+    _emit_boolean_fields(u, E, t)
+    E.raw("    if (lane < rows) A.coll_out[base + lane] = hit ? 1 : 0;")
+    E.raw("    if (A.via_n > 0 && A.via_partial) spec_via_partial_flags(A, wblock, via_traj0, via_slot, hit, via_outside, lane < rows, lane);     // wave-uniform")
+    E.raw("}")
+    return E.lines
+
+
+def _fkh_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
+    """k_fkh_bi / _bg: FK matrices of ALL links (trk_fk_forward with every link selected = compute_forward_kinematics_all_links,
+    robot_tree.py:267-301): the same stateless walk as the fused rollout; a link's 4x4 leaves as soon as it exists -- each lane puts its
+    16 floats into a [64][17] LDS tile ([64][33] for pairs of links), the wave writes them as 8-byte write-through vectors, eight
+    consecutive lanes completing one sample's 64 bytes (two whole sectors).  The kernel is a pure write stream (704 B per sample for Panda).
+    (Round 5: a copy with NON-TEMPORAL stores for outputs beyond the Infinity Cache -- what pays for the fused rollout's contiguous 1 KiB
+    chunks, trk_spec_common.h F32Stream -- was built and measured: SLOWER for these 8-byte pieces, dual Panda 90.3 -> 116.1 us,
+    UR10 + Allegro 96.9 -> 101.5 us, Panda (in cache) 27.4 -> 47.2 us; profiles/r05_bench_fkh_stream.txt.  Dropped.)"""
+    kin, L, D = u.kin, u.L, u.D
+    ls = 33 if u.fkh_pair else 17
+    E = Emitter()
+    _kernel_head(E, "k_fkh_bi" if base_identity else "k_fkh_bg", 4 if D <= 16 else 2, max(ls, D))
+    E.raw("    float q[D];")
+    E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
+    R, t, passv = _root_pose(base_identity)
+    _emit_angles(E, kin)
+    E.raw(f"    float* hrow = lds + lane * {ls};")
+
+    def emit_h(i, p):
+        vals = []
+        for r in range(3):
+            vals += [E.expr(R[i][r][c]) for c in range(3)] + [E.expr(t[i][r])]
+        vals += ["0.0f", "0.0f", "0.0f", "1.0f"]
+        if u.fkh_pair:
+            off = 16 * (p % 2)
+            E.raw("    " + " ".join(f"hrow[{off + k}] = {v};" for k, v in enumerate(vals)))
+            if p % 2 == 1:
+                E.raw(f"    spec_flush_chunk<{16 * L}, 32, {ls}, 2>(A.fk_H, base, {16 * (i - 1)}, rows, lane, lds);")
+            elif p == L - 1:
+                E.raw(f"    spec_flush_chunk<{16 * L}, 16, {ls}, 2>(A.fk_H, base, {16 * i}, rows, lane, lds);")
+        else:
+            E.raw("    " + " ".join(f"hrow[{k}] = {v};" for k, v in enumerate(vals)))
+            E.raw(f"    spec_flush_chunk<{16 * L}, 16, {ls}, 2>(A.fk_H, base, {16 * i}, rows, lane, lds);")
+    emit_h(int(kin.order[0]), 0)
+    for p in range(1, L):
+        i = int(kin.order[p])
+        _emit_fk_link(E, kin, i, R, t, passv, u.snap)
+        emit_h(i, p)
+    E.raw("}")
+    return E.lines
+
+
+def _fields_kernel(u: _LinkUnit, boolean: bool) -> List[str]:
+    """k_fields: the collision fields on GIVEN link positions (trk_cost_fields: EmbodimentDistanceFieldBase.compute_embodiment_cost,
+    distance_fields.py:107-124, for the fields selected by the caller): positions in through the LDS transpose, the fused kernel's
+    objective code on them, cost + position gradient out.  No kinematics: the unit is found by its collision template (columns = all
+    links of the robot), so the reference-style call `field.compute_cost(q, link_pos)` runs the same arithmetic as the fused rollout.
+    k_collf (boolean): the same for the boolean fields (trk_collision_fields; distance_fields.py:210-215, 283-291)."""
+    L = u.L
+    E = Emitter()
+    _kernel_head(E, "k_collf" if boolean else "k_fields", 4 if 3 * L <= 48 else 2, 3 * L, spheres=True)
+    E.raw(f"    float p[{3 * L}];")
+    E.raw(f"    spec_load_q<{3 * L}>(A.fld_pos, base, rows, lane, lds, p);")
+    E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
+    tp = {i: [S(1.0, f"p[{3 * i + k}]") for k in range(3)] for i in range(L)}
+    if boolean:
+        _emit_boolean_fields(u, E, tp)
+        E.raw("    if (lane < rows) A.coll_out[base + lane] = hit ? 1 : 0;")
+        E.raw("}")
+        return E.lines
+    E.raw("    const NoFlush flush;")
+    _emit_collision_objectives(u, E, tp, _Ticks())
+    E.raw("    if (lane < rows) store_wt_f1(A.cost + base + lane, cost);")
+    E.raw("    if (A.fld_g) {")
+    E.raw("        const float sc = (A.fld_gcost && lane < rows) ? A.fld_gcost[base + lane] : 1.0f;")
+    gl = []
+    for i in range(L):
+        gl += [f"sc * tb{i}_{k}" if i in u.real_adj else "0.0f" for k in range(3)]
+    E.raw(f"        const float gv[{3 * L}] = {{{', '.join(gl)}}};")
+    E.raw(f"        spec_store_gq<{3 * L}>(A.fld_g, base, rows, lane, lds, gv);")
+    E.raw("    }")
+    E.raw("}")
+    return E.lines
+
+
+def _fk1_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
+    """k_fk1_bi / _bg: FK matrix of ONE link (trk_fk_forward with a single link selected: compute_forward_kinematics(..., state_less=True)
+    robot_tree.py:192-216, RobotPanda.get_EE_pose robot_panda.py:172-184): the stateless walk with a wave-uniform early exit after the
+    target (a run-time argument, captured by a wave-uniform switch), 64 bytes per sample out through the LDS transpose"""
+    kin, L, D = u.kin, u.L, u.D
+    E = Emitter()
+    _kernel_head(E, "k_fk1_bi" if base_identity else "k_fk1_bg", 4 if D <= 16 else 2, max(16, D))
+    E.raw("    float q[D];")
+    E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
+    R, t, passv = _root_pose(base_identity)
+    _emit_angles(E, kin)
+    E.raw("    float hv[16] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f};")
+
+    def capture_h(i):
+        body = "; ".join(f"hv[{4 * r + c}] = {E.expr(R[i][r][c])}" for r in range(3) for c in range(3))
+        body += "; " + "; ".join(f"hv[{4 * r + 3}] = {E.expr(t[i][r])}" for r in range(3))
+        E.raw(f"    if (A.jac_link == {i}) {{ {body}; }}       // wave-uniform")
+    capture_h(int(kin.order[0]))
+    E.raw("    do {                               // the walk stops after the target's pre-order position")
+    for p in range(1, L):
+        i = int(kin.order[p])
+        E.raw(f"    if (A.jac_p_end <= {p}) break;")
+        _emit_fk_link(E, kin, i, R, t, passv, u.snap)
+        capture_h(i)
+    E.raw("    } while (0);")
+    E.raw("    spec_store_gq<16>(A.fk_H, base, rows, lane, lds, hv);")
+    E.raw("}")
+    return E.lines
+
+
+def _fkhbwd_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
+    """k_fkhbwd_bi / _bg: reverse mode of the all-links FK matrices (trk_fk_backward with every link selected): FK again, then the
+    reverse walk; a link's adjoint (its 4x4 block of gH, bottom row ignored) comes in through an LDS transpose right before the walk
+    consumes it, so only one block per lane is live"""
+    kin, L, D = u.kin, u.L, u.D
+    ls = 18
+    E = Emitter()
+    # two wavefronts per SIMD: the rotation adjoint of EVERY link needs that link's rotation, so all of them stay live (Panda
+    # at four per SIMD: 63 registers spilled, and on this ISA a spill reload waits for every outstanding load)
+    _kernel_head(E, "k_fkhbwd_bi" if base_identity else "k_fkhbwd_bg", 2, max(ls, D))
+    E.raw("    float q[D];")
+    E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
+    R, t, passv = _root_pose(base_identity)
+    _emit_angles(E, kin)
+    for p in range(1, L):
+        _emit_fk_link(E, kin, int(kin.order[p]), R, t, passv, u.snap)
+    E.raw(f"    const float* gh = lds + lane * {ls};")
+
+    def fetch_adjoint(i):
+        E.raw(f"    spec_load_chunk<{16 * L}, 16, {ls}, 2>(A.fk_H, base, {16 * i}, rows, lane, lds);")
+        E.raw(f"    const float gR{i}[9] = {{gh[0], gh[1], gh[2], gh[4], gh[5], gh[6], gh[8], gh[9], gh[10]}};")
+        E.raw(f"    const float gt{i}_0 = gh[3], gt{i}_1 = gh[7], gt{i}_2 = gh[11];")
+    gq_expr = _emit_reverse_links(E, kin, R, t, {i: [f"gt{i}_{k}" for k in range(3)] for i in range(1, L)},
+                                  {i: f"gR{i}" for i in range(1, L)}, u.masked, pre_link=fetch_adjoint)
+    E.raw(f"    const float gv[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
+    E.raw("    spec_store_gq<D>(static_cast<float*>(A.gq), base, rows, lane, lds, gv);")
+    E.raw("}")
+    return E.lines
+
+
+def _ik_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
+    """k_ik_bi / _bg: Adam IK on the unit's tracked link (trk_ik_steps; robot_tree.py:345-442): the configurations AND the optimiser state
+    live in registers for all iterations of a launch -- FK, SE3 distance, reverse pass, joint-limit hinge, termination test and the Adam
+    update per lane, nothing but the result goes back to memory.  (The table-driven kernel keeps them in LDS and walks the tree from
+    tables: ~9 us per iteration whatever the batch.)"""
+    kin, L, D, ee = u.kin, u.L, u.D, u.tmpl.ee_link
+    E = Emitter()
+    _kernel_head(E, "k_ik_bi" if base_identity else "k_ik_bg", 4 if D <= 8 else 2, "D", args="IkArgs")
+    E.raw("    float q[D], am[D], av[D];")
+    E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
+    E.raw("    if (A.lr > 0.0f) {")
+    E.raw("        spec_load_q<D>(static_cast<const float*>(A.adam_m), base, rows, lane, lds, am);")
+    E.raw("        spec_load_q<D>(static_cast<const float*>(A.adam_v), base, rows, lane, lds, av);")
+    E.raw("    } else {")
+    E.raw("#pragma unroll")
+    E.raw("        for (int d = 0; d < D; ++d) { am[d] = 0.0f; av[d] = 0.0f; }")
+    E.raw("    }")
+    E.raw("    float Ht[16];")
+    E.raw("    {")
+    E.raw("        const float* tp = A.H_target + (A.per_sample ? min(base + lane, A.n - 1) * 16 : 0);")
+    E.raw("#pragma unroll")
+    E.raw("        for (int k = 0; k < 12; ++k) Ht[k] = tp[k];")
+    E.raw("    }")
+    E.raw("    float loss0 = 0.0f;")
+    E.raw("    bool ok0 = false;")
+    E.raw("    for (int it = 0; it < A.n_steps; ++it) {")
+    R, t, passv = _root_pose(base_identity)
+    _emit_angles(E, kin)
+    # only the chain of the tracked link matters: the other branches' poses would be dead code
+    chain = [int(kin.order[p]) for p in range(1, L) if int(kin.order[p]) in _ancestry(kin, [ee])]
+    for i in chain:
+        _emit_fk_link(E, kin, i, R, t, passv, u.snap)
+    E.raw(f"    const float eR[9] = {{{', '.join(E.expr(R[ee][r][c]) for r in range(3) for c in range(3))}}};")
+    E.raw(f"    const float et[3] = {{{', '.join(E.expr(t[ee][k]) for k in range(3))}}};")
+    E.raw("    float gR[9], gt[3];")
+    E.raw("    const float err = ee_cost_eval(eR, et, Ht, 1.0f, 1.0f, 0, gR, gt);      // SE3_distance, w_pos = w_rot = 1 (robot_tree.py:386-417)")
+    gq_expr = _emit_reverse_links(E, kin, R, t, {ee: ["gt[0]", "gt[1]", "gt[2]"]}, {ee: "gR"}, u.masked, order=[int(kin.order[0])] + chain,
+                                  n_links=len(chain) + 1)
+    E.raw(f"    const float g_[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
+    E.raw("    bool ok = err < A.se3_eps;")
+    E.raw("    float jl = 0.0f;")
+    E.raw("    const float bc1 = A.sched.bc1[it], rsqrt_bc2 = A.sched.rsqrt_bc2[it];")
+    E.raw("#pragma unroll")
+    E.raw("    for (int d = 0; d < D; ++d) {      // hinge on the (shrunk) limits, validity, torch.optim.Adam's update")
+    E.raw("        const float qv = q[d], lo = cptr(A.lower)[d], hi = cptr(A.upper)[d];")
+    E.raw("        float g = g_[d];")
+    E.raw("        if (qv < lo) { const float e = lo - qv; jl = fmaf(e, e, jl); g = fmaf(-2.0f * A.w_jl, e, g); }")
+    E.raw("        if (qv > hi) { const float e = hi - qv; jl = fmaf(e, e, jl); g = fmaf(-2.0f * A.w_jl, e, g); }")
+    E.raw("        ok = ok && (qv >= lo) && (qv <= hi);")
+    E.raw("        if (A.lr > 0.0f) {")
+    E.raw("            const float m1 = fmaf(0.9f, am[d], 0.1f * g);")
+    E.raw("            const float v1 = fmaf(0.999f, av[d], 0.001f * g * g);")
+    E.raw("            am[d] = m1; av[d] = v1;")
+    E.raw("            const float denom = fmaf(sqrtf(v1), rsqrt_bc2, 1e-8f);")
+    E.raw("            q[d] = qv - (A.lr / bc1) * (m1 / denom);")
+    E.raw("        }")
+    E.raw("    }")
+    E.raw("    if (it == 0) { loss0 = fmaf(A.w_jl, jl, err); ok0 = ok; }")
+    E.raw("    }")
+    E.raw("    if (lane < rows) {")
+    E.raw("        if (A.loss) A.loss[base + lane] = loss0;")
+    E.raw("        if (A.valid) A.valid[base + lane] = ok0 ? 1 : 0;")
+    E.raw("    }")
+    E.raw("    if (A.lr > 0.0f) {")
+    E.raw("        spec_store_gq<D>(A.q, base, rows, lane, lds, q);")
+    E.raw("        spec_store_gq<D>(A.adam_m, base, rows, lane, lds, am);")
+    E.raw("        spec_store_gq<D>(A.adam_v, base, rows, lane, lds, av);")
+    E.raw("    }")
+    E.raw("}")
+    return E.lines
+
+
+def _ikgn_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
+    """k_ikgn_bi / _bg: Gauss-Newton / Levenberg-Marquardt IK on the unit's tracked link (trk_ik_gn_steps; BUILD-DEFINED: the reference's
+    loop is Adam, robot_tree.py:303-384, its geometric Jacobian :218-248 is what a Newton step is made of; oracle: orc_ik_gn_step).  Per
+    iteration and lane: stateful FK of the links that matter, the Jacobian columns of the reference's rule, the pose residual, J^T J +
+    lambda I and J^T r as straight-line FMAs on the symbolic columns (structural zeros fold away), a Cholesky solve in registers, the
+    clamped step.  The Jacobian never leaves the registers -- the two-launch form (trk_fk_jacobian + trk_jtj) writes and re-reads 416
+    bytes per sample and iteration."""
+    kin, L, D, ee = u.kin, u.L, u.D, u.tmpl.ee_link
+    E = Emitter()
+    _kernel_head(E, "k_ikgn_bi" if base_identity else "k_ikgn_bg", 4 if D <= 8 else 2, "D", args="IkGnArgs")
+    E.raw("    float q[D];")
+    E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
+    E.raw("    float Ht[12];")
+    E.raw("    {")
+    E.raw("        const float* tp = A.H_target + (A.per_sample ? min(base + lane, A.n - 1) * 16 : 0);")
+    E.raw("#pragma unroll")
+    E.raw("        for (int k = 0; k < 12; ++k) Ht[k] = tp[k];")
+    E.raw("    }")
+    E.raw("    float lo[D], hi[D];")
+    E.raw("#pragma unroll")
+    E.raw("    for (int d = 0; d < D; ++d) { lo[d] = cptr(A.lower)[d]; hi[d] = cptr(A.upper)[d]; }")
+    E.raw("    float err0 = 0.0f;")
+    E.raw("    bool ok0 = false;")
+    E.raw("    for (int it = 0; it < A.n_steps; ++it) {")
+    R, t, passv = _root_pose(base_identity)
+    need = _ancestry(kin, [ee] + u.ee_jac_cols)
+    _emit_stateful_angles(E, kin, links=need)
+    for p in range(1, L):
+        i = int(kin.order[p])
+        if i in need:
+            _emit_fk_link(E, kin, i, R, t, passv, u.snap, stateful=True)
+    E.raw(f"    const float eR[9] = {{{', '.join(E.expr(R[ee][r][c]) for r in range(3) for c in range(3))}}};")
+    E.raw(f"    const float et[3] = {{{', '.join(E.expr(t[ee][k]) for k in range(3))}}};")
+    # residual r = [p* - p ; rotvec(R* R^T)]
+    E.raw("    float Re[9];")
+    E.raw("#pragma unroll")
+    E.raw("    for (int a = 0; a < 3; ++a)")
+    E.raw("#pragma unroll")
+    E.raw("        for (int b = 0; b < 3; ++b) Re[3 * a + b] = fmaf(Ht[4 * a], eR[3 * b], fmaf(Ht[4 * a + 1], eR[3 * b + 1], Ht[4 * a + 2] * eR[3 * b + 2]));")
+    E.raw("    float r6[6] = {Ht[3] - et[0], Ht[7] - et[1], Ht[11] - et[2], 0.0f, 0.0f, 0.0f};")
+    E.raw("    trk_rotvec(Re, r6 + 3);")
+    E.raw("    if (it == 0) {          // what the caller learns about q as passed in: the metric of ik_termination (robot_tree.py:419-442)")
+    E.raw("        float gR_[9], gt_[3];")
+    E.raw("        err0 = ee_cost_eval(eR, et, Ht, 1.0f, 1.0f, 0, gR_, gt_);")
+    E.raw("        ok0 = err0 < A.se3_eps;")
+    E.raw("#pragma unroll")
+    E.raw("        for (int d = 0; d < D; ++d) ok0 = ok0 && (q[d] >= lo[d]) && (q[d] <= hi[d]);")
+    E.raw("    }")
+    E.raw("    const float lam = fmaf(A.lm_gain, fmaf(r6[0], r6[0], fmaf(r6[1], r6[1], fmaf(r6[2], r6[2], fmaf(r6[3], r6[3], fmaf(r6[4], r6[4], r6[5] * r6[5]))))), A.damping);")
+    # symbolic Jacobian columns: rows 0-2 linear z x (p_ee - p_joint), rows 3-5 angular z
+    col: Dict[int, List[S]] = {}
+    pe = [S(1.0, f"et[{k}]") for k in range(3)]
+    for i in u.ee_jac_cols:
+        d, ax = int(kin.dof_idx[i]), int(kin.jac_axis[i])
+        z = [E.named(R[i][r][ax]) for r in range(3)]
+        rel = [E.named(E.lincomb([(pe[k], ONE), (t[i][k], S(-1.0))])) for k in range(3)]
+        lin = [E.named(v) for v in E.cross(z, rel)]
+        col[d] = lin + z
+    rr = [S(1.0, f"r6[{k}]") for k in range(6)]
+    for d in range(D):
+        if d in col:
+            E.raw(f"    const float g{d}_ = {E.expr(E.lincomb([(col[d][k], rr[k]) for k in range(6)]))};")
+    E.raw(f"    float An[{D * (D + 1) // 2}], gn[D];")
+    for i in range(D):
+        E.raw(f"    gn[{i}] = {f'g{i}_' if i in col else '0.0f'};")
+        for j in range(i + 1):
+            idx = i * (i + 1) // 2 + j
+            if i in col and j in col:
+                a = E.lincomb([(col[i][k], col[j][k]) for k in range(6)])
+                E.raw(f"    An[{idx}] = {E.expr(a)}{' + lam' if i == j else ''};")
+            else:
+                E.raw(f"    An[{idx}] = {'lam' if i == j else '0.0f'};")
+    E.raw("    trk_chol_solve<D>(An, gn);")
+    E.raw("#pragma unroll")
+    E.raw("    for (int d = 0; d < D; ++d) q[d] = __builtin_amdgcn_fmed3f(fmaf(A.step_scale, gn[d], q[d]), lo[d], hi[d]);")
+    E.raw("    }")
+    E.raw("    if (lane < rows) {")
+    E.raw("        if (A.err) A.err[base + lane] = err0;")
+    E.raw("        if (A.valid) A.valid[base + lane] = ok0 ? 1 : 0;")
+    E.raw("    }")
+    E.raw("    spec_store_gq<D>(A.q, base, rows, lane, lds, q);")
+    E.raw("}")
+    return E.lines
+
+
+def _jac_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
+    """k_jac_bi / _bg: stateful FK + geometric Jacobian of ONE link (trk_fk_jacobian; robot_tree.py:136-190, 218-248): the walk unrolled
+    with the stateful path's quirks (clamp wherever limits exist, rotation about the axis with its sign ignored); every joint that can
+    receive a column writes its (z, p) -- straight into the output tiles (jac_direct), or as a record in LDS that the table-driven
+    kernel's read-out (trk_jac_readout) maps --, the target link (a run-time argument) is picked by a wave-uniform switch.  One wavefront
+    per workgroup."""
+    kin, L, D, direct = u.kin, u.L, u.D, u.jac_direct
+    E = Emitter()
+    kname = "k_jac_bi" if base_identity else "k_jac_bg"
+    E.raw(f"__global__ void __launch_bounds__(TRK_WAVE) {kname}(SpecArgs A) {{")
+    E.raw("    extern __shared__ __attribute__((aligned(16))) float lds[];     // 64 x max(record stride, D) floats + the slot table")
+    if not direct:
+        E.raw("    const int rstride = (6 * A.jac_n_cols + 3) | 1;       // records only for the joints that get a column")
+    E.raw("    const int lane = threadIdx.x;")
+    E.raw("    const int64_t base = (int64_t)blockIdx.x * TRK_WAVE;")
+    E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
+    E.raw("    float q[D];")
+    E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
+    R, t, passv = _root_pose(base_identity)
+    _emit_stateful_angles(E, kin)
+    if direct:
+        E.raw(f"    float* lin_row = lds + lane * {3 * D};                       // this sample's row of the two [64][3D] output tiles")
+        E.raw(f"    float* ang_row = lds + TRK_WAVE * {3 * D} + lane * {3 * D};")
+        E.raw("    spec_wave_sync();                  // the q transpose is done with this LDS")
+        E.raw("#pragma unroll")
+        E.raw(f"    for (int k = 0; k < {3 * D}; ++k) {{ lin_row[k] = 0.0f; ang_row[k] = 0.0f; }}")
+    else:
+        E.raw("    float* rec = lds + lane * rstride;")
+        E.raw("    spec_wave_sync();                  // the q transpose is done with this LDS")
+    E.raw("    float eR[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f}, et[3] = {0.0f, 0.0f, 0.0f};")
+
+    def capture(i):
+        rl = "; ".join(f"eR[{3 * r + c}] = {E.expr(R[i][r][c])}" for r in range(3) for c in range(3))
+        tl = "; ".join(f"et[{r}] = {E.expr(t[i][r])}" for r in range(3))
+        E.raw(f"    if (A.jac_link == {i}) {{ {rl}; {tl}; }}       // wave-uniform")
+    capture(int(kin.order[0]))
+    E.raw("    do {                               // the walk stops after the last pre-order position that matters")
+    for p in range(1, L):
+        i = int(kin.order[p])
+        E.raw(f"    if (A.jac_p_end <= {p}) break;")
+        _emit_fk_link(E, kin, i, R, t, passv, u.snap, stateful=True)
+        if i in u.jac_joints:
+            d, ax = int(kin.dof_idx[i]), int(kin.jac_axis[i])
+            vals = [E.expr(R[i][r][ax]) for r in range(3)] + [E.expr(t[i][r]) for r in range(3)]
+            if direct:      # the axis is final (angular rows); the joint origin waits in the linear rows for the link's position
+                body = " ".join([f"ang_row[{r * D + d}] = {vals[r]};" for r in range(3)] +
+                                [f"lin_row[{r * D + d}] = {vals[3 + r]};" for r in range(3)])
+                E.raw(f"    if (A.jac_slot[{d}] >= 0) {{ {body} }}      // wave-uniform")
+            else:
+                body = " ".join(f"j[{r}] = {v};" for r, v in enumerate(vals))
+                E.raw(f"    if (A.jac_slot[{d}] >= 0) {{ float* j = rec + 6 * A.jac_slot[{d}]; {body} }}      // wave-uniform")
+        capture(i)
+    E.raw("    } while (0);")
+    if direct:
+        for i in u.jac_joints:
+            d = int(kin.dof_idx[i])
+            E.raw(f"    if (A.jac_slot[{d}] >= 0) {{      // wave-uniform: lin = z x (p_link - p_joint)")
+            E.raw(f"        const float z0 = ang_row[{d}], z1 = ang_row[{D + d}], z2 = ang_row[{2 * D + d}];")
+            E.raw(f"        const float r0 = et[0] - lin_row[{d}], r1 = et[1] - lin_row[{D + d}], r2 = et[2] - lin_row[{2 * D + d}];")
+            E.raw(f"        lin_row[{d}] = z1 * r2 - z2 * r1; lin_row[{D + d}] = z2 * r0 - z0 * r2; lin_row[{2 * D + d}] = z0 * r1 - z1 * r0;")
+            E.raw("    }")
+        E.raw("    spec_wave_sync();")
+        E.raw(f"    spec_store_tile<{3 * D}>(A.jac_lin, base, rows, lane, lds);")
+        E.raw(f"    spec_store_tile<{3 * D}>(A.jac_ang, base, rows, lane, lds + TRK_WAVE * {3 * D});")
+    else:
+        E.raw("    rec[6 * A.jac_n_cols] = et[0]; rec[6 * A.jac_n_cols + 1] = et[1]; rec[6 * A.jac_n_cols + 2] = et[2];")
+        E.raw(f"    int* slot = reinterpret_cast<int*>(lds + TRK_WAVE * max(rstride, {D}));")
+        for d in range(D):
+            E.raw(f"    if (lane == {d}) slot[{d}] = A.jac_slot[{d}];")
+        E.raw("    spec_wave_sync();")
+        E.raw("    trk_jac_readout(lds, slot, rstride, A.jac_n_cols, D, rows, A.jac_lin + base * 3 * D, A.jac_ang + base * 3 * D, lane);")
+    E.raw("    if (lane >= rows) return;")
+    E.raw("    const int64_t s = base + lane;")
+    E.raw("    A.jac_pos[s * 3] = et[0]; A.jac_pos[s * 3 + 1] = et[1]; A.jac_pos[s * 3 + 2] = et[2];")
+    E.raw("    float qo[4];")
+    E.raw("    frame_quat_wxyz(eR, qo);")
+    E.raw("    *reinterpret_cast<float4*>(A.jac_quat + s * 4) = make_float4(qo[0], qo[1], qo[2], qo[3]);")
+    E.raw("}")
+    return E.lines
+
+
+def _ajac_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
+    """k_ajac_bi / _bg: analytic Jacobian of EVERY link (trk_fk_analytic_jacobian; robot_tree.py:250-265): d [pos, quat_wxyz] / d q,
+    [N, L, 7, D].  The stateless walk unrolled; a joint leaves (omega = pass * sign * its axis in the world, its origin) in registers, every
+    link combines the joints of its chain into its 7 x D block in an LDS tile (off-chain columns are literal zeros), and the block leaves
+    as the sample's contiguous run of 7 D floats.  One wavefront per workgroup.  The table-driven kernel walks the same tables at one
+    instruction per ~25 cycles (Panda 4096 x 64: 340 us for 572 MB)."""
+    kin, L, D, arp = u.kin, u.L, u.D, u.arp
+    dof_link = {int(kin.dof_idx[i]): i for i in range(1, L) if int(kin.dof_idx[i]) >= 0}
+    chain = {i: _ancestry(kin, [i]) for i in range(L)}
+    aring_t = f"RingFlusher<{arp.W}, {arp.V}, {'true' if arp.aligned else 'false'}, float>"
+    E = Emitter()
+    kname = "k_ajac_bi" if base_identity else "k_ajac_bg"
+    E.raw(f"__global__ void __launch_bounds__(TRK_WAVE) {kname}(SpecArgs A) {{")
+    E.raw(f"    extern __shared__ __attribute__((aligned(16))) float lds[];     // the wavefront's ring [64][{arp.stride}] (first: the q transpose)")
+    E.raw("    const int lane = threadIdx.x;")
+    E.raw("    const int64_t base = (int64_t)blockIdx.x * TRK_WAVE;")
+    E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
+    E.raw("    float q[D];")
+    E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
+    _emit_angles(E, kin)
+    E.raw(f"    static_assert({aring_t}::LS == {arp.stride} && {aring_t}::HX == {arp.hx} && {aring_t}::NFULL == {arp.n_full} && {aring_t}::NP == {arp.pieces}, "
+          '"generator and RingFlusher disagree on the ring geometry");')
+    E.raw("    spec_wave_sync();                  // the q transpose is done with this LDS")
+    # (write-through pieces.  Non-temporal ones were measured for outputs beyond the Infinity Cache: 2.4 -> 1.8 TB/s -- an 8-byte piece
+    # is not the 1 KiB contiguous store that policy pays for)
+    E.raw(f"    const {aring_t} ring = spec_make_ring<{arp.W}, {arp.V}, {'true' if arp.aligned else 'false'}, float>(A.jac_lin, base, rows, lane, lds);")
+    E.raw("    float* const prow = ring.row();        // this lane's ring; prow_a: the same, shifted by the lane's head")
+    E.raw("    float* const prow_a = ring.row_a();")
+    R, t, passv = _root_pose(base_identity)
+    ready_at: Dict[int, List[int]] = {}
+    for c in range(arp.n_full + 1):
+        ready_at.setdefault(arp.ready_float(c), []).append(c)
+
+    def stage_float(f, x):
+        """float f of the sample's row into the ring; a chunk that is complete leaves at once (its 16 pieces back to back: the next
+        floats overwrite the OTHER half of the ring, nothing waits for these stores)"""
+        if arp.regular(f):
+            E.raw(f"        prow_a[{f & 63}] = {x};")
+        else:
+            E.raw(f"        prow[ring.slot({f})] = {x};")
+        if f < arp.hx:
+            E.raw(f"        prow[{64 + f}] = {x};")
+        for c in ready_at.get(f, []):
+            E.raw(f"        ring.template done<{c}>();")
+            for kk in range(arp.pieces):
+                E.raw(f"        ring.template piece<{c}, {kk}>();")
+
+    def emit_block(i):
+        E.raw(f"    {{   // link {i}: its 7 x D block of the Jacobian")
+        on = []
+        for d in range(D):
+            jd = dof_link[d]
+            if jd in chain[i] and (int(kin.joint_type[jd]) == JOINT_PRISMATIC or float(kin.rot_sign[jd]) != 0.0):
+                on.append(d)
+        if any(int(kin.joint_type[dof_link[d]]) != JOINT_PRISMATIC for d in on):
+            E.raw("        const float Ri[9] = {" + ", ".join(E.expr(R[i][r][c]) for r in range(3) for c in range(3)) + "};")
+            E.raw("        const QuatSel qs = quat_sel(Ri);")
+        tt = ", ".join(E.expr(t[i][r]) for r in range(3))
+        for d in on:
+            if int(kin.joint_type[dof_link[d]]) == JOINT_PRISMATIC:
+                E.raw(f"        const float c{d}[7] = {{aw{d}_0, aw{d}_1, aw{d}_2, 0.0f, 0.0f, 0.0f, 0.0f}};")
+            else:
+                E.raw(f"        float c{d}[7];")
+                E.raw(f"        spec_ajac_col_revolute(c{d}, Ri, qs, {tt}, aw{d}_0, aw{d}_1, aw{d}_2, ap{d}_0, ap{d}_1, ap{d}_2);")
+        for k in range(7):
+            for d in range(D):
+                stage_float(7 * D * i + k * D + d, f"c{d}[{k}]" if d in on else "0.0f")
+        E.raw("    }")
+    # the row is staged in MEMORY order (link index), the walk visits the links in pre-order: a link's block is emitted when every
+    # link in front of it (by index) has been walked
+    walked = {int(kin.order[0])}
+    next_block = [0]
+
+    def flush_blocks():
+        while next_block[0] < L and next_block[0] in walked:
+            emit_block(next_block[0])
+            next_block[0] += 1
+    flush_blocks()
+    for p in range(1, L):
+        i = int(kin.order[p])
+        _emit_fk_link(E, kin, i, R, t, passv, u.snap)
+        jt, d = int(kin.joint_type[i]), int(kin.dof_idx[i])
+        if jt != JOINT_FIXED and d >= 0:
+            mask = (lambda e, d=d: f"((passbits & {1 << d}u) ? {e} : 0.0f)") if kin.clamp[i] else (lambda e: e)
+            if jt == JOINT_PRISMATIC:
+                par = int(kin.parent[i])
+                dirw = [E.lincomb([(R[par][r][k], S(float(kin.axis[i][k]))) for k in range(3)]) for r in range(3)]
+                for k in range(3):
+                    E.raw(f"    const float aw{d}_{k} = {mask(E.expr(dirw[k]))};")
+            elif float(kin.rot_sign[i]) != 0.0:
+                sg, ax = float(kin.rot_sign[i]), int(kin.rot_axis[i])
+                for k in range(3):
+                    z = R[i][k][ax]
+                    E.raw(f"    const float aw{d}_{k} = {mask(E.expr(S(z.c * sg, z.n)))};")
+                    E.raw(f"    const float ap{d}_{k} = {E.expr(t[i][k])};")
+        walked.add(i)
+        flush_blocks()
+    assert next_block[0] == L
+    E.raw("}")                      # (the tail chunk -- what is left of every row and the head of the next one -- left with the last float)
+    return E.lines
+
+
+def _launcher_lines(stem: str, args: str = "SpecArgs", per_wave: bool = False, lds: Sequence[str] = ()) -> List[str]:
+    """launch_<stem>: k_<stem>_bi or k_<stem>_bg over the batch, a workgroup of SPEC_BLOCK samples (per_wave: one wavefront per
+    workgroup, `lds`: the lines that set the launch's dynamic LDS bytes `lds`)"""
+    blk = "TRK_WAVE" if per_wave else "SPEC_BLOCK"
+    shm = "lds" if lds else "0"
+    return [f"static void launch_{stem}(const SpecEntry*, const {args}& a, int base_identity, hipStream_t st) {{",
+            f"    const unsigned grid = (unsigned)((a.n + {blk} - 1) / {blk});",
+            *lds,
+            f"    if (base_identity) hipLaunchKernelGGL(k_{stem}_bi, dim3(grid), dim3({blk}), {shm}, st, a);",
+            f"    else hipLaunchKernelGGL(k_{stem}_bg, dim3(grid), dim3({blk}), {shm}, st, a);",
+            "}"]
+
+
+def _rollout_switches(u: _LinkUnit) -> List[str]:
+    """the launch-time conditions that pick k_rollout's compile-time switches, in template-parameter order after IO: POS (ring-staged
+    units), then FAST or BOX (box objects -- the (value, index) primitive loop over the LDS table -- and / or a voxel grid)"""
+    return (["a.link_pos != nullptr"] if u.chunked else []) + [u.scene_switch]
+
+
+def _rollout_launcher_lines(u: _LinkUnit) -> List[str]:
+    out = ["static void launch(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {",
+           "    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);"]
+    # every (IO, [POS,] [FAST,] [BOX,] base) instantiation: one generic lambda per compile-time switch, in template-parameter order
+    switches = _rollout_switches(u)
     n_sw = len(switches)
     targs = ", ".join(f"decltype(c{k})::value" for k in range(n_sw))
     params = ", ".join(f"auto c{k}" for k in range(n_sw))
@@ -2219,160 +2007,203 @@ def generate_rollout_source(kin: KinModel, tmpl: CollisionTemplate, ident: str, 
         prev = f"sw{k}"
     out.append("    // fp32 launches whose working set exceeds the Infinity Cache take the non-temporal-store instantiation (spec_stream_stores)")
     out.append(f"    if (a.io_f16 == TRK_IO_F16) sw0(_Float16{{}}); else if (a.io_f16 == TRK_IO_F16_G32) sw0(HalfG32{{}}); "
-               f"else if (spec_stream_stores(a, {L}, {D})) sw0(F32Stream{{}}); else sw0(float{{}});")
+               f"else if (spec_stream_stores(a, {u.L}, {u.D})) sw0(F32Stream{{}}); else sw0(float{{}});")
     out.append("}")
-    if jacf_ok:
-        # fused rollout + geometric Jacobian of the tracked link (trk_rollout_jacobian_cost_grad): fp32 I/O, positions wanted;
-        # returns 1 when this call is not served (the C ABI then runs the two launches)
-        out.append("static int launch_rjac(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {")
-        # ring-staged units instantiate JAC with positions (POS = true) only; the others take the positions as a run-time option
-        out.append(f"    if (a.io_f16 != TRK_IO_F32 || {'!a.link_pos || ' if chunked else ''}a.jac_link != {tmpl.ee_link}) return 1;")
-        out.append("    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);")
-        pos_t = "true, " if chunked else ""
-        out.append(f"    if ({'scene_is_fast(a.C)' if D > 8 else 'scene_is_general(a.C)'}) {{")
-        out.append(f"        if (base_identity) hipLaunchKernelGGL((k_rollout_bi<float, {pos_t}true, true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-        out.append(f"        else hipLaunchKernelGGL((k_rollout_bg<float, {pos_t}true, true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-        out.append("    } else {")
-        out.append(f"        if (base_identity) hipLaunchKernelGGL((k_rollout_bi<float, {pos_t}false, true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-        out.append(f"        else hipLaunchKernelGGL((k_rollout_bg<float, {pos_t}false, true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-        out.append("    }")
-        out.append("    return 0;")
-        out.append("}")
-    if gp_ok or gpt_ok:
-        out.append("static int launch_gp(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {")
-        out.append("    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);")
-        sw = "scene_is_fast(a.C)" if D > 8 else "scene_is_general(a.C)"
-        if use_seg and gp_cross_pairs:
-            out.append("    if (a.w.w_self != 0.0f) return 1;      // self pairs between independently scheduled subtrees: the two-launch form serves them")
-        kn = "k_rollout_gp_" if use_seg else "k_rollout_gpt_"
-        if arm_plan is not None:
-            # one arm per lane: sphere scenes, no (cross-arm) self pairs -- and fp32 I/O only by default.  Measured on one box, alternating
-            # (profiles/r06_ab_c5_arm_lanes.txt, _box1.txt): fp32 I/O 23.0 - 23.5 -> 20.5 - 22.7 us box to box, but fp16 I/O 21.0 -> 22.1 - 22.4 us and mixed 20.8 -> 22.2: at four
-            # wavefronts per SIMD the lone-wavefront latency drops (9.1 -> 7.6 us) while every wavefront of 32 samples costs 1.9 us of issue
-            # time against 2.3 us for 64 samples -- 19 % more instructions per arm (SQ counters: profiles/r06_sq_c5_arm_vs_robot_lane.txt).
-            # TRK_GP_ARM_LANES=0 / 1 in the environment forces the choice (read per launch, like TRK_STREAM_STORES: same-process A/Bs).
-            out.append("    {")
-            out.append("        const char* env_ = std::getenv(\"TRK_GP_ARM_LANES\");")
-            out.append("        const bool want_ = env_ ? std::atoi(env_) != 0 : a.io_f16 == TRK_IO_F32;")
-            out.append("        if (a.w.w_self == 0.0f && scene_is_fast(a.C) && want_) {")
-            out.append("            const unsigned grid2 = (unsigned)((a.n + SPEC_WAVES * (TRK_WAVE / 2) - 1) / (SPEC_WAVES * (TRK_WAVE / 2)));")
-            out.append("            auto ga = [&](auto io) {")
-            out.append("                using IOT = decltype(io);")
-            out.append("                if (base_identity) hipLaunchKernelGGL((k_rollout_gpa_bi<IOT>), dim3(grid2), dim3(SPEC_BLOCK), 0, st, a);")
-            out.append("                else hipLaunchKernelGGL((k_rollout_gpa_bg<IOT>), dim3(grid2), dim3(SPEC_BLOCK), 0, st, a);")
-            out.append("            };")
-            out.append("            if (a.io_f16 == TRK_IO_F16) ga(_Float16{}); else if (a.io_f16 == TRK_IO_F16_G32) ga(HalfG32{}); else ga(float{});")
-            out.append("            return 0;")
-            out.append("        }")
-            out.append("    }")
-        out.append("    auto go = [&](auto io, auto c0) {")
-        out.append("        using IOT = decltype(io);")
-        out.append(f"        if (base_identity) hipLaunchKernelGGL(({kn}bi<IOT, decltype(c0)::value>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-        out.append(f"        else hipLaunchKernelGGL(({kn}bg<IOT, decltype(c0)::value>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-        out.append("    };")
-        out.append(f"    auto sw = [&](auto io) {{ if ({sw}) go(io, std::true_type{{}}); else go(io, std::false_type{{}}); }};")
-        out.append("    if (a.io_f16 == TRK_IO_F16) sw(_Float16{}); else if (a.io_f16 == TRK_IO_F16_G32) sw(HalfG32{}); else sw(float{});")
-        out.append("    return 0;")
-        out.append("}")
-    out.append("static void launch_posbwd(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {")
-    out.append("    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);")
-    out.append("    if (base_identity) hipLaunchKernelGGL(k_posbwd_bi, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-    out.append("    else hipLaunchKernelGGL(k_posbwd_bg, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-    out.append("}")
-    out.append("static void launch_coll(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {")
-    out.append("    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);")
-    out.append("    if (base_identity) hipLaunchKernelGGL(k_coll_bi, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-    out.append("    else hipLaunchKernelGGL(k_coll_bg, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-    out.append("}")
-    out.append("static void launch_fkh(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {")
-    out.append("    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);")
-    out.append("    if (base_identity) hipLaunchKernelGGL(k_fkh_bi, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-    out.append("    else hipLaunchKernelGGL(k_fkh_bg, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-    out.append("}")
-    if fkhbwd_ok:
-        out.append("static void launch_fkhbwd(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {")
-        out.append("    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);")
-        out.append("    if (base_identity) hipLaunchKernelGGL(k_fkhbwd_bi, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-        out.append("    else hipLaunchKernelGGL(k_fkhbwd_bg, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-        out.append("}")
-    if fields_ok:
-        out.append("static void launch_fields(const SpecEntry*, const SpecArgs& a, int, hipStream_t st) {      // coll_out set: the boolean fields")
-        out.append("    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);")
-        out.append("    if (a.coll_out) hipLaunchKernelGGL(k_collf, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-        out.append("    else hipLaunchKernelGGL(k_fields, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-        out.append("}")
-    out.append("static void launch_fk1(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {")
-    out.append("    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);")
-    out.append("    if (base_identity) hipLaunchKernelGGL(k_fk1_bi, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-    out.append("    else hipLaunchKernelGGL(k_fk1_bg, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-    out.append("}")
-    if ik_ok:
-        out.append("static void launch_ik(const SpecEntry*, const IkArgs& a, int base_identity, hipStream_t st) {")
-        out.append("    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);")
-        out.append("    if (base_identity) hipLaunchKernelGGL(k_ik_bi, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-        out.append("    else hipLaunchKernelGGL(k_ik_bg, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-        out.append("}")
-    if ikgn_ok:
-        out.append("static void launch_ikgn(const SpecEntry*, const IkGnArgs& a, int base_identity, hipStream_t st) {")
-        out.append("    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);")
-        out.append("    if (base_identity) hipLaunchKernelGGL(k_ikgn_bi, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-        out.append("    else hipLaunchKernelGGL(k_ikgn_bg, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-        out.append("}")
-    out.append("static void launch_jac(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {")
-    out.append("    const unsigned grid = (unsigned)((a.n + TRK_WAVE - 1) / TRK_WAVE);")
-    if direct:
-        out.append(f"    const size_t lds = sizeof(float) * (size_t)TRK_WAVE * {6 * D};")
+    return out
+
+
+def _rjac_launcher_lines(u: _LinkUnit) -> List[str]:
+    """fused rollout + geometric Jacobian of the tracked link (trk_rollout_jacobian_cost_grad): fp32 I/O, positions wanted; returns 1
+    when this call is not served (the C ABI then runs the two launches).  Ring-staged units instantiate JAC with positions (POS = true)
+    only; the others take the positions as a run-time option."""
+    pos_t = "true, " if u.chunked else ""
+    out = ["static int launch_rjac(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {",
+           f"    if (a.io_f16 != TRK_IO_F32 || {'!a.link_pos || ' if u.chunked else ''}a.jac_link != {u.tmpl.ee_link}) return 1;",
+           "    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);",
+           f"    if ({u.scene_switch}) {{",
+           f"        if (base_identity) hipLaunchKernelGGL((k_rollout_bi<float, {pos_t}true, true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+           f"        else hipLaunchKernelGGL((k_rollout_bg<float, {pos_t}true, true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+           "    } else {",
+           f"        if (base_identity) hipLaunchKernelGGL((k_rollout_bi<float, {pos_t}false, true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+           f"        else hipLaunchKernelGGL((k_rollout_bg<float, {pos_t}false, true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+           "    }",
+           "    return 0;",
+           "}"]
+    return out
+
+
+def _gp_launcher_lines(u: _LinkUnit) -> List[str]:
+    out = ["static int launch_gp(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {",
+           "    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);"]
+    if u.use_seg and u.gp_cross_pairs:
+        out.append("    if (a.w.w_self != 0.0f) return 1;      // self pairs between independently scheduled subtrees: the two-launch form serves them")
+    kn = "k_rollout_gp_" if u.use_seg else "k_rollout_gpt_"
+    if u.arm_plan is not None:
+        # one arm per lane: sphere scenes, no (cross-arm) self pairs -- and fp32 I/O only by default.  Measured on one box, alternating
+        # (profiles/r06_ab_c5_arm_lanes.txt, _box1.txt): fp32 I/O 23.0 - 23.5 -> 20.5 - 22.7 us box to box, but fp16 I/O 21.0 -> 22.1 - 22.4 us and mixed 20.8 -> 22.2: at four
+        # wavefronts per SIMD the lone-wavefront latency drops (9.1 -> 7.6 us) while every wavefront of 32 samples costs 1.9 us of issue
+        # time against 2.3 us for 64 samples -- 19 % more instructions per arm (SQ counters: profiles/r06_sq_c5_arm_vs_robot_lane.txt).
+        # TRK_GP_ARM_LANES=0 / 1 in the environment forces the choice (read per launch, like TRK_STREAM_STORES: same-process A/Bs).
+        out += ["    {",
+                "        const char* env_ = std::getenv(\"TRK_GP_ARM_LANES\");",
+                "        const bool want_ = env_ ? std::atoi(env_) != 0 : a.io_f16 == TRK_IO_F32;",
+                "        if (a.w.w_self == 0.0f && scene_is_fast(a.C) && want_) {",
+                "            const unsigned grid2 = (unsigned)((a.n + SPEC_WAVES * (TRK_WAVE / 2) - 1) / (SPEC_WAVES * (TRK_WAVE / 2)));",
+                "            auto ga = [&](auto io) {",
+                "                using IOT = decltype(io);",
+                "                if (base_identity) hipLaunchKernelGGL((k_rollout_gpa_bi<IOT>), dim3(grid2), dim3(SPEC_BLOCK), 0, st, a);",
+                "                else hipLaunchKernelGGL((k_rollout_gpa_bg<IOT>), dim3(grid2), dim3(SPEC_BLOCK), 0, st, a);",
+                "            };",
+                "            if (a.io_f16 == TRK_IO_F16) ga(_Float16{}); else if (a.io_f16 == TRK_IO_F16_G32) ga(HalfG32{}); else ga(float{});",
+                "            return 0;",
+                "        }",
+                "    }"]
+    return out + ["    auto go = [&](auto io, auto c0) {",
+                  "        using IOT = decltype(io);",
+                  f"        if (base_identity) hipLaunchKernelGGL(({kn}bi<IOT, decltype(c0)::value>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+                  f"        else hipLaunchKernelGGL(({kn}bg<IOT, decltype(c0)::value>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+                  "    };",
+                  f"    auto sw = [&](auto io) {{ if ({u.scene_switch}) go(io, std::true_type{{}}); else go(io, std::false_type{{}}); }};",
+                  "    if (a.io_f16 == TRK_IO_F16) sw(_Float16{}); else if (a.io_f16 == TRK_IO_F16_G32) sw(HalfG32{}); else sw(float{});",
+                  "    return 0;",
+                  "}"]
+
+
+def _link_host_lines(u: _LinkUnit) -> List[str]:
+    """the unit's host half: launchers and its registry entry (SpecEntry: positional, in the order of its fields)"""
+    kin, tmpl, D = u.kin, u.tmpl, u.D
+    obj = ", ".join(str(i) for i in tmpl.obj_links) or "0"
+    pairs = ", ".join(f"{a}, {b}" for a, b in tmpl.self_pairs) or "0"
+    vsrc = ", ".join(f"{r[0]}, {r[1]}" for r in tmpl.virtual) or "0"
+    vw = ", ".join(f"{flit(float(np.float32(r[2])))}, {flit(float(np.float32(r[3])))}" for r in tmpl.virtual) or "0.0f"
+    out = ["#ifndef __HIPCC_RTC__          // the unit's host half: launchers and its registry entry",
+           f"static const int32_t kObjLinks[] = {{{obj}}};",
+           f"static const int32_t kSelfPairs[] = {{{pairs}}};",
+           f"static const int32_t kVirtualSrc[] = {{{vsrc}}};",
+           f"static const float kVirtualW[] = {{{vw}}};"]
+    out += _rollout_launcher_lines(u)
+    if u.jacf_ok:
+        out += _rjac_launcher_lines(u)
+    if u.gpt_ok:
+        out += _gp_launcher_lines(u)
+    out += _launcher_lines("posbwd") + _launcher_lines("coll") + _launcher_lines("fkh")
+    if u.fkhbwd_ok:
+        out += _launcher_lines("fkhbwd")
+    if u.fields_ok:
+        out += ["static void launch_fields(const SpecEntry*, const SpecArgs& a, int, hipStream_t st) {      // coll_out set: the boolean fields",
+                "    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);",
+                "    if (a.coll_out) hipLaunchKernelGGL(k_collf, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+                "    else hipLaunchKernelGGL(k_fields, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+                "}"]
+    out += _launcher_lines("fk1")
+    if u.ik_ok:
+        out += _launcher_lines("ik", "IkArgs")
+    if u.ikgn_ok:
+        out += _launcher_lines("ikgn", "IkGnArgs")
+    if u.jac_direct:
+        jac_lds = [f"    const size_t lds = sizeof(float) * (size_t)TRK_WAVE * {6 * D};"]
     else:
-        out.append("    const int rstride = (6 * a.jac_n_cols + 3) | 1;")
-        out.append("    const size_t lds = sizeof(float) * ((size_t)TRK_WAVE * (rstride > D ? rstride : D) + TRK_MAX_DOFS);")
-    out.append("    if (base_identity) hipLaunchKernelGGL(k_jac_bi, dim3(grid), dim3(TRK_WAVE), lds, st, a);")
-    out.append("    else hipLaunchKernelGGL(k_jac_bg, dim3(grid), dim3(TRK_WAVE), lds, st, a);")
-    out.append("}")
-    if ajac_ok:
-        out.append("static void launch_ajac(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {")
-        out.append("    const unsigned grid = (unsigned)((a.n + TRK_WAVE - 1) / TRK_WAVE);")
-        out.append(f"    const size_t lds = sizeof(float) * (size_t)TRK_WAVE * {max(arp.stride, D)};")
-        out.append("    if (base_identity) hipLaunchKernelGGL(k_ajac_bi, dim3(grid), dim3(TRK_WAVE), lds, st, a);")
-        out.append("    else hipLaunchKernelGGL(k_ajac_bg, dim3(grid), dim3(TRK_WAVE), lds, st, a);")
-        out.append("}")
-    jac_ok = (TRK_WAVE_ * JAC_LDS + 32) * 4 <= 64 * 1024            # default dynamic-LDS limit of a launch
+        jac_lds = ["    const int rstride = (6 * a.jac_n_cols + 3) | 1;",
+                   "    const size_t lds = sizeof(float) * ((size_t)TRK_WAVE * (rstride > D ? rstride : D) + TRK_MAX_DOFS);"]
+    out += _launcher_lines("jac", per_wave=True, lds=jac_lds)         # (k_jac is compiled whatever jac_ok: the entry decides)
+    if u.ajac_ok:
+        out += _launcher_lines("ajac", per_wave=True, lds=[f"    const size_t lds = sizeof(float) * (size_t)TRK_WAVE * {max(u.arp.stride, D)};"])
+
+    def slot(ok: bool, name: str) -> str:
+        return name if ok else "nullptr"
     out.append(f"static const SpecEntry kEntry = {{SPEC_ENTRY_STAMP, 0x{model_hash(kin):016x}ull, L, D, NL, kObjLinks, "
-               f"{len(tmpl.self_pairs)}, kSelfPairs, {tmpl.ee_link}, \"{ident}\", launch, 0, 0ull, launch_posbwd, {tmpl.ee2_link}, "
-               f"{'launch_jac' if jac_ok else 'nullptr'}, launch_coll, launch_fkh, {'launch_fkhbwd' if fkhbwd_ok else 'nullptr'}, "
-               f"{'launch_ik' if ik_ok else 'nullptr'}, launch_fk1, {'launch_fields' if fields_ok else 'nullptr'}, "
-               f"{len(tmpl.virtual)}, kVirtualSrc, kVirtualW, {'launch_ikgn' if ikgn_ok else 'nullptr'}, {'launch_gp' if (gp_ok or gpt_ok) else 'nullptr'}, nullptr, "
-               f"{'launch_rjac' if jacf_ok else 'nullptr'}, {'launch_ajac' if ajac_ok else 'nullptr'}}};")
+               f"{len(tmpl.self_pairs)}, kSelfPairs, {tmpl.ee_link}, \"{u.ident}\", launch, 0, 0ull, launch_posbwd, {tmpl.ee2_link}, "
+               f"{slot(u.jac_ok, 'launch_jac')}, launch_coll, launch_fkh, {slot(u.fkhbwd_ok, 'launch_fkhbwd')}, "
+               f"{slot(u.ik_ok, 'launch_ik')}, launch_fk1, {slot(u.fields_ok, 'launch_fields')}, "
+               f"{len(tmpl.virtual)}, kVirtualSrc, kVirtualW, {slot(u.ikgn_ok, 'launch_ikgn')}, {slot(u.gpt_ok, 'launch_gp')}, nullptr, "
+               f"{slot(u.jacf_ok, 'launch_rjac')}, {slot(u.ajac_ok, 'launch_ajac')}}};")
     out.append("static struct Reg { Reg() { trk_spec_register(&kEntry); } } reg;")
     out.append("#endif      // !__HIPCC_RTC__")
+    return out
+
+
+def _link_meta(u: _LinkUnit) -> dict:
+    """what a loader of the unit's DEVICE code alone needs (jit.py's hipRTC path, where libtrk.so's generic launchers play the host
+    half): the name expressions of the kernels those launchers call, and the traits that tell them which exist"""
+    ns = f"spec_{u.ident}::"
+    rtc_gp = u.gpt_ok and not u.use_seg           # the generic GP launcher runs the tree schedule
+    sw_sets = [[]]
+    for _ in _rollout_switches(u):
+        sw_sets = [v + [b] for v in sw_sets for b in ("false", "true")]
+    per_base = [("posbwd", True), ("coll", True), ("fkh", True), ("fk1", True), ("fkhbwd", u.fkhbwd_ok), ("ik", u.ik_ok),
+                ("ikgn", u.ikgn_ok), ("jac", u.jac_ok)]
+    names = []
+    for b in ("bi", "bg"):
+        for io in ("float", "_Float16", "HalfG32"):
+            names += [f"{ns}k_rollout_{b}<{', '.join([io] + sw)}>" for sw in sw_sets]
+            if rtc_gp:
+                names += [f"{ns}k_rollout_gpt_{b}<{io}, {v}>" for v in ("false", "true")]
+        names += [f"{ns}k_{stem}_{b}" for stem, ok in per_base if ok]
+    if u.fields_ok:
+        names += [f"{ns}k_fields", f"{ns}k_collf"]
+    return dict(ident=u.ident, kernels=names, chunked=bool(u.chunked), fast_switch=bool(u.fast_switch), fkhbwd_ok=bool(u.fkhbwd_ok),
+                fields_ok=bool(u.fields_ok), ik_ok=bool(u.ik_ok), ikgn_ok=bool(u.ikgn_ok), jac_ok=bool(u.jac_ok),
+                jac_direct=bool(u.jac_direct), gp_ok=bool(rtc_gp), n_links=u.L, n_dofs=u.D)
+
+
+def generate_rollout_source(kin: KinModel, tmpl: CollisionTemplate, ident: str, snap: float = SNAP, meta: Optional[dict] = None) -> str:
+    """meta (optional): receives what a loader of the unit's DEVICE code alone needs (jit.py's hipRTC fall-back: the host half of the
+    unit -- launchers, registry entry -- is then played by libtrk.so's generic launchers): the kernels' name expressions and the
+    unit's traits."""
+    u = _LinkUnit(kin, tmpl, ident, snap)
+    L, D = u.L, u.D
+    out: List[str] = [f"// GENERATED by torch_robotics_amd/codegen.py for model '{kin.name}' ({L} links, {D} DOF) -- do not edit."]
+    # Value-changing-but-bounded FP freedoms for this unit (NOT finite-math-only): reassociation + contraction turn
+    # mul/add chains into FMAs, 1/x may use v_rcp.  Same-box A/B on the headline kernel: 11.55 -> 11.06 us; deviation from
+    # the fp64 oracle on 65 536 samples unchanged for positions (2.5e-7) and 6.4e-7 -> 1.0e-6 of max for the gradient
+    # (tools/accuracy_check.py).  The attached-point generator does not use it (its kernels got slower: register pressure).
+    out.append("#pragma clang fp reassociate(on) contract(fast) reciprocal(on)")
+    out.append('#include "trk_spec_common.h"')
+    out.append(f"namespace spec_{ident} {{")
+    out.append(f"constexpr int L = {L}, D = {D}, NL = {u.NL};")
+    out.append(f'static_assert(TRK_OBJ_TICK_SLOTS == {OBJ_TICK_SLOTS}, "chunk numbering of this unit assumes another TRK_OBJ_TICK_SLOTS");')
+    if u.chunked:
+        out.append("template <class R> struct RingTail {      // tick slot CH of the objectives -> store piece CH of the tail chunk")
+        out.append("    const R& r;")
+        out.append("    template <int CH> __device__ __forceinline__ void chunk() const { r.template piece<R::NFULL, CH>(); }")
+        out.append("    template <int A, int B> __device__ __forceinline__ void range() const { if constexpr (A < B && A < R::NP) { chunk<A>(); range<A + 1, B>(); } }")
+        out.append("    template <int A> __device__ __forceinline__ void rest() const { range<A, R::NP>(); }")
+        out.append("};")
+
+    def per_base(emit, *args):
+        for base_identity in (True, False):
+            out.extend(emit(u, base_identity, *args) + [""])
+    per_base(_rollout_kernel, False)
+    if u.gpt_ok:
+        per_base(_rollout_kernel, True)
+    if u.arm_plan is not None:
+        out.extend(_arm_lane_kernel_lines(kin, tmpl, u.arm_plan, snap))
+    if u.use_seg:
+        per_base(_gp_segments_kernel)
+    if u.posbwd_chunked:
+        out.extend(_chunked_posbwd_lines(kin, list(range(L)), np.zeros((L, 3), np.float32), snap, w_expr=str(3 * L)))
+    else:
+        per_base(_posbwd_kernel)
+    per_base(_coll_kernel)
+    per_base(_fkh_kernel)
+    if u.fields_ok:
+        out.extend(_fields_kernel(u, boolean=False) + [""] + _fields_kernel(u, boolean=True) + [""])
+    per_base(_fk1_kernel)
+    if u.fkhbwd_ok:
+        per_base(_fkhbwd_kernel)
+    if u.ik_ok:
+        per_base(_ik_kernel)
+    if u.ikgn_ok:
+        per_base(_ikgn_kernel)
+    per_base(_jac_kernel)
+    if u.ajac_ok:
+        out.append("#ifndef __HIPCC_RTC__          // (linked / dlopen-ed units only: a code-object unit keeps the table-driven kernel)")
+        per_base(_ajac_kernel)
+        out.append("#endif      // !__HIPCC_RTC__")
+    out += _link_host_lines(u)
     out.append(f"}}  // namespace spec_{ident}")
     if meta is not None:
-        ns = f"spec_{ident}::"
-        ios = ("float", "_Float16", "HalfG32")
-        n_sw = (1 if chunked else 0) + 1
-        sw_sets = [[]]
-        for _ in range(n_sw):
-            sw_sets = [v + [b] for v in sw_sets for b in ("false", "true")]
-        names = []
-        for b in ("bi", "bg"):
-            for io in ios:
-                for sw in sw_sets:
-                    names.append(f"{ns}k_rollout_{b}<{', '.join([io] + sw)}>")
-                if gpt_ok and not use_seg:
-                    names += [f"{ns}k_rollout_gpt_{b}<{io}, {v}>" for v in ("false", "true")]
-            names += [f"{ns}k_posbwd_{b}", f"{ns}k_coll_{b}", f"{ns}k_fkh_{b}", f"{ns}k_fk1_{b}"]
-            if fkhbwd_ok:
-                names.append(f"{ns}k_fkhbwd_{b}")
-            if ik_ok:
-                names.append(f"{ns}k_ik_{b}")
-            if ikgn_ok:
-                names.append(f"{ns}k_ikgn_{b}")
-            if jac_ok:
-                names.append(f"{ns}k_jac_{b}")
-        if fields_ok:
-            names += [f"{ns}k_fields", f"{ns}k_collf"]
-        meta.update(ident=ident, kernels=names, chunked=bool(chunked), fast_switch=bool(D > 8), fkhbwd_ok=bool(fkhbwd_ok), fields_ok=bool(fields_ok),
-                    ik_ok=bool(ik_ok), ikgn_ok=bool(ikgn_ok), jac_ok=bool(jac_ok), jac_direct=bool(direct), gp_ok=bool(gpt_ok and not use_seg),
-                    n_links=L, n_dofs=D)
+        meta.update(_link_meta(u))
     return "\n".join(out) + "\n"
 
 
@@ -2405,10 +2236,8 @@ class PointsTemplate:
 CHUNKED_STAGING_MIN_FLOATS = 80       # link kernels with more position floats per sample than this stream them out in chunks
 LINK_OBJ_GROUP_MAX = 12    # link kernels: up to this many collision links are scored in one scene evaluation (more ILP: dual Panda 5+5 was ~1 us slower) ...
 LINK_OBJ_GROUP = 5         # ... more are split into groups of about this size
-CHUNK_FLOATS = 36          # 12 columns: 144 B per sample and chunk, a multiple of 16 B (rounds 2 - 4; the baseline of tools/ab_chunk_floats.sh)
 # The fused point rollout stages 64 floats per sample and chunk (256 B: one store instruction writes whole 256-byte segments of 4 / 2 / 1
-# samples, and the lane -> (sample, vector) map is a shift).  Same-box A/B (tools/ab_chunk_floats.sh, profiles/r05_ab_chunk_floats.txt),
-# 36 -> 64 floats: 45 spheres 67.0 -> 60.9 us, grasped box 44.6 -> 41.9, both 98.1 -> 86.3; positions only 36.2 -> 30.5, 25.0 -> 21.2,
+# samples, and the lane -> (sample, vector) map is a shift).  Same-box A/B (profiles/r05_ab_chunk_floats.txt), 36 -> 64 floats: 45 spheres 67.0 -> 60.9 us, grasped box 44.6 -> 41.9, both 98.1 -> 86.3; positions only 36.2 -> 30.5, 25.0 -> 21.2,
 # 61.1 -> 46.5 (a row's 144-byte pieces were partial lines for two instructions each).  17.4 KB of LDS per wavefront: still two workgroups per CU.
 ROLLOUT_CHUNK_FLOATS = 64
 RING_FLOATS = 32           # link kernels with ring staging (RingFlusher in trk_spec_common.h): floats per chunk
@@ -2453,7 +2282,7 @@ def ring_plan(W: int) -> RingPlan:
     return RingPlan(W=W, V=V, aligned=False, hx=0, n_full=n_full, tail=W - RING_FLOATS * n_full, pieces=64 // (64 // (RING_FLOATS // V)))
 
 
-OBJ_GROUP = int(os.environ.get("TRK_EXP_OBJ_GROUP", "6"))     # points evaluated against the scene together (register arrays of this size)
+OBJ_GROUP = 6       # points evaluated against the scene together (register arrays of this size; 4 / 8 / 12: within the noise, r05_ab_obj_group.txt)
 
 
 def _chunked_posbwd_lines(kin: KinModel, point_link, point_offset, snap: float = SNAP, w_expr: Optional[str] = None) -> List[str]:
@@ -2472,7 +2301,7 @@ def _chunked_posbwd_lines(kin: KinModel, point_link, point_offset, snap: float =
     pos_of = {int(kin.order[p]): p for p in range(L)}
     cols_of_link: Dict[int, List[int]] = {i: [c for c in range(P) if pl[c] == i] for i in range(L)}
     masked = _masked_factory(kin)
-    BNF = int(os.environ.get("TRK_EXP_BWD_CHUNK_FLOATS", str(ROLLOUT_CHUNK_FLOATS)))  # 36 -> 64 measured 43.7 -> 42.8, 21.3 -> 19.9, 66.7 -> 47.5 us
+    BNF = ROLLOUT_CHUNK_FLOATS      # 36 -> 64 measured 43.7 -> 42.8, 21.3 -> 19.9, 66.7 -> 47.5 us
     BLS = BNF if BNF % 32 else BNF + 4
     out: List[str] = []
     # ---- explicit reverse mode of the point positions (trk_fk_points_backward): FK again, the adjoint rows arrive through
@@ -2607,9 +2436,8 @@ def generate_points_rollout_source(kin: KinModel, pt: PointsTemplate, ident: str
     masked = _masked_factory(kin)
     # the rollout's chunk: NF floats of every sample's row leave together; LS = the per-lane stride of the staging buffer (a multiple of
     # 4 floats for the 16-byte reads, and NOT a multiple of 32: the per-lane row writes would all hit one bank)
-    NF = int(os.environ.get("TRK_EXP_CHUNK_FLOATS", str(ROLLOUT_CHUNK_FLOATS)))
+    NF = ROLLOUT_CHUNK_FLOATS
     LS = NF if NF % 32 else NF + 4
-    WIDE = (not link_mode) and os.environ.get("TRK_EXP_CHUNK_WIDE", "0") != "0"
     lds_per_lane = max(LS, D)
     joint_links = [i for i in range(1, L) if int(kin.joint_type[i]) != JOINT_FIXED]
     ancestors: Dict[int, List[int]] = {}
@@ -2736,11 +2564,9 @@ def generate_points_rollout_source(kin: KinModel, pt: PointsTemplate, ident: str
                     E.raw(f"    row[{f - chunk_start}] = {E.expr(colpos[c][k])};")
                     if f + 1 - chunk_start == NF or f + 1 == W:
                         nf = f + 1 - chunk_start
-                        # vector width of this chunk's stores.  The LDS side is always aligned (LS and the chunk start are multiples of
-                        # 4 floats); the HBM side is aligned only when the row length is a multiple of the vector too -- this chip takes
-                        # the 4- / 8-byte-aligned wide stores of the other row lengths as they are (half / a quarter of the instructions)
-                        Vc = V if not WIDE else (4 if nf % 4 == 0 else (2 if nf % 2 == 0 else 1))
-                        E.raw(f"    if (pos_out) spec_flush_chunk<W, {nf}, {LS}, {Vc}, IO, {'true' if Vc > V else 'false'}>(pos_out, base, {chunk_start}, rows, lane, lds);")
+                        # vector width V of this chunk's stores: the row's (wider stores at 4- / 8-byte alignment for the odd row lengths
+                        # are legal on this chip and measured the same time)
+                        E.raw(f"    if (pos_out) spec_flush_chunk<W, {nf}, {LS}, {V}, IO, false>(pos_out, base, {chunk_start}, rows, lane, lds);")
                         chunk_start = f + 1
             # ---- objects / workspace box on this link's collision columns, a few at a time
             ocols = [c for c in cols if c in obj_rank]
@@ -2877,11 +2703,7 @@ def _points_entry_lines(kin: KinModel, pt: PointsTemplate, ident: str, link_mode
     else:
         out.append("    launch_io<float>(a, base_identity, st);")
     out.append("}")
-    out.append("static void launch_posbwd(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {")
-    out.append("    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);")
-    out.append("    if (base_identity) hipLaunchKernelGGL(k_posbwd_bi, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-    out.append("    else hipLaunchKernelGGL(k_posbwd_bg, dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-    out.append("}")
+    out += _launcher_lines("posbwd")
     n_points = 0 if link_mode else len(pt.point_link)
     phash = 0 if link_mode else points_hash(pt.point_link, pt.point_offset)
     out.append(f"static const SpecEntry kEntry = {{SPEC_ENTRY_STAMP, 0x{model_hash(kin):016x}ull, {kin.n_links}, {kin.n_dofs}, {len(pt.obj_cols)}, kObjCols, "
