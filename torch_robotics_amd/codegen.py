@@ -450,14 +450,14 @@ def _arm_lane_kernel_lines(kin: KinModel, tmpl: CollisionTemplate, plan: ArmLane
         E.raw("    constexpr int WAVE_B0 = Img::BYTES > 2 * Raw::BYTES ? Img::BYTES : 2 * Raw::BYTES;")
         E.raw("    constexpr int WAVE_B = ((WAVE_B0 > GQ_B ? WAVE_B0 : GQ_B) + 15) / 16 * 16;      // one region per wavefront: raw tiles -> gqd tile -> image -> gq tile")
         E.raw("    __shared__ __attribute__((aligned(16))) unsigned char lds_all[SPEC_WAVES * (WAVE_B + TRK_LDS_SPHERES * 16) + SPEC_WAVES * 4];")
-        E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
-        E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);")
+        E.raw("    const int lane = __builtin_amdgcn_workitem_id_x() & (TRK_WAVE - 1);")
+        E.raw("    const int wave = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_workitem_id_x() / TRK_WAVE);")
         E.raw("    unsigned char* wl = lds_all + wave * WAVE_B;")
         E.raw("    float* lds = reinterpret_cast<float*>(wl);")
         E.raw("    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_WAVES * WAVE_B) + wave * TRK_LDS_SPHERES;")
         E.raw("    float* wsum = reinterpret_cast<float*>(lds_all + SPEC_WAVES * (WAVE_B + TRK_LDS_SPHERES * 16));      // the wavefronts' cost sums: two of them make one 64-sample block")
         E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);   // waited for together with the rows below")
-        E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;     // index of this wave's 32-sample block")
+        E.raw("    const int64_t wblock = (int64_t)__builtin_amdgcn_workgroup_id_x() * SPEC_WAVES + wave;     // index of this wave's 32-sample block")
         E.raw("    const int64_t base_s = wblock * ROWS, base_h = wblock * TRK_WAVE;   // first sample; first half row of the (2N, DA) view")
         E.raw("    const int rows_s = (int)max((int64_t)0, min((int64_t)ROWS, A.n - base_s)), rows = 2 * rows_s;")
         E.raw("    const bool odd = (lane & 1) != 0;                                   // the arm this lane evaluates")
@@ -769,13 +769,13 @@ def _kernel_head(E: Emitter, kname: str, occupancy, lds_lane, args: str = "SpecA
     """signature, the static LDS (lds_lane floats per lane; spheres: plus the wavefronts' sphere tables) and the wavefront's rows"""
     E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, {occupancy}) {kname}({args} A) {{")
     E.raw(f"    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * {lds_lane}{' + SPEC_WAVES * TRK_LDS_SPHERES * 4' if spheres else ''}];")
-    E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
-    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);")
+    E.raw("    const int lane = __builtin_amdgcn_workitem_id_x() & (TRK_WAVE - 1);")
+    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_workitem_id_x() / TRK_WAVE);")
     E.raw(f"    float* lds = lds_all + wave * (TRK_WAVE * {lds_lane});")
     if spheres:
         E.raw(f"    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * {lds_lane}) + wave * TRK_LDS_SPHERES;")
         E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);   // waited for together with the rows below")
-    E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;")
+    E.raw("    const int64_t wblock = (int64_t)__builtin_amdgcn_workgroup_id_x() * SPEC_WAVES + wave;")
     E.raw("    const int64_t base = wblock * TRK_WAVE;")
     E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
 
@@ -1185,15 +1185,15 @@ def _rollout_kernel(u: _LinkUnit, base_identity: bool, GPT: bool) -> List[str]:
     E.raw(f"    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * {lds_lane} + SPEC_WAVES * (TRK_LDS_SPHERES * 4 + (BOX ? TRK_LDS_PRIMS * 8 : 0))];")
     E.raw("    typedef typename IoTraits<IO>::Q IOQ;      // q, link_pos in HBM")
     E.raw("    typedef typename IoTraits<IO>::G IOG;      // gq in HBM (fp16 q: scaled by A.grad_scale, fp16 stores saturate)")
-    E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
-    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);   // wave-uniform -> SGPR")
+    E.raw("    const int lane = __builtin_amdgcn_workitem_id_x() & (TRK_WAVE - 1);")
+    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_workitem_id_x() / TRK_WAVE);   // wave-uniform -> SGPR")
     E.raw(f"    float* lds = lds_all + wave * (TRK_WAVE * {lds_lane});")
     E.raw(f"    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * {lds_lane}) + wave * (TRK_LDS_SPHERES + (BOX ? 2 * TRK_LDS_PRIMS : 0));")
     E.raw("    float4* lds_prm = BOX ? lds_sph + TRK_LDS_SPHERES : nullptr;        // box scenes: the primitive records, for the winning box's gather")
     E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);   // waited for together with the rows below")
     E.raw("    SpheresInFlight prm{};")
     E.raw("    if constexpr (BOX) prm = spec_load_prims_issue(A.C, lane);")
-    E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;     // index of this wave's 64-sample block")
+    E.raw("    const int64_t wblock = (int64_t)__builtin_amdgcn_workgroup_id_x() * SPEC_WAVES + wave;     // index of this wave's 64-sample block")
     E.raw("    const int64_t base = wblock * TRK_WAVE;")
     E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
     E.raw("    spec_stamp(A.stamps, wblock, 0, lane);")
@@ -1313,8 +1313,8 @@ def _gp_segments_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     E.raw("    constexpr int WAVE_B = ACC_B + QL_B + IMG_B;")
     E.raw("    // the sphere (and primitive) tables are shared by the workgroup's wavefronts here: one barrier at the top, 192 bytes of LDS per wavefront saved")
     E.raw("    __shared__ __attribute__((aligned(16))) unsigned char lds_all[SPEC_WAVES * WAVE_B + TRK_LDS_SPHERES * 16 + (BOX ? TRK_LDS_PRIMS * 32 : 0)];")
-    E.raw("    const int lane = threadIdx.x & (TRK_WAVE - 1);")
-    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TRK_WAVE);")
+    E.raw("    const int lane = __builtin_amdgcn_workitem_id_x() & (TRK_WAVE - 1);")
+    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_workitem_id_x() / TRK_WAVE);")
     E.raw("    unsigned char* wl = lds_all + wave * WAVE_B;")
     E.raw("    float* acc = reinterpret_cast<float*>(wl);                      // [64][D] fp32: d cost / d q, prior first, then the segments")
     E.raw("    IOQ* qlater = reinterpret_cast<IOQ*>(wl + ACC_B);              // [64][DL]: raw q of the later segments' joints")
@@ -1324,11 +1324,11 @@ def _gp_segments_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     E.raw("    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_WAVES * WAVE_B);")
     E.raw("    float4* lds_prm = BOX ? lds_sph + TRK_LDS_SPHERES : nullptr;")
     E.raw("    {")
-    E.raw("        const int tid = threadIdx.x;")
+    E.raw("        const int tid = __builtin_amdgcn_workitem_id_x();")
     E.raw("        if (tid < TRK_LDS_SPHERES && tid < 2 * A.C.n_sphere_pairs) lds_sph[tid] = A.C.spheres[tid];")
     E.raw("        if constexpr (BOX) { if (A.C.n_box_objects > 0 && A.C.n_prims <= TRK_LDS_PRIMS && tid < 2 * A.C.n_prims) lds_prm[tid] = reinterpret_cast<const float4*>(A.C.prims)[tid]; }")
     E.raw("    }")
-    E.raw("    const int64_t wblock = (int64_t)blockIdx.x * SPEC_WAVES + wave;")
+    E.raw("    const int64_t wblock = (int64_t)__builtin_amdgcn_workgroup_id_x() * SPEC_WAVES + wave;")
     E.raw("    const int64_t base = wblock * TRK_WAVE;")
     E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
     E.raw("    // time steps: the block starts at step t0 of its trajectory (wave-uniform), a lane sits at (t0 + lane) mod H")
@@ -1794,8 +1794,8 @@ def _jac_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     E.raw("    extern __shared__ __attribute__((aligned(16))) float lds[];     // 64 x max(record stride, D) floats + the slot table")
     if not direct:
         E.raw("    const int rstride = (6 * A.jac_n_cols + 3) | 1;       // records only for the joints that get a column")
-    E.raw("    const int lane = threadIdx.x;")
-    E.raw("    const int64_t base = (int64_t)blockIdx.x * TRK_WAVE;")
+    E.raw("    const int lane = __builtin_amdgcn_workitem_id_x();")
+    E.raw("    const int64_t base = (int64_t)__builtin_amdgcn_workgroup_id_x() * TRK_WAVE;")
     E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
     E.raw("    float q[D];")
     E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
@@ -1876,8 +1876,8 @@ def _ajac_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     kname = "k_ajac_bi" if base_identity else "k_ajac_bg"
     E.raw(f"__global__ void __launch_bounds__(TRK_WAVE) {kname}(SpecArgs A) {{")
     E.raw(f"    extern __shared__ __attribute__((aligned(16))) float lds[];     // the wavefront's ring [64][{arp.stride}] (first: the q transpose)")
-    E.raw("    const int lane = threadIdx.x;")
-    E.raw("    const int64_t base = (int64_t)blockIdx.x * TRK_WAVE;")
+    E.raw("    const int lane = __builtin_amdgcn_workitem_id_x();")
+    E.raw("    const int64_t base = (int64_t)__builtin_amdgcn_workgroup_id_x() * TRK_WAVE;")
     E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
     E.raw("    float q[D];")
     E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")

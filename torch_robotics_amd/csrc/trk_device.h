@@ -952,6 +952,29 @@ __device__ __forceinline__ void frame_quat_wxyz(const float* R, float* out) {
     out[0] = qw * sc; out[1] = qx * sc; out[2] = qy * sc; out[3] = qz * sc;
 }
 
+// atan2f of finite arguments, instruction for instruction what the device library's atan2f compiles to on gfx950 (frexp-scaled
+// 2.5-ulp quotient min/max, odd polynomial, quadrant selects).  Written out because a unit built with -mno-amdgpu-ieee cannot
+// inline the library function: every call was an out-of-line s_swappc_b64 whose callee starts with a full s_waitcnt.
+__device__ __forceinline__ float trk_atan2f(float y, float x) {
+    const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
+    const float v = __builtin_fminf(ax, ay), u = __builtin_fmaxf(ax, ay);
+    const float r = __builtin_amdgcn_ldexpf(__builtin_amdgcn_frexp_mantf(v) * __builtin_amdgcn_rcpf(__builtin_amdgcn_frexp_mantf(u)),
+                                           __builtin_amdgcn_frexp_expf(v) - __builtin_amdgcn_frexp_expf(u));
+    const float t = r * r;
+    float p = fmaf(t, __uint_as_float(0x3b2d2a58u), __uint_as_float(0xbc7a590cu));
+    p = fmaf(t, p, __uint_as_float(0x3d29fb3fu));
+    p = fmaf(t, p, __uint_as_float(0xbd97d4d7u));
+    p = fmaf(t, p, __uint_as_float(0x3dd931b2u));
+    p = fmaf(t, p, __uint_as_float(0xbe1160e6u));
+    p = fmaf(t, p, __uint_as_float(0x3e4cb8bfu));
+    p = fmaf(t, p, __uint_as_float(0xbeaaaa62u));
+    float a = fmaf(r, t * p, r);                                            // atan(v / u)
+    a = ay > ax ? __uint_as_float(0x3fc90fdbu) - a : a;                     // pi/2 - a
+    a = x < 0.0f ? __uint_as_float(0x40490fdbu) - a : a;                    // pi - a
+    a = y == 0.0f ? ((int)__float_as_uint(x) < 0 ? __uint_as_float(0x40490fdbu) : 0.0f) : a;
+    return __builtin_copysignf(a, y);
+}
+
 // Rotation vector of a rotation matrix Re (row-major 3x3) for the Gauss-Newton IK residual (BUILD-DEFINED, oracle_impl.inc
 // orc_ik_gn_step): quaternion (w, v) by Frame.get_quaternion's trace method, sign chosen so that w >= 0, then
 // v / |v| * 2 atan2(|v|, w) -- well conditioned up to a rotation of pi, where |v| -> 1.
@@ -962,7 +985,7 @@ __device__ __forceinline__ void trk_rotvec(const float* Re, float* out) {
     const float w = __builtin_fminf(qe[0] * sgn, 1.0f);
     const float vx = qe[1] * sgn, vy = qe[2] * sgn, vz = qe[3] * sgn;
     const float nv = sqrtf(fmaf(vx, vx, fmaf(vy, vy, vz * vz)));
-    const float sc = 2.0f * atan2f(nv, w) / __builtin_fmaxf(nv, 1e-12f);
+    const float sc = 2.0f * trk_atan2f(nv, w) / __builtin_fmaxf(nv, 1e-12f);
     out[0] = vx * sc; out[1] = vy * sc; out[2] = vz * sc;
 }
 

@@ -439,24 +439,38 @@ template <int D, class IO>
 __device__ __forceinline__ void spec_load_q(const IO* __restrict__ q, int64_t base, int rows, int lane,
                                             float* lds, float (&qv)[D]) {
     // the wave's 64*D floats are one contiguous span: 16-byte loads (2 instructions for D = 7) into LDS, then a
-    // stride-D read back (D odd -> conflict-free); ragged / unaligned tails take the dword path
+    // stride-D read back (D odd -> conflict-free); ragged / unaligned tails take the dword path.
+    // Either path puts ALL of the wave's loads in flight before its first LDS write, and branch-free: a lane without an element of
+    // its own loads one that exists (the span's last vector, which it also writes back to where it belongs; q[0], dropped).  A
+    // load under `if (k < ..)` -- or a load whose only use is a store under such an `if`, which the compiler sinks into the branch
+    // -- cost a vmcnt(0) per chunk: the chunks, and the scene table loads issued before them, took one memory round trip each.
     const int64_t first = base * D;
     const IO* src = q + first;
-    constexpr int NV = TRK_WAVE * D / 4;
-    if (rows == TRK_WAVE && (TRK_WAVE * D) % 4 == 0 && ((reinterpret_cast<uintptr_t>(src) & IoQuad<IO>::kAlignMask) == 0)) {
+    constexpr int NV = TRK_WAVE * D / 4, NJ = (NV + TRK_WAVE - 1) / TRK_WAVE;
+    if (__builtin_expect(rows == TRK_WAVE && (TRK_WAVE * D) % 4 == 0 && ((reinterpret_cast<uintptr_t>(src) & IoQuad<IO>::kAlignMask) == 0), 1)) {
+        float4 v[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = lane + TRK_WAVE * j;
+            v[j] = IoQuad<IO>::load(src, k < NV ? k : NV - 1);
+        }
         float4* lds4 = reinterpret_cast<float4*>(lds);
 #pragma unroll
-        for (int j = 0; j < (NV + TRK_WAVE - 1) / TRK_WAVE; ++j) {
+        for (int j = 0; j < NJ; ++j) {
             const int k = lane + TRK_WAVE * j;
-            if (k < NV) lds4[k] = IoQuad<IO>::load(src, k);
+            lds4[k < NV ? k : NV - 1] = v[j];
         }
     } else {
         const int count = rows * D;
+        float v[D];
 #pragma unroll
         for (int j = 0; j < D; ++j) {
             const int k = lane + TRK_WAVE * j;
-            lds[k] = k < count ? (float)src[k] : 0.0f;
+            const float x = (float)*(k < count ? src + k : q);
+            v[j] = k < count ? x : 0.0f;
         }
+#pragma unroll
+        for (int j = 0; j < D; ++j) lds[lane + TRK_WAVE * j] = v[j];
     }
     spec_wave_sync();
 #pragma unroll
@@ -1029,9 +1043,11 @@ __device__ __forceinline__ RawRowsInFlight<D, IO, ROWS> spec_raw_rows_issue(cons
         const int k = lane + TRK_WAVE * j;
         r.v[j] = (r.fast && k < Raw::NV) ? reinterpret_cast<const trk_f4*>(src)[k] : trk_f4{0.0f, 0.0f, 0.0f, 0.0f};
     }
-    r.edge = (IO)0.0f;
-    if (lane < D && has_prev) r.edge = src[lane - D];                   // the D elements in front of the block
-    if (lane >= 32 && lane < 32 + D && has_next) r.edge = src[ROWS * D + (lane - 32)];
+    // the D elements in front of the block (lanes 0 .. D-1), the D behind it (lanes 32 ..): ONE load per lane, branch-free (the other
+    // lanes read in[0] and drop it) -- two conditional loads into one register cost a vmcnt(0) between them
+    const bool prev = lane < D && has_prev, next = lane >= 32 && lane < 32 + D && has_next;
+    const IO e = *(prev ? src + (lane - D) : next ? src + (ROWS * D + (lane - 32)) : in);
+    r.edge = prev || next ? e : (IO)0.0f;
     return r;
 }
 template <int D, class IO, int ROWS = TRK_WAVE>
@@ -1039,7 +1055,7 @@ __device__ __forceinline__ IO* spec_raw_rows_finish(const RawRowsInFlight<D, IO,
                                                     int lane, IO* tile) {
     typedef RawRowsInFlight<D, IO, ROWS> Raw;
     IO* body = tile + Raw::PAD;
-    if (r.fast) {
+    if (__builtin_expect(r.fast, 1)) {      // the ragged / unaligned path out of line, behind the transpose
         trk_f4* b4 = reinterpret_cast<trk_f4*>(body);
 #pragma unroll
         for (int j = 0; j < Raw::NJ; ++j) {
