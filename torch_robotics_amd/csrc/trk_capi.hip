@@ -1167,12 +1167,23 @@ int trk_cost_model_create(const TrkCostModelDesc* d, TrkCostModel** out) {
     // of the duplicate wins addresses the same centre (n_spheres stays the real count for every other path).
     if (spheres.size() & 1) spheres.push_back(spheres.back());
     if (!spheres.empty()) std::memcpy(blob.data() + o_sph, spheres.data(), sizeof(float4) * spheres.size());
+    // ranking origin o: the fp32-rounded centroid of the centres.  The ranking tables hold c' = c - o, rounded once from the double
+    // difference, and the kernels rank q = p - o (see scene_min_sdf), so the keys cancel |q|^2 instead of |p|^2.
+    float sph_o[3] = {0.0f, 0.0f, 0.0f};
+    float sph_rho2 = 0.0f;
     {
+        double acc[3] = {0.0, 0.0, 0.0};
+        for (const float4& sp : spheres) { acc[0] += sp.x; acc[1] += sp.y; acc[2] += sp.z; }
+        if (!spheres.empty())
+            for (int k = 0; k < 3; ++k) sph_o[k] = (float)(acc[k] / (double)spheres.size());
         float4* sel = reinterpret_cast<float4*>(blob.data() + o_sel);
         for (size_t k = 0; k < spheres.size(); ++k) {
             const float4& sp = spheres[k];
-            sel[k].x = -2.0f * sp.x; sel[k].y = -2.0f * sp.y; sel[k].z = -2.0f * sp.z;
-            sel[k].w = (float)((double)sp.x * sp.x + (double)sp.y * sp.y + (double)sp.z * sp.z);
+            const float cx = (float)((double)sp.x - sph_o[0]), cy = (float)((double)sp.y - sph_o[1]), cz = (float)((double)sp.z - sph_o[2]);
+            sel[k].x = -2.0f * cx; sel[k].y = -2.0f * cy; sel[k].z = -2.0f * cz;
+            const double c2 = (double)cx * cx + (double)cy * cy + (double)cz * cz;
+            sel[k].w = (float)c2;
+            sph_rho2 = std::max(sph_rho2, std::nextafter((float)c2, INFINITY));
         }
         // the same rows, two spheres (S, T) interleaved per record: [Sx Tx | Sy Ty | Sz Tz | Sw Tw] -- the operand layout of
         // v_pk_fma_f32 with one packed lane per sphere
@@ -1235,6 +1246,8 @@ int trk_cost_model_create(const TrkCostModelDesc* d, TrkCostModel** out) {
     h.n_spheres = (int32_t)n_real_spheres;
     h.sphere_pairs = reinterpret_cast<const float*>(base + o_pair);
     h.n_sphere_pairs = n_sphere_pairs;
+    std::memcpy(h.sphere_o, sph_o, sizeof(sph_o));
+    h.sphere_rho2 = sph_rho2;
     h.clamp_fields = d->clamp_fields & 7;
     h.n_virtual = d->n_virtual; h.self_single = self_single ? 1 : 0;
     h.virtual_src = reinterpret_cast<const int32_t*>(base + o_vsrc);

@@ -96,7 +96,7 @@ struct DevCostHdr {
     // rotation-invariant, so the object pose folds into the centre; max over objects of (margin - sdf) is a
     // min over the union).  float4 = (cx, cy, cz, r).  Objects keep only their non-sphere primitives here.
     const float4* spheres;         // device
-    const float4* spheres_sel;     // device: (-2cx, -2cy, -2cz, |c|^2): |p-c|^2 - |p|^2 = p . sel.xyz + sel.w (3 FMAs)
+    const float4* spheres_sel;     // device: with c' = c - sphere_o, q = p - sphere_o: (-2c'x, -2c'y, -2c'z, |c'|^2): |q-c'|^2 - |q|^2 = q . sel.xyz + sel.w
     int32_t n_spheres;
     int32_t spheres_uniform_r;     // 1: every radius equals sphere_r (arg-min by squared distance, one sqrt)
     float sphere_r;
@@ -116,6 +116,11 @@ struct DevCostHdr {
     const float* virtual_w;        // device [2 * n_virtual]
     int32_t n_prims;               // entries of prims[] (a fused kernel keeps up to TRK_LDS_PRIMS of them in LDS)
     int32_t _pad_prims;
+    // The ranking origin o of spheres_sel / sphere_pairs (fp32-rounded centroid of the sphere centres): the tables hold c - o (rounded
+    // once from the double difference) and the kernels rank q = p - o, so the keys' cancellation scales with the scene's extent, not with
+    // its distance from the world origin.  sphere_rho2 = max over spheres of |c - o|^2 (fp32 rounded up): sizes the fast path's band.
+    float sphere_o[3];
+    float sphere_rho2;
 };
 
 // Points rigidly attached to links (grasped-object points robot_panda.py:154-168, per-link collision spheres):
@@ -457,7 +462,7 @@ template <int J, class Tick>
 __device__ __forceinline__ void scene_all_ticks(const Tick& tick) {
     if constexpr (J < TRK_OBJ_TICK_SLOTS) { tick.template at<J>(); scene_all_ticks<J + 1>(tick); }
 }
-// One guarded trip of the pair-ranking loop (see scene_min_sdf): pair J of at most 8.
+// One guarded trip of the pair-ranking loop (see scene_min_sdf): pair J of at most 8, on points relative to the ranking origin.
 template <int NL, int J, class Tick>
 __device__ __forceinline__ void scene_rank_pairs(const TRK_CAS float* tab, int np, const float (&px)[NL], const float (&py)[NL],
                                                  const float (&pz)[NL], float (&bk)[NL], const Tick& tick) {
@@ -681,13 +686,20 @@ __device__ __forceinline__ void scene_min_sdf(const DevCostHdr& C, const float (
     }
     if (FAST || C.n_spheres > 0) {
         if (FAST || C.spheres_uniform_r) {
-            // equal radii: arg-min over spheres of |p-c|^2, ranked by |p-c|^2 - |p|^2 = p.(-2c) + |c|^2 (3 FMAs per
-            // sphere and point); the exact distance is recomputed for the winner only (one sqrt per point).
+            // equal radii: arg-min over spheres of |p-c|^2, ranked by |q-c'|^2 - |q|^2 = q.(-2c') + |c'|^2 (3 FMAs per
+            // sphere and point) about the scene's ranking origin o (q = p - o, c' = c - o: three subtractions per point).  About the
+            // world origin the key would cancel |p|^2 and its rounding would grow with the distance of robot and scene from it
+            // (4.5e-5 m of distance error at 3 m).  The exact distance is recomputed for the winner only (one sqrt per point),
+            // from the absolute centre.
             int bi[NL];
+            float qx[NL], qy[NL], qz[NL];
+#pragma unroll
+            for (int l = 0; l < NL; ++l) { qx[l] = px[l] - C.sphere_o[0]; qy[l] = py[l] - C.sphere_o[1]; qz[l] = pz[l] - C.sphere_o[2]; }
             if (FAST || C.n_spheres <= 16) {
                 // index rides in the 4 low mantissa bits of the ranking key: one v_and_or + half a v_min3 per sphere and
-                // point.  Only near-ties (relative gap < 2^-19) can pick the other sphere, and then both distances
-                // agree to ~2e-6 -- below the stated cost tolerance; the value itself is always exact.
+                // point.  Only near-ties can pick the other sphere: the key's rounding and the masked bits are ~2^-19 of
+                // max(|q|^2, |c'|^2), a scene-sized quantity, and the distance then differs from the nearest sphere's by a few
+                // 1e-6 m (tests/test_gpu_edges.py: the same bound at 30 m as at the origin); the value is the chosen sphere's exact one.
                 // Two spheres (S, T) per trip, one packed lane each: key(S), key(T) of a point are ONE v_pk_fma_f32 chain
                 // over the pair record [Sx Tx | Sy Ty | Sz Tz | Sw Tw] (measured on gfx950: v_pk_fma_f32 4.4 cycles per
                 // wave = 2.2 per FMA, a scalar FMA with an SGPR operand 4.2; tools/valu_microbench3.hip).
@@ -711,16 +723,16 @@ __device__ __forceinline__ void scene_min_sdf(const DevCostHdr& C, const float (
                                      cw = {rec.v[6], rec.v[7]};
 #pragma unroll
                         for (int l = 0; l < NL; ++l) {
-                            const trk_f2 key = __builtin_elementwise_fma(trk_f2{px[l], px[l]}, cx,
-                                               __builtin_elementwise_fma(trk_f2{py[l], py[l]}, cy,
-                                               __builtin_elementwise_fma(trk_f2{pz[l], pz[l]}, cz, cw)));
+                            const trk_f2 key = __builtin_elementwise_fma(trk_f2{qx[l], qx[l]}, cx,
+                                               __builtin_elementwise_fma(trk_f2{qy[l], qy[l]}, cy,
+                                               __builtin_elementwise_fma(trk_f2{qz[l], qz[l]}, cz, cw)));
                             const float ks = __uint_as_float((__float_as_uint(key.x) & ~15u) | k0);
                             const float kt = __uint_as_float((__float_as_uint(key.y) & ~15u) | k1);
                             bk[l] = __builtin_fminf(bk[l], __builtin_fminf(ks, kt));
                         }
                     }
                 } else {
-                    scene_rank_pairs<NL, 0>(tab, np, px, py, pz, bk, tick);
+                    scene_rank_pairs<NL, 0>(tab, np, qx, qy, qz, bk, tick);
                 }
 #pragma unroll
                 for (int l = 0; l < NL; ++l) bi[l] = (int)(__float_as_uint(bk[l]) & 15u);
@@ -747,7 +759,7 @@ __device__ __forceinline__ void scene_min_sdf(const DevCostHdr& C, const float (
                     const F4 S = load_f4_uniform(C.spheres_sel, k);
 #pragma unroll
                     for (int l = 0; l < NL; ++l) {
-                        const float t = fmaf(px[l], S.x, fmaf(py[l], S.y, fmaf(pz[l], S.z, S.w)));
+                        const float t = fmaf(qx[l], S.x, fmaf(qy[l], S.y, fmaf(qz[l], S.z, S.w)));
                         const bool lt = t < bn[l];
                         bi[l] = lt ? k : bi[l];
                         bn[l] = lt ? t : bn[l];

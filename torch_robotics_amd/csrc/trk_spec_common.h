@@ -505,17 +505,27 @@ __device__ __forceinline__ void spec_load_q_via(const SpecArgs& A, int64_t base,
                                         // the END of the last segment -- tested only by the wavefronts that hold such a segment (wave-uniform
                                         // branch: one wavefront in ~60).  "v outside [lo, hi] or NaN" == "the BITS of clamp(v) differ from v's"
                                         // (v_med3 returns a bound for a NaN input; the generated units are compiled with -fno-honor-nans, so
-                                        // no floating-point comparison is asked about a NaN): three instructions per value
+                                        // no floating-point comparison is asked about a NaN) -- once the zeros are canonical: -0.0 == +0.0 is
+                                        // inside for `>=` / `<=`, but clamp(-0.0) to [+0.0, hi] returns the other zero's bits.  `x + 0.0f` turns
+                                        // -0.0 into +0.0 and leaves every other value (NaN included) as it is; the units grant no nsz, so it
+                                        // is not folded away (tests/test_isa_limit_flags_cpu.py): four instructions per value
+        float lo[D], hi[D];
+#pragma unroll
+        for (int j = 0; j < D; ++j) { lo[j] = cptr(A.via_qmin)[j] + 0.0f; hi[j] = cptr(A.via_qmax)[j] + 0.0f; }
         unsigned acc = 0u;
 #pragma unroll
-        for (int j = 0; j < D; ++j)
-            acc |= __float_as_uint(__builtin_amdgcn_fmed3f(pa[j], cptr(A.via_qmin)[j], cptr(A.via_qmax)[j])) ^ __float_as_uint(pa[j]);
+        for (int j = 0; j < D; ++j) {
+            const float v = pa[j] + 0.0f;
+            acc |= __float_as_uint(__builtin_amdgcn_fmed3f(v, lo[j], hi[j])) ^ __float_as_uint(v);
+        }
         const bool last_seg = on && i == (unsigned)(A.via_H - 2);
         if (__builtin_amdgcn_ballot_w64(last_seg) != 0ull) {
             unsigned accb = 0u;
 #pragma unroll
-            for (int j = 0; j < D; ++j)
-                accb |= __float_as_uint(__builtin_amdgcn_fmed3f(pb[j], cptr(A.via_qmin)[j], cptr(A.via_qmax)[j])) ^ __float_as_uint(pb[j]);
+            for (int j = 0; j < D; ++j) {
+                const float v = pb[j] + 0.0f;
+                accb |= __float_as_uint(__builtin_amdgcn_fmed3f(v, lo[j], hi[j])) ^ __float_as_uint(v);
+            }
             acc |= last_seg ? accb : 0u;
         }
         outside = acc != 0u && on;
@@ -1268,8 +1278,9 @@ __device__ __forceinline__ float spec_object_cost_uniform_point(const DevCostHdr
 // boolean collision fields on NL link points held in registers (distance_fields.py:210-215, 283-291; tasks.py:227-228 ORs the
 // fields).  Objects: the scene's minimum signed distance comes from the same ranking as the cost (one rsq per point); a
 // lane whose distance lies within 1e-5 of its margin -- where the last-ulp difference between n2 * rsq(n2) and the
-// reference's sqrt could flip the comparison -- re-evaluates that point with IEEE sqrt object by object, so the byte equals
-// the table-driven kernel's (and the oracle's) on every input.
+// reference's sqrt, or a near-tie ranked to the other sphere (a few 1e-6 m, see scene_min_sdf), could flip the comparison --
+// re-evaluates that point with IEEE sqrt object by object, so the byte equals the table-driven kernel's and the fp64 decision
+// wherever the distance lies more than its own fp32 rounding (a few ulp) from the threshold.
 // ---------------------------------------------------------------------------------------------------------
 #ifndef TRK_COLL_FAST_SPHERES
 #define TRK_COLL_FAST_SPHERES 1      // 0: experiment / A-B -- every scene takes the ranking path with the arg-min index
@@ -1284,31 +1295,42 @@ __device__ __forceinline__ bool spec_collision_links(const DevCostHdr& C, int fi
     for (int l = 0; l < NL; ++l) mg[l] = use_default ? cptr(C.obj_link_margin)[mbase + l] : margin;
     if ((fields & TRK_FIELD_OBJECTS) && C.n_objects > 0 && scene_is_fast(C) && TRK_COLL_FAST_SPHERES) {
         // Round 6 -- a scene of <= 16 spheres of one radius r and nothing else (wave-uniform): the boolean needs the nearest sphere's
-        // DISTANCE, not the sphere.  min_c |p - c|^2 = min_c (p.(-2c) + |c|^2) + |p|^2: the ranking keys without an index riding in
-        // their mantissas (no v_and_or per sphere and point), no gather of the winner's centre, no second evaluation -- and the test
-        // d < margin + r in squared form.  A lane within 1e-5 of its threshold (in d: |d^2 - thr^2| = (d + thr) |d - thr|) re-evaluates
-        // object by object with IEEE sqrt exactly like the general path below, so the byte is the same on every input.
-        float bk[NL];
+        // DISTANCE, not the sphere.  With q = p - o, c' = c - o about the ranking origin o (DevCostHdr::sphere_o):
+        // min_c |p - c|^2 = |q|^2 + min_c (q.(-2c') + |c'|^2) -- the ranking keys without an index riding in their mantissas (no
+        // v_and_or per sphere and point), no gather of the winner's centre, no second evaluation -- and the test d < margin + r in
+        // squared form.  A lane whose d^2 lies within the error of that form of thr^2 re-evaluates object by object with IEEE sqrt
+        // exactly like the general path below, so the byte equals the table-driven kernel's and the oracle's outside the rounding of
+        // d itself.  The band: every partial sum of the key chain and of |q|^2 + key is bounded by (|q| + rho)^2 <= 2 (|q|^2 + rho^2)
+        // (rho^2 = max |c'|^2, DevCostHdr::sphere_rho2), six fp32 roundings of it plus |c'|^2's own make <= 14 u (|q|^2 + rho^2), and
+        // the rounding of c' to fp32 moves a centre by <= sqrt(3) u rho, i.e. d^2 by <= 2 sqrt(3) u d rho <= 3.5 u (|q|^2 + rho^2) more
+        // (u = 2^-24): 2e-6 (|q|^2 + rho^2) = 34 u (...) covers both, and |q|^2 <= d^2 + |key| avoids a second dot product.  The
+        // floor 2.5e-5 max(thr, 0.04) covers the rsq-versus-sqrt last place.  Both sides scale with the scene's extent about o, not
+        // with |p|: robot and scene far from the world origin re-evaluate as rarely as at the origin.
+        float bk[NL], qx[NL], qy[NL], qz[NL];
 #pragma unroll
-        for (int l = 0; l < NL; ++l) bk[l] = __builtin_inff();
+        for (int l = 0; l < NL; ++l) {
+            bk[l] = __builtin_inff();
+            qx[l] = px[l] - C.sphere_o[0]; qy[l] = py[l] - C.sphere_o[1]; qz[l] = pz[l] - C.sphere_o[2];
+        }
         const TRK_CAS float* tab = cptr(C.sphere_pairs);
         for (int j = 0; j < C.n_sphere_pairs; ++j) {
             const F8 rec = load_f8_uniform(tab, j);
             const trk_f2 cx = {rec.v[0], rec.v[1]}, cy = {rec.v[2], rec.v[3]}, cz = {rec.v[4], rec.v[5]}, cw = {rec.v[6], rec.v[7]};
 #pragma unroll
             for (int l = 0; l < NL; ++l) {
-                const trk_f2 key = __builtin_elementwise_fma(trk_f2{px[l], px[l]}, cx,
-                                   __builtin_elementwise_fma(trk_f2{py[l], py[l]}, cy,
-                                   __builtin_elementwise_fma(trk_f2{pz[l], pz[l]}, cz, cw)));
+                const trk_f2 key = __builtin_elementwise_fma(trk_f2{qx[l], qx[l]}, cx,
+                                   __builtin_elementwise_fma(trk_f2{qy[l], qy[l]}, cy,
+                                   __builtin_elementwise_fma(trk_f2{qz[l], qz[l]}, cz, cw)));
                 bk[l] = __builtin_fminf(bk[l], __builtin_fminf(key.x, key.y));
             }
         }
 #pragma unroll
         for (int l = 0; l < NL; ++l) {
             const float thr = mg[l] + C.sphere_r;                          // wave-uniform
-            const float d2 = fmaf(px[l], px[l], fmaf(py[l], py[l], fmaf(pz[l], pz[l], bk[l])));
+            const float d2 = fmaf(qx[l], qx[l], fmaf(qy[l], qy[l], fmaf(qz[l], qz[l], bk[l])));
+            const float band = __builtin_fmaxf(2.5e-5f * __builtin_fmaxf(thr, 0.04f), 2e-6f * (d2 + __builtin_fabsf(bk[l]) + C.sphere_rho2));
             bool h = thr > 0.0f && d2 < thr * thr;
-            if (__builtin_fabsf(d2 - thr * thr) < 2.5e-5f * __builtin_fmaxf(thr, 0.04f) || !(thr > 1e-4f)) {      // rare: exact, object by object
+            if (__builtin_fabsf(d2 - thr * thr) < band || !(thr > 1e-4f)) {      // rare: exact, object by object
                 h = false;
                 for (int o = 0; o < C.n_objects; ++o) {
                     float gx, gy, gz;
