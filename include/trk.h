@@ -736,6 +736,82 @@ int trk_grid_precompute(const TrkCostModel* cm, const int32_t dims[3], const flo
 int trk_sdf_points(const TrkCostModel* cm, const float* points, int64_t n, float* sdf, float* grad,
                    trk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * 2-D point mass in a planar scene (csrc/trk_planar.hip).
+ * reference: RobotPointMass robot_point_mass.py:13-32 (identity "kinematics", one collision point) +
+ *            PlanningTask tasks.py:131-232 with the object and workspace fields, distance_fields.py:107-130, 298-332,
+ *            ObjectField in 2-D primitives.py:387-405, GridMapSDF in 2-D grid_map_sdf.py:34-114.
+ * A sample is one point q = (x, y).  With m = the scene's margin (link margin + cutoff margin, added in fp32 on the host):
+ *   objects:   max over the scene's df objects (the grid first, then the analytic objects in order) of (m - sdf_o(q)); an analytic
+ *              object is the min over its primitives of the primitive's SDF at R(ori)^T ((x, y, 0) - pos), first two coordinates;
+ *              the grid is the stored value of the nearest-lower cell floor((q - lim_min) / map_dim * dims), clamped to the grid.
+ *   workspace: max over the four faces q - ws_min, ws_max - q (in that order) of (m - d); d/dq of sign(d) |d| is 0 at d == 0.
+ *   cost = objects + workspace; clamp != 0 applies relu to both terms (clamp_sdf=True).  The gradient follows the first arg-max
+ *   object and, inside it, the first arg-min primitive; a grid cell contributes its stored gradient.
+ * --------------------------------------------------------------------------------- */
+#define TRK_PLANAR_MAX_OBJECTS 64
+#define TRK_PLANAR_MAX_PRIMS 256
+
+typedef struct TrkPrim2D {      /* TrkPrimType; center / half sizes in the object frame; sphere radius or rounding radius */
+    int32_t type;
+    int32_t _pad;
+    float center[2];
+    float half[2];
+    float radius;
+    float _pad2;
+} TrkPrim2D;
+
+typedef struct TrkObject2D {    /* ObjectField: 3-D pos and q_to_rotation_matrix(ori) row-major, primitives [prim_begin, prim_end) */
+    float pos[3];
+    float R[9];
+    int32_t prim_begin;
+    int32_t prim_end;
+} TrkObject2D;
+
+typedef struct TrkScene2DDesc {
+    int32_t abi_version;        /* TRK_ABI_VERSION */
+    int32_t n_objects;          /* analytic objects (fixed objects without a grid, then the extra objects), <= TRK_PLANAR_MAX_OBJECTS */
+    const TrkObject2D* objects; /* host */
+    int32_t n_prims;            /* <= TRK_PLANAR_MAX_PRIMS */
+    const TrkPrim2D* prims;     /* host */
+    int32_t has_grid;           /* 1: the fixed objects are a precomputed grid (evaluated before the analytic objects) */
+    int32_t grid_dims[2];
+    const float* grid_cells;    /* DEVICE [nx, ny, 4] = (sdf, gx, gy, 0) as written by trk_grid2d_precompute; copied at create() */
+    float grid_lim_min[2];
+    float grid_map_dim[2];      /* |lim_max - lim_min| in fp32 */
+    int32_t has_ws;
+    float ws_min[2];
+    float ws_max[2];
+    float margin;               /* link margin + cutoff margin */
+} TrkScene2DDesc;
+
+typedef struct TrkScene2D TrkScene2D;
+
+int trk_scene2d_create(const TrkScene2DDesc* desc, TrkScene2D** out);
+void trk_scene2d_destroy(TrkScene2D* scene);
+
+/* q [n, 2] -> cost [n]; grad (nullable) [n, 2] = d cost / d q.  clamp: relu of each term (clamp_sdf). */
+int trk_scene2d_cost_grad(const TrkScene2D* scene, const float* q, int64_t n, int32_t clamp, float* cost, float* grad,
+                          trk_stream_t stream);
+/* any(sdf_o(q) < margin) over the objects and the workspace faces -> in_collision [n] (uint8 0 / 1).
+ * margin_override: NaN = the scene's margin, else the `margin=` kwarg (tasks.py:131-133, distance_fields.py:283-291). */
+int trk_scene2d_collision(const TrkScene2D* scene, const float* q, int64_t n, float margin_override, uint8_t* in_collision,
+                          trk_stream_t stream);
+/* trk_interpolate_via_points + trk_scene2d_collision in one launch (the interpolated points never reach memory): x [n_traj, horizon,
+ * state_dim >= 2] -> in_collision [n_traj, (horizon - 1) * n_interp], sample (t, i, a) = x[t, i] * alpha[a] + x[t, i + 1] * beta[a]
+ * rounded like trk_interpolate_via_points.  The result is trk_traj_validate's `waypoint_collisions`.  tasks.py:244-251. */
+int trk_scene2d_collision_via(const TrkScene2D* scene, const float* x, int64_t n_traj, int32_t horizon, int32_t state_dim,
+                              int32_t n_interp, const float* alpha, const float* beta, float margin_override,
+                              uint8_t* in_collision, trk_stream_t stream);
+/* GridMapSDF.precompute_sdf in 2-D (grid_map_sdf.py:34-63): the min over the scene's analytic objects and its gradient at the
+ * torch.linspace grid points -> cells [dims[0], dims[1], 4] = (sdf, gx, gy, 0).  Ties between objects split the gradient evenly
+ * (torch.minimum). */
+int trk_grid2d_precompute(const TrkScene2D* scene, const int32_t dims[2], const float lim_min[2], const float lim_max[2],
+                          float* cells, trk_stream_t stream);
+/* Signed distance of points to each df object of the scene (the grid first, then the analytic objects):
+ * points [n, 2] -> sdf [n, n_df], grad (nullable) [n, n_df, 2].  ObjectField / GridMapSDF.compute_signed_distance. */
+int trk_scene2d_sdf_points(const TrkScene2D* scene, const float* points, int64_t n, float* sdf, float* grad, trk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,9 @@ from .kinematics import (DifferentiableTree, DifferentiableFrankaPanda, Differen
                          link_quat_from_link_tensor)
 from .environments import (MultiSphereField, MultiBoxField, MultiSharpBoxField, ObjectField, GridMapSDF,  # noqa: F401
                            EnvBase, EnvSpheres3D, EnvSpheres3DExtraObjects, EnvTableShelf, EnvMazeBoxes3D,
-                           GraspedObject, GraspedObjectPandaBox)
+                           GraspedObject, GraspedObjectPandaBox,
+                           EnvSimple2D, EnvDense2D, EnvNarrowPassageDense2D, EnvSquare2D, EnvCircle2D, EnvGridCircles2D,
+                           EnvSimple2DExtraObjects, EnvDense2DExtraObjects, EnvNarrowPassageDense2DExtraObjects)
 from .fields import (DistanceField, CollisionSelfField, CollisionObjectDistanceField,  # noqa: F401
                      CollisionWorkspaceBoundariesDistanceField, EESE3DistanceField, SE3_distance)
 from .robots import RobotBase, RobotPanda, RobotPointMass, RobotPointMass3D, compute_path_length, compute_smoothness, finite_difference_vector  # noqa: F401

@@ -99,6 +99,27 @@ class GpPrior(C.Structure):         # TrkGpPrior
     _fields_ = [("dt", C.c_float), ("sigma", C.c_float), ("weight", C.c_float)]
 
 
+TRK_PLANAR_MAX_OBJECTS = 64
+TRK_PLANAR_MAX_PRIMS = 256
+
+
+class Prim2D(C.Structure):          # TrkPrim2D
+    _fields_ = [("type", C.c_int32), ("_pad", C.c_int32), ("center", C.c_float * 2), ("half", C.c_float * 2),
+                ("radius", C.c_float), ("_pad2", C.c_float)]
+
+
+class Object2D(C.Structure):        # TrkObject2D
+    _fields_ = [("pos", C.c_float * 3), ("R", C.c_float * 9), ("prim_begin", C.c_int32), ("prim_end", C.c_int32)]
+
+
+class Scene2DDesc(C.Structure):     # TrkScene2DDesc
+    _fields_ = [("abi_version", C.c_int32), ("n_objects", C.c_int32), ("objects", C.POINTER(Object2D)),
+                ("n_prims", C.c_int32), ("prims", C.POINTER(Prim2D)),
+                ("has_grid", C.c_int32), ("grid_dims", C.c_int32 * 2), ("grid_cells", C.c_void_p),
+                ("grid_lim_min", C.c_float * 2), ("grid_map_dim", C.c_float * 2),
+                ("has_ws", C.c_int32), ("ws_min", C.c_float * 2), ("ws_max", C.c_float * 2), ("margin", C.c_float)]
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 

@@ -35,6 +35,8 @@ EXPORTS = [
     "trk_scale_rows", "trk_jtj", "trk_pack_sums", "trk_pack_sums_scratch_bytes", "trk_rollout_is_specialized", "trk_ik_gn_steps", "trk_rollout_gp_cost_grad",
     "trk_spec_register_module", "trk_spec_layout_stamp", "trk_last_dispatch", "trk_set_strict_specialized", "trk_rollout_points_is_specialized", "trk_rollout_jacobian_cost_grad",
     "trk_handle_kind", "trk_mailbox_create", "trk_mailbox_ipc_handle", "trk_mailbox_connect", "trk_mailbox_send", "trk_mailbox_recv", "trk_mailbox_exchange", "trk_mailbox_status", "trk_mailbox_destroy",
+    "trk_scene2d_create", "trk_scene2d_destroy", "trk_scene2d_cost_grad", "trk_scene2d_collision", "trk_scene2d_collision_via",
+    "trk_grid2d_precompute", "trk_scene2d_sdf_points",
 ]
 
 
@@ -179,10 +181,19 @@ def lib():
     L.trk_fk_points.argtypes = [vp, vp, vp, i64, vp, vp]
     L.trk_fk_points_backward.argtypes = [vp, vp, vp, vp, i64, vp, vp]
     L.trk_rollout_points_cost_grad.argtypes = [vp, vp, vp, C.POINTER(_abi.RolloutWeights), vp, i64, i32, vp, vp, vp, vp, vp]
+    L.trk_scene2d_create.argtypes = [C.POINTER(_abi.Scene2DDesc), C.POINTER(vp)]
+    L.trk_scene2d_destroy.argtypes = [vp]
+    L.trk_scene2d_destroy.restype = None
+    L.trk_scene2d_cost_grad.argtypes = [vp, vp, i64, i32, vp, vp, vp]
+    L.trk_scene2d_collision.argtypes = [vp, vp, i64, f32, vp, vp]
+    L.trk_scene2d_collision_via.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, f32, vp, vp]
+    L.trk_grid2d_precompute.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.trk_scene2d_sdf_points.argtypes = [vp, vp, i64, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)        # AttributeError here = the library does not export the ABI
         if name not in ("trk_last_error", "trk_model_destroy", "trk_cost_model_destroy", "trk_point_set_destroy",
-                        "trk_pack_sums_scratch_bytes", "trk_mailbox_destroy", "trk_via_partial_flags_bytes"):
+                        "trk_pack_sums_scratch_bytes", "trk_mailbox_destroy", "trk_via_partial_flags_bytes",
+                        "trk_scene2d_destroy"):
             fn.restype = C.c_int
     if L.trk_abi_version() != _abi.TRK_ABI_VERSION:
         raise TrkError("libtrk.so ABI version mismatch; rebuild it")

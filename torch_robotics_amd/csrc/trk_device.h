@@ -380,17 +380,19 @@ __host__ __device__ __forceinline__ int64_t grid_record(int nb1, int nb2, int i,
 }
 // grid_map_sdf.py:84-114: nearest-lower cell, stored gradient
 typedef float trk_f3u __attribute__((ext_vector_type(3), aligned(4)));       // a 12-byte gradient record: one dwordx3 load
+// one axis of the lookup: floor((X - lim_min) / map_dim * cmap_dim), clamped to [0, dim - 1] (the 3-D grid and the 2-D one)
+__device__ __forceinline__ int grid_axis_cell(float p, float lim_min, float map_dim, float fdim, int dim) {
+    const float f = floorf((p - lim_min) / map_dim * fdim);
+    int v = (int)f;
+    v = v < 0 ? 0 : v;
+    v = v > dim - 1 ? dim - 1 : v;
+    return v;
+}
 __device__ __forceinline__ int64_t grid_cell(const DevGrid& G, float x, float y, float z) {
     const float p[3] = {x, y, z};
     int idx[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float f = floorf((p[k] - G.lim_min[k]) / G.map_dim[k] * G.fdims[k]);
-        int v = (int)f;
-        v = v < 0 ? 0 : v;
-        v = v > G.dims[k] - 1 ? G.dims[k] - 1 : v;
-        idx[k] = v;
-    }
+    for (int k = 0; k < 3; ++k) idx[k] = grid_axis_cell(p[k], G.lim_min[k], G.map_dim[k], G.fdims[k], G.dims[k]);
     // The records are TILED: 4 x 4 x 4 bricks of 1 KiB, inside a brick 2 x 2 x 2 cubes of 128 bytes (one L2 line).  A planner's
     // trajectories are smooth along the horizon -- the 64 lanes of a wavefront are consecutive time steps --, so neighbouring lanes
     // ask for neighbouring cells: in x-major order a step along x or y lands 640 KB / 3.2 KB away, here it stays in the line or

@@ -1,0 +1,469 @@
+// trk_planar.hip -- the 2-D point mass in a planar scene (include/trk.h, "2-D point mass"): RobotPointMass + PlanningTask on the
+// reference's 2-D scenes (EnvDense2D, EnvNarrowPassageDense2D, ...).  A sample is one point, so every kernel is one lane per sample:
+// q in as one float2, the cost out as one coalesced fp32 store and the gradient as one float2.
+//
+// The scene is a handful of analytic objects (at most a few dozen primitives) and/or a precomputed 2-D SDF grid.  The analytic
+// tables are the same for every lane: the kernels walk them with loop counters through the constant address space, so the compiler
+// fetches them with scalar loads into SGPRs.  The grid is packed as float4 (sdf, gx, gy, 0) per cell, so a lookup is ONE 16-byte
+// gather; 400 x 400 cells are 2.56 MB and stay in an XCD's 4 MiB L2 across launches.
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+#include "trk_launch.h"
+
+namespace {
+
+struct alignas(16) P2Prim {     // 8 dwords
+    int32_t type;
+    float cx, cy, hx, hy, r;
+    int32_t _pad[2];
+};
+
+struct alignas(16) P2Obj {      // 16 dwords
+    float pos[3];
+    float R[9];
+    int32_t begin, end;
+    int32_t kind;               // 0: R = I and pos = 0 (local = q), 1: R = I (local = q - pos), 2: general
+    int32_t _pad;
+};
+
+// Passed to kernels by value (kernarg segment, scalar-loaded).
+struct P2Hdr {
+    const P2Obj* objs;          // device [n_objects]
+    const P2Prim* prims;        // device
+    const float4* cells;        // device [nx * ny] = (sdf, gx, gy, 0), row-major (i, j)
+    int32_t n_objects, has_grid, nx, ny;
+    float lim0, lim1, md0, md1, fd0, fd1;
+    float ws_min0, ws_min1, ws_max0, ws_max1;
+    float margin;
+};
+
+// sphere primitives.py:108-112, sharp box :220-223, rounded box :327-334 in 2-D, with the gradients torch's autograd gives them:
+// norm' = v / |v| (0 at 0), abs' = sign (0 at +-0), max(dim)' to the first maximum, amax' split evenly between equal values,
+// minimum(a, 0)' split at a == 0, relu'(0) = 0.
+__device__ __forceinline__ float prim2d_sdf(const TRK_CAS P2Prim* P, float x, float y, float& gx, float& gy) {
+    const int type = P->type;
+    const float dx = x - P->cx, dy = y - P->cy;
+    if (type == TRK_PRIM_SPHERE) {
+        const float n = sqrtf(dx * dx + dy * dy);
+        const float inv = n > 0.0f ? 1.0f / n : 0.0f;
+        gx = dx * inv; gy = dy * inv;
+        return n - P->r;
+    }
+    const float sx = dx > 0.0f ? 1.0f : (dx < 0.0f ? -1.0f : 0.0f);
+    const float sy = dy > 0.0f ? 1.0f : (dy < 0.0f ? -1.0f : 0.0f);
+    if (type == TRK_PRIM_SHARP_BOX) {
+        const float ux = fabsf(dx) - P->hx, uy = fabsf(dy) - P->hy;
+        const bool ay = uy > ux;                                   // first maximum wins
+        gx = ay ? 0.0f : sx; gy = ay ? sy : 0.0f;
+        return ay ? uy : ux;
+    }
+    const float r = P->r;
+    const float ux = fabsf(dx) - P->hx + r, uy = fabsf(dy) - P->hy + r;
+    const float mu = fmaxf(ux, uy);
+    const float wx = ux == uy ? 0.5f : (ux > uy ? 1.0f : 0.0f), wy = 1.0f - wx;       // amax: ties share
+    const float inside = mu < 0.0f ? 1.0f : (mu == 0.0f ? 0.5f : 0.0f);               // minimum(max_q, 0)
+    const float rx = fmaxf(ux, 0.0f), ry = fmaxf(uy, 0.0f);
+    const float nn = sqrtf(rx * rx + ry * ry);
+    const float inv = nn > 0.0f ? 1.0f / nn : 0.0f;
+    gx = (inside * wx + rx * inv) * sx;
+    gy = (inside * wy + ry * inv) * sy;
+    return (fminf(mu, 0.0f) + nn) - r;
+}
+
+// ObjectField in 2-D (primitives.py:387-405): (x, y, 0) - pos, rotated by R^T, first two coordinates; min over the primitives (first
+// minimum wins); the gradient goes back through the upper-left 2 x 2 block of R.
+__device__ __forceinline__ float object2d_sdf(const P2Hdr& S, int o, float x, float y, float& gx, float& gy) {
+    const TRK_CAS P2Obj* O = cptr(S.objs) + o;
+    const int kind = O->kind;
+    float lx = x, ly = y;
+    if (kind == 1) { lx = x - O->pos[0]; ly = y - O->pos[1]; }
+    else if (kind == 2) {
+        const float dx = x - O->pos[0], dy = y - O->pos[1], dz = 0.0f - O->pos[2];
+        lx = O->R[0] * dx + O->R[3] * dy + O->R[6] * dz;
+        ly = O->R[1] * dx + O->R[4] * dy + O->R[7] * dz;
+    }
+    float best = __builtin_inff(), bx = 0.0f, by = 0.0f;
+    const int end = O->end;
+    for (int i = O->begin; i < end; ++i) {
+        float px, py;
+        const float v = prim2d_sdf(cptr(S.prims) + i, lx, ly, px, py);
+        const bool take = v < best;
+        best = take ? v : best; bx = take ? px : bx; by = take ? py : by;
+    }
+    if (kind == 2) { gx = O->R[0] * bx + O->R[1] * by; gy = O->R[3] * bx + O->R[4] * by; }
+    else { gx = bx; gy = by; }
+    return best;
+}
+
+// GridMapSDF.get_sdf in 2-D (grid_map_sdf.py:81-114): the nearest-lower cell, clamped; its stored value and gradient
+__device__ __forceinline__ float4 grid2d_cell(const P2Hdr& S, float x, float y) {
+    const int i = grid_axis_cell(x, S.lim0, S.md0, S.fd0, S.nx);
+    const int j = grid_axis_cell(y, S.lim1, S.md1, S.fd1, S.ny);
+    return S.cells[(int64_t)i * S.ny + j];
+}
+
+// torch.linspace(lo, hi, n)[i]: start + i * step for the first half, end - (n - 1 - i) * step after (the 3-D precompute's rule)
+__device__ __forceinline__ float linspace_at(float lo, float hi, int n, int i) {
+    const float step = n > 1 ? (hi - lo) / (float)(n - 1) : 0.0f;
+    return i < n / 2 ? lo + step * (float)i : hi - step * (float)(n - 1 - i);
+}
+
+// The object term: max over the df objects of (m - sdf_o), first maximum wins; gradient -grad sdf of that object.
+template <bool GRID, bool ANALYTIC>
+__device__ __forceinline__ float objects_term(const P2Hdr& S, float m, float x, float y, float& gx, float& gy) {
+    float best = -__builtin_inff(), bx = 0.0f, by = 0.0f;
+    if (GRID) {
+        const float4 c = grid2d_cell(S, x, y);
+        best = m - c.x; bx = c.y; by = c.z;
+    }
+    if (ANALYTIC) {
+        for (int o = 0; o < S.n_objects; ++o) {
+            float ox, oy;
+            const float v = m - object2d_sdf(S, o, x, y, ox, oy);
+            const bool take = v > best;
+            best = take ? v : best; bx = take ? ox : bx; by = take ? oy : by;
+        }
+    }
+    gx = -bx; gy = -by;
+    return best;
+}
+
+// CollisionWorkspaceBoundariesDistanceField (distance_fields.py:319-332): faces x - min, y - min, max - x, max - y, each through
+// sign(d) |d| (value d, derivative 0 at d == 0); max over the faces of (m - d), first maximum wins.
+__device__ __forceinline__ float ws_term(const P2Hdr& S, float m, float x, float y, float& gx, float& gy) {
+    const float d0 = x - S.ws_min0, d1 = y - S.ws_min1, d2 = S.ws_max0 - x, d3 = S.ws_max1 - y;
+    float best = m - d0; int k = 0;
+    if (m - d1 > best) { best = m - d1; k = 1; }
+    if (m - d2 > best) { best = m - d2; k = 2; }
+    if (m - d3 > best) { best = m - d3; k = 3; }
+    const float d = k == 0 ? d0 : (k == 1 ? d1 : (k == 2 ? d2 : d3));
+    const float s = d != 0.0f ? 1.0f : 0.0f;
+    gx = k == 0 ? -s : (k == 2 ? s : 0.0f);
+    gy = k == 1 ? -s : (k == 3 ? s : 0.0f);
+    return best;
+}
+
+template <bool GRID, bool ANALYTIC, bool WS>
+__device__ __forceinline__ bool collides(const P2Hdr& S, float m, float x, float y) {
+    bool hit = false;
+    if (GRID) hit = grid2d_cell(S, x, y).x < m;
+    if (ANALYTIC) {
+        for (int o = 0; o < S.n_objects; ++o) {
+            float gx, gy;
+            hit = hit || object2d_sdf(S, o, x, y, gx, gy) < m;
+        }
+    }
+    if (WS) hit = hit || (x - S.ws_min0) < m || (y - S.ws_min1) < m || (S.ws_max0 - x) < m || (S.ws_max1 - y) < m;
+    return hit;
+}
+
+template <bool GRID, bool ANALYTIC, bool WS, bool CLAMP, bool GRAD>
+__global__ void __launch_bounds__(256)
+k_planar_cost(P2Hdr S, const float2* __restrict__ q, int64_t n, float* __restrict__ cost, float2* __restrict__ grad) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const float2 p = q[s];
+    float c = 0.0f, gx = 0.0f, gy = 0.0f;
+    if (GRID || ANALYTIC) {
+        float ox, oy;
+        const float v = objects_term<GRID, ANALYTIC>(S, S.margin, p.x, p.y, ox, oy);
+        const bool live = !CLAMP || v > 0.0f;                      // relu: no gradient at or below zero
+        c = CLAMP ? fmaxf(v, 0.0f) : v;
+        gx = live ? ox : 0.0f; gy = live ? oy : 0.0f;
+    }
+    if (WS) {
+        float wx, wy;
+        const float v = ws_term(S, S.margin, p.x, p.y, wx, wy);
+        const bool live = !CLAMP || v > 0.0f;
+        c = c + (CLAMP ? fmaxf(v, 0.0f) : v);
+        gx = gx + (live ? wx : 0.0f); gy = gy + (live ? wy : 0.0f);
+    }
+    cost[s] = c;
+    if (GRAD) grad[s] = make_float2(gx, gy);
+}
+
+template <bool GRID, bool ANALYTIC, bool WS>
+__global__ void __launch_bounds__(256)
+k_planar_collision(P2Hdr S, const float2* __restrict__ q, int64_t n, float m, uint8_t* __restrict__ out) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const float2 p = q[s];
+    out[s] = collides<GRID, ANALYTIC, WS>(S, m, p.x, p.y) ? 1 : 0;
+}
+
+// Via points: sample (t, i, a) = x[t, i] * alpha[a] + x[t, i + 1] * beta[a], each product and the sum rounded once, exactly as
+// k_interpolate_via_points; the point is tested where it is formed and never stored.
+template <bool GRID, bool ANALYTIC, bool WS>
+__global__ void __launch_bounds__(256)
+k_planar_collision_via(P2Hdr S, const float* __restrict__ x, int64_t total, int H, int SD, int n_interp,
+                       const float* __restrict__ alpha, const float* __restrict__ beta, float m, uint8_t* __restrict__ out) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= total) return;
+    const int per = (H - 1) * n_interp;
+    const int64_t t = s / per;
+    const int r = (int)(s - t * per);
+    const int i = r / n_interp, a = r - i * n_interp;
+    const float* w0 = x + (t * H + i) * (int64_t)SD;
+    const float* w1 = w0 + SD;
+    const float al = alpha[a], be = beta[a];
+    const float px = __fadd_rn(__fmul_rn(w0[0], al), __fmul_rn(w1[0], be));
+    const float py = __fadd_rn(__fmul_rn(w0[1], al), __fmul_rn(w1[1], be));
+    out[s] = collides<GRID, ANALYTIC, WS>(S, m, px, py) ? 1 : 0;
+}
+
+// GridMapSDF.precompute_sdf in 2-D: min over the analytic objects with torch.minimum's gradient (ties share it evenly, folded in
+// object order like the reference's running minimum).  One float4 store per cell.
+__global__ void __launch_bounds__(256)
+k_grid2d_precompute(P2Hdr S, int nx, int ny, float lo0, float lo1, float hi0, float hi1, float4* __restrict__ cells) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)nx * ny) return;
+    const int i = (int)(idx / ny), j = (int)(idx - (int64_t)i * ny);
+    const float x = linspace_at(lo0, hi0, nx, i), y = linspace_at(lo1, hi1, ny, j);
+    float best = __builtin_inff(), bx = 0.0f, by = 0.0f;
+    for (int o = 0; o < S.n_objects; ++o) {
+        float gx, gy;
+        const float v = object2d_sdf(S, o, x, y, gx, gy);
+        if (o == 0 || v < best) { best = v; bx = gx; by = gy; }
+        else if (v == best) { bx = 0.5f * bx + 0.5f * gx; by = 0.5f * by + 0.5f * gy; }
+    }
+    cells[idx] = make_float4(best, bx, by, 0.0f);
+}
+
+__global__ void __launch_bounds__(256)
+k_planar_sdf_points(P2Hdr S, const float2* __restrict__ pts, int64_t n, int n_df, float* __restrict__ sdf, float2* __restrict__ grad) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const float2 p = pts[s];
+    int k = 0;
+    if (S.has_grid) {
+        const float4 c = grid2d_cell(S, p.x, p.y);
+        sdf[s * n_df] = c.x;
+        if (grad) grad[s * n_df] = make_float2(c.y, c.z);
+        k = 1;
+    }
+    for (int o = 0; o < S.n_objects; ++o, ++k) {
+        float gx, gy;
+        sdf[s * n_df + k] = object2d_sdf(S, o, p.x, p.y, gx, gy);
+        if (grad) grad[s * n_df + k] = make_float2(gx, gy);
+    }
+}
+
+inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+template <bool G, bool A, bool W>
+void launch_cost3(const P2Hdr& S, const float2* q, int64_t n, bool clamp, float* cost, float2* grad, hipStream_t st) {
+    const dim3 g(blocks_for(n)), b(256);
+    if (clamp) {
+        if (grad) hipLaunchKernelGGL((k_planar_cost<G, A, W, true, true>), g, b, 0, st, S, q, n, cost, grad);
+        else hipLaunchKernelGGL((k_planar_cost<G, A, W, true, false>), g, b, 0, st, S, q, n, cost, grad);
+    } else {
+        if (grad) hipLaunchKernelGGL((k_planar_cost<G, A, W, false, true>), g, b, 0, st, S, q, n, cost, grad);
+        else hipLaunchKernelGGL((k_planar_cost<G, A, W, false, false>), g, b, 0, st, S, q, n, cost, grad);
+    }
+}
+
+// (grid, analytic, workspace) -> the compiled variant: f.go<G, A, W>()
+template <class F>
+void dispatch3(bool g, bool a, bool w, F&& f) {
+    if (g) {
+        if (a) { if (w) f.template go<true, true, true>(); else f.template go<true, true, false>(); }
+        else   { if (w) f.template go<true, false, true>(); else f.template go<true, false, false>(); }
+    } else {
+        if (a) { if (w) f.template go<false, true, true>(); else f.template go<false, true, false>(); }
+        else   { if (w) f.template go<false, false, true>(); else f.template go<false, false, false>(); }
+    }
+}
+
+// the three launchers behind dispatch3: one struct per entry point, go<G, A, W>() starts that variant
+struct CostGo {
+    const P2Hdr& S; const float2* q; int64_t n; bool clamp; float* cost; float2* grad; hipStream_t st;
+    template <bool G, bool A, bool W> void go() { launch_cost3<G, A, W>(S, q, n, clamp, cost, grad, st); }
+};
+struct CollGo {
+    const P2Hdr& S; const float2* q; int64_t n; float m; uint8_t* out; hipStream_t st;
+    template <bool G, bool A, bool W> void go() {
+        hipLaunchKernelGGL((k_planar_collision<G, A, W>), dim3(blocks_for(n)), dim3(256), 0, st, S, q, n, m, out);
+    }
+};
+struct ViaGo {
+    const P2Hdr& S; const float* x; int64_t total; int H, SD, ni; const float* al; const float* be; float m; uint8_t* out; hipStream_t st;
+    template <bool G, bool A, bool W> void go() {
+        hipLaunchKernelGGL((k_planar_collision_via<G, A, W>), dim3(blocks_for(total)), dim3(256), 0, st, S, x, total, H, SD, ni, al, be, m, out);
+    }
+};
+
+}  // namespace
+
+struct TrkScene2D {
+    P2Hdr hdr{};
+    P2Obj* d_objs = nullptr;
+    P2Prim* d_prims = nullptr;
+    float4* d_cells = nullptr;
+    int n_df = 0;
+    int has_ws = 0;
+};
+
+extern "C" {
+
+int trk_scene2d_create(const TrkScene2DDesc* d, TrkScene2D** out) {
+    if (!d || !out) return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_create: null argument");
+    if (d->abi_version != TRK_ABI_VERSION) return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_create: abi_version mismatch");
+    if (d->n_objects < 0 || d->n_objects > TRK_PLANAR_MAX_OBJECTS)
+        return trk_fail(TRK_ERR_UNSUPPORTED, "trk_scene2d_create: n_objects out of range (0 .. TRK_PLANAR_MAX_OBJECTS)");
+    if (d->n_prims < 0 || d->n_prims > TRK_PLANAR_MAX_PRIMS)
+        return trk_fail(TRK_ERR_UNSUPPORTED, "trk_scene2d_create: n_prims out of range (0 .. TRK_PLANAR_MAX_PRIMS)");
+    if ((d->n_objects > 0 && !d->objects) || (d->n_prims > 0 && !d->prims))
+        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_create: null object / primitive table");
+    for (int o = 0; o < d->n_objects; ++o) {
+        const TrkObject2D& O = d->objects[o];
+        if (O.prim_begin < 0 || O.prim_begin > O.prim_end || O.prim_end > d->n_prims)
+            return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_create: object primitive range out of bounds");
+    }
+    for (int i = 0; i < d->n_prims; ++i) {
+        const TrkPrim2D& P = d->prims[i];
+        if (P.type != TRK_PRIM_SPHERE && P.type != TRK_PRIM_ROUNDED_BOX && P.type != TRK_PRIM_SHARP_BOX)
+            return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_create: unknown primitive type");
+    }
+    if (d->has_grid) {
+        if (!d->grid_cells || d->grid_dims[0] < 1 || d->grid_dims[1] < 1 || (int64_t)d->grid_dims[0] * d->grid_dims[1] > (1ll << 28) ||
+            !(d->grid_map_dim[0] > 0.0f) || !(d->grid_map_dim[1] > 0.0f))
+            return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_create: bad grid (cells, dims or map_dim)");
+        if (reinterpret_cast<uintptr_t>(d->grid_cells) % 16)
+            return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_create: grid_cells must be 16-byte aligned");
+    }
+    if (!std::isfinite(d->margin)) return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_create: margin must be finite");
+    int rc = trk_ensure_init();
+    if (rc) return rc;
+
+    TrkScene2D* s = new (std::nothrow) TrkScene2D();
+    if (!s) return trk_fail(TRK_ERR_HIP, "trk_scene2d_create: out of host memory");
+    std::vector<P2Obj> objs(d->n_objects > 0 ? d->n_objects : 1);
+    std::vector<P2Prim> prims(d->n_prims > 0 ? d->n_prims : 1);
+    for (int o = 0; o < d->n_objects; ++o) {
+        const TrkObject2D& O = d->objects[o];
+        P2Obj& D = objs[o];
+        std::memset(&D, 0, sizeof(D));
+        std::memcpy(D.pos, O.pos, sizeof(D.pos));
+        std::memcpy(D.R, O.R, sizeof(D.R));
+        D.begin = O.prim_begin; D.end = O.prim_end;
+        const bool ident = O.R[0] == 1.0f && O.R[1] == 0.0f && O.R[2] == 0.0f && O.R[3] == 0.0f && O.R[4] == 1.0f &&
+                           O.R[5] == 0.0f && O.R[6] == 0.0f && O.R[7] == 0.0f && O.R[8] == 1.0f;
+        D.kind = !ident ? 2 : (O.pos[0] == 0.0f && O.pos[1] == 0.0f ? 0 : 1);
+    }
+    for (int i = 0; i < d->n_prims; ++i) {
+        const TrkPrim2D& P = d->prims[i];
+        P2Prim& D = prims[i];
+        std::memset(&D, 0, sizeof(D));
+        D.type = P.type; D.cx = P.center[0]; D.cy = P.center[1]; D.hx = P.half[0]; D.hy = P.half[1];
+        D.r = P.type == TRK_PRIM_SHARP_BOX ? 0.0f : P.radius;
+    }
+    auto cleanup = [&](hipError_t e, const char* what) {
+        if (s->d_objs) (void)hipFree(s->d_objs);
+        if (s->d_prims) (void)hipFree(s->d_prims);
+        if (s->d_cells) (void)hipFree(s->d_cells);
+        delete s;
+        return trk_hip_fail((int)e, what);
+    };
+    hipError_t e;
+    if ((e = hipMalloc(&s->d_objs, sizeof(P2Obj) * objs.size())) != hipSuccess) return cleanup(e, "hipMalloc(objects)");
+    if ((e = hipMalloc(&s->d_prims, sizeof(P2Prim) * prims.size())) != hipSuccess) return cleanup(e, "hipMalloc(prims)");
+    if ((e = hipMemcpy(s->d_objs, objs.data(), sizeof(P2Obj) * objs.size(), hipMemcpyHostToDevice)) != hipSuccess)
+        return cleanup(e, "hipMemcpy(objects)");
+    if ((e = hipMemcpy(s->d_prims, prims.data(), sizeof(P2Prim) * prims.size(), hipMemcpyHostToDevice)) != hipSuccess)
+        return cleanup(e, "hipMemcpy(prims)");
+    P2Hdr& H = s->hdr;
+    H.objs = s->d_objs; H.prims = s->d_prims; H.n_objects = d->n_objects;
+    if (d->has_grid) {                                      // a snapshot, like trk_cost_model_create's grid
+        const size_t bytes = sizeof(float4) * (size_t)d->grid_dims[0] * d->grid_dims[1];
+        if ((e = hipMalloc(&s->d_cells, bytes)) != hipSuccess) return cleanup(e, "hipMalloc(grid)");
+        if ((e = hipMemcpy(s->d_cells, d->grid_cells, bytes, hipMemcpyDeviceToDevice)) != hipSuccess) return cleanup(e, "hipMemcpy(grid)");
+        H.cells = s->d_cells; H.has_grid = 1;
+        H.nx = d->grid_dims[0]; H.ny = d->grid_dims[1];
+        H.lim0 = d->grid_lim_min[0]; H.lim1 = d->grid_lim_min[1];
+        H.md0 = d->grid_map_dim[0]; H.md1 = d->grid_map_dim[1];
+        H.fd0 = (float)H.nx; H.fd1 = (float)H.ny;
+    }
+    s->has_ws = d->has_ws ? 1 : 0;
+    H.ws_min0 = d->ws_min[0]; H.ws_min1 = d->ws_min[1]; H.ws_max0 = d->ws_max[0]; H.ws_max1 = d->ws_max[1];
+    H.margin = d->margin;
+    s->n_df = d->n_objects + (d->has_grid ? 1 : 0);
+    *out = s;
+    return TRK_OK;
+}
+
+void trk_scene2d_destroy(TrkScene2D* s) {
+    if (!s) return;
+    if (s->d_objs) (void)hipFree(s->d_objs);
+    if (s->d_prims) (void)hipFree(s->d_prims);
+    if (s->d_cells) (void)hipFree(s->d_cells);
+    delete s;
+}
+
+static bool aligned_to(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+
+int trk_scene2d_cost_grad(const TrkScene2D* s, const float* q, int64_t n, int32_t clamp, float* cost, float* grad, trk_stream_t stream) {
+    if (!s || n < 0 || (n > 0 && (!q || !cost))) return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_cost_grad: bad argument");
+    if (!aligned_to(q, 8) || (grad && !aligned_to(grad, 8)))
+        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_cost_grad: q and grad must be 8-byte aligned (one float2 per sample)");
+    if (n == 0) return TRK_OK;
+    CostGo f{s->hdr, (const float2*)q, n, clamp != 0, cost, (float2*)grad, (hipStream_t)stream};
+    dispatch3(s->hdr.has_grid != 0, s->hdr.n_objects > 0, s->has_ws != 0, f);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? TRK_OK : trk_hip_fail((int)e, "k_planar_cost");
+}
+
+int trk_scene2d_collision(const TrkScene2D* s, const float* q, int64_t n, float margin_override, uint8_t* out, trk_stream_t stream) {
+    if (!s || n < 0 || (n > 0 && (!q || !out))) return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_collision: bad argument");
+    if (!aligned_to(q, 8)) return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_collision: q must be 8-byte aligned");
+    if (n == 0) return TRK_OK;
+    const float m = std::isnan(margin_override) ? s->hdr.margin : margin_override;
+    CollGo f{s->hdr, (const float2*)q, n, m, out, (hipStream_t)stream};
+    dispatch3(s->hdr.has_grid != 0, s->hdr.n_objects > 0, s->has_ws != 0, f);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? TRK_OK : trk_hip_fail((int)e, "k_planar_collision");
+}
+
+int trk_scene2d_collision_via(const TrkScene2D* s, const float* x, int64_t n_traj, int32_t horizon, int32_t state_dim, int32_t n_interp,
+                              const float* alpha, const float* beta, float margin_override, uint8_t* out, trk_stream_t stream) {
+    if (!s || n_traj < 0 || horizon < 2 || state_dim < 2 || n_interp < 1 || !alpha || !beta || (n_traj > 0 && (!x || !out)))
+        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_collision_via: bad argument");
+    if ((int64_t)(horizon - 1) * n_interp > (1ll << 30) || (int64_t)horizon * state_dim > (1ll << 30))
+        return trk_fail(TRK_ERR_UNSUPPORTED, "trk_scene2d_collision_via: trajectory too long");
+    if (n_traj == 0) return TRK_OK;
+    const float m = std::isnan(margin_override) ? s->hdr.margin : margin_override;
+    const int64_t total = n_traj * (int64_t)(horizon - 1) * n_interp;
+    ViaGo f{s->hdr, x, total, horizon, state_dim, n_interp, alpha, beta, m, out, (hipStream_t)stream};
+    dispatch3(s->hdr.has_grid != 0, s->hdr.n_objects > 0, s->has_ws != 0, f);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? TRK_OK : trk_hip_fail((int)e, "k_planar_collision_via");
+}
+
+int trk_grid2d_precompute(const TrkScene2D* s, const int32_t dims[2], const float lim_min[2], const float lim_max[2], float* cells,
+                          trk_stream_t stream) {
+    if (!s || !dims || !lim_min || !lim_max || !cells) return trk_fail(TRK_ERR_INVALID_ARG, "trk_grid2d_precompute: null argument");
+    if (dims[0] < 1 || dims[1] < 1 || (int64_t)dims[0] * dims[1] > (1ll << 28))
+        return trk_fail(TRK_ERR_INVALID_ARG, "trk_grid2d_precompute: bad dims");
+    if (!aligned_to(cells, 16)) return trk_fail(TRK_ERR_INVALID_ARG, "trk_grid2d_precompute: cells must be 16-byte aligned");
+    if (s->hdr.n_objects < 1) return trk_fail(TRK_ERR_INVALID_ARG, "trk_grid2d_precompute: the scene has no analytic objects");
+    const int64_t total = (int64_t)dims[0] * dims[1];
+    hipLaunchKernelGGL(k_grid2d_precompute, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, s->hdr, dims[0], dims[1],
+                       lim_min[0], lim_min[1], lim_max[0], lim_max[1], (float4*)cells);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? TRK_OK : trk_hip_fail((int)e, "k_grid2d_precompute");
+}
+
+int trk_scene2d_sdf_points(const TrkScene2D* s, const float* points, int64_t n, float* sdf, float* grad, trk_stream_t stream) {
+    if (!s || n < 0 || (n > 0 && (!points || !sdf))) return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_sdf_points: bad argument");
+    if (!aligned_to(points, 8) || (grad && !aligned_to(grad, 8)))
+        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_sdf_points: points and grad must be 8-byte aligned");
+    if (n == 0 || s->n_df == 0) return TRK_OK;
+    hipLaunchKernelGGL(k_planar_sdf_points, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, s->hdr, (const float2*)points, n,
+                       s->n_df, sdf, (float2*)grad);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? TRK_OK : trk_hip_fail((int)e, "k_planar_sdf_points");
+}
+
+}  // extern "C"

@@ -1,20 +1,21 @@
-"""Scene description: analytic SDF primitives, posed objects, voxel SDF grid, 3-D scenes.
+"""Scene description: analytic SDF primitives, posed objects, voxel SDF grid, 3-D and 2-D scenes.
 
 Mirrors the data side of `torch_robotics/environments/` (primitives.py, grid_map_sdf.py,
 env_base.py, env_spheres_3d.py, env_table_shelf.py, env_maze_boxes_3d.py,
-env_spheres_3d_extra_objects.py).  Objects hold plain numbers; every distance evaluation goes to
+env_spheres_3d_extra_objects.py, and the nine 2-D scenes env_*_2d*.py).  Objects hold plain numbers; every distance evaluation goes to
 the HIP kernels through a `CostHandle` (there is no torch arithmetic here).
 """
 from __future__ import annotations
 
 import itertools
 from copy import copy
+from pathlib import Path
 from typing import List
 
 import numpy as np
 import torch
 
-from . import ops
+from . import _abi, ops
 from .costmodel import panda_box_base_points, CostModelSpec, box_prims, grid_object, make_object, sphere_prims
 from .kinmodel import quat_wxyz_to_rot
 
@@ -82,6 +83,12 @@ class MultiSphereField(PrimitiveShapeField):                 # primitives.py:88-
         c = self.centers if self.dim == 3 else np.concatenate([self.centers, np.zeros((len(self.centers), 1), np.float32)], 1)
         return sphere_prims(c, self.radii)
 
+    def prims2d(self) -> np.ndarray:
+        """rows (type, cx, cy, hx, hy, radius) of the 2-D kernels (csrc/trk_planar.hip)"""
+        c, r = self.centers.reshape(-1, 2), self.radii.reshape(-1)
+        z = np.zeros(len(c), np.float32)
+        return np.stack([np.full(len(c), _abi.PRIM_SPHERE, np.float32), c[:, 0], c[:, 1], z, z, r], 1).astype(np.float32)
+
 
 class MultiSharpBoxField(PrimitiveShapeField):               # primitives.py:197-228
     rounded = False
@@ -95,8 +102,15 @@ class MultiSharpBoxField(PrimitiveShapeField):               # primitives.py:197
 
     def prims(self):
         if self.dim != 3:
-            raise NotImplementedError("2-D boxes are outside the 3-D hot path")
+            raise NotImplementedError("2-D boxes enter the 2-D scene tables (prims2d), not a 3-D cost model")
         return box_prims(self.centers, self.sizes, rounded=self.rounded)
+
+    def prims2d(self) -> np.ndarray:
+        """rows (type, cx, cy, hx, hy, radius): half sizes sizes / 2 and, rounded, radius 0.15 * min size, in fp32 (primitives.py:212, 321)"""
+        c, h = self.centers.reshape(-1, 2), self.half_sizes.reshape(-1, 2)
+        r = self.radius.reshape(-1) if self.rounded else np.zeros(len(c), np.float32)
+        t = _abi.PRIM_ROUNDED_BOX if self.rounded else _abi.PRIM_SHARP_BOX
+        return np.stack([np.full(len(c), t, np.float32), c[:, 0], c[:, 1], h[:, 0], h[:, 1], r], 1).astype(np.float32)
 
 
 class MultiBoxField(MultiSharpBoxField):                     # rounded boxes, primitives.py:304-334
@@ -121,6 +135,50 @@ class _SDFPoints(torch.autograd.Function):
     def backward(ctx, gs):
         (grad,) = ctx.saved_tensors
         return (gs.unsqueeze(-1) * grad).sum(1), None
+
+
+class _SDFPoints2D(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, scene):
+        sdf, grad = ops.planar_sdf_points(scene, x, want_grad=True)
+        ctx.save_for_backward(grad)
+        return sdf
+
+    @staticmethod
+    def backward(ctx, gs):
+        (grad,) = ctx.saved_tensors
+        return (gs.unsqueeze(-1) * grad).sum(1), None
+
+
+def _planar_sdf(scene, x):
+    """per-df-object signed distances (N, n_df) of points x (..., 2), differentiable w.r.t. x"""
+    flat = x.reshape(-1, 2)
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _SDFPoints2D.apply(flat.contiguous(), scene)
+    return ops.planar_sdf_points(scene, flat)
+
+
+def planar_tables(obj_list):
+    """The 2-D kernels' host tables of ObjectFields: ([(pos, R, prim_begin, prim_end)], prims (k, 6) float32)."""
+    objects, rows, k = [], [], 0
+    for o in obj_list:
+        p = np.concatenate([f.prims2d() for f in o.fields], 0) if o.fields else np.zeros((0, 6), np.float32)
+        objects.append((o.pos, quat_wxyz_to_rot(o.ori), k, k + len(p)))
+        rows.append(p)
+        k += len(p)
+    return objects, (np.concatenate(rows, 0) if rows else np.zeros((0, 6), np.float32))
+
+
+def planar_scene(df_obj_list, device, ws=None, margin=0.0) -> "ops.Scene2DHandle":
+    """A 2-D scene handle of df objects in the order of EnvBase.get_df_obj_list: at most one GridMapSDF, first, then ObjectFields."""
+    grid = None
+    objs = list(df_obj_list)
+    if objs and isinstance(objs[0], GridMapSDF):
+        grid = objs.pop(0).planar_grid(device)
+    if any(isinstance(o, GridMapSDF) for o in objs):
+        raise NotImplementedError("a 2-D scene evaluates one SDF grid, ahead of its analytic objects (EnvBase.get_df_obj_list's order)")
+    objects, prims = planar_tables(objs)
+    return ops.Scene2DHandle(objects, prims, ops.compute_device(device), grid=grid, ws=ws, margin=margin)
 
 
 class ObjectField(PrimitiveShapeField):                      # primitives.py:346-420
@@ -167,7 +225,12 @@ class ObjectField(PrimitiveShapeField):                      # primitives.py:346
 
     @ops.host_round_trip
     def compute_signed_distance(self, x):
-        """x (..., 3) on the GPU -> (...) signed distance (differentiable w.r.t. x)."""
+        """x (..., 3) -- or (..., 2) for a 2-D object -- on the GPU -> (...) signed distance (differentiable w.r.t. x)."""
+        if self.dim == 2:
+            key = ("2d", x.device, self._version) + tuple(k for f in self.fields for k in f.array_ids())
+            if self._cm is None or self._cm_key != key:
+                self._cm, self._cm_key = planar_scene([self], x.device), key
+            return _planar_sdf(self._cm, x).reshape(x.shape[:-1])
         # keyed by the device, the pose version AND the primitive fields' geometry versions: `field.centers = new` must be seen here
         key = (x.device, self._version) + tuple(k for f in self.fields for k in f.array_ids())
         if self._cm is None or self._cm_key != key:
@@ -215,8 +278,8 @@ class GridMapSDF:                                            # grid_map_sdf.py:9
         self.tensor_args = DEFAULT_TENSOR_ARGS if tensor_args is None else tensor_args
         self.limits = torch.as_tensor(_np(limits), dtype=torch.float32)
         self.dim = self.limits.shape[-1]
-        if self.dim != 3:
-            raise NotImplementedError("2-D grids are outside the 3-D hot path")
+        if self.dim not in (2, 3):
+            raise NotImplementedError("GridMapSDF: 2-D and 3-D grids only")
         self.obj_list = obj_list
         self.cell_size = cell_size
         map_dim = torch.abs(self.limits[1] - self.limits[0])                  # fp32, as grid_map_sdf.py:24-27
@@ -227,10 +290,24 @@ class GridMapSDF:                                            # grid_map_sdf.py:9
         self.precompute_sdf()
 
     def precompute_sdf(self):
+        if self.dim == 2:
+            # one float4 (sdf, gx, gy, 0) per cell (trk_grid2d_precompute): a lookup is one 16-byte gather; the reference-shaped
+            # sdf_tensor (nx, ny) / grad_sdf_tensor (nx, ny, 2) are views of it
+            dev = ops.compute_device(self.tensor_args["device"])
+            self.cells = ops.grid2d_precompute(planar_scene(self.obj_list, dev), self.cmap_dim.numpy(), self.limits[0].numpy(),
+                                               self.limits[1].numpy())
+            self.sdf_tensor, self.grad_sdf_tensor = self.cells[..., 0], self.cells[..., 1:3]
+            return
         spec = CostModelSpec(n_links_in=1, objects=[o.as_object() for o in self.obj_list])
         cm = ops.CostHandle(spec, ops.compute_device(self.tensor_args["device"]))      # the grid lives where it is computed and queried: on the GPU
         self.sdf_tensor, self.grad_sdf_tensor = ops.grid_precompute(
             cm, self.cmap_dim.numpy(), self.limits[0].numpy(), self.limits[1].numpy())
+
+    def planar_grid(self, device) -> dict:
+        """the grid of a 2-D scene handle (ops.Scene2DHandle)"""
+        if self.dim != 2:
+            raise NotImplementedError("a 3-D grid enters a 3-D cost model (grid_dict)")
+        return dict(cells=self.cells.to(ops.compute_device(device)), lim_min=self.limits[0].numpy(), map_dim=self.map_dim.numpy())
 
     def grid_dict(self) -> dict:
         return dict(dims=self.cmap_dim.numpy().astype(np.int32), lim_min=self.limits[0].numpy(),
@@ -247,6 +324,10 @@ class GridMapSDF:                                            # grid_map_sdf.py:9
     def compute_signed_distance(self, X, **kwargs):           # grid_map_sdf.py:81-114
         """Nearest-lower-cell lookup; differentiable w.r.t. X with the STORED gradient of that cell, like the reference's
         `sdf[idx] + (X * g).sum() - (X.detach() * g).sum()`."""
+        if self.dim == 2:
+            if getattr(self, "_q2d", None) is None or self._q2d[0] != str(X.device):
+                self._q2d = (str(X.device), planar_scene([self], X.device))
+            return _planar_sdf(self._q2d[1], X).reshape(X.shape[:-1])
         cm = self._query_handle(X.device)
         flat = X.reshape(-1, 3)
         if torch.is_grad_enabled() and X.requires_grad:
@@ -296,6 +377,17 @@ class EnvBase:                                               # env_base.py:17-10
         objs = self.get_df_obj_list()
         if not objs:
             return None
+        if self.dim == 2:
+            # the per-object distances come from one kernel launch; the reference folds them with torch.minimum (ties share the
+            # gradient), which is what is done with them here
+            key = ("2d", str(x.device), scene_version(objs))
+            if getattr(self, "_sdf_cm", None) is None or self._sdf_cm[0] != key:
+                self._sdf_cm = (key, planar_scene(objs, x.device))
+            per_obj = _planar_sdf(self._sdf_cm[1], x)
+            sdf = per_obj[:, 0]
+            for k in range(1, per_obj.shape[1]):
+                sdf = torch.minimum(sdf, per_obj[:, k])
+            return sdf.reshape(reshape_shape) if reshape_shape else sdf.reshape(x.shape[:-1])
         key = (str(x.device), scene_version(objs))
         if getattr(self, "_sdf_cm", None) is None or self._sdf_cm[0] != key:
             spec = CostModelSpec(n_links_in=1)
@@ -401,3 +493,119 @@ class EnvMazeBoxes3D(EnvBase):                               # env_maze_boxes_3d
     def __init__(self, tensor_args=None, **kwargs):
         super().__init__(name=self.__class__.__name__, limits=np.array([[-1, -1, -1], [1, 1, 1]], np.float32),
                          obj_fixed_list=create_3d_rectangles_objects(tensor_args), tensor_args=tensor_args, **kwargs)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# 2-D scenes (env_simple_2d.py, env_dense_2d.py, env_narrow_passage_dense_2d.py, env_square_2d.py, env_circle_2d.py,
+# env_grid_circles_2d.py and the three *_extra_objects.py).  Their obstacle tables are data of the reference: they are read from the
+# recorded fixture tests/golden/scenes_2d.npz (tools/gen_golden_2d.py), not restated here.
+# ------------------------------------------------------------------------------------------------------------------------------
+SCENES_2D_PATH = Path(__file__).resolve().parent.parent / "tests" / "golden" / "scenes_2d.npz"
+_FIELD_KIND_2D = {0: MultiSphereField, 1: MultiBoxField, 2: MultiSharpBoxField}
+_scenes_2d = None
+
+
+def load_scene_2d(name: str, tensor_args=None) -> dict:
+    """The recorded tables of one 2-D scene -> dict(limits (2, 2), grid_on, cell, fixed=[ObjectField], extra=[ObjectField])."""
+    global _scenes_2d
+    if _scenes_2d is None:
+        if not SCENES_2D_PATH.exists():
+            raise FileNotFoundError(f"{SCENES_2D_PATH} is missing: the 2-D scenes read their obstacle tables from it (a repository "
+                                    f"checkout carries it; tools/gen_golden_2d.py records it from the reference)")
+        with np.load(SCENES_2D_PATH) as z:
+            _scenes_2d = {k: z[k] for k in z.files}
+    z = _scenes_2d
+    if f"{name}/limits" not in z:
+        raise KeyError(f"scenes_2d.npz has no scene {name!r}")
+    fields, prims = z[f"{name}/fields"], z[f"{name}/prims"]
+    n_obj = len(z[f"{name}/obj_pos"])
+    per_obj = [[] for _ in range(n_obj)]
+    row = 0
+    for o, _, kind, n in fields:                   # rows (object, field, kind, n primitives), primitives in the same order
+        p = prims[row:row + n]
+        row += n
+        cls = _FIELD_KIND_2D[int(kind)]
+        per_obj[int(o)].append(cls(p[:, :2], p[:, 2] if kind == 0 else p[:, 2:4], tensor_args=tensor_args))
+    out = dict(limits=z[f"{name}/limits"], grid_on=bool(z[f"{name}/grid_on"]), cell=float(z[f"{name}/cell"]), fixed=[], extra=[])
+    for k in range(n_obj):
+        obj = ObjectField(per_obj[k], str(z[f"{name}/obj_name"][k]), pos=z[f"{name}/obj_pos"][k], ori=z[f"{name}/obj_ori"][k])
+        out["extra" if z[f"{name}/obj_extra"][k] else "fixed"].append(obj)
+    return out
+
+
+class _Env2D(EnvBase):
+    """A recorded 2-D scene: `_SCENE` names its tables; the subclasses keep the reference's constructor arguments and defaults."""
+    _SCENE = None
+
+    def _init_2d(self, name, tensor_args, **kwargs):
+        t = load_scene_2d(self._SCENE, tensor_args)
+        EnvBase.__init__(self, name=name, limits=t["limits"], obj_fixed_list=t["fixed"], tensor_args=tensor_args, **kwargs)
+
+
+class EnvSimple2D(_Env2D):                                   # env_simple_2d.py: 15 spheres, grid 400 x 400
+    _SCENE = "EnvSimple2D"
+
+    def __init__(self, name="EnvDense2D", tensor_args=None, precompute_sdf_obj_fixed=True, sdf_cell_size=0.005, **kwargs):
+        self._init_2d(name, tensor_args, precompute_sdf_obj_fixed=precompute_sdf_obj_fixed, sdf_cell_size=sdf_cell_size, **kwargs)
+
+
+class EnvDense2D(_Env2D):                                    # env_dense_2d.py: 16 spheres + 14 rounded boxes, grid 400 x 400
+    _SCENE = "EnvDense2D"
+
+    def __init__(self, name="EnvDense2D", tensor_args=None, precompute_sdf_obj_fixed=True, sdf_cell_size=0.005, **kwargs):
+        self._init_2d(name, tensor_args, precompute_sdf_obj_fixed=precompute_sdf_obj_fixed, sdf_cell_size=sdf_cell_size, **kwargs)
+
+
+class EnvNarrowPassageDense2D(_Env2D):                       # env_narrow_passage_dense_2d.py: 8 spheres + 11 boxes, analytic
+    _SCENE = "EnvNarrowPassageDense2D"
+
+    def __init__(self, name="EnvDense2D", tensor_args=None, **kwargs):
+        self._init_2d(name, tensor_args, **kwargs)
+
+
+class EnvSquare2D(_Env2D):                                   # env_square_2d.py: 1 rounded box, analytic
+    _SCENE = "EnvSquare2D"
+
+    def __init__(self, tensor_args=None, **kwargs):
+        self._init_2d(self.__class__.__name__, tensor_args, **kwargs)
+
+
+class EnvCircle2D(_Env2D):                                   # env_circle_2d.py: 1 sphere, grid 400 x 400
+    _SCENE = "EnvCircle2D"
+
+    def __init__(self, name="EnvDense2D", tensor_args=None, precompute_sdf_obj_fixed=True, sdf_cell_size=0.005, **kwargs):
+        self._init_2d(name, tensor_args, precompute_sdf_obj_fixed=precompute_sdf_obj_fixed, sdf_cell_size=sdf_cell_size, **kwargs)
+
+
+class EnvGridCircles2D(_Env2D):                              # env_grid_circles_2d.py: 7 x 7 spheres, analytic
+    _SCENE = "EnvGridCircles2D"
+
+    def __init__(self, tensor_args=None, **kwargs):
+        self._init_2d(self.__class__.__name__, tensor_args, **kwargs)
+
+
+def _extra_objects(scene, tensor_args):
+    return load_scene_2d(scene, tensor_args)["extra"]
+
+
+class EnvSimple2DExtraObjects(EnvSimple2D):                 # env_simple_2d_extra_objects.py: + 9 spheres, 3 boxes
+    def __init__(self, tensor_args=None, **kwargs):
+        super().__init__(name=self.__class__.__name__, obj_extra_list=_extra_objects("EnvSimple2DExtraObjects", tensor_args),
+                         tensor_args=tensor_args, **kwargs)
+
+
+class EnvDense2DExtraObjects(EnvDense2D):                   # env_dense_2d_extra_objects.py: + 3 spheres, 4 boxes
+    def __init__(self, tensor_args=None, **kwargs):
+        super().__init__(name=self.__class__.__name__, obj_extra_list=_extra_objects("EnvDense2DExtraObjects", tensor_args),
+                         tensor_args=tensor_args, **kwargs)
+
+
+class EnvNarrowPassageDense2DExtraObjects(EnvNarrowPassageDense2D):   # env_narrow_passage_dense_2d_extra_objects.py: + 8 spheres, 6 boxes
+    def __init__(self, tensor_args=None, **kwargs):
+        super().__init__(name=self.__class__.__name__,
+                         obj_extra_list=_extra_objects("EnvNarrowPassageDense2DExtraObjects", tensor_args),
+                         tensor_args=tensor_args, **kwargs)
+
+
+SCENES_2D = (EnvSimple2D, EnvDense2D, EnvNarrowPassageDense2D, EnvSquare2D, EnvCircle2D, EnvGridCircles2D,
+             EnvSimple2DExtraObjects, EnvDense2DExtraObjects, EnvNarrowPassageDense2DExtraObjects)

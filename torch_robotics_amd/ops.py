@@ -1411,6 +1411,159 @@ def scale_rows(g: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# 2-D point mass in a planar scene (csrc/trk_planar.hip)
+# ------------------------------------------------------------------------------------------------------------------------------
+class Scene2DHandle:
+    """Owns a TrkScene2D*: the analytic objects of a 2-D scene (copied at create), optionally a snapshot of its SDF grid, the
+    workspace box and the margin.  objects: [(pos (3,), R (3, 3), prim_begin, prim_end)]; prims: float32 (k, 6) rows
+    (type, cx, cy, hx, hy, radius); grid: dict(cells=(nx, ny, 4) fp32 tensor on `device`, lim_min=(2,), map_dim=(2,)) or None;
+    ws: (ws_min (2,), ws_max (2,)) or None."""
+
+    def __init__(self, objects, prims, device, grid=None, ws=None, margin: float = 0.0):
+        self.device = torch.device(device)
+        prims = np.asarray(prims, np.float32).reshape(-1, 6)
+        if len(objects) > _abi.TRK_PLANAR_MAX_OBJECTS or len(prims) > _abi.TRK_PLANAR_MAX_PRIMS:
+            raise NotImplementedError(f"Scene2DHandle: {len(objects)} objects / {len(prims)} primitives, the 2-D kernels take at most "
+                                      f"{_abi.TRK_PLANAR_MAX_OBJECTS} / {_abi.TRK_PLANAR_MAX_PRIMS}")
+        d = _abi.Scene2DDesc()
+        d.abi_version = _abi.TRK_ABI_VERSION
+        objs = (_abi.Object2D * max(1, len(objects)))()
+        for k, (pos, R, b, e) in enumerate(objects):
+            objs[k].pos = (C.c_float * 3)(*np.asarray(pos, np.float32).reshape(3))
+            objs[k].R = (C.c_float * 9)(*np.asarray(R, np.float32).reshape(9))
+            objs[k].prim_begin, objs[k].prim_end = int(b), int(e)
+        pr = (_abi.Prim2D * max(1, len(prims)))()
+        for k, row in enumerate(prims):
+            pr[k].type = int(row[0])
+            pr[k].center = (C.c_float * 2)(row[1], row[2])
+            pr[k].half = (C.c_float * 2)(row[3], row[4])
+            pr[k].radius = float(row[5])
+        d.n_objects, d.objects, d.n_prims, d.prims = len(objects), objs, len(prims), pr
+        self.n_df = len(objects)
+        cells = None
+        if grid is not None:
+            cells = grid["cells"]
+            if not (isinstance(cells, torch.Tensor) and cells.device == self.device and cells.dtype == torch.float32 and cells.dim() == 3
+                    and cells.shape[-1] == 4 and cells.is_contiguous()):
+                raise ValueError("Scene2DHandle: grid cells must be a contiguous float32 (nx, ny, 4) tensor on the scene's device")
+            d.has_grid = 1
+            d.grid_dims = (C.c_int32 * 2)(int(cells.shape[0]), int(cells.shape[1]))
+            d.grid_cells = cells.data_ptr()
+            d.grid_lim_min = (C.c_float * 2)(*np.asarray(grid["lim_min"], np.float32).reshape(2))
+            d.grid_map_dim = (C.c_float * 2)(*np.asarray(grid["map_dim"], np.float32).reshape(2))
+            self.n_df += 1
+        if ws is not None:
+            d.has_ws = 1
+            d.ws_min = (C.c_float * 2)(*np.asarray(ws[0], np.float32).reshape(2))
+            d.ws_max = (C.c_float * 2)(*np.asarray(ws[1], np.float32).reshape(2))
+        d.margin = float(np.float32(margin))
+        self.margin = d.margin
+        h = C.c_void_p()
+        with _on(self.device):
+            if cells is not None:               # trk_scene2d_create copies the grid on the NULL stream: wait for torch's stream first
+                torch.cuda.current_stream(self.device).synchronize()
+            check(lib().trk_scene2d_create(C.byref(d), C.byref(h)), "trk_scene2d_create")
+        self._h = h
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                lib().trk_scene2d_destroy(h)
+            except Exception:
+                pass
+
+
+def _points2d(q: torch.Tensor, what: str) -> torch.Tensor:
+    """(..., 2) fp32, contiguous, 8-byte aligned (the kernels load one float2 per point)."""
+    q = _dev_f32(q, what)
+    if q.dim() == 0 or q.shape[-1] != 2:
+        raise ValueError(f"{what}: expected points (..., 2), got {tuple(q.shape)}")
+    return q if q.data_ptr() % 8 == 0 else q.clone()
+
+
+def planar_cost_grad(scene: Scene2DHandle, q: torch.Tensor, clamp: bool = False, want_grad: bool = True):
+    """Point-mass collision cost of q (..., 2): objects + workspace terms (include/trk.h) -> cost (...), grad (..., 2) or None."""
+    x = _points2d(q, "planar_cost_grad(q)")
+    n = x.numel() // 2
+    cost = torch.empty(x.shape[:-1], device=x.device, dtype=torch.float32)
+    g = torch.empty_like(x) if want_grad else None
+    with _on(x.device):
+        check(lib().trk_scene2d_cost_grad(scene._h, x.data_ptr(), n, int(bool(clamp)), cost.data_ptr(), _ptr(g), _stream(x)),
+              "trk_scene2d_cost_grad")
+    return cost, g
+
+
+class _PlanarCost(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, scene, clamp):
+        cost, g = planar_cost_grad(scene, q, clamp, want_grad=True)
+        ctx.save_for_backward(g)
+        return cost
+
+    @staticmethod
+    def backward(ctx, gcost):
+        (g,) = ctx.saved_tensors
+        return scale_rows(g, gcost), None, None          # the kernel's gradient times the upstream one, per sample
+
+
+def planar_cost(scene: Scene2DHandle, q: torch.Tensor, clamp: bool = False) -> torch.Tensor:
+    """planar_cost_grad's cost, differentiable w.r.t. q: backward reuses the gradient the forward kernel wrote."""
+    if torch.is_grad_enabled() and q.requires_grad:
+        return _PlanarCost.apply(q, scene, bool(clamp))
+    return planar_cost_grad(scene, q, clamp, want_grad=False)[0]
+
+
+def planar_collision(scene: Scene2DHandle, q: torch.Tensor, margin: Optional[float] = None) -> torch.Tensor:
+    """q (..., 2) -> bool (...): some df object or workspace face closer than the margin (the scene's, or `margin`)."""
+    x = _points2d(q, "planar_collision(q)")
+    out = torch.empty(x.shape[:-1], device=x.device, dtype=torch.bool)
+    with _on(x.device):
+        check(lib().trk_scene2d_collision(scene._h, x.data_ptr(), x.numel() // 2, float("nan") if margin is None else float(margin),
+                                          out.data_ptr(), _stream(x)), "trk_scene2d_collision")
+    return out
+
+
+def planar_collision_via(scene: Scene2DHandle, trajs: torch.Tensor, num_interpolation: int, margin: Optional[float] = None) -> torch.Tensor:
+    """planar_collision of the interpolated via points of trajs (T, H, S >= 2) without materialising them -> bool (T, (H-1) n)."""
+    x = _dev_f32(trajs, "planar_collision_via(trajs)")
+    if x.dim() != 3 or x.shape[-1] < 2 or x.shape[1] < 2:
+        raise ValueError(f"planar_collision_via: expected trajectories (T, H >= 2, S >= 2), got {tuple(x.shape)}")
+    T, H, S = (int(v) for v in x.shape)
+    n = int(num_interpolation)
+    alpha, beta = via_point_weights(n, x.device)
+    out = torch.empty((T, (H - 1) * n), device=x.device, dtype=torch.bool)
+    with _on(x.device):
+        check(lib().trk_scene2d_collision_via(scene._h, x.data_ptr(), T, H, S, n, alpha.data_ptr(), beta.data_ptr(),
+                                              float("nan") if margin is None else float(margin), out.data_ptr(), _stream(x)),
+              "trk_scene2d_collision_via")
+    return out
+
+
+def grid2d_precompute(scene: Scene2DHandle, dims, lim_min, lim_max) -> torch.Tensor:
+    """GridMapSDF.precompute_sdf in 2-D from the scene's analytic objects -> cells (nx, ny, 4) = (sdf, gx, gy, 0) on its device."""
+    dims_a = np.ascontiguousarray(np.asarray(dims, np.int64).reshape(2).astype(np.int32))
+    lo = np.ascontiguousarray(np.asarray(lim_min, np.float32).reshape(2))
+    hi = np.ascontiguousarray(np.asarray(lim_max, np.float32).reshape(2))
+    cells = torch.empty((int(dims_a[0]), int(dims_a[1]), 4), device=scene.device, dtype=torch.float32)
+    with _on(scene.device):
+        check(lib().trk_grid2d_precompute(scene._h, dims_a.ctypes.data, lo.ctypes.data, hi.ctypes.data, cells.data_ptr(),
+                                          _stream_of(scene.device)), "trk_grid2d_precompute")
+    return cells
+
+
+def planar_sdf_points(scene: Scene2DHandle, pts: torch.Tensor, want_grad: bool = False):
+    """Signed distance of points (N, 2) to each df object of the scene (grid first) -> sdf (N, n_df)[, grad (N, n_df, 2)]."""
+    x = _points2d(pts, "planar_sdf_points(pts)").reshape(-1, 2)
+    n = x.shape[0]
+    sdf = torch.empty((n, scene.n_df), device=x.device, dtype=torch.float32)
+    g = torch.empty((n, scene.n_df, 2), device=x.device, dtype=torch.float32) if want_grad else None
+    with _on(x.device):
+        check(lib().trk_scene2d_sdf_points(scene._h, x.data_ptr(), n, sdf.data_ptr(), _ptr(g), _stream(x)), "trk_scene2d_sdf_points")
+    return (sdf, g) if want_grad else sdf
+
+
 def reduce_sum(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Deterministic sum of a float32 device vector (fixed association order)."""
     x = _dev_f32(x, "reduce_sum(x)").reshape(-1)

@@ -12,7 +12,7 @@ import torch
 from . import ops
 from ._abi import FIELD_OBJECTS, FIELD_SELF, FIELD_WS
 from .costmodel import CostModelSpec
-from .environments import _np, objects_to_spec_parts, scene_version
+from .environments import _np, objects_to_spec_parts, planar_scene, scene_version
 from .fields import CollisionObjectDistanceField, CollisionWorkspaceBoundariesDistanceField
 
 
@@ -113,6 +113,25 @@ class PlanningTask(Task):
     def _has_tree(self) -> bool:
         """False for robots without kinematics (RobotPointMass3D: task space == configuration space)."""
         return getattr(self.robot, "diff_panda", None) is not None
+
+    @property
+    def _planar(self) -> bool:
+        """RobotPointMass in a 2-D scene: the point-mass kernels of csrc/trk_planar.hip serve every evaluation."""
+        return not self._has_tree and self.robot.q_dim == 2
+
+    def _planar_handles(self, device):
+        """(scene handle, clamp) for the 2-D point mass: the df objects (grid first), the workspace box and the margin -- link margin +
+        cutoff margin in fp32, the same for both fields (distance_fields.py:112) -- keyed like _fused_handles by the objects' poses."""
+        objs, ws = self.df_collision_objects, self.df_collision_ws_boundaries
+        clamps = {self.clamp_sdf or bool(getattr(f, "clamp_sdf", False)) for f in (objs, ws)}
+        key = (str(device), scene_version(self.env.get_df_obj_list()), tuple(clamps))
+        if self._fused is None or self._fused[2] != key:
+            if len(clamps) != 1:
+                raise NotImplementedError("2-D point mass: the object and workspace fields must agree on clamp_sdf")
+            margin = objs._margin_vector(1)[0]
+            scene = planar_scene(self.env.get_df_obj_list(), device, ws=(_np(self.ws_min), _np(self.ws_max)), margin=margin)
+            self._fused = (None, (scene, clamps.pop()), key)
+        return self._fused[1]
 
     def _n_columns(self) -> int:
         """Width of fk_map_collision's output: the links, plus the grasped object's points if there is one."""
@@ -256,6 +275,13 @@ class PlanningTask(Task):
             q = q.unsqueeze(1)
         elif q.ndim > 3:
             raise NotImplementedError
+        if self._planar:                                   # RobotPointMass in a 2-D scene: positions are q itself
+            if self.df_collision_self is not None:
+                raise NotImplementedError("2-D point mass: a self-collision field is outside the 2-D kernels")
+            scene, clamp = self._planar_handles(q.device)
+            if field_type == "occupancy":
+                return ops.planar_collision(scene, q.detach(), margin=kwargs.get("margin", None)).reshape(q.shape[:-1])
+            return ops.planar_cost(scene, q, clamp).reshape(q.shape[:-1])
         model, cm = self._fused_handles(q.device)
         fields = FIELD_OBJECTS | FIELD_WS | (FIELD_SELF if self.df_collision_self is not None else 0)
         if model is None:                                  # RobotPointMass3D: positions are q itself (robot_point_mass.py:29-32)
@@ -292,6 +318,10 @@ class PlanningTask(Task):
     def _waypoint_collisions_and_flags(self, flat, num_interpolation, limits=None):
         """`_waypoint_collisions`; with limits=(q_min, q_max): -> (bool (T, W), flags or None) -- the per-trajectory flags folded into
         the same launch when a generated kernel serves the call (ops.rollout_collision_via)."""
+        if self._planar and num_interpolation > 0 and flat.shape[1] >= 2:
+            # 2-D point mass: interpolation and the boolean test in one launch, the via points never stored
+            wp = ops.planar_collision_via(self._planar_handles(flat.device)[0], flat, num_interpolation, margin=0.)
+            return wp if limits is None else (wp, None)
         if self._has_tree and self._points(flat.device) is None and num_interpolation > 0 and flat.shape[1] >= 2:
             model, cm = self._fused_handles(flat.device)
             fields = FIELD_OBJECTS | FIELD_WS | (FIELD_SELF if self.df_collision_self is not None else 0)
