@@ -9,6 +9,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 #include "trk_launch.h"
@@ -324,7 +325,6 @@ static const SpecEntry* model_spec(const TrkModel* m) {
     if (!m->spec) m->spec = trk_spec_find(m->hash, m->hdr.n_links, m->hdr.n_dofs);
     return m->spec;
 }
-static const SpecEntry* model_spec_for(const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w);
 
 struct TrkPointSet {
     DevPointSet dev;
@@ -396,6 +396,7 @@ static const SpecEntry* points_spec(const TrkPointSet* ps) {
     if (!ps->spec) ps->spec = trk_spec_find_points(ps->model->hash, ps->hash, ps->dev.n_points);
     return ps->spec;
 }
+static const SpecEntry* enabled_points_spec(const TrkPointSet* ps) { return ps->model->spec_enabled ? points_spec(ps) : nullptr; }
 static const SpecEntry* points_spec_for(const TrkPointSet* ps, const TrkCostModel* cm, const TrkRolloutWeights* w) {
     for (const SpecEntry* e : spec_registry())
         if (e->n_points == ps->dev.n_points && e->n_points > 0 && e->model_hash == ps->model->hash &&
@@ -418,6 +419,130 @@ static const SpecEntry* model_spec_for(const TrkModel* m, const TrkCostModel* cm
             spec_matches(e, cm, w))
             return e;
     return nullptr;
+}
+
+// SpecArgs for launches that evaluate no objective (all weights zero): every table pointer of the cost header points at a
+// small zero-filled device buffer instead of NULL, so a scalar load the compiler moved out of a weight-guarded branch
+// reads zeros rather than faulting.
+static void* g_zero_blob = nullptr;
+static int blank_spec_args(SpecArgs& a) {
+    if (!g_zero_blob) {
+        hipError_t e = hipMalloc(&g_zero_blob, 4096);
+        if (e == hipSuccess) e = hipMemset(g_zero_blob, 0, 4096);
+        if (e != hipSuccess) { g_zero_blob = nullptr; return hip_fail(e, "zero table allocation"); }
+    }
+    std::memset(&a, 0, sizeof(a));
+    DevCostHdr& h = a.C;
+    h.ee_link = -1; h.ee2_link = -1;
+    h.obj_link_idx = static_cast<const int32_t*>(g_zero_blob); h.obj_link_margin = static_cast<const float*>(g_zero_blob);
+    h.objects = static_cast<const DevObj*>(g_zero_blob); h.prims = static_cast<const DevPrim*>(g_zero_blob);
+    h.self_pairs = static_cast<const int32_t*>(g_zero_blob); h.self_margin = static_cast<const float*>(g_zero_blob);
+    h.spheres = static_cast<const float4*>(g_zero_blob); h.spheres_sel = static_cast<const float4*>(g_zero_blob);
+    h.box_objects = static_cast<const int32_t*>(g_zero_blob);
+    h.sphere_pairs = static_cast<const float*>(g_zero_blob);
+    h.virtual_src = static_cast<const int32_t*>(g_zero_blob); h.virtual_w = static_cast<const float*>(g_zero_blob);
+    return TRK_OK;
+}
+
+static int base_is_identity(const TrkModel* m) {
+    const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Z[3] = {0, 0, 0};
+    return std::memcmp(m->hdr.base_R, I, sizeof(I)) == 0 && std::memcmp(m->hdr.base_t, Z, sizeof(Z)) == 0;
+}
+// the generated kernels produce / consume all links in file order
+static bool all_links_selected(const TrkModel* m, const SelMap& sel, int ns) {
+    if (ns != m->hdr.n_links) return false;
+    for (int k = 0; k < ns; ++k) if (sel.col[k] != k) return false;
+    return true;
+}
+
+static int check_model(const TrkModel* m, const char* who) {
+    if (!m) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null model");
+    if (m->unsupported) return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": model has a joint type other than fixed/revolute/continuous/prismatic");
+    return TRK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// The dispatch vocabulary (DESIGN.md "The dispatch path").  Every entry point that a generated unit can serve reads:
+// validate, choose the unit, spec_args + bind the outputs, spec_launch -- else the table-driven kernel.
+// ------------------------------------------------------------------------------------------------------------------------------
+// Unit lookup.  enabled_spec: any unit of the model (the FK / Jacobian / IK entries); enabled_spec_for: the unit whose baked link
+// sets equal the cost model's for the non-zero weights (the rollout family).  Both honour trk_model_enable_specialized and see units
+// registered after the model was created.
+static const SpecEntry* enabled_spec(const TrkModel* m) { return m->spec_enabled ? model_spec(m) : nullptr; }
+static const SpecEntry* enabled_spec_for(const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w) {
+    return m->spec_enabled ? model_spec_for(m, cm, w) : nullptr;
+}
+
+// the model's base pose, for every argument struct that carries one (SpecArgs, IkArgs, IkGnArgs)
+template <class Args>
+static void set_base_pose(Args& a, const TrkModel* m) {
+    std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
+    std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
+}
+// SpecArgs of one launch, everything else zero: the cost header and weights of (cm, w) -- or, for a launch that evaluates no
+// objective (cm == nullptr), the blanked header -- and the base pose of m (nullptr: the field kernels on given positions, which
+// involve no model and are launched with base_identity = 1).
+static int spec_args(SpecArgs& a, const TrkModel* m, const TrkCostModel* cm = nullptr, const TrkRolloutWeights* w = nullptr) {
+    if (cm) { std::memset(&a, 0, sizeof(a)); a.C = cm->hdr; a.w = *w; }
+    else if (int rc = blank_spec_args(a)) return rc;
+    if (m) set_base_pose(a, m);
+    return TRK_OK;
+}
+// output binders: the fused rollout's outputs, boolean mode, the geometric Jacobian of one link
+static void bind_rollout(SpecArgs& a, const void* q, int64_t n, void* link_pos, float* cost, void* gq, float* cost_sum, int io_mode,
+                         float grad_scale, unsigned long long* stamps) {
+    a.q = q; a.n = n; a.link_pos = link_pos; a.cost = cost; a.gq = gq; a.cost_sum = cost_sum;
+    a.stamps = stamps; a.io_f16 = io_mode; a.grad_scale = grad_scale;
+}
+static void bind_collision(SpecArgs& a, uint8_t* in_collision, int32_t fields, float margin_override) {
+    a.coll_out = in_collision; a.coll_fields = fields;
+    a.coll_use_default = std::isnan(margin_override) ? 1 : 0;          // NaN: the cost model's per-link margins and cutoff
+    a.coll_margin = a.coll_use_default ? 0.0f : margin_override;
+}
+static void bind_jacobian(SpecArgs& a, const TrkModel* m, int32_t link, float* pos, float* quat, float* lin_jac, float* ang_jac) {
+    a.jac_link = link; a.jac_joint_idx = m->joint_list_idx[link];
+    a.jac_pos = pos; a.jac_quat = quat; a.jac_lin = lin_jac; a.jac_ang = ang_jac;
+}
+
+// Launch through one of a unit's pointers and report a failed launch.  The int-returning pointers (launch_gp, launch_rjac) answer 1
+// when the unit does not serve this call: nothing was launched, SPEC_DECLINED comes back and the caller takes its two-launch form.
+enum { SPEC_DECLINED = 1 };
+template <class Fn, class Args>
+static int spec_launch(Fn fn, const SpecEntry* e, const Args& a, const TrkModel* m, trk_stream_t stream) {
+    const int base_identity = m ? base_is_identity(m) : 1;
+    if constexpr (std::is_void_v<decltype(fn(e, a, base_identity, (hipStream_t)stream))>) fn(e, a, base_identity, (hipStream_t)stream);
+    else if (fn(e, a, base_identity, (hipStream_t)stream) != 0) return SPEC_DECLINED;
+    TRK_HIP(last_launch_error());
+    return TRK_OK;
+}
+// the rollout family records which kernel family served the call (trk_last_dispatch); the other entry points do not
+static int served_generated(int rc) {
+    if (rc == TRK_OK) g_last_dispatch = TRK_DISPATCH_GENERATED;
+    return rc;
+}
+
+// Field mask -> weights, for the entry points that take a TRK_FIELD_* mask.  Two conventions, on purpose:
+//  * given positions (trk_cost_fields, trk_collision_fields; ws_implies_obj = false): the weights are what the field kernel
+//    multiplies each term by, so the workspace field alone must leave the object term at zero;
+//  * boolean rollouts (trk_rollout_collision, ..._via; ws_implies_obj = true): the tests are chosen by coll_fields, the weights only
+//    choose the unit -- and the workspace test walks the unit's baked OBJECT-link set, so it asks for that set like the object field
+//    does.  (spec_matches compares the set for either weight, so the unit chosen is the same; the value is kept because it travels
+//    to the kernel in SpecArgs.)
+static TrkRolloutWeights field_weights(int32_t fields, bool ws_implies_obj) {
+    const int32_t obj = TRK_FIELD_OBJECTS | (ws_implies_obj ? TRK_FIELD_WS : 0);
+    return TrkRolloutWeights{(fields & TRK_FIELD_SELF) ? 1.0f : 0.0f, (fields & obj) ? 1.0f : 0.0f, (fields & TRK_FIELD_WS) ? 1.0f : 0.0f, 0.0f};
+}
+
+// What the rollout family's entry points check alike; what belongs to one entry (its outputs, link range, prior, point set, LDS
+// size) stays there.  link_columns = false: the cost model's columns are not the model's links (attached points; the caller checks).
+static int check_rollout_call(const char* who, const TrkModel* m, const TrkCostModel* cm, int64_t batch, int32_t horizon,
+                              bool link_columns = true) {
+    int rc = check_model(m, who);
+    if (rc) return rc;
+    if (!cm) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null cost model");
+    if (batch < 0 || horizon < 1) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": bad batch/horizon");
+    if (link_columns && cm->hdr.n_links_in != m->hdr.n_links) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": cost model n_links_in != model n_links");
+    return TRK_OK;
 }
 
 extern "C" {
@@ -557,46 +682,6 @@ static int make_sel(const TrkModel* m, const int32_t* link_sel, int32_t n_sel, S
     return TRK_OK;
 }
 
-// SpecArgs for launches that evaluate no objective (all weights zero): every table pointer of the cost header points at a
-// small zero-filled device buffer instead of NULL, so a scalar load the compiler moved out of a weight-guarded branch
-// reads zeros rather than faulting.
-static void* g_zero_blob = nullptr;
-static int blank_spec_args(SpecArgs& a) {
-    if (!g_zero_blob) {
-        hipError_t e = hipMalloc(&g_zero_blob, 4096);
-        if (e == hipSuccess) e = hipMemset(g_zero_blob, 0, 4096);
-        if (e != hipSuccess) { g_zero_blob = nullptr; return hip_fail(e, "zero table allocation"); }
-    }
-    std::memset(&a, 0, sizeof(a));
-    DevCostHdr& h = a.C;
-    h.ee_link = -1; h.ee2_link = -1;
-    h.obj_link_idx = static_cast<const int32_t*>(g_zero_blob); h.obj_link_margin = static_cast<const float*>(g_zero_blob);
-    h.objects = static_cast<const DevObj*>(g_zero_blob); h.prims = static_cast<const DevPrim*>(g_zero_blob);
-    h.self_pairs = static_cast<const int32_t*>(g_zero_blob); h.self_margin = static_cast<const float*>(g_zero_blob);
-    h.spheres = static_cast<const float4*>(g_zero_blob); h.spheres_sel = static_cast<const float4*>(g_zero_blob);
-    h.box_objects = static_cast<const int32_t*>(g_zero_blob);
-    h.sphere_pairs = static_cast<const float*>(g_zero_blob);
-    h.virtual_src = static_cast<const int32_t*>(g_zero_blob); h.virtual_w = static_cast<const float*>(g_zero_blob);
-    return TRK_OK;
-}
-
-static int base_is_identity(const TrkModel* m) {
-    const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Z[3] = {0, 0, 0};
-    return std::memcmp(m->hdr.base_R, I, sizeof(I)) == 0 && std::memcmp(m->hdr.base_t, Z, sizeof(Z)) == 0;
-}
-// the generated kernels produce / consume all links in file order
-static bool spec_all_links(const TrkModel* m, const SelMap& sel, int ns) {
-    if (!model_spec(m) || !m->spec_enabled || ns != m->hdr.n_links) return false;
-    for (int k = 0; k < ns; ++k) if (sel.col[k] != k) return false;
-    return true;
-}
-
-static int check_model(const TrkModel* m, const char* who) {
-    if (!m) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null model");
-    if (m->unsupported) return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": model has a joint type other than fixed/revolute/continuous/prismatic");
-    return TRK_OK;
-}
-
 static int fk_fwd(int mode, const TrkModel* m, const float* q, int64_t n, const int32_t* link_sel, int32_t n_sel,
                   float* out, trk_stream_t stream, const char* who) {
     int rc = check_model(m, who);
@@ -606,46 +691,24 @@ static int fk_fwd(int mode, const TrkModel* m, const float* q, int64_t n, const 
     rc = make_sel(m, link_sel, n_sel, sel, ns, who);
     if (rc) return rc;
     if (n == 0) return TRK_OK;
-    if (mode == 1 && spec_all_links(m, sel, ns)) {
-        // generated kernel, positions-only exit (gq == nullptr): same FK code as the fused rollout
-        SpecArgs a{};
-        rc = blank_spec_args(a);
-        if (rc) return rc;
-        std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-        std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
-        a.q = q; a.n = n; a.link_pos = out;
-        m->spec->launch(m->spec, a, base_is_identity(m), (hipStream_t)stream);
-        TRK_HIP(last_launch_error());
-        return TRK_OK;
-    }
-    if (mode == 0 && ns == 1 && model_spec(m) && m->spec_enabled && m->spec->launch_fk1) {
-        // generated kernel: the unrolled stateless walk up to the one selected link
-        SpecArgs a{};
-        rc = blank_spec_args(a);
-        if (rc) return rc;
-        std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-        std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
-        a.q = q; a.n = n; a.fk_H = out;
-        a.jac_link = -1; a.jac_p_end = 1;
-        for (int l = 0; l < m->hdr.n_links; ++l) if (sel.col[l] == 0) a.jac_link = l;
-        for (int p = 0; p < m->hdr.n_links; ++p) if (m->links[p].link == a.jac_link) a.jac_p_end = p + 1;
-        if (a.jac_link >= 0) {
-            m->spec->launch_fk1(m->spec, a, base_is_identity(m), (hipStream_t)stream);
-            TRK_HIP(last_launch_error());
-            return TRK_OK;
+    // generated kernels: positions through the fused rollout's positions-only exit (gq == nullptr: the same FK code); matrices
+    // through the unrolled stateless walk, up to the one selected link (fk1) or with every link's 4x4 streamed out as it exists (fkh)
+    const SpecEntry* e = enabled_spec(m);
+    const bool all = e && all_links_selected(m, sel, ns);
+    int fk1_link = -1;
+    if (e && mode == 0 && ns == 1 && e->launch_fk1)
+        for (int l = 0; l < m->hdr.n_links; ++l) if (sel.col[l] == 0) fk1_link = l;
+    const SpecLaunchFn fn = mode == 1 ? (all ? e->launch : nullptr) : fk1_link >= 0 ? e->launch_fk1 : (all ? e->launch_fkh : nullptr);
+    if (fn) {
+        SpecArgs a;
+        if ((rc = spec_args(a, m)) != TRK_OK) return rc;
+        a.q = q; a.n = n;
+        if (mode == 1) a.link_pos = out; else a.fk_H = out;
+        if (fk1_link >= 0) {
+            a.jac_link = fk1_link; a.jac_p_end = 1;
+            for (int p = 0; p < m->hdr.n_links; ++p) if (m->links[p].link == fk1_link) a.jac_p_end = p + 1;
         }
-    }
-    if (mode == 0 && spec_all_links(m, sel, ns) && m->spec->launch_fkh) {
-        // generated kernel: the unrolled stateless walk, every link's 4x4 streamed out as it exists
-        SpecArgs a{};
-        rc = blank_spec_args(a);
-        if (rc) return rc;
-        std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-        std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
-        a.q = q; a.n = n; a.fk_H = out;
-        m->spec->launch_fkh(m->spec, a, base_is_identity(m), (hipStream_t)stream);
-        TRK_HIP(last_launch_error());
-        return TRK_OK;
+        return spec_launch(fn, e, a, m, stream);
     }
     trk_launch_fk_forward(mode, m->hdr, m->d_links, sel, ns, q, n, out, (hipStream_t)stream);
     TRK_HIP(last_launch_error());
@@ -668,27 +731,15 @@ static int fk_bwd(int mode, const TrkModel* m, const float* q, const float* gin,
     rc = make_sel(m, link_sel, n_sel, sel, ns, who);
     if (rc) return rc;
     if (n == 0 || m->hdr.n_dofs == 0) return TRK_OK;
-    if (mode == 0 && spec_all_links(m, sel, ns) && m->spec->launch_fkhbwd) {
-        SpecArgs a{};
-        rc = blank_spec_args(a);
-        if (rc) return rc;
-        std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-        std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
-        a.q = q; a.n = n; a.fk_H = const_cast<float*>(gin); a.gq = gq;
-        m->spec->launch_fkhbwd(m->spec, a, base_is_identity(m), (hipStream_t)stream);
-        TRK_HIP(last_launch_error());
-        return TRK_OK;
-    }
-    if (mode == 1 && spec_all_links(m, sel, ns) && m->spec->launch_posbwd) {
-        SpecArgs a{};
-        rc = blank_spec_args(a);
-        if (rc) return rc;
-        std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-        std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
-        a.q = q; a.n = n; a.link_pos = const_cast<float*>(gin); a.gq = gq;
-        m->spec->launch_posbwd(m->spec, a, base_is_identity(m), (hipStream_t)stream);
-        TRK_HIP(last_launch_error());
-        return TRK_OK;
+    // generated reverse mode (every link selected): the adjoint travels in the slot of the forward output it belongs to
+    const SpecEntry* e = enabled_spec(m);
+    const SpecLaunchFn fn = e && all_links_selected(m, sel, ns) ? (mode == 0 ? e->launch_fkhbwd : e->launch_posbwd) : nullptr;
+    if (fn) {
+        SpecArgs a;
+        if ((rc = spec_args(a, m)) != TRK_OK) return rc;
+        a.q = q; a.n = n; a.gq = gq;
+        if (mode == 0) a.fk_H = const_cast<float*>(gin); else a.link_pos = const_cast<float*>(gin);
+        return spec_launch(fn, e, a, m, stream);
     }
     SelMap selp;
     for (int k = 0; k < TRK_MAX_LINKS; ++k) selp.col[k] = -1;
@@ -760,7 +811,7 @@ void trk_point_set_destroy(TrkPointSet* ps) {
 }
 
 int trk_point_set_size(const TrkPointSet* ps) { return ps ? ps->dev.n_points : TRK_ERR_INVALID_ARG; }
-int trk_point_set_is_specialized(const TrkPointSet* ps) { return (ps && points_spec(ps) && ps->model->spec_enabled) ? 1 : 0; }
+int trk_point_set_is_specialized(const TrkPointSet* ps) { return (ps && enabled_points_spec(ps)) ? 1 : 0; }
 
 static const size_t kMaxLds = 160 * 1024;
 
@@ -771,17 +822,13 @@ int trk_fk_points(const TrkModel* m, const TrkPointSet* ps, const float* q, int6
     if (n < 0 || (n > 0 && (!pos_out || (!q && m->hdr.n_dofs > 0)))) return fail(TRK_ERR_INVALID_ARG, "trk_fk_points: bad q/out/n");
     if (trk_lds_fk_points(m->hdr, ps->dev.n_points, false) > kMaxLds) return fail(TRK_ERR_UNSUPPORTED, "trk_fk_points: point tile exceeds the 160 KiB LDS");
     if (n == 0) return TRK_OK;
-    if (points_spec(ps) && m->spec_enabled && (reinterpret_cast<uintptr_t>(pos_out) & 15) == 0) {
+    const SpecEntry* e = enabled_points_spec(ps);
+    if (e && (reinterpret_cast<uintptr_t>(pos_out) & 15) == 0) {
         // generated kernel with this point set baked in, all weights zero and no gradient output: FK + positions only
-        SpecArgs a{};
-        rc = blank_spec_args(a);
-        if (rc) return rc;
-        std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-        std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
+        SpecArgs a;
+        if ((rc = spec_args(a, m)) != TRK_OK) return rc;
         a.q = q; a.n = n; a.link_pos = pos_out;
-        ps->spec->launch(ps->spec, a, base_is_identity(m), (hipStream_t)stream);
-        TRK_HIP(last_launch_error());
-        return TRK_OK;
+        return spec_launch(e->launch, e, a, m, stream);
     }
     trk_launch_fk_points(m->hdr, m->d_links, ps->dev, q, n, pos_out, (hipStream_t)stream);
     TRK_HIP(last_launch_error());
@@ -796,16 +843,12 @@ int trk_fk_points_backward(const TrkModel* m, const TrkPointSet* ps, const float
     if (n < 0 || (n > 0 && (!gpos || ((!q || !gq) && m->hdr.n_dofs > 0)))) return fail(TRK_ERR_INVALID_ARG, "trk_fk_points_backward: bad q/g/n");
     if (trk_lds_fk_points(m->hdr, ps->dev.n_points, true) > kMaxLds) return fail(TRK_ERR_UNSUPPORTED, "trk_fk_points_backward: point tile exceeds the 160 KiB LDS");
     if (n == 0 || m->hdr.n_dofs == 0) return TRK_OK;
-    if (points_spec(ps) && ps->spec->launch_posbwd && m->spec_enabled && (reinterpret_cast<uintptr_t>(gpos) & 15) == 0) {
-        SpecArgs a{};
-        rc = blank_spec_args(a);
-        if (rc) return rc;
-        std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-        std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
+    const SpecEntry* e = enabled_points_spec(ps);
+    if (e && e->launch_posbwd && (reinterpret_cast<uintptr_t>(gpos) & 15) == 0) {
+        SpecArgs a;
+        if ((rc = spec_args(a, m)) != TRK_OK) return rc;
         a.q = q; a.n = n; a.link_pos = const_cast<float*>(gpos); a.gq = gq;
-        ps->spec->launch_posbwd(ps->spec, a, base_is_identity(m), (hipStream_t)stream);
-        TRK_HIP(last_launch_error());
-        return TRK_OK;
+        return spec_launch(e->launch_posbwd, e, a, m, stream);
     }
     trk_launch_fk_points_backward(m->hdr, m->d_links, m->d_fin, ps->dev, q, gpos, n, gq, (hipStream_t)stream);
     TRK_HIP(last_launch_error());
@@ -819,14 +862,13 @@ int trk_fk_jacobian(const TrkModel* m, const float* q, const float* qd, int64_t 
     if (link < 0 || link >= m->hdr.n_links) return fail(TRK_ERR_INVALID_ARG, "trk_fk_jacobian: link out of range");
     if (n < 0 || (n > 0 && (!q || !pos || !quat || !lin_jac || !ang_jac))) return fail(TRK_ERR_INVALID_ARG, "trk_fk_jacobian: null argument");
     if (n == 0) return TRK_OK;
-    if (m->spec_enabled && m->spec && m->spec->launch_jac && !vel_lin && !vel_ang) {
+    const SpecEntry* e = enabled_spec(m);
+    if (e && e->launch_jac && !vel_lin && !vel_ang) {
         // generated kernel: the stateful walk unrolled with the URDF constants folded; the link velocities stay table-driven
-        SpecArgs a{};
-        rc = blank_spec_args(a);
-        if (rc) return rc;
-        std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-        std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
-        a.q = q; a.n = n; a.jac_link = link; a.jac_joint_idx = m->joint_list_idx[link];
+        SpecArgs a;
+        if ((rc = spec_args(a, m)) != TRK_OK) return rc;
+        a.q = q; a.n = n;
+        bind_jacobian(a, m, link, pos, quat, lin_jac, ang_jac);
         // which DOFs get a column and where the walk may stop (same rule as trk_launch_fk_jacobian: robot_tree.py:239-244)
         a.jac_p_end = 1; a.jac_n_cols = 0;
         for (int d = 0; d < TRK_MAX_DOFS; ++d) a.jac_slot[d] = -1;
@@ -838,10 +880,7 @@ int trk_fk_jacobian(const TrkModel* m, const float* q, const float* qd, int64_t 
                 a.jac_p_end = std::max(a.jac_p_end, p + 1);
             }
         }
-        a.jac_pos = pos; a.jac_quat = quat; a.jac_lin = lin_jac; a.jac_ang = ang_jac;
-        m->spec->launch_jac(m->spec, a, base_is_identity(m), (hipStream_t)stream);
-        TRK_HIP(last_launch_error());
-        return TRK_OK;
+        return spec_launch(e->launch_jac, e, a, m, stream);
     }
     trk_launch_fk_jacobian(m->hdr, m->d_links, m->links.data(), q, qd, n, link, m->joint_list_idx[link], pos, quat, lin_jac, ang_jac,
                            vel_lin, vel_ang, (hipStream_t)stream);
@@ -854,14 +893,12 @@ int trk_fk_analytic_jacobian(const TrkModel* m, const float* q, int64_t n, float
     if (rc) return rc;
     if (n < 0 || (n > 0 && (!J || (!q && m->hdr.n_dofs > 0)))) return fail(TRK_ERR_INVALID_ARG, "trk_fk_analytic_jacobian: bad q/J/n");
     if (n == 0 || m->hdr.n_dofs == 0) return TRK_OK;
-    if (m->spec_enabled && model_spec(m) && m->spec->launch_ajac) {
-        SpecArgs a{};
-        std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-        std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
+    const SpecEntry* e = enabled_spec(m);
+    if (e && e->launch_ajac) {
+        SpecArgs a;
+        if ((rc = spec_args(a, m)) != TRK_OK) return rc;
         a.q = q; a.n = n; a.jac_lin = J;
-        m->spec->launch_ajac(m->spec, a, base_is_identity(m), (hipStream_t)stream);
-        TRK_HIP(last_launch_error());
-        return TRK_OK;
+        return spec_launch(e->launch_ajac, e, a, m, stream);
     }
     trk_launch_fk_analytic_jacobian(m->hdr, m->d_links, m->d_dofs, q, n, J, (hipStream_t)stream);
     TRK_HIP(last_launch_error());
@@ -879,7 +916,8 @@ int trk_ik_steps(const TrkModel* m, int32_t link, const float* H_target, int32_t
     if (lr <= 0.0f && n_steps != 1) return fail(TRK_ERR_INVALID_ARG, "trk_ik_steps: lr = 0 only evaluates, n_steps must be 1");
     if (n == 0 || m->hdr.n_dofs == 0) return TRK_OK;
     // generated kernel (configurations and Adam state in registers) when the target is the link the unit tracks
-    const SpecEntry* gen = (model_spec(m) && m->spec_enabled && m->spec->launch_ik && m->spec->ee_link == link) ? m->spec : nullptr;
+    const SpecEntry* gen = enabled_spec(m);
+    if (gen && !(gen->launch_ik && gen->ee_link == link)) gen = nullptr;
     // at most TRK_IK_MAX_STEPS iterations per launch; loss / valid come from the first launch (q as the caller passed it)
     for (int32_t done = 0; done < n_steps; done += TRK_IK_MAX_STEPS) {
         const int32_t k = std::min<int32_t>(TRK_IK_MAX_STEPS, n_steps - done);
@@ -891,14 +929,12 @@ int trk_ik_steps(const TrkModel* m, int32_t link, const float* H_target, int32_t
         }
         if (gen) {
             IkArgs a{};
-            std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-            std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
+            set_base_pose(a, m);
             a.H_target = H_target; a.per_sample = per_sample_target; a.n_steps = k; a.lower = lower; a.upper = upper;
             a.w_jl = w_joint_limits; a.se3_eps = se3_eps; a.lr = lr; a.sched = sched; a.n = n;
             a.q = q; a.adam_m = adam_m; a.adam_v = adam_v;
             a.loss = done == 0 ? loss : nullptr; a.valid = done == 0 ? valid : nullptr;
-            gen->launch_ik(gen, a, base_is_identity(m), (hipStream_t)stream);
-            TRK_HIP(last_launch_error());
+            if ((rc = spec_launch(gen->launch_ik, gen, a, m, stream)) != TRK_OK) return rc;
             continue;
         }
         trk_launch_ik_step(m->hdr, m->d_links, m->d_fin, link, H_target, per_sample_target, lower, upper, w_joint_limits,
@@ -931,14 +967,11 @@ int trk_ik_gn_steps(const TrkModel* m, int32_t link, const float* H_target, int3
                                          "torch_robotics_amd.jit.specialize(kin, obj_links, ee_link=link)); the two-launch form is "
                                          "trk_fk_jacobian + trk_jtj");
     IkGnArgs a{};
-    std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-    std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
+    set_base_pose(a, m);
     a.H_target = H_target; a.per_sample = per_sample_target; a.n_steps = n_steps; a.lower = lower; a.upper = upper;
     a.damping = damping; a.lm_gain = lm_gain; a.step_scale = step_scale; a.se3_eps = se3_eps; a.n = n;
     a.q = q; a.err = err; a.valid = valid;
-    gen->launch_ikgn(gen, a, base_is_identity(m), (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return spec_launch(gen->launch_ikgn, gen, a, m, stream);
 }
 
 int trk_ik_step(const TrkModel* m, int32_t link, const float* H_target, int32_t per_sample_target, const float* lower,
@@ -1314,18 +1347,12 @@ int trk_cost_fields(const TrkCostModel* cm, int32_t fields, const float* link_po
     if (!cm) return fail(TRK_ERR_INVALID_ARG, "trk_cost_fields: null cost model");
     if (n < 0 || (n > 0 && (!link_pos || !cost)) || (fields & ~7) || !fields) return fail(TRK_ERR_INVALID_ARG, "trk_cost_fields: bad argument");
     if (n == 0) return TRK_OK;
-    {
-        const TrkRolloutWeights w = effective_weights(cm, TrkRolloutWeights{(fields & TRK_FIELD_SELF) ? 1.0f : 0.0f,
-                                                                            (fields & TRK_FIELD_OBJECTS) ? 1.0f : 0.0f,
-                                                                            (fields & TRK_FIELD_WS) ? 1.0f : 0.0f, 0.0f});
-        if (const SpecEntry* e = fields_spec_for(cm, &w)) {      // the fused kernel's objective code on the caller's positions
-            SpecArgs a{};
-            a.C = cm->hdr; a.w = w;
-            a.n = n; a.fld_pos = link_pos; a.fld_gcost = gcost; a.fld_g = g_link_pos; a.cost = cost;
-            e->launch_fields(e, a, 1, (hipStream_t)stream);
-            TRK_HIP(last_launch_error());
-            return TRK_OK;
-        }
+    const TrkRolloutWeights w = effective_weights(cm, field_weights(fields, false));      // vacuous terms dropped, like the rollouts
+    if (const SpecEntry* e = fields_spec_for(cm, &w)) {      // the fused kernel's objective code on the caller's positions
+        SpecArgs a;
+        spec_args(a, nullptr, cm, &w);
+        a.n = n; a.fld_pos = link_pos; a.fld_gcost = gcost; a.fld_g = g_link_pos; a.cost = cost;
+        return spec_launch(e->launch_fields, e, a, nullptr, stream);
     }
     trk_launch_cost_fields(cm->hdr, fields, link_pos, n, gcost, cost, g_link_pos, (hipStream_t)stream);
     TRK_HIP(last_launch_error());
@@ -1338,18 +1365,15 @@ int trk_collision_fields(const TrkCostModel* cm, int32_t fields, const float* li
     if (n < 0 || (n > 0 && (!link_pos || !in_collision)) || (fields & ~7) || !fields) return fail(TRK_ERR_INVALID_ARG, "trk_collision_fields: bad argument");
     if (n == 0) return TRK_OK;
     const int use_default = std::isnan(margin_override) ? 1 : 0;
-    {
-        TrkRolloutWeights w{(fields & TRK_FIELD_SELF) ? 1.0f : 0.0f, (fields & TRK_FIELD_OBJECTS) ? 1.0f : 0.0f,
-                            (fields & TRK_FIELD_WS) ? 1.0f : 0.0f, 0.0f};
-        if (const SpecEntry* e = fields_spec_for(cm, &w)) {      // the fused boolean kernel's tests on the caller's positions
-            SpecArgs a{};
-            a.C = cm->hdr; a.w = w;
-            a.n = n; a.fld_pos = link_pos; a.coll_out = in_collision; a.coll_fields = fields;
-            a.coll_use_default = use_default; a.coll_margin = use_default ? 0.0f : margin_override;
-            e->launch_fields(e, a, 1, (hipStream_t)stream);
-            TRK_HIP(last_launch_error());
-            return TRK_OK;
-        }
+    // the mask as given: neither effective_fields nor effective_weights is applied here (a vacuous field still asks for a unit
+    // that bakes the cost model's empty set; its test finds nothing either way)
+    const TrkRolloutWeights w = field_weights(fields, false);
+    if (const SpecEntry* e = fields_spec_for(cm, &w)) {      // the fused boolean kernel's tests on the caller's positions
+        SpecArgs a;
+        spec_args(a, nullptr, cm, &w);
+        a.n = n; a.fld_pos = link_pos;
+        bind_collision(a, in_collision, fields, margin_override);
+        return spec_launch(e->launch_fields, e, a, nullptr, stream);
     }
     trk_launch_collision_fields(cm->hdr, fields, link_pos, n, use_default ? 0.0f : margin_override, use_default, in_collision, (hipStream_t)stream);
     TRK_HIP(last_launch_error());
@@ -1370,30 +1394,19 @@ int trk_ee_cost(const TrkCostModel* cm, const float* H_ee, int64_t n, int64_t st
 static int rollout_impl(const char* who, const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w, int io_f16, float grad_scale,
                         const void* q, int64_t batch, int32_t horizon, void* link_pos_out, float* cost, void* gq,
                         float* cost_sum, trk_stream_t stream) {
-    int rc = check_model(m, who);
+    int rc = check_rollout_call(who, m, cm, batch, horizon);
     if (rc) return rc;
-    if (!cm || !w) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null argument");
-    if (batch < 0 || horizon < 1) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": bad batch/horizon");
-    if (cm->hdr.n_links_in != m->hdr.n_links) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": cost model n_links_in != model n_links");
     const int64_t n = batch * horizon;
-    if (n > 0 && (!q || !cost || !gq)) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null q/cost/gq");
+    if (!w || (n > 0 && (!q || !cost || !gq))) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null weights/q/cost/gq");
     if (n == 0) return TRK_OK;
     const TrkRolloutWeights we = effective_weights(cm, *w);
     w = &we;
-    if (m->spec_enabled) {
-        // a generated kernel has the robot's collision-link sets baked in: use the unit whose sets equal the cost model's
-        if (const SpecEntry* e = model_spec_for(m, cm, w)) {
-            SpecArgs a{};
-            a.C = cm->hdr; a.w = *w;
-            std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-            std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
-            a.q = q; a.n = n; a.link_pos = link_pos_out; a.cost = cost; a.gq = gq; a.cost_sum = cost_sum;
-            a.stamps = g_stamps; a.io_f16 = io_f16; a.grad_scale = grad_scale;
-            e->launch(e, a, base_is_identity(m), (hipStream_t)stream);
-            TRK_HIP(last_launch_error());
-            g_last_dispatch = TRK_DISPATCH_GENERATED;
-            return TRK_OK;
-        }
+    // a generated kernel has the robot's collision-link sets baked in: use the unit whose sets equal the cost model's
+    if (const SpecEntry* e = enabled_spec_for(m, cm, w)) {
+        SpecArgs a;
+        spec_args(a, m, cm, w);
+        bind_rollout(a, q, n, link_pos_out, cost, gq, cost_sum, io_f16, grad_scale, g_stamps);
+        return served_generated(spec_launch(e->launch, e, a, m, stream));
     }
     if ((rc = strict_refusal(who, m)) != TRK_OK) return rc;
     g_last_dispatch = TRK_DISPATCH_TABLE;
@@ -1424,11 +1437,9 @@ int trk_rollout_points_is_specialized(const TrkPointSet* ps, const TrkCostModel*
 
 int trk_rollout_collision(const TrkModel* m, const TrkCostModel* cm, int32_t fields, const float* q, int64_t batch, int32_t horizon,
                           float margin_override, uint8_t* in_collision, float* link_pos_ws, trk_stream_t stream) {
-    int rc = check_model(m, "trk_rollout_collision");
+    int rc = check_rollout_call("trk_rollout_collision", m, cm, batch, horizon);
     if (rc) return rc;
-    if (!cm) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_collision: null cost model");
-    if (batch < 0 || horizon < 1 || (fields & ~7) || !fields) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_collision: bad batch / horizon / fields");
-    if (cm->hdr.n_links_in != m->hdr.n_links) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_collision: cost model n_links_in != model n_links");
+    if ((fields & ~7) || !fields) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_collision: bad fields");
     const int64_t n = batch * horizon;
     if (n > 0 && (!q || !in_collision)) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_collision: null q / in_collision");
     if (n == 0) return TRK_OK;
@@ -1439,26 +1450,15 @@ int trk_rollout_collision(const TrkModel* m, const TrkCostModel* cm, int32_t fie
         g_last_dispatch = TRK_DISPATCH_NONE;
         return TRK_OK;
     }
-    if (m->spec_enabled) {
-        // the unit's baked link sets must equal the cost model's for every field that is asked for
-        TrkRolloutWeights w{};
-        w.w_self = (fields & TRK_FIELD_SELF) ? 1.0f : 0.0f;
-        w.w_obj = (fields & (TRK_FIELD_OBJECTS | TRK_FIELD_WS)) ? 1.0f : 0.0f;
-        w.w_ws = (fields & TRK_FIELD_WS) ? 1.0f : 0.0f;
-        const SpecEntry* e = model_spec_for(m, cm, &w);
-        if (e && e->launch_coll) {
-            SpecArgs a{};
-            a.C = cm->hdr; a.w = w;
-            std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-            std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
-            a.q = q; a.n = n;
-            a.coll_out = in_collision; a.coll_fields = fields; a.coll_use_default = use_default;
-            a.coll_margin = use_default ? 0.0f : margin_override;
-            e->launch_coll(e, a, base_is_identity(m), (hipStream_t)stream);
-            TRK_HIP(last_launch_error());
-            g_last_dispatch = TRK_DISPATCH_GENERATED;
-            return TRK_OK;
-        }
+    // the unit's baked link sets must equal the cost model's for every field that is asked for (the mask is already effective)
+    const TrkRolloutWeights w = field_weights(fields, true);
+    const SpecEntry* e = enabled_spec_for(m, cm, &w);
+    if (e && e->launch_coll) {
+        SpecArgs a;
+        spec_args(a, m, cm, &w);
+        a.q = q; a.n = n;
+        bind_collision(a, in_collision, fields, margin_override);
+        return served_generated(spec_launch(e->launch_coll, e, a, m, stream));
     }
     if ((rc = strict_refusal("trk_rollout_collision", m)) != TRK_OK) return rc;
     g_last_dispatch = TRK_DISPATCH_TABLE;
@@ -1474,7 +1474,38 @@ int trk_rollout_collision(const TrkModel* m, const TrkCostModel* cm, int32_t fie
 static int rollout_collision_via_impl(const TrkModel* m, const TrkCostModel* cm, int32_t fields, const float* x, int64_t n_traj,
                                       int32_t horizon, int32_t state_dim, int32_t n_interp, const float* alpha, const float* beta,
                                       float margin_override, uint8_t* in_collision, uint8_t* traj_flags, const float* q_min, const float* q_max,
-                                      trk_stream_t stream);
+                                      trk_stream_t stream) {
+    const char* who = "trk_rollout_collision_via";
+    int rc = check_rollout_call(who, m, cm, n_traj, horizon);
+    if (rc) return rc;
+    if (horizon < 2 || n_interp < 1 || state_dim < m->hdr.n_dofs || (fields & ~7) || !fields || !alpha || !beta)
+        return fail(TRK_ERR_INVALID_ARG, "trk_rollout_collision_via: bad argument");
+    const int64_t hi = (int64_t)(horizon - 1) * n_interp;
+    if (hi > 0x7fffffff - 64) return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_collision_via: (horizon - 1) * n_interp too large");
+    const int64_t n = n_traj * hi;
+    if (n > 0 && (!x || !in_collision)) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_collision_via: null x / in_collision");
+    if (n == 0) return TRK_OK;
+    if (!m->spec_enabled) return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_collision_via: generated kernels are disabled for this model");
+    fields = effective_fields(cm, fields);
+    // (the fused flags need the generated kernel even when no field has anything to test: the joint limits are looked at there)
+    if (!fields && !traj_flags) {
+        TRK_HIP(hipMemsetAsync(in_collision, 0, (size_t)n, (hipStream_t)stream));
+        g_last_dispatch = TRK_DISPATCH_NONE;
+        return TRK_OK;
+    }
+    const TrkRolloutWeights w = field_weights(fields, true);
+    const SpecEntry* e = enabled_spec_for(m, cm, &w);
+    if (!e || !e->launch_coll)
+        return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_collision_via: no generated kernel serves this model / cost model "
+                                         "(use trk_interpolate_via_points + trk_rollout_collision)");
+    SpecArgs a;
+    spec_args(a, m, cm, &w);
+    a.q = x; a.n = n;
+    bind_collision(a, in_collision, fields, margin_override);
+    a.via_alpha = alpha; a.via_beta = beta; a.via_n = n_interp; a.via_H = horizon; a.via_S = state_dim;
+    if (traj_flags) { a.via_partial = traj_flags; a.via_slots = trk_via_slots(hi); a.via_qmin = q_min; a.via_qmax = q_max; }
+    return served_generated(spec_launch(e->launch_coll, e, a, m, stream));
+}
 
 int trk_rollout_collision_via(const TrkModel* m, const TrkCostModel* cm, int32_t fields, const float* x, int64_t n_traj,
                               int32_t horizon, int32_t state_dim, int32_t n_interp, const float* alpha, const float* beta,
@@ -1499,53 +1530,6 @@ int trk_rollout_collision_via_flags(const TrkModel* m, const TrkCostModel* cm, i
                                       traj_flags, q_min, q_max, stream);
 }
 
-static int rollout_collision_via_impl(const TrkModel* m, const TrkCostModel* cm, int32_t fields, const float* x, int64_t n_traj,
-                                      int32_t horizon, int32_t state_dim, int32_t n_interp, const float* alpha, const float* beta,
-                                      float margin_override, uint8_t* in_collision, uint8_t* traj_flags, const float* q_min, const float* q_max,
-                                      trk_stream_t stream) {
-    int rc = check_model(m, "trk_rollout_collision_via");
-    if (rc) return rc;
-    if (!cm) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_collision_via: null cost model");
-    if (n_traj < 0 || horizon < 2 || n_interp < 1 || state_dim < m->hdr.n_dofs || (fields & ~7) || !fields || !alpha || !beta)
-        return fail(TRK_ERR_INVALID_ARG, "trk_rollout_collision_via: bad argument");
-    if (cm->hdr.n_links_in != m->hdr.n_links) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_collision_via: cost model n_links_in != model n_links");
-    const int64_t hi = (int64_t)(horizon - 1) * n_interp;
-    if (hi > 0x7fffffff - 64) return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_collision_via: (horizon - 1) * n_interp too large");
-    const int64_t n = n_traj * hi;
-    if (n > 0 && (!x || !in_collision)) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_collision_via: null x / in_collision");
-    if (n == 0) return TRK_OK;
-    if (!m->spec_enabled) return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_collision_via: generated kernels are disabled for this model");
-    const int use_default = std::isnan(margin_override) ? 1 : 0;
-    fields = effective_fields(cm, fields);
-    // (the fused flags need the generated kernel even when no field has anything to test: the joint limits are looked at there)
-    if (!fields && !traj_flags) {
-        TRK_HIP(hipMemsetAsync(in_collision, 0, (size_t)n, (hipStream_t)stream));
-        g_last_dispatch = TRK_DISPATCH_NONE;
-        return TRK_OK;
-    }
-    TrkRolloutWeights w{};
-    w.w_self = (fields & TRK_FIELD_SELF) ? 1.0f : 0.0f;
-    w.w_obj = (fields & (TRK_FIELD_OBJECTS | TRK_FIELD_WS)) ? 1.0f : 0.0f;
-    w.w_ws = (fields & TRK_FIELD_WS) ? 1.0f : 0.0f;
-    const SpecEntry* e = model_spec_for(m, cm, &w);
-    if (!e || !e->launch_coll)
-        return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_collision_via: no generated kernel serves this model / cost model "
-                                         "(use trk_interpolate_via_points + trk_rollout_collision)");
-    SpecArgs a{};
-    a.C = cm->hdr; a.w = w;
-    std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-    std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
-    a.q = x; a.n = n;
-    a.coll_out = in_collision; a.coll_fields = fields; a.coll_use_default = use_default;
-    a.coll_margin = use_default ? 0.0f : margin_override;
-    a.via_alpha = alpha; a.via_beta = beta; a.via_n = n_interp; a.via_H = horizon; a.via_S = state_dim;
-    if (traj_flags) { a.via_partial = traj_flags; a.via_slots = trk_via_slots(hi); a.via_qmin = q_min; a.via_qmax = q_max; }
-    e->launch_coll(e, a, base_is_identity(m), (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    g_last_dispatch = TRK_DISPATCH_GENERATED;
-    return TRK_OK;
-}
-
 int trk_traj_validate(const uint8_t* waypoint_collisions, const float* x, int64_t n_traj, int32_t horizon, int32_t state_dim,
                       int32_t n_waypoints, int32_t n_dofs, const float* q_min, const float* q_max, int64_t inner,
                       uint8_t* flags, int64_t* idx, int32_t* counts, int32_t* counts_host, int32_t ticket, float* gathered,
@@ -1568,35 +1552,24 @@ int trk_rollout_jacobian_cost_grad(const TrkModel* m, const TrkCostModel* cm, co
                                    int32_t horizon, int32_t link, float* link_pos_out, float* cost, float* gq, float* cost_sum, float* pos,
                                    float* quat, float* lin_jac, float* ang_jac, trk_stream_t stream) {
     const char* who = "trk_rollout_jacobian_cost_grad";
-    int rc = check_model(m, who);
+    int rc = check_rollout_call(who, m, cm, batch, horizon);
     if (rc) return rc;
-    if (!cm || !w) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null argument");
-    if (batch < 0 || horizon < 1 || link < 0 || link >= m->hdr.n_links) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": bad batch / horizon / link");
-    if (cm->hdr.n_links_in != m->hdr.n_links) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": cost model n_links_in != model n_links");
+    if (link < 0 || link >= m->hdr.n_links) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": link out of range");
     const int64_t n = batch * horizon;
-    if (n > 0 && (!q || !cost || !gq || !pos || !quat || !lin_jac || !ang_jac)) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null q / cost / gq / Jacobian output");
+    if (!w || (n > 0 && (!q || !cost || !gq || !pos || !quat || !lin_jac || !ang_jac)))
+        return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null weights / q / cost / gq / Jacobian output");
     if (n == 0) return TRK_OK;
     const TrkRolloutWeights we = effective_weights(cm, *w);
-    if (m->spec_enabled) {
-        const SpecEntry* e = model_spec_for(m, cm, &we);
-        if (e && e->launch_rjac) {
-            SpecArgs a{};
-            a.C = cm->hdr; a.w = we;
-            std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-            std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
-            a.q = q; a.n = n; a.link_pos = link_pos_out; a.cost = cost; a.gq = gq; a.cost_sum = cost_sum;
-            a.stamps = g_stamps; a.io_f16 = 0; a.grad_scale = 1.0f;
-            a.jac_link = link; a.jac_joint_idx = m->joint_list_idx[link];
-            a.jac_pos = pos; a.jac_quat = quat; a.jac_lin = lin_jac; a.jac_ang = ang_jac;
-            // q in; positions, cost, gradient, pos, quat, lin_jac, ang_jac out: beyond the Infinity Cache the Jacobian tiles stream
-            a.jac_stream = spec_stream_bytes((double)n * (8.0 * m->hdr.n_dofs + 4.0 + (link_pos_out ? 12.0 * m->hdr.n_links : 0.0) + 28.0 +
-                                                          24.0 * m->hdr.n_dofs)) ? 1 : 0;
-            if (e->launch_rjac(e, a, base_is_identity(m), (hipStream_t)stream) == 0) {
-                TRK_HIP(last_launch_error());
-                g_last_dispatch = TRK_DISPATCH_GENERATED;
-                return TRK_OK;
-            }
-        }
+    const SpecEntry* e = enabled_spec_for(m, cm, &we);
+    if (e && e->launch_rjac) {
+        SpecArgs a;
+        spec_args(a, m, cm, &we);
+        bind_rollout(a, q, n, link_pos_out, cost, gq, cost_sum, 0, 1.0f, g_stamps);
+        bind_jacobian(a, m, link, pos, quat, lin_jac, ang_jac);
+        // q in; positions, cost, gradient, pos, quat, lin_jac, ang_jac out: beyond the Infinity Cache the Jacobian tiles stream
+        a.jac_stream = spec_stream_bytes((double)n * (8.0 * m->hdr.n_dofs + 4.0 + (link_pos_out ? 12.0 * m->hdr.n_links : 0.0) + 28.0 +
+                                                      24.0 * m->hdr.n_dofs)) ? 1 : 0;
+        if ((rc = spec_launch(e->launch_rjac, e, a, m, stream)) != SPEC_DECLINED) return served_generated(rc);
     }
     // the two-launch form: the fused rollout, then the Jacobian kernel (a second walk of the chain)
     rc = rollout_impl(who, m, cm, w, 0, 1.0f, q, batch, horizon, link_pos_out, cost, gq, cost_sum, stream);
@@ -1626,39 +1599,28 @@ int trk_rollout_gp_cost_grad(const TrkModel* m, const TrkCostModel* cm, const Tr
                              const void* q, const void* qd, int64_t batch, int32_t horizon, int32_t io_dtype, void* link_pos_out,
                              float* cost, void* gq, void* gqd, int32_t grad_dtype, float grad_scale, float* cost_sum, trk_stream_t stream) {
     const char* who = "trk_rollout_gp_cost_grad";
-    int rc = check_model(m, who);
+    int rc = check_rollout_call(who, m, cm, batch, horizon);
     if (rc) return rc;
-    if (!cm || !w || !gp) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null argument");
-    if (batch < 0 || horizon < 1) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": bad batch/horizon");
+    if (!w || !gp) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null weights / prior");
     if ((io_dtype != TRK_F32 && io_dtype != TRK_F16) || (grad_dtype != TRK_F32 && grad_dtype != TRK_F16) ||
         (io_dtype == TRK_F32 && (grad_dtype != TRK_F32 || grad_scale != 1.0f)) || !(grad_scale > 0.0f) || !std::isfinite(grad_scale))
         return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": io_dtype / grad_dtype must be TRK_F32 / TRK_F16 (fp32 trajectories: fp32 gradient, "
                                          "grad_scale 1), grad_scale finite and > 0");
     if (!(gp->dt > 0.0f) || !(gp->sigma > 0.0f)) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": the prior needs dt > 0 and sigma > 0");
-    if (cm->hdr.n_links_in != m->hdr.n_links) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": cost model n_links_in != model n_links");
     const int64_t n = batch * horizon;
     if (n > 0 && (!q || !qd || !cost || !gq || !gqd)) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null q/qd/cost/gq/gqd");
     if (n == 0) return TRK_OK;
     const int io_mode = io_dtype == TRK_F32 ? 0 : (grad_dtype == TRK_F16 ? 1 : 2);
     const TrkRolloutWeights we = effective_weights(cm, *w);
-    if (m->spec_enabled) {
-        const SpecEntry* e = model_spec_for(m, cm, &we);
-        if (e && e->launch_gp) {
-            SpecArgs a{};
-            a.C = cm->hdr; a.w = we;
-            std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-            std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
-            a.q = q; a.n = n; a.link_pos = link_pos_out; a.cost = cost; a.gq = gq; a.cost_sum = cost_sum;
-            a.stamps = g_stamps; a.io_f16 = io_mode; a.grad_scale = grad_scale;
-            const float s2 = 1.0f / (gp->sigma * gp->sigma);
-            a.qd = qd; a.gqd = gqd; a.gp_dt = gp->dt; a.gp_w = gp->weight; a.gp_H = horizon;
-            a.gp_a = 12.0f * s2 / (gp->dt * gp->dt * gp->dt); a.gp_b = -6.0f * s2 / (gp->dt * gp->dt); a.gp_c = 4.0f * s2 / gp->dt;
-            if (e->launch_gp(e, a, base_is_identity(m), (hipStream_t)stream) == 0) {
-                TRK_HIP(last_launch_error());
-                g_last_dispatch = TRK_DISPATCH_GENERATED;
-                return TRK_OK;
-            }
-        }
+    const SpecEntry* e = enabled_spec_for(m, cm, &we);
+    if (e && e->launch_gp) {
+        SpecArgs a;
+        spec_args(a, m, cm, &we);
+        bind_rollout(a, q, n, link_pos_out, cost, gq, cost_sum, io_mode, grad_scale, g_stamps);
+        const float s2 = 1.0f / (gp->sigma * gp->sigma);
+        a.qd = qd; a.gqd = gqd; a.gp_dt = gp->dt; a.gp_w = gp->weight; a.gp_H = horizon;
+        a.gp_a = 12.0f * s2 / (gp->dt * gp->dt * gp->dt); a.gp_b = -6.0f * s2 / (gp->dt * gp->dt); a.gp_c = 4.0f * s2 / gp->dt;
+        if ((rc = spec_launch(e->launch_gp, e, a, m, stream)) != SPEC_DECLINED) return served_generated(rc);
     }
     // the two-launch form: the rollout, then the prior accumulated into its gradient, its factor costs into the per-sample costs
     rc = rollout_impl(who, m, cm, w, io_mode, grad_scale, q, batch, horizon, link_pos_out, cost, gq, nullptr, stream);
@@ -1682,34 +1644,27 @@ int trk_rollout_gp_cost_grad(const TrkModel* m, const TrkCostModel* cm, const Tr
 int trk_rollout_points_cost_grad(const TrkModel* m, const TrkPointSet* ps, const TrkCostModel* cm, const TrkRolloutWeights* w,
                                  const float* q, int64_t batch, int32_t horizon, float* point_pos_out, float* cost, float* gq,
                                  float* cost_sum, trk_stream_t stream) {
-    int rc = check_model(m, "trk_rollout_points_cost_grad");
+    const char* who = "trk_rollout_points_cost_grad";
+    int rc = check_rollout_call(who, m, cm, batch, horizon, /*link_columns=*/false);
     if (rc) return rc;
-    if (!cm || !w) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_points_cost_grad: null argument");
     if (!ps || ps->model != m) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_points_cost_grad: point set does not belong to this model");
-    if (batch < 0 || horizon < 1) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_points_cost_grad: bad batch/horizon");
     if (cm->hdr.n_links_in != ps->dev.n_points) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_points_cost_grad: cost model n_links_in != number of points");
     if (cm->hdr.ee_link >= m->hdr.n_links || cm->hdr.ee2_link >= m->hdr.n_links)
         return fail(TRK_ERR_INVALID_ARG, "trk_rollout_points_cost_grad: ee_link is not a link of the model");
     if (trk_lds_rollout(m->hdr, ps->dev.n_points + cm->hdr.n_virtual) > kMaxLds) return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_points_cost_grad: point tiles exceed the 160 KiB LDS");
     const int64_t n = batch * horizon;
-    if (n > 0 && (!q || !cost || !gq)) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_points_cost_grad: null q/cost/gq");
+    if (!w || (n > 0 && (!q || !cost || !gq))) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_points_cost_grad: null weights/q/cost/gq");
     if (n == 0) return TRK_OK;
     const TrkRolloutWeights we = effective_weights(cm, *w);
     w = &we;
-    if (m->spec_enabled && (reinterpret_cast<uintptr_t>(point_pos_out) & 15) == 0) {
-        // generated kernel with this point set baked in whose cost columns equal the cost model's
-        if (const SpecEntry* e = points_spec_for(ps, cm, w)) {
-            SpecArgs a{};
-            a.C = cm->hdr; a.w = *w;
-            std::memcpy(a.base_R, m->hdr.base_R, sizeof(a.base_R));
-            std::memcpy(a.base_t, m->hdr.base_t, sizeof(a.base_t));
-            a.q = q; a.n = n; a.link_pos = point_pos_out; a.cost = cost; a.gq = gq; a.cost_sum = cost_sum;
-            a.stamps = nullptr; a.io_f16 = 0;
-            e->launch(e, a, base_is_identity(m), (hipStream_t)stream);
-            TRK_HIP(last_launch_error());
-            g_last_dispatch = TRK_DISPATCH_GENERATED;
-            return TRK_OK;
-        }
+    // generated kernel with this point set baked in whose cost columns equal the cost model's
+    const SpecEntry* e = m->spec_enabled && (reinterpret_cast<uintptr_t>(point_pos_out) & 15) == 0 ? points_spec_for(ps, cm, w) : nullptr;
+    if (e) {
+        SpecArgs a;
+        spec_args(a, m, cm, w);
+        // (no stamp buffer and grad_scale 0 where the link rollouts pass g_stamps and 1: as this entry always has)
+        bind_rollout(a, q, n, point_pos_out, cost, gq, cost_sum, 0, 0.0f, nullptr);
+        return served_generated(spec_launch(e->launch, e, a, m, stream));
     }
     if (strict_specialized() && m->spec_enabled && points_spec(ps))
         return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_points_cost_grad: strict mode: the point set has generated kernels but none bakes this cost model's columns "

@@ -157,6 +157,29 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _lead_batch_horizon(q: torch.Tensor, n_dofs: int):
+    """q (B,H,D) or (N,D) -> (q as the C ABI reads it, leading shape of the results, B, H): an (N,D) batch is N trajectories of one step."""
+    lead = tuple(q.shape[:-1])
+    if q.dim() == 3:
+        return q, lead, int(q.shape[0]), int(q.shape[1])
+    q = q.reshape(-1, n_dofs)
+    return q, lead, int(q.shape[0]), 1
+
+
+class _Plan:
+    """Base of the pre-bound plans: __init__ resolves `device`, the C function `_fn` and its leading arguments `_args` once."""
+
+    def _launch(self, stream: Optional[int], *tail) -> None:
+        """The per-launch host path: `_fn(*_args, *tail, stream)` on torch's current stream of the plan's device (or the caller's
+        `stream`) -- one ctypes call; an error is reported under the name of the C function that was called."""
+        with _on(self.device):                  # free when the device is already current
+            if stream is None:
+                stream = _stream_of(self.device)
+            rc = self._fn(*self._args, *tail, stream)
+        if rc:
+            check(rc, self._fn.__name__)
+
+
 # Integer ids of the live handles, for the dispatcher ops (torch.ops.trk.*, custom_ops.py): an op schema carries tensors and
 # scalars only, so a model / cost model / point set travels as the value of its C pointer.
 _handles: "weakref.WeakValueDictionary[int, object]" = weakref.WeakValueDictionary()
@@ -390,7 +413,7 @@ def fk_jacobian(model: ModelHandle, q: torch.Tensor, qd: Optional[torch.Tensor],
     return (pos, quat, lin, ang, vl, va) if want_vel else (pos, quat, lin, ang)
 
 
-class JacobianPlan:
+class JacobianPlan(_Plan):
     """Pre-bound `trk_fk_jacobian` (stateful FK + geometric Jacobian of one link, robot_tree.py:218-248): outputs are allocated once,
     `launch()` is one C call -- `pos` (N,3), `quat` (N,4 wxyz), `lin_jac` / `ang_jac` (N,3,D) are rewritten in place."""
 
@@ -409,12 +432,7 @@ class JacobianPlan:
                       self.ang_jac.data_ptr(), None, None)
 
     def launch(self, stream: Optional[int] = None) -> None:
-        with _on(self.device):
-            if stream is None:
-                stream = _stream_of(self.device)
-            rc = self._fn(*self._args, stream)
-        if rc:
-            check(rc, "trk_fk_jacobian")
+        self._launch(stream)
 
 
 def fk_analytic_jacobian(model: ModelHandle, q: torch.Tensor) -> torch.Tensor:
@@ -813,8 +831,9 @@ def _weights_struct(weights):
     return w
 
 
-def _grad_mode(f16: bool, grad_dtype, grad_scale, who: str):
-    """(torch dtype of the gradient, TRK_F32 / TRK_F16, scale) of a reduced-precision call; fp32 trajectories take no options."""
+def _grad_mode(f16: bool, grad_dtype, grad_scale, who: str, fp32_scale: bool = False):
+    """(torch dtype of the gradient, TRK_F32 / TRK_F16, scale) of a reduced-precision call; fp32 trajectories take no options
+    (fp32_scale: the GP-prior launch on its own scales an fp32 gradient too)."""
     if grad_dtype is None:
         grad_dtype = torch.float16 if f16 else torch.float32
     if grad_dtype not in (torch.float16, torch.float32) or (not f16 and grad_dtype != torch.float32):
@@ -822,6 +841,8 @@ def _grad_mode(f16: bool, grad_dtype, grad_scale, who: str):
     gs = float(grad_scale)
     if not (gs > 0.0 and math.isfinite(gs)):
         raise ValueError(f"{who}: grad_scale must be a finite positive number")
+    if not f16 and gs != 1.0 and not fp32_scale:
+        raise ValueError(f"{who}: grad_scale applies to float16 trajectories only")
     return grad_dtype, int(grad_dtype == torch.float16), gs
 
 
@@ -852,21 +873,13 @@ def rollout_cost_grad(model: ModelHandle, cm: CostHandle, weights, q: torch.Tens
         q = _dev_f32(q, "rollout_cost_grad(q)")
     io = torch.float16 if f16 else torch.float32
     gio, gcode, gs = _grad_mode(f16, grad_dtype, grad_scale, "rollout_cost_grad")
-    if not f16 and gs != 1.0:
-        raise ValueError("rollout_cost_grad: grad_scale applies to float16 trajectories only")
     _check_q_dofs(q, model.n_dofs, "rollout_cost_grad(q)")
-    lead = q.shape[:-1]
-    if q.dim() == 3:
-        B, Hh = int(q.shape[0]), int(q.shape[1])
-    else:
-        q = q.reshape(-1, model.n_dofs)
-        B, Hh = int(q.shape[0]), 1
+    q, lead, B, Hh = _lead_batch_horizon(q, model.n_dofs)
     n, L, D = B * Hh, model.n_links, model.n_dofs
     if out is None:         # allocated in their final shapes: a reshape of a fresh tensor is ~0.7 us of host time each
-        lt = tuple(lead)
-        pos = torch.empty(lt + (L, 3), device=q.device, dtype=io) if want_pos else None
-        cost = torch.empty(lt, device=q.device, dtype=torch.float32)
-        gq = torch.empty(lt + (D,), device=q.device, dtype=gio)
+        pos = torch.empty(lead + (L, 3), device=q.device, dtype=io) if want_pos else None
+        cost = torch.empty(lead, device=q.device, dtype=torch.float32)
+        gq = torch.empty(lead + (D,), device=q.device, dtype=gio)
     else:
         pos, cost, gq = out
         _check_buffer(pos, n * L * 3, io, q.device, "rollout_cost_grad(out[0] = link_pos)")
@@ -885,8 +898,7 @@ def rollout_cost_grad(model: ModelHandle, cm: CostHandle, weights, q: torch.Tens
                                               gq.data_ptr(), _ptr(cost_sum), _stream(q)), "trk_rollout_cost_grad")
     if out is None:
         return pos, cost, gq
-    return (None if pos is None else pos.reshape(tuple(lead) + (L, 3)), cost.reshape(tuple(lead)),
-            gq.reshape(tuple(lead) + (D,)))
+    return None if pos is None else pos.reshape(lead + (L, 3)), cost.reshape(lead), gq.reshape(lead + (D,))
 
 
 def rollout_is_specialized(model: ModelHandle, cm: CostHandle, weights) -> bool:
@@ -944,12 +956,7 @@ def rollout_collision(model: ModelHandle, cm: CostHandle, fields: int, q: torch.
     (`PlanningTask.compute_collision`, tasks.py:131-133); `margin=None` uses the fields' own margins."""
     q = _dev_f32(q, "rollout_collision(q)")
     _check_q_dofs(q, model.n_dofs, "rollout_collision(q)")
-    lead = q.shape[:-1]
-    if q.dim() == 3:
-        B, Hh = int(q.shape[0]), int(q.shape[1])
-    else:
-        q = q.reshape(-1, model.n_dofs)
-        B, Hh = int(q.shape[0]), 1
+    q, lead, B, Hh = _lead_batch_horizon(q, model.n_dofs)
     n = B * Hh
     out = torch.empty((n,), device=q.device, dtype=torch.bool)      # the kernel writes 0 / 1 bytes
     # scratch for the table-driven fallback only (a model / cost model that no generated kernel serves)
@@ -961,7 +968,7 @@ def rollout_collision(model: ModelHandle, cm: CostHandle, fields: int, q: torch.
             ws = torch.empty((n, model.n_links, 3), device=q.device, dtype=torch.float32)
             rc = lib().trk_rollout_collision(model._h, cm._h, int(fields), q.data_ptr(), B, Hh, m, out.data_ptr(), ws.data_ptr(), _stream(q))
         check(rc, "trk_rollout_collision")
-    return out.reshape(tuple(lead))
+    return out.reshape(lead)
 
 
 def rollout_points_cost_grad(ps: PointSetHandle, cm: CostHandle, weights, q: torch.Tensor, want_pos: bool = True,
@@ -971,24 +978,18 @@ def rollout_points_cost_grad(ps: PointSetHandle, cm: CostHandle, weights, q: tor
     model = ps.model
     q = _dev_f32(q, "rollout_points_cost_grad(q)")
     _check_q_dofs(q, model.n_dofs, "rollout_points_cost_grad(q)")
-    lead = q.shape[:-1]
-    if q.dim() == 3:
-        B, Hh = int(q.shape[0]), int(q.shape[1])
-    else:
-        q = q.reshape(-1, model.n_dofs)
-        B, Hh = int(q.shape[0]), 1
+    q, lead, B, Hh = _lead_batch_horizon(q, model.n_dofs)
     n, P, D = B * Hh, ps.n_points, model.n_dofs
     pos = torch.empty((n, P, 3), device=q.device, dtype=torch.float32) if want_pos else None
     cost = torch.empty((n,), device=q.device, dtype=torch.float32)
     gq = torch.empty((n, D), device=q.device, dtype=torch.float32)
     _check_buffer(cost_sum, n_blocks(n), torch.float32, q.device, "rollout_points_cost_grad(cost_sum)", at_least=True)
-    w = _abi.RolloutWeights(*[float(v) for v in weights])
+    w = _weights_struct(weights)
     with _on(q.device):
         check(lib().trk_rollout_points_cost_grad(model._h, ps._h, cm._h, C.byref(w), q.data_ptr(), B, Hh, _ptr(pos),
                                                  cost.data_ptr(), gq.data_ptr(), _ptr(cost_sum), _stream(q)),
               "trk_rollout_points_cost_grad")
-    return (None if pos is None else pos.reshape(tuple(lead) + (P, 3)), cost.reshape(tuple(lead)),
-            gq.reshape(tuple(lead) + (D,)))
+    return None if pos is None else pos.reshape(lead + (P, 3)), cost.reshape(lead), gq.reshape(lead + (D,))
 
 
 def gp_prior_cost_grad(q: torch.Tensor, qd: torch.Tensor, dt: float, sigma: float, weight: float = 1.0,
@@ -998,29 +999,9 @@ def gp_prior_cost_grad(q: torch.Tensor, qd: torch.Tensor, dt: float, sigma: floa
     by default; float32 with float16 trajectories = the mixed mode); a float16 gradient saturates at +-65504 instead of inf --
     `gp_grad_scale(dt, sigma, ...)` picks a scale that keeps it finite.  accumulate_into=(gq, gqd) adds into existing buffers
     (which hold gradients of the same scale)."""
-    if q.device.type != "cuda" or qd.device != q.device:
-        raise ValueError("gp_prior_cost_grad: q and qd must be tensors on the same GPU (there is no CPU path)")
-    if q.dim() != 3 or qd.shape != q.shape or q.dtype != qd.dtype or q.dtype not in (torch.float32, torch.float16):
-        raise ValueError("gp_prior_cost_grad: q, qd must be (batch, horizon, dof) of the same fp32 / fp16 dtype")
-    q, qd = q.contiguous(), qd.contiguous()
-    B, H, D = (int(v) for v in q.shape)
-    if accumulate_into is not None and grad_dtype is None:
-        grad_dtype = accumulate_into[0].dtype
-    gio, gcode, gs = _grad_mode(q.dtype == torch.float16, grad_dtype, grad_scale, "gp_prior_cost_grad")
-    cost = torch.empty((B,), device=q.device, dtype=torch.float32)
-    if accumulate_into is None:
-        gq, gqd, acc = torch.empty_like(q, dtype=gio), torch.empty_like(q, dtype=gio), 0
-    else:
-        gq, gqd = accumulate_into
-        acc = 1
-        if gq.shape != q.shape or gqd.shape != q.shape or gq.dtype != gio or gqd.dtype != gio or \
-                not (gq.is_contiguous() and gqd.is_contiguous()):
-            raise ValueError("gp_prior_cost_grad: accumulate_into buffers must match q (shape, contiguous) and grad_dtype")
-    with _on(q.device):
-        check(lib().trk_gp_prior_cost_grad(q.data_ptr(), qd.data_ptr(), B, H, D, int(q.dtype == torch.float16), float(dt),
-                                           float(sigma), float(weight), cost.data_ptr(), gq.data_ptr(), gqd.data_ptr(), gcode, gs,
-                                           acc, _stream(q)), "trk_gp_prior_cost_grad")
-    return cost, gq, gqd
+    plan = GPPriorPlan(q.contiguous(), qd.contiguous(), dt, sigma, weight, accumulate_into, grad_dtype, grad_scale, who="gp_prior_cost_grad")
+    plan.launch()
+    return plan.cost, plan.gq, plan.gqd
 
 
 def _gp_args(model, q, qd, who):
@@ -1029,11 +1010,12 @@ def _gp_args(model, q, qd, who):
     if q.dim() != 3 or qd.shape != q.shape or q.dtype != qd.dtype or q.dtype not in (torch.float32, torch.float16) or \
             not (q.is_contiguous() and qd.is_contiguous()):
         raise ValueError(f"{who}: q, qd must be contiguous (batch, horizon, dof) tensors of the same fp32 / fp16 dtype")
-    _check_q_dofs(q, model.n_dofs, f"{who}(q)")
+    if model is not None:
+        _check_q_dofs(q, model.n_dofs, f"{who}(q)")
     return (int(v) for v in q.shape)
 
 
-class RolloutGpPlan:
+class RolloutGpPlan(_Plan):
     """BASELINE config 5's objective as ONE pre-bound launch (include/trk.h: trk_rollout_gp_cost_grad): fused FK + collision / EE
     objectives + the constant-velocity GP prior + both gradients.  q, qd (B,H,D) fp32 or fp16 are read in place on every `launch()`;
     `cost` (B,H) fp32 is the rollout's cost plus the prior's factor t -> t+1 at sample t, `gq` / `gqd` hold grad_scale x the gradients
@@ -1047,27 +1029,20 @@ class RolloutGpPlan:
         B, H, D = _gp_args(model, q, qd, "RolloutGpPlan")
         f16 = q.dtype == torch.float16
         gio, gcode, gs = _grad_mode(f16, grad_dtype, grad_scale, "RolloutGpPlan")
-        if not f16 and gs != 1.0:
-            raise ValueError("RolloutGpPlan: grad_scale applies to float16 trajectories only")
         self.model, self.cm, self.q, self.qd, self.device, self.grad_scale = model, cm, q, qd, q.device, gs
         self.B, self.H = B, H
         self.link_pos = torch.empty((B, H, model.n_links, 3), device=q.device, dtype=q.dtype) if want_pos else None
         self.cost = torch.empty((B, H), device=q.device, dtype=torch.float32)
         self.gq = torch.empty((B, H, D), device=q.device, dtype=gio)
         self.gqd = torch.empty((B, H, D), device=q.device, dtype=gio)
-        self._w = _abi.RolloutWeights(*[float(v) for v in weights])
+        self._w = _weights_struct(weights)        # the plan's own reference: the cache may be cleared
         self._gp = _abi.GpPrior(float(dt), float(sigma), float(gp_weight))
         self._fn = lib().trk_rollout_gp_cost_grad
         self._args = (model._h, cm._h, C.byref(self._w), C.byref(self._gp), q.data_ptr(), qd.data_ptr(), B, H, int(f16), _ptr(self.link_pos),
                       self.cost.data_ptr(), self.gq.data_ptr(), self.gqd.data_ptr(), gcode, gs)
 
     def launch(self, cost_sum_ptr: Optional[int] = None, stream: Optional[int] = None) -> None:
-        with _on(self.device):
-            if stream is None:
-                stream = _stream_of(self.device)
-            rc = self._fn(*self._args, cost_sum_ptr, stream)
-        if rc:
-            check(rc, "trk_rollout_gp_cost_grad")
+        self._launch(stream, cost_sum_ptr)
 
 
 def rollout_gp_cost_grad(model: ModelHandle, cm: CostHandle, weights, q: torch.Tensor, qd: torch.Tensor, dt: float, sigma: float,
@@ -1080,22 +1055,17 @@ def rollout_gp_cost_grad(model: ModelHandle, cm: CostHandle, weights, q: torch.T
     return plan.link_pos, plan.cost, plan.gq, plan.gqd
 
 
-class GPPriorPlan:
+class GPPriorPlan(_Plan):
     """Pre-bound GP-prior launch (the counterpart of `RolloutPlan`): buffers and arguments are resolved once, `launch()` is one
     C call (~3 us of host time instead of ~12 us through `gp_prior_cost_grad`).  q, qd (B,H,D) are read in place on every launch;
     results land in `cost` (B,), `gq`, `gqd` -- or are ADDED into `accumulate_into=(gq, gqd)`, e.g. a RolloutPlan's `gq`."""
 
     def __init__(self, q: torch.Tensor, qd: torch.Tensor, dt: float, sigma: float, weight: float = 1.0, accumulate_into=None,
-                 grad_dtype=None, grad_scale: float = 1.0):
-        if q.device.type != "cuda" or qd.device != q.device:
-            raise ValueError("GPPriorPlan: q and qd must be tensors on the same GPU (there is no CPU path)")
-        if q.dim() != 3 or qd.shape != q.shape or q.dtype != qd.dtype or q.dtype not in (torch.float32, torch.float16) or \
-                not (q.is_contiguous() and qd.is_contiguous()):
-            raise ValueError("GPPriorPlan: q, qd must be contiguous (batch, horizon, dof) tensors of the same fp32 / fp16 dtype")
-        B, H, D = (int(v) for v in q.shape)
+                 grad_dtype=None, grad_scale: float = 1.0, who: str = "GPPriorPlan"):
+        B, H, D = _gp_args(None, q, qd, who)
         if accumulate_into is not None and grad_dtype is None:
             grad_dtype = accumulate_into[0].dtype
-        gio, gcode, gs = _grad_mode(q.dtype == torch.float16, grad_dtype, grad_scale, "GPPriorPlan")
+        gio, gcode, gs = _grad_mode(q.dtype == torch.float16, grad_dtype, grad_scale, who, fp32_scale=True)
         self.q, self.qd, self.device, self.grad_scale = q, qd, q.device, gs
         self.cost = torch.empty((B,), device=q.device, dtype=torch.float32)
         if accumulate_into is None:
@@ -1105,18 +1075,13 @@ class GPPriorPlan:
             acc = 1
             for g in (self.gq, self.gqd):
                 if g.numel() != q.numel() or g.dtype != gio or g.device != q.device or not g.is_contiguous():
-                    raise ValueError("GPPriorPlan: accumulate_into buffers must match q (size, device, contiguous) and grad_dtype")
+                    raise ValueError(f"{who}: accumulate_into buffers must match q (size, device, contiguous) and grad_dtype")
         self._fn = lib().trk_gp_prior_cost_grad
         self._args = (q.data_ptr(), qd.data_ptr(), B, H, D, int(q.dtype == torch.float16), float(dt), float(sigma), float(weight),
                       self.cost.data_ptr(), self.gq.data_ptr(), self.gqd.data_ptr(), gcode, gs, acc)
 
     def launch(self, stream: Optional[int] = None) -> None:
-        with _on(self.device):                  # free when the device is already current
-            if stream is None:
-                stream = _stream_of(self.device)
-            rc = self._fn(*self._args, stream)
-        if rc:
-            check(rc, "trk_gp_prior_cost_grad")
+        self._launch(stream)
 
 
 class _GPPrior(torch.autograd.Function):
@@ -1803,7 +1768,7 @@ def rollout_ad(model: ModelHandle, cm: CostHandle, weights, q: torch.Tensor, ps:
     return _Rollout.apply(_dev_f32(q, "rollout(q)"), model, cm, tuple(float(w) for w in weights), ps, bool(want_pos))
 
 
-class RolloutPlan:
+class RolloutPlan(_Plan):
     """Pre-bound fused-rollout launch: every argument is resolved once, so a step costs one ctypes call
     (a planner's inner loop re-evaluates the same buffers thousands of times)."""
 
@@ -1818,8 +1783,6 @@ class RolloutPlan:
             _require_generated("RolloutPlan", model, self.generated)
         f16 = q.dtype == torch.float16
         gio, gcode, gs = _grad_mode(f16, grad_dtype, grad_scale, "RolloutPlan")
-        if not f16 and gs != 1.0:
-            raise ValueError("RolloutPlan: grad_scale applies to float16 trajectories only")
         self.grad_scale = gs
         q = q.contiguous() if (f16 and q.device.type == "cuda") else _dev_f32(q, "RolloutPlan(q)")
         if q.dim() != 3:
@@ -1836,19 +1799,14 @@ class RolloutPlan:
             self.gq = gq_out.view(self.B, self.H, D)
         else:
             self.gq = torch.empty((self.B, self.H, D), device=q.device, dtype=gio)
-        self._w = _abi.RolloutWeights(*[float(v) for v in weights])
+        self._w = _weights_struct(weights)        # the plan's own reference: the cache may be cleared
         self._fn = lib().trk_rollout_cost_grad_f16 if f16 else lib().trk_rollout_cost_grad
         self._args = (model._h, cm._h, C.byref(self._w), q.data_ptr(), self.B, self.H, _ptr(self.link_pos),
                       self.cost.data_ptr(), self.gq.data_ptr()) + ((gcode, gs) if f16 else ())
         self.device = q.device
 
     def launch(self, cost_sum_ptr: Optional[int] = None, stream: Optional[int] = None) -> None:
-        with _on(self.device):                  # free when the device is already current
-            if stream is None:
-                stream = _stream_of(self.device)
-            rc = self._fn(*self._args, cost_sum_ptr, stream)
-        if rc:
-            check(rc, "trk_rollout_cost_grad")
+        self._launch(stream, cost_sum_ptr)
 
 
 class RolloutJacobianPlan(RolloutPlan):
@@ -1872,15 +1830,10 @@ class RolloutJacobianPlan(RolloutPlan):
         self._tail = (self.pos.data_ptr(), self.quat.data_ptr(), self.lin_jac.data_ptr(), self.ang_jac.data_ptr())
 
     def launch(self, cost_sum_ptr: Optional[int] = None, stream: Optional[int] = None) -> None:
-        with _on(self.device):
-            if stream is None:
-                stream = _stream_of(self.device)
-            rc = self._fn(*self._args, cost_sum_ptr, *self._tail, stream)
-        if rc:
-            check(rc, "trk_rollout_jacobian_cost_grad")
+        self._launch(stream, cost_sum_ptr, *self._tail)
 
 
-class PointsRolloutPlan:
+class PointsRolloutPlan(_Plan):
     """RolloutPlan for the attached-point models (link spheres, grasped-object points; `trk_rollout_points_cost_grad`): the collision
     fields' columns are the points of `ps`, `link_pos` (B, H, P, 3) their world positions.  Same interface as RolloutPlan (launch(),
     link_pos / cost / gq), so step graphs, `ShardedRollout` and `PackedSums` take it unchanged."""
@@ -1906,16 +1859,11 @@ class PointsRolloutPlan:
         else:
             self.gq = torch.empty((self.B, self.H, D), device=q.device, dtype=torch.float32)
         self.grad_scale = 1.0
-        self._w = _abi.RolloutWeights(*[float(v) for v in weights])
+        self._w = _weights_struct(weights)        # the plan's own reference: the cache may be cleared
         self._fn = lib().trk_rollout_points_cost_grad
         self._args = (model._h, ps._h, cm._h, C.byref(self._w), q.data_ptr(), self.B, self.H, _ptr(self.link_pos),
                       self.cost.data_ptr(), self.gq.data_ptr())
         self.device = q.device
 
     def launch(self, cost_sum_ptr: Optional[int] = None, stream: Optional[int] = None) -> None:
-        with _on(self.device):
-            if stream is None:
-                stream = _stream_of(self.device)
-            rc = self._fn(*self._args, cost_sum_ptr, stream)
-        if rc:
-            check(rc, "trk_rollout_points_cost_grad")
+        self._launch(stream, cost_sum_ptr)
