@@ -237,3 +237,244 @@ def tree_cost_spec(name):
         spec.ee2_link, spec.ee2_target = int(g["ee_links"][1]), g["ee_targets"][1]
     spec.validate()
     return m, spec, g
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# 2-D point mass: recorded synthetic scenes (tests/golden/pointmass2d_synth_*.npz) and the objective restated in fp64
+# ---------------------------------------------------------------------------------------------------------------------------
+SYNTH_2D = ["ties", "posed", "sharp", "gridposed", "gridtie", "gridthin"]
+PLANAR_BATCH_N = 20011          # the ragged batch of the seeded tests: 78 blocks of 256 and a tail of 43
+
+
+def planar_bad_rows(got, ref):
+    """Rows whose gradient misses DESIGN section 2's per-element bound 1e-4 |ref| + 5e-6 max|ref|: candidates for a kink."""
+    got, ref = np.asarray(got, np.float64).reshape(-1, 2), np.asarray(ref, np.float64).reshape(-1, 2)
+    return (np.abs(got - ref) > GRAD_RTOL * np.abs(ref) + GRAD_ATOL * max(1e-30, np.abs(ref).max())).any(-1)
+
+
+def planar_fixture_scene(g) -> dict:
+    """The scene a synthetic fixture carries as data (layout of tools/gen_golden_2d.scene_tables under the key prefix 'scene/')
+    -> dict(limits (2, 2), cell, grid_on, objects=[dict(pos (3,), ori wxyz (4,), extra, name, fields=[(kind, centers (k, 2), ab (k, 2))])])
+    with kind 0 sphere (ab = radius, 0), 1 rounded box, 2 sharp box (ab = the two sizes)."""
+    fields, prims = g["scene/fields"], g["scene/prims"]
+    objects = [dict(pos=g["scene/obj_pos"][k], ori=g["scene/obj_ori"][k], extra=bool(g["scene/obj_extra"][k]),
+                    name=str(g["scene/obj_name"][k]), fields=[]) for k in range(len(g["scene/obj_pos"]))]
+    row = 0
+    for o, _, kind, n in fields:
+        p = prims[row:row + n]
+        row += n
+        objects[int(o)]["fields"].append((int(kind), p[:, :2].copy(), p[:, 2:4].copy()))
+    return dict(limits=g["scene/limits"], cell=float(g["scene/cell"]), grid_on=bool(g["scene/grid_on"]), objects=objects)
+
+
+def planar_build_env(tra, scene, tensor_args, grid=None, objects=None):
+    """This package's EnvBase of a recorded scene: fixed objects, extra objects, the grid as recorded (or `grid` on / off)."""
+    kinds = {0: tra.MultiSphereField, 1: tra.MultiBoxField, 2: tra.MultiSharpBoxField}
+    fixed, extra = [], []
+    for o in (scene["objects"] if objects is None else objects):
+        fl = [kinds[k](c, ab[:, 0] if k == 0 else ab, tensor_args=tensor_args) for k, c, ab in o["fields"]]
+        (extra if o["extra"] else fixed).append(tra.ObjectField(fl, o["name"], pos=o["pos"], ori=o["ori"]))
+    return tra.EnvBase(name="synth", limits=scene["limits"], obj_fixed_list=fixed, obj_extra_list=extra or None,
+                       precompute_sdf_obj_fixed=scene["grid_on"] if grid is None else grid, sdf_cell_size=scene["cell"],
+                       tensor_args=tensor_args)
+
+
+def quat_rot64(ori):
+    """q_to_rotation_matrix (quaternion.py:102-120) of the recorded fp32 wxyz quaternion, in fp64; it need not have unit length."""
+    w, x, y, z = (float(v) for v in np.asarray(ori, np.float32).reshape(4))
+    dc = 2.0 / (w * w + x * x + y * y + z * z)
+    return np.array([[1 - dc * (y * y + z * z), dc * (x * y - z * w), dc * (x * z + y * w)],
+                     [dc * (x * y + z * w), 1 - dc * (x * x + z * z), dc * (y * z - x * w)],
+                     [dc * (x * z - y * w), dc * (y * z + x * w), 1 - dc * (x * x + y * y)]], np.float64)
+
+
+def planar_grid_index(q32, lo, md, dims):
+    """GridMapSDF.get_sdf's own fp32 index arithmetic (grid_map_sdf.py:84-93): floor((X - lim_min) / map_dim * cmap_dim), clamped."""
+    q32 = np.asarray(q32, np.float32).reshape(-1, 2)
+    f = np.floor((q32 - np.asarray(lo, np.float32)) / np.asarray(md, np.float32) * np.asarray(dims).astype(np.float32))
+    f = np.clip(np.nan_to_num(f, nan=0.0, posinf=1e9, neginf=-1e9), 0, np.asarray(dims, np.float64) - 1)
+    return f.astype(np.int64)
+
+
+def planar_object_sdf64(x, obj):
+    """ObjectField.compute_signed_distance_impl in 2-D (primitives.py:387-405) in torch fp64: ((x, y, 0) - pos) rotated by R^T, first
+    two coordinates; sphere :108-112, sharp box :220-223 (its own formula), rounded box :327-334; min over a field, then over the fields."""
+    import torch
+    R, pos = torch.from_numpy(quat_rot64(obj["ori"])), torch.from_numpy(np.asarray(obj["pos"], np.float32).astype(np.float64))
+    loc = ((torch.cat([x, torch.zeros_like(x[:, :1])], -1) - pos) @ R)[:, :2]
+    per_field = []
+    for kind, centers, ab in obj["fields"]:
+        c = torch.from_numpy(np.asarray(centers, np.float32).astype(np.float64))
+        ab32 = np.asarray(ab, np.float32)
+        d = loc.unsqueeze(-2) - c.unsqueeze(0)
+        if kind == 0:
+            sdfs = torch.linalg.norm(d, dim=-1) - torch.from_numpy(ab32[:, 0].astype(np.float64))
+        else:
+            half = torch.from_numpy((ab32 / np.float32(2)).astype(np.float64))          # fp32 half sizes, as the field stores them
+            if kind == 2:
+                sdfs = torch.max(d.abs() - half, dim=-1)[0]
+            else:
+                r = torch.from_numpy((ab32.min(-1) * np.float32(0.15)).astype(np.float64))
+                u = d.abs() - half + r.unsqueeze(-1)
+                mu = torch.amax(u, -1)
+                sdfs = torch.minimum(mu, torch.zeros_like(mu)) + torch.linalg.norm(torch.relu(u), dim=-1) - r
+        per_field.append(torch.min(sdfs, dim=-1)[0])
+    return torch.min(torch.stack(per_field, -1), dim=-1)[0]
+
+
+def planar64(objects, q, margin, ws=None, grid=None, clamp=False, want_grad=True, margin_ws=None):
+    """The reference's 2-D point-mass objective restated in torch fp64 on the CPU (primitives.py, grid_map_sdf.py,
+    distance_fields.py:112-123, 319-332) -> (cost (n,), gradient (n, 2), signed distances (n, n_df), boolean (n,)) as numpy fp64 / bool.
+    objects: dicts of planar_fixture_scene; grid: None or dict(sdf (nx, ny), grad (nx, ny, 2), lo (2,), md (2,)), evaluated first with
+    the lookup's own fp32 index; ws: None or (min (2,), max (2,)); margin: the threshold of both fields (`margin_ws`: another one for the
+    workspace field).  The boolean is any(sdf < margin) over the df objects and the workspace faces.  q in fp32 is evaluated at its
+    exact value; q in fp64 (probe points) is evaluated as given, a grid's cell being taken at the fp32-rounded point."""
+    import torch
+    q32 = np.asarray(q, np.float32).reshape(-1, 2)
+    x = torch.from_numpy(np.asarray(q).reshape(-1, 2).astype(np.float64)).requires_grad_(True)
+    m = float(margin)
+    mw = m if margin_ws is None else float(margin_ws)
+    dfs = []
+    if grid is not None:
+        idx = planar_grid_index(q32, grid["lo"], grid["md"], grid["sdf"].shape)
+        s = torch.from_numpy(np.asarray(grid["sdf"], np.float64)[idx[:, 0], idx[:, 1]])
+        gg = torch.from_numpy(np.asarray(grid["grad"], np.float64)[idx[:, 0], idx[:, 1]])
+        dfs.append(s + (x * gg).sum(-1) - (x.detach() * gg).sum(-1))
+    dfs += [planar_object_sdf64(x, o) for o in objects]
+    cost = torch.zeros(len(q32), dtype=torch.float64)
+    sdf = torch.stack(dfs, -1) if dfs else torch.zeros(len(q32), 0, dtype=torch.float64)
+    coll = (sdf.detach() < m).any(-1)
+    if dfs:
+        c = m - sdf
+        cost = cost + (torch.relu(c) if clamp else c).max(-1)[0]
+    if ws is not None:
+        wmin, wmax = (torch.from_numpy(np.asarray(w, np.float32).astype(np.float64)) for w in ws)
+        d = torch.cat([x - wmin, wmax - x], -1)
+        d = torch.sign(d) * d.abs()                      # distance_fields.py:326: value d, derivative 0 at d == 0
+        w = mw - d
+        cost = cost + (torch.relu(w) if clamp else w).max(-1)[0]
+        coll = coll | (d.detach() < mw).any(-1)
+    gq = np.zeros((len(q32), 2))
+    if want_grad and cost.requires_grad:
+        gq = torch.autograd.grad(cost.sum(), x)[0].numpy()
+    return cost.detach().numpy(), gq, sdf.detach().numpy(), coll.numpy()
+
+
+def planar_hinge_decided(sdf64, q, ws, margin, band):
+    """Rows where both hinges of the clamp_sdf objective (relu of margin - nearest object distance, relu of margin - nearest face
+    distance) are further than `band` from zero: there fp32 and fp64 are on the same side of relu's kink, as for the boolean."""
+    q64 = np.asarray(q, np.float32).reshape(-1, 2).astype(np.float64)
+    ok = np.ones(len(q64), bool)
+    if sdf64.shape[1]:
+        ok &= np.abs(sdf64.min(-1) - margin) > band
+    if ws is not None:
+        faces = np.concatenate([q64 - np.asarray(ws[0], np.float32).astype(np.float64), np.asarray(ws[1], np.float32).astype(np.float64) - q64], -1)
+        ok &= np.abs(faces.min(-1) - margin) > band
+    return ok
+
+
+PLANAR_MARGIN_OVERRIDE = float(np.float32(0.05))
+
+
+def planar_margins(margin):
+    """the thresholds the booleans are tested at: the scene's, an explicit finite override, and the override 0"""
+    return (float(margin), PLANAR_MARGIN_OVERRIDE, 0.0)
+
+
+def planar_grid64(objects, nodes):
+    """GridMapSDF.compute_signed_distance_raw (grid_map_sdf.py:67-75) at `nodes` (n, 2) in fp64: torch.minimum folded in object order,
+    whose gradient is shared evenly where two objects tie -> (sdf (n,), grad (n, 2))."""
+    import torch
+    x = torch.from_numpy(np.asarray(nodes, np.float64).reshape(-1, 2)).requires_grad_(True)
+    sdf = None
+    for o in objects:
+        v = planar_object_sdf64(x, o)
+        sdf = v if sdf is None else torch.minimum(sdf, v)
+    return sdf.detach().numpy(), torch.autograd.grad(sdf.sum(), x)[0].numpy()
+
+
+def planar_hinge_sides64(objects, q, margin, delta, ws=None, grid=None):
+    """The fp64 clamp_sdf gradients on either side of each hinge's kink: the threshold of the object field and of the workspace field
+    moved by -delta / +delta independently -> (4, n, 2).  A hinge relu(margin - d) depends on the margin through its side alone (the
+    arg-max over objects or faces does not move with it), so these are exactly the one-sided gradients at q of the clamped and the
+    unclamped branch of each field."""
+    out = []
+    for mo in (margin - delta, margin + delta):
+        for mw in (margin - delta, margin + delta):
+            out.append(planar64(objects, q, mo, ws=ws, grid=grid, clamp=True, margin_ws=mw)[1])
+    return np.stack(out)
+
+
+def planar_rows_match_any(got, cands):
+    """Rows of `got` (n, 2) within DESIGN section 2's per-element bound of at least one of the candidate gradients (k, n, 2)."""
+    got = np.asarray(got, np.float64).reshape(-1, 2)
+    ok = np.zeros(len(got), bool)
+    scale = max(1e-30, float(np.abs(np.asarray(cands)).max()))
+    for c in cands:
+        ok |= (np.abs(got - c) <= GRAD_RTOL * np.abs(c) + GRAD_ATOL * scale).all(-1)
+    return ok
+
+
+def planar_nearest64(objects, q, ws=None, grid=None):
+    """The distance the boolean compares with the margin: min over the df objects and the workspace faces, fp64 (n,)."""
+    _, _, sdf, _ = planar64(objects, q, 0.0, ws=None, grid=grid, want_grad=False)
+    d = sdf.min(-1) if sdf.shape[1] else np.full(len(sdf), np.inf)
+    if ws is not None:
+        q64 = np.asarray(q, np.float32).reshape(-1, 2).astype(np.float64)
+        faces = np.concatenate([q64 - np.asarray(ws[0], np.float32).astype(np.float64), np.asarray(ws[1], np.float32).astype(np.float64) - q64], -1)
+        d = np.minimum(d, faces.min(-1))
+    return d
+
+
+def planar_batch(objects, limits, margins, n, seed, ws=True, rung=5e-8, rungs=40):
+    """A seeded batch (n, 2) fp32 for a 2-D scene: one half uniform over the workspace grown by 15 % (points inside and beyond it), the
+    other half a LADDER about the margin -- uniform points pulled along the fp64 gradient of the nearest analytic distance (objects and
+    workspace faces; a grid's stored distance is piecewise constant and has no ladder) until that distance is margin + k * rung, k
+    uniform in [-rungs, rungs], for each margin of `margins` in turn -- so the boolean is exercised within 2e-6 of its threshold on both sides, in steps below one fp32 ulp of
+    the coordinates.  Built on the CPU from the fp64 restatement alone, as tests/test_gpu_edges.py builds its ladders."""
+    rng = np.random.default_rng(seed)
+    lo, hi = np.asarray(limits, np.float64)
+    ext = hi - lo
+    n_lad = n // 2
+    uni = rng.uniform(lo - 0.15 * ext, hi + 0.15 * ext, (n - n_lad, 2))
+    p = rng.uniform(lo + 0.02 * ext, hi - 0.02 * ext, (n_lad, 2))
+    start = p.copy()
+    wsb = (limits[0], limits[1]) if ws else None
+    target = np.resize(np.asarray(margins, np.float64), n_lad) + rng.integers(-rungs, rungs + 1, n_lad) * rung
+    for _ in range(6):                                   # Newton steps on d(p) = target along grad d; |grad d| = 1 almost everywhere
+        d = _nearest_exact(objects, p, wsb)
+        g = _nearest_grad64(objects, p, wsb)
+        nn = (g * g).sum(-1, keepdims=True)
+        p = p - (d - target)[:, None] * g / np.maximum(nn, 1e-12)
+    # a rung that slid onto a kink of the distance (a medial axis, a sharp box's diagonal), where the one-sided slopes differ, or that
+    # never reached its target, goes back to where it started: the ladder probes the threshold, the kinks have tests of their own
+    h, e = 1e-5, np.eye(2)
+    d = _nearest_exact(objects, p, wsb)
+    kink = np.abs(d - target) > 1e-9
+    for k in range(2):
+        fwd, bwd = _nearest_exact(objects, p + h * e[k], wsb) - d, d - _nearest_exact(objects, p - h * e[k], wsb)
+        kink |= np.abs(fwd - bwd) > 1e-3 * h
+    p[kink] = start[kink]
+    return rng.permutation(np.concatenate([uni, p]).astype(np.float32), axis=0)     # every prefix holds both halves
+
+
+def _nearest_grad64(objects, q, ws, h=1e-7):
+    q = np.asarray(q, np.float64)
+    g = np.zeros_like(q)
+    for k in range(2):
+        e = np.zeros(2); e[k] = h
+        g[:, k] = (_nearest_exact(objects, q + e, ws) - _nearest_exact(objects, q - e, ws)) / (2 * h)
+    return g
+
+
+def _nearest_exact(objects, q64, ws):
+    """planar_nearest64 of fp64 points, analytic objects and workspace only (a grid's distance is piecewise constant: no ladder)"""
+    import torch
+    x = torch.from_numpy(np.asarray(q64, np.float64))
+    d = np.full(len(q64), np.inf)
+    for o in objects:
+        d = np.minimum(d, planar_object_sdf64(x, o).numpy())
+    if ws is not None:
+        faces = np.concatenate([q64 - np.asarray(ws[0], np.float64), np.asarray(ws[1], np.float64) - q64], -1)
+        d = np.minimum(d, faces.min(-1))
+    return d

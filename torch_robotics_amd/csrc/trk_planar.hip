@@ -105,9 +105,11 @@ __device__ __forceinline__ float4 grid2d_cell(const P2Hdr& S, float x, float y) 
     return S.cells[(int64_t)i * S.ny + j];
 }
 
-// torch.linspace(lo, hi, n)[i]: start + i * step for the first half, end - (n - 1 - i) * step after (the 3-D precompute's rule)
+// torch.linspace(lo, hi, n)[i]: start + i * step for the first half, end - (n - 1 - i) * step after (the 3-D precompute's rule);
+// a single node is the START, torch.linspace(lo, hi, 1) = [lo]
 __device__ __forceinline__ float linspace_at(float lo, float hi, int n, int i) {
-    const float step = n > 1 ? (hi - lo) / (float)(n - 1) : 0.0f;
+    if (n == 1) return lo;
+    const float step = (hi - lo) / (float)(n - 1);
     return i < n / 2 ? lo + step * (float)i : hi - step * (float)(n - 1 - i);
 }
 
