@@ -8,7 +8,10 @@ where the collision hinge is `PlanningTask(clamp_sdf=True).compute_collision_cos
 kernel) and the prior is `ops.gp_prior_cost_grad`.  The fraction of collision-free trajectories (`compute_fraction_free_trajs`: 5 via
 points per segment, interpolated and tested in one launch) is reported before and after.  Needs the MI355X: there is no CPU path.
 
-    python examples/plan_point_mass_2d.py [--batch 512] [--horizon 64] [--iters 300]
+    python examples/plan_point_mass_2d.py [--batch 512] [--horizon 64] [--iters 300] [--fused]
+
+--fused runs the same problem through `task.trajectory_optimizer`: the hinge, the prior, the pins and Adam in one kernel that keeps the
+trajectories and the optimiser's state in registers, one launch per 32 iterations (`trk_scene2d_traj_adam_steps`).
 """
 import argparse
 import sys
@@ -23,7 +26,7 @@ import torch_robotics_amd as tra
 from torch_robotics_amd import ops
 
 
-def main(batch=512, horizon=64, iters=300, device="cuda:0", verbose=True, seed=0):
+def main(batch=512, horizon=64, iters=300, device="cuda:0", verbose=True, seed=0, fused=False):
     torch.manual_seed(seed)
     ta = dict(device=torch.device(device), dtype=torch.float32)
     env = tra.EnvDense2D(tensor_args=ta)
@@ -32,11 +35,13 @@ def main(batch=512, horizon=64, iters=300, device="cuda:0", verbose=True, seed=0
     start = task.random_coll_free_q(n_samples=1).reshape(1, 1, 2)
     goal = task.random_coll_free_q(n_samples=batch).reshape(batch, 1, 2)
     s = torch.linspace(0.0, 1.0, horizon, **ta).reshape(1, horizon, 1)
-    q = (start + s * (goal - start)).contiguous().requires_grad_(True)
-    qd = ((goal - start) / T).expand(batch, horizon, -1).contiguous().requires_grad_(True)
+    q = (start + s * (goal - start)).contiguous().requires_grad_(not fused)
+    qd = ((goal - start) / T).expand(batch, horizon, -1).contiguous().requires_grad_(not fused)
     before = task.compute_fraction_free_trajs(torch.cat([q, qd], -1).detach())
-    opt = torch.optim.Adam([q, qd], lr=5e-3)
     w_obj, sigma = 20.0, 1.0
+    if fused:
+        return _main_fused(task, q, qd, dt, sigma, w_obj, iters, before, verbose)
+    opt = torch.optim.Adam([q, qd], lr=5e-3)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(iters):
@@ -58,11 +63,27 @@ def main(batch=512, horizon=64, iters=300, device="cuda:0", verbose=True, seed=0
     return before, after
 
 
+def _main_fused(task, q, qd, dt, sigma, w_obj, iters, before, verbose):
+    """the loop of main() on the chip: same objective, same pins (start and goal positions), same Adam"""
+    plan = task.trajectory_optimizer(q, qd, dt, sigma, w_obj=w_obj, lr=5e-3)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    plan.step(iters)
+    torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+    after = task.compute_fraction_free_trajs(torch.cat([q, qd], -1))
+    if verbose:
+        print(f"EnvDense2D, {q.shape[0]} trajectories x {q.shape[1]} steps, fused: fraction of free trajectories {before:.3f} -> {after:.3f} "
+              f"after {iters} Adam iterations ({1e3 * elapsed / iters:.3f} ms / iteration)")
+    return before, after
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--horizon", type=int, default=64)
     ap.add_argument("--iters", type=int, default=300)
+    ap.add_argument("--fused", action="store_true", help="the whole loop in one kernel (task.trajectory_optimizer)")
     a = ap.parse_args()
-    b, f = main(a.batch, a.horizon, a.iters)
+    b, f = main(a.batch, a.horizon, a.iters, fused=a.fused)
     sys.exit(0 if f > b else 1)

@@ -812,6 +812,44 @@ int trk_grid2d_precompute(const TrkScene2D* scene, const int32_t dims[2], const 
  * points [n, 2] -> sdf [n, n_df], grad (nullable) [n, n_df, 2].  ObjectField / GridMapSDF.compute_signed_distance. */
 int trk_scene2d_sdf_points(const TrkScene2D* scene, const float* points, int64_t n, float* sdf, float* grad, trk_stream_t stream);
 
+/* The planners' trajectory objective of the 2-D point mass in ONE launch: trk_scene2d_cost_grad's hinge and the constant-velocity
+ * GP prior (trk_gp_prior_cost_grad) with both gradients.  BUILD-DEFINED like the prior; the hinge half is the arithmetic of
+ * trk_scene2d_cost_grad (bit for bit at w_obj = 1, gp.weight = 0), the prior half is checked against the fp64 oracle.
+ *   q, qd [batch, horizon, 2] fp32, the samples of a trajectory consecutive; any horizon >= 1 (horizon 1 has no factor);
+ *   cost [batch, horizon] = w_obj * (trk_scene2d_cost_grad's cost at q[b,t] with this clamp) + gp.weight/2 e_t^T Q^-1 e_t, the
+ *       factor between t and t+1 attributed to sample t and 0 at t = horizon-1 (trk_rollout_gp_cost_grad's convention);
+ *   gq [batch, horizon, 2] = w_obj d hinge / d q + d prior / d q,  gqd [batch, horizon, 2] = d prior / d qd; gq and gqd are
+ *       nullable TOGETHER (cost only).  q, qd, gq, gqd 8-byte aligned. */
+typedef struct TrkPlanarObjective {
+    float w_obj;                /* finite */
+    int32_t clamp;              /* relu of each hinge term (clamp_sdf) */
+    TrkGpPrior gp;              /* dt > 0, sigma > 0, weight finite (0 = no prior) */
+} TrkPlanarObjective;
+int trk_scene2d_traj_cost_grad(const TrkScene2D* scene, const TrkPlanarObjective* objective, const float* q, const float* qd,
+                               int64_t batch, int32_t horizon, float* cost, float* gq, float* gqd, trk_stream_t stream);
+
+/* n_steps iterations of Adam (torch.optim.Adam's defaults, trk_ik_steps' arithmetic) on that objective with the trajectories and
+ * the optimiser's state on the chip: q, qd [batch, horizon, 2] and adam_m, adam_v [batch, horizon, 4] = (q.x, q.y, qd.x, qd.y)
+ * per sample are read once and written once per launch, at most 32 iterations per launch (more = several launches inside the
+ * call; the result does not depend on how the iterations are grouped into calls).  Iterations first_step .. first_step +
+ * n_steps - 1 are 1-based; adam_m / adam_v are zero before iteration 1.  Per component, with g its gradient:
+ *   m1 = 0.9 m + 0.1 g,  v1 = 0.999 v + 0.001 g^2,  x -= (lr / bc1) * m1 / (sqrt(v1) / sqrt(bc2) + 1e-8),
+ *   bc1 = 1 - 0.9^k and 1 / sqrt(bc2) = 1 / sqrt(1 - 0.999^k) formed in double on the host and rounded once to fp32.
+ * pin: bit 1 q[:,0], 2 q[:,horizon-1], 4 qd[:,0], 8 qd[:,horizon-1] -- the gradient of a pinned component is taken as zero
+ * (its value stays bit-unchanged, its m and v stay zero).  cost (nullable) [batch, horizon]: the objective of the state as
+ * passed in.  lr = 0 (or n_steps = 0) only evaluates: nothing but cost is written.
+ * 1 <= horizon <= TRK_PLANAR_MAX_HORIZON (one lane per sample, a workgroup owns whole trajectories): TRK_ERR_UNSUPPORTED above. */
+#define TRK_PLANAR_MAX_HORIZON 256
+typedef struct TrkPlanarAdam {
+    float lr;                   /* finite */
+    int32_t pin;                /* 0 .. 15 */
+    int32_t first_step;         /* >= 1 */
+    int32_t n_steps;            /* >= 0 */
+} TrkPlanarAdam;
+int trk_scene2d_traj_adam_steps(const TrkScene2D* scene, const TrkPlanarObjective* objective, const TrkPlanarAdam* adam, float* q,
+                                float* qd, float* adam_m, float* adam_v, int64_t batch, int32_t horizon, float* cost,
+                                trk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

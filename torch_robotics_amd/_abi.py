@@ -120,6 +120,17 @@ class Scene2DDesc(C.Structure):     # TrkScene2DDesc
                 ("has_ws", C.c_int32), ("ws_min", C.c_float * 2), ("ws_max", C.c_float * 2), ("margin", C.c_float)]
 
 
+TRK_PLANAR_MAX_HORIZON = 256
+
+
+class PlanarObjective(C.Structure):     # TrkPlanarObjective
+    _fields_ = [("w_obj", C.c_float), ("clamp", C.c_int32), ("gp", GpPrior)]
+
+
+class PlanarAdam(C.Structure):          # TrkPlanarAdam
+    _fields_ = [("lr", C.c_float), ("pin", C.c_int32), ("first_step", C.c_int32), ("n_steps", C.c_int32)]
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 

@@ -7,7 +7,10 @@
 // fetches them with scalar loads into SGPRs.  The grid is packed as float4 (sdf, gx, gy, 0) per cell, so a lookup is ONE 16-byte
 // gather; 400 x 400 cells are 2.56 MB and stay in an XCD's 4 MiB L2 across launches.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -162,12 +165,10 @@ __device__ __forceinline__ bool collides(const P2Hdr& S, float m, float x, float
     return hit;
 }
 
-template <bool GRID, bool ANALYTIC, bool WS, bool CLAMP, bool GRAD>
-__global__ void __launch_bounds__(256)
-k_planar_cost(P2Hdr S, const float2* __restrict__ q, int64_t n, float* __restrict__ cost, float2* __restrict__ grad) {
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= n) return;
-    const float2 p = q[s];
+// The hinge of one sample, cost and gradient: the body of k_planar_cost, and of the trajectory kernels below -- one function, so
+// that all of them run the same instruction sequence on a sample (what the trajectory kernels' tests lean on).
+template <bool GRID, bool ANALYTIC, bool WS, bool CLAMP>
+__device__ __forceinline__ float hinge_term(const P2Hdr& S, float2 p, float& gx_out, float& gy_out) {
     float c = 0.0f, gx = 0.0f, gy = 0.0f;
     if (GRID || ANALYTIC) {
         float ox, oy;
@@ -183,8 +184,153 @@ k_planar_cost(P2Hdr S, const float2* __restrict__ q, int64_t n, float* __restric
         c = c + (CLAMP ? fmaxf(v, 0.0f) : v);
         gx = gx + (live ? wx : 0.0f); gy = gy + (live ? wy : 0.0f);
     }
-    cost[s] = c;
+    gx_out = gx; gy_out = gy;
+    return c;
+}
+
+template <bool GRID, bool ANALYTIC, bool WS, bool CLAMP, bool GRAD>
+__global__ void __launch_bounds__(256)
+k_planar_cost(P2Hdr S, const float2* __restrict__ q, int64_t n, float* __restrict__ cost, float2* __restrict__ grad) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    float gx, gy;
+    cost[s] = hinge_term<GRID, ANALYTIC, WS, CLAMP>(S, q[s], gx, gy);
     if (GRAD) grad[s] = make_float2(gx, gy);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The trajectory objective: w_obj x the hinge + the constant-velocity GP prior on (q, qd), one lane per sample (include/trk.h).
+// ---------------------------------------------------------------------------------------------------------------------------
+struct TrajPar { float w_obj, dt, a, b, c, w; };        // a, b, c: the entries of Q^-1 as trk_launch_gp_prior forms them
+
+// One coordinate of the prior at sample t from its neighbours: k_gp_prior's element(), the same operations in the same order.
+// acc gathers the factor t -> t+1 (attributed to t); gp, gv are d prior / d q[t], d prior / d qd[t].
+__device__ __forceinline__ void gp_coord(const TrajPar& P, bool has_prev, bool has_next, float p0, float v0, float pm, float vm,
+                                         float pn, float vn, float& acc, float& gp, float& gv) {
+    gp = 0.0f; gv = 0.0f;
+    if (has_next) {
+        const float ep = fmaf(P.dt, v0, p0) - pn, ev = v0 - vn;
+        const float rp = fmaf(P.a, ep, P.b * ev), rv = fmaf(P.b, ep, P.c * ev);
+        acc = fmaf(0.5f, fmaf(ep, rp, ev * rv), acc);
+        gp = rp; gv = fmaf(P.dt, rp, rv);
+    }
+    if (has_prev) {
+        const float ep = fmaf(P.dt, vm, pm) - p0, ev = vm - v0;
+        gp -= fmaf(P.a, ep, P.b * ev); gv -= fmaf(P.b, ep, P.c * ev);
+    }
+    gp *= P.w; gv *= P.w;
+}
+
+// x = (q.x, q.y, qd.x, qd.y) of the sample, xm / xn of its neighbours t - 1 / t + 1 (read only where they exist)
+// -> the sample's cost; g = d objective / d x.  At w_obj = 1, w = 0 the cost and g[0..1] are hinge_term's own bits.
+template <bool GRID, bool ANALYTIC, bool WS, bool CLAMP>
+__device__ __forceinline__ float traj_objective(const P2Hdr& S, const TrajPar& P, bool has_prev, bool has_next, const float4& x,
+                                                const float4& xm, const float4& xn, float g[4]) {
+    float hx, hy;
+    const float h = hinge_term<GRID, ANALYTIC, WS, CLAMP>(S, make_float2(x.x, x.y), hx, hy);
+    float acc = 0.0f, gpx, gvx, gpy, gvy;
+    gp_coord(P, has_prev, has_next, x.x, x.z, xm.x, xm.z, xn.x, xn.z, acc, gpx, gvx);
+    gp_coord(P, has_prev, has_next, x.y, x.w, xm.y, xm.w, xn.y, xn.w, acc, gpy, gvy);
+    g[0] = fmaf(P.w_obj, hx, gpx); g[1] = fmaf(P.w_obj, hy, gpy); g[2] = gvx; g[3] = gvy;
+    return fmaf(P.w_obj, h, P.w * acc);
+}
+
+// trk_scene2d_traj_cost_grad: any horizon; a lane takes its neighbours' rows with global loads of its own (the same cache lines
+// its neighbour lanes load, so they cost issue slots and no traffic).
+template <bool GRID, bool ANALYTIC, bool WS, bool CLAMP, bool GRAD>
+__global__ void __launch_bounds__(256)
+k_planar_traj_cost(P2Hdr S, TrajPar P, const float2* __restrict__ q, const float2* __restrict__ qd, int64_t n, int H,
+                   float* __restrict__ cost, float2* __restrict__ gq, float2* __restrict__ gqd) {
+    const int64_t base = (int64_t)blockIdx.x * 256;
+    const int64_t s = base + threadIdx.x;
+    if (s >= n) return;
+    const unsigned t = ((unsigned)(base % H) + threadIdx.x) % (unsigned)H;         // the 64-bit remainder is uniform: scalar
+    const bool has_prev = t > 0, has_next = t + 1 < (unsigned)H;
+    const float2 p = q[s], v = qd[s];
+    const float4 x = make_float4(p.x, p.y, v.x, v.y);
+    float4 xm = x, xn = x;
+    if (has_prev) { const float2 a = q[s - 1], b = qd[s - 1]; xm = make_float4(a.x, a.y, b.x, b.y); }
+    if (has_next) { const float2 a = q[s + 1], b = qd[s + 1]; xn = make_float4(a.x, a.y, b.x, b.y); }
+    float g[4];
+    cost[s] = traj_objective<GRID, ANALYTIC, WS, CLAMP>(S, P, has_prev, has_next, x, xm, xn, g);
+    if (GRAD) { gq[s] = make_float2(g[0], g[1]); gqd[s] = make_float2(g[2], g[3]); }
+}
+
+// trk_scene2d_traj_adam_steps: bias corrections of the iterations of one launch, by value like IkSchedule
+constexpr int PLANAR_ADAM_MAX_STEPS = 32;
+struct AdamPar {
+    float lr; int32_t pin, n_steps, update;             // update == 0: evaluate only (cost), nothing else is written
+    float bc1[PLANAR_ADAM_MAX_STEPS], rsqrt_bc2[PLANAR_ADAM_MAX_STEPS];
+};
+
+// trk_ik_step's Adam on one component
+__device__ __forceinline__ void adam_component(float g, float step, float rsqrt_bc2, float& x, float& m, float& v) {
+    const float m1 = fmaf(0.9f, m, 0.1f * g);
+    const float v1 = fmaf(0.999f, v, 0.001f * g * g);
+    m = m1; v = v1;
+    const float denom = fmaf(sqrtf(v1), rsqrt_bc2, 1e-8f);
+    x = x - step * (m1 / denom);
+}
+
+// One lane per sample, a workgroup of 256 lanes owns floor(256 / H) whole trajectories (lanes beyond them idle); (q, qd, m, v) of a
+// sample stay in its lane's registers for the n_steps iterations of the launch.  Each iteration a lane needs (q, qd) of t - 1 and t + 1:
+//   WAVE (H == 64, a wavefront is a trajectory): two DPP wavefront shifts per value, no LDS and no barrier;
+//   otherwise: through LDS, two buffers used in turn and ONE barrier per iteration -- a lane that writes buffer k & 1 for iteration
+//   k + 2 has passed the barrier of iteration k + 1, which every lane reaches only after its reads of iteration k.
+template <bool GRID, bool ANALYTIC, bool WS, bool CLAMP, bool WAVE>
+__global__ void __launch_bounds__(256)
+k_planar_traj_adam(P2Hdr S, TrajPar P, AdamPar A, float2* __restrict__ q, float2* __restrict__ qd, float4* __restrict__ mom,
+                   float4* __restrict__ vel, int64_t B, int H, float* __restrict__ cost) {
+    __shared__ float4 xch[WAVE ? 1 : 2][WAVE ? 1 : 256];
+    const int tid = threadIdx.x;
+    const int per_wg = WAVE ? 4 : 256 / H;
+    const int tl = WAVE ? tid >> 6 : tid / H;                      // the lane's trajectory within the workgroup
+    const int t = WAVE ? tid & 63 : tid - tl * H;
+    const int64_t traj = (int64_t)blockIdx.x * per_wg + tl;
+    const bool active = tl < per_wg && traj < B;
+    if (WAVE && !active) return;                                   // a whole wavefront: the DPP shifts below see all 64 lanes
+    const int64_t s = traj * H + t;
+    const bool has_prev = t > 0, has_next = t + 1 < H;
+    const bool update = A.update != 0;
+    float4 x = make_float4(0.0f, 0.0f, 0.0f, 0.0f), m = x, v = x;
+    if (active) {
+        const float2 a = q[s], b = qd[s];
+        x = make_float4(a.x, a.y, b.x, b.y);
+        if (update) { m = mom[s]; v = vel[s]; }
+    }
+    // a pinned component's gradient is taken as zero
+    const bool pin_q = ((A.pin & 1) && t == 0) || ((A.pin & 2) && t == H - 1);
+    const bool pin_qd = ((A.pin & 4) && t == 0) || ((A.pin & 8) && t == H - 1);
+    for (int it = 0; it < A.n_steps; ++it) {
+        float4 xm = x, xn = x;
+        if (WAVE) {
+            xm.x = trk_dpp_from_prev(x.x, x.x); xm.y = trk_dpp_from_prev(x.y, x.y);
+            xm.z = trk_dpp_from_prev(x.z, x.z); xm.w = trk_dpp_from_prev(x.w, x.w);
+            xn.x = trk_dpp_from_next(x.x, x.x); xn.y = trk_dpp_from_next(x.y, x.y);
+            xn.z = trk_dpp_from_next(x.z, x.z); xn.w = trk_dpp_from_next(x.w, x.w);
+        } else {
+            xch[it & 1][tid] = x;
+            __syncthreads();
+            if (active && has_prev) xm = xch[it & 1][tid - 1];
+            if (active && has_next) xn = xch[it & 1][tid + 1];
+        }
+        if (active) {
+            float g[4];
+            const float c = traj_objective<GRID, ANALYTIC, WS, CLAMP>(S, P, has_prev, has_next, x, xm, xn, g);
+            if (it == 0 && cost) cost[s] = c;
+            if (update) {
+                const float step = A.lr / A.bc1[it], rs = A.rsqrt_bc2[it];
+                adam_component(pin_q ? 0.0f : g[0], step, rs, x.x, m.x, v.x);
+                adam_component(pin_q ? 0.0f : g[1], step, rs, x.y, m.y, v.y);
+                adam_component(pin_qd ? 0.0f : g[2], step, rs, x.z, m.z, v.z);
+                adam_component(pin_qd ? 0.0f : g[3], step, rs, x.w, m.w, v.w);
+            }
+        }
+    }
+    if (active && update) {
+        q[s] = make_float2(x.x, x.y); qd[s] = make_float2(x.z, x.w);
+        mom[s] = m; vel[s] = v;
+    }
 }
 
 template <bool GRID, bool ANALYTIC, bool WS>
@@ -294,6 +440,31 @@ struct ViaGo {
     const P2Hdr& S; const float* x; int64_t total; int H, SD, ni; const float* al; const float* be; float m; uint8_t* out; hipStream_t st;
     template <bool G, bool A, bool W> void go() {
         hipLaunchKernelGGL((k_planar_collision_via<G, A, W>), dim3(blocks_for(total)), dim3(256), 0, st, S, x, total, H, SD, ni, al, be, m, out);
+    }
+};
+
+struct TrajCostGo {
+    const P2Hdr& S; const TrajPar& P; const float2* q; const float2* qd; int64_t n; int H; bool clamp; float* cost; float2* gq; float2* gqd;
+    hipStream_t st;
+    template <bool G, bool A, bool W, bool C, bool GR> void launch() {
+        hipLaunchKernelGGL((k_planar_traj_cost<G, A, W, C, GR>), dim3(blocks_for(n)), dim3(256), 0, st, S, P, q, qd, n, H, cost, gq, gqd);
+    }
+    template <bool G, bool A, bool W> void go() {
+        if (clamp) { if (gq) launch<G, A, W, true, true>(); else launch<G, A, W, true, false>(); }
+        else { if (gq) launch<G, A, W, false, true>(); else launch<G, A, W, false, false>(); }
+    }
+};
+struct TrajAdamGo {
+    const P2Hdr& S; const TrajPar& P; const AdamPar& Ad; float2* q; float2* qd; float4* m; float4* v; int64_t B; int H; bool clamp, wave;
+    float* cost; hipStream_t st;
+    template <bool G, bool A, bool W, bool C, bool WV> void launch() {
+        const int per_wg = WV ? 4 : 256 / H;
+        hipLaunchKernelGGL((k_planar_traj_adam<G, A, W, C, WV>), dim3((unsigned)((B + per_wg - 1) / per_wg)), dim3(256), 0, st, S, P, Ad,
+                           q, qd, m, v, B, H, cost);
+    }
+    template <bool G, bool A, bool W> void go() {
+        if (clamp) { if (wave) launch<G, A, W, true, true>(); else launch<G, A, W, true, false>(); }
+        else { if (wave) launch<G, A, W, false, true>(); else launch<G, A, W, false, false>(); }
     }
 };
 
@@ -466,6 +637,84 @@ int trk_scene2d_sdf_points(const TrkScene2D* s, const float* points, int64_t n, 
                        s->n_df, sdf, (float2*)grad);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? TRK_OK : trk_hip_fail((int)e, "k_planar_sdf_points");
+}
+
+// What both trajectory entry points ask of their common arguments, before anything is dereferenced or launched; fills P.
+static int check_traj_call(const char* who, const TrkScene2D* s, const TrkPlanarObjective* o, int64_t batch, int32_t horizon, TrajPar& P) {
+    static thread_local char msg[160];
+    const char* bad = nullptr;
+    if (!s || !o) bad = "null scene / objective";
+    else if (batch < 0 || horizon < 1) bad = "batch must be >= 0 and horizon >= 1";
+    else if (!(o->gp.dt > 0.0f) || !std::isfinite(o->gp.dt) || !(o->gp.sigma > 0.0f) || !std::isfinite(o->gp.sigma))
+        bad = "the prior needs finite dt > 0 and sigma > 0";
+    else if (!std::isfinite(o->w_obj) || !std::isfinite(o->gp.weight)) bad = "w_obj and gp.weight must be finite";
+    if (bad) { snprintf(msg, sizeof(msg), "%s: %s", who, bad); return trk_fail(TRK_ERR_INVALID_ARG, msg); }
+    if (batch > 0x7fffffff || (batch * (int64_t)horizon + 255) / 256 > 0x7fffffff) {
+        snprintf(msg, sizeof(msg), "%s: batch x horizon too large", who);
+        return trk_fail(TRK_ERR_UNSUPPORTED, msg);
+    }
+    const float dt = o->gp.dt, s2 = 1.0f / (o->gp.sigma * o->gp.sigma);               // as trk_launch_gp_prior forms them
+    P = TrajPar{o->w_obj, dt, 12.0f * s2 / (dt * dt * dt), -6.0f * s2 / (dt * dt), 4.0f * s2 / dt, o->gp.weight};
+    return TRK_OK;
+}
+
+int trk_scene2d_traj_cost_grad(const TrkScene2D* s, const TrkPlanarObjective* o, const float* q, const float* qd, int64_t batch,
+                               int32_t horizon, float* cost, float* gq, float* gqd, trk_stream_t stream) {
+    const char* who = "trk_scene2d_traj_cost_grad";
+    TrajPar P;
+    int rc = check_traj_call(who, s, o, batch, horizon, P);
+    if (rc) return rc;
+    if ((batch > 0 && (!q || !qd || !cost)) || (gq == nullptr) != (gqd == nullptr))
+        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_cost_grad: null q / qd / cost, or only one of gq / gqd");
+    if (!aligned_to(q, 8) || !aligned_to(qd, 8) || !aligned_to(gq, 8) || !aligned_to(gqd, 8))
+        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_cost_grad: q, qd, gq and gqd must be 8-byte aligned (one float2 per sample)");
+    if (batch == 0) return TRK_OK;
+    TrajCostGo f{s->hdr, P, (const float2*)q, (const float2*)qd, batch * horizon, horizon, o->clamp != 0, cost, (float2*)gq, (float2*)gqd,
+                 (hipStream_t)stream};
+    dispatch3(s->hdr.has_grid != 0, s->hdr.n_objects > 0, s->has_ws != 0, f);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? TRK_OK : trk_hip_fail((int)e, "k_planar_traj_cost");
+}
+
+int trk_scene2d_traj_adam_steps(const TrkScene2D* s, const TrkPlanarObjective* o, const TrkPlanarAdam* ad, float* q, float* qd,
+                                float* adam_m, float* adam_v, int64_t batch, int32_t horizon, float* cost, trk_stream_t stream) {
+    const char* who = "trk_scene2d_traj_adam_steps";
+    TrajPar P;
+    int rc = check_traj_call(who, s, o, batch, horizon, P);
+    if (rc) return rc;
+    if (!ad) return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_adam_steps: null TrkPlanarAdam");
+    if (ad->n_steps < 0 || ad->first_step < 1 || !std::isfinite(ad->lr) || ad->pin < 0 || ad->pin > 15)
+        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_adam_steps: n_steps >= 0, first_step >= 1, lr finite and pin in 0 .. 15");
+    const bool update = ad->lr != 0.0f && ad->n_steps > 0;
+    if (batch > 0 && (!q || !qd || (update && (!adam_m || !adam_v))))
+        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_adam_steps: null q / qd / adam_m / adam_v");
+    if (!aligned_to(q, 8) || !aligned_to(qd, 8) || !aligned_to(adam_m, 16) || !aligned_to(adam_v, 16))
+        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_adam_steps: q, qd must be 8-byte and adam_m, adam_v 16-byte aligned");
+    if (horizon > TRK_PLANAR_MAX_HORIZON)
+        return trk_fail(TRK_ERR_UNSUPPORTED, "trk_scene2d_traj_adam_steps: horizon above TRK_PLANAR_MAX_HORIZON (256): a workgroup owns "
+                                             "whole trajectories; trk_scene2d_traj_cost_grad serves any horizon");
+    if (batch == 0 || (!update && !cost)) return TRK_OK;
+    // H == 64: a wavefront is a trajectory and the neighbours come by DPP; TRK_PLANAR_ADAM_LDS64=1 runs the LDS form there too
+    // (the same arithmetic, for measuring one exchange against the other)
+    static const bool lds64 = [] { const char* v = getenv("TRK_PLANAR_ADAM_LDS64"); return v && v[0] == '1'; }();
+    // at most PLANAR_ADAM_MAX_STEPS iterations per launch; the cost comes from the first launch (the state as the caller passed it)
+    const int32_t total = update ? ad->n_steps : 1;
+    for (int32_t done = 0; done < total; done += PLANAR_ADAM_MAX_STEPS) {
+        AdamPar A{};
+        A.lr = ad->lr; A.pin = ad->pin; A.update = update ? 1 : 0;
+        A.n_steps = std::min<int32_t>(PLANAR_ADAM_MAX_STEPS, total - done);
+        for (int32_t i = 0; i < A.n_steps; ++i) {
+            const double k = (double)ad->first_step + (double)done + (double)i;
+            A.bc1[i] = (float)(1.0 - std::pow(0.9, k));
+            A.rsqrt_bc2[i] = (float)(1.0 / std::sqrt(1.0 - std::pow(0.999, k)));
+        }
+        TrajAdamGo f{s->hdr, P, A, (float2*)q, (float2*)qd, (float4*)adam_m, (float4*)adam_v, batch, horizon, o->clamp != 0,
+                     horizon == 64 && !lds64, done == 0 ? cost : nullptr, (hipStream_t)stream};
+        dispatch3(s->hdr.has_grid != 0, s->hdr.n_objects > 0, s->has_ws != 0, f);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return trk_hip_fail((int)e, "k_planar_traj_adam");
+    }
+    return TRK_OK;
 }
 
 }  // extern "C"

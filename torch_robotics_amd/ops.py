@@ -1529,6 +1529,77 @@ def planar_sdf_points(scene: Scene2DHandle, pts: torch.Tensor, want_grad: bool =
     return (sdf, g) if want_grad else sdf
 
 
+def _planar_traj_args(q: torch.Tensor, qd: torch.Tensor, who: str):
+    """q, qd: contiguous fp32 (batch, horizon, 2) on one GPU, as the kernels read them in place -> (B, H)"""
+    if not (isinstance(q, torch.Tensor) and isinstance(qd, torch.Tensor)) or q.device.type != "cuda" or qd.device != q.device:
+        raise ValueError(f"{who}: q and qd must be tensors on the same GPU (there is no CPU path)")
+    if q.dim() != 3 or q.shape[-1] != 2 or qd.shape != q.shape or q.dtype != torch.float32 or qd.dtype != torch.float32 or \
+            not (q.is_contiguous() and qd.is_contiguous()) or q.data_ptr() % 8 or qd.data_ptr() % 8:
+        raise ValueError(f"{who}: q, qd must be contiguous float32 (batch, horizon, 2) tensors")
+    return int(q.shape[0]), int(q.shape[1])
+
+
+def _planar_objective(dt, sigma, gp_weight, w_obj, clamp) -> "_abi.PlanarObjective":
+    return _abi.PlanarObjective(float(w_obj), int(bool(clamp)), _abi.GpPrior(float(dt), float(sigma), float(gp_weight)))
+
+
+def planar_traj_cost_grad(scene: Scene2DHandle, q: torch.Tensor, qd: torch.Tensor, dt: float, sigma: float, gp_weight: float = 1.0,
+                          w_obj: float = 1.0, clamp: bool = False, want_grad: bool = True):
+    """The 2-D point mass's trajectory objective in one launch (include/trk.h: trk_scene2d_traj_cost_grad): w_obj x planar_cost_grad's
+    hinge + the constant-velocity GP prior on q, qd (B,H,2) -> (cost (B,H) with the prior's factor t -> t+1 at sample t, gq, gqd),
+    the gradients None without want_grad."""
+    B, H = _planar_traj_args(q, qd, "planar_traj_cost_grad")
+    obj = _planar_objective(dt, sigma, gp_weight, w_obj, clamp)
+    cost = torch.empty((B, H), device=q.device, dtype=torch.float32)
+    gq, gqd = (torch.empty_like(q), torch.empty_like(q)) if want_grad else (None, None)
+    with _on(q.device):
+        check(lib().trk_scene2d_traj_cost_grad(scene._h, C.byref(obj), q.data_ptr(), qd.data_ptr(), B, H, cost.data_ptr(), _ptr(gq), _ptr(gqd),
+                                               _stream(q)), "trk_scene2d_traj_cost_grad")
+    return cost, gq, gqd
+
+
+def planar_adam_bias_terms(step: int):
+    """(bc1, 1 / sqrt(bc2)) of Adam's 1-based iteration `step` as trk_scene2d_traj_adam_steps passes them to its kernel: formed in
+    double, rounded once to fp32."""
+    return float(np.float32(1.0 - 0.9 ** float(step))), float(np.float32(1.0 / np.sqrt(1.0 - 0.999 ** float(step))))
+
+
+class PlanarAdamPlan(_Plan):
+    """Adam on planar_traj_cost_grad's objective with the trajectories and the optimiser's state on the chip (include/trk.h:
+    trk_scene2d_traj_adam_steps).  Pre-bound: `step(n)` runs the next n iterations on the caller's q, qd (B,H,2) IN PLACE -- one
+    launch per 32 iterations -- and returns the (B,H) cost of the state it started from.  The plan owns `m`, `v` (B,H,4) and the
+    iteration counter `t`.  pin_*: the start / goal position (velocity) keeps its value.  lr = 0 only evaluates."""
+
+    def __init__(self, scene: Scene2DHandle, q: torch.Tensor, qd: torch.Tensor, dt: float, sigma: float, gp_weight: float = 1.0,
+                 w_obj: float = 1.0, clamp: bool = False, lr: float = 5e-3, pin_start: bool = True, pin_goal: bool = True,
+                 pin_start_vel: bool = False, pin_goal_vel: bool = False):
+        B, H = _planar_traj_args(q, qd, "PlanarAdamPlan")
+        if H > _abi.TRK_PLANAR_MAX_HORIZON:
+            raise NotImplementedError(f"PlanarAdamPlan: horizon {H} is above the {_abi.TRK_PLANAR_MAX_HORIZON} samples a workgroup of the "
+                                      f"persistent kernel holds (planar_traj_cost_grad serves any horizon)")
+        self.scene, self.q, self.qd, self.device, self.B, self.H = scene, q, qd, q.device, B, H
+        self.m = torch.zeros((B, H, 4), device=q.device, dtype=torch.float32)
+        self.v = torch.zeros((B, H, 4), device=q.device, dtype=torch.float32)
+        self.cost = torch.empty((B, H), device=q.device, dtype=torch.float32)
+        self.t = 0                              # iterations done
+        self.pin = 1 * bool(pin_start) | 2 * bool(pin_goal) | 4 * bool(pin_start_vel) | 8 * bool(pin_goal_vel)
+        self._obj = _planar_objective(dt, sigma, gp_weight, w_obj, clamp)
+        self._adam = _abi.PlanarAdam(float(lr), self.pin, 1, 0)
+        self._fn = lib().trk_scene2d_traj_adam_steps
+        self._args = (scene._h, C.byref(self._obj), C.byref(self._adam), q.data_ptr(), qd.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                      B, H, self.cost.data_ptr())
+
+    def step(self, n: int = 1, stream: Optional[int] = None) -> torch.Tensor:
+        n = int(n)
+        if n < 0:
+            raise ValueError("PlanarAdamPlan.step: n must be >= 0")
+        self._adam.first_step, self._adam.n_steps = self.t + 1, n
+        self._launch(stream)
+        if self._adam.lr != 0.0:
+            self.t += n
+        return self.cost
+
+
 def reduce_sum(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Deterministic sum of a float32 device vector (fixed association order)."""
     x = _dev_f32(x, "reduce_sum(x)").reshape(-1)
