@@ -459,6 +459,14 @@ enum {
                                              * trk_rollout_jacobian_cost_grad: generated rollout, the Jacobian as a launch of its own */
 };
 int trk_last_dispatch(void);
+/* The generated rollout kernels come in two families: the generic one, and a plan-specialised one that has the objective terms with
+ * non-zero weight, the requested outputs and the scene's sphere-pair count compiled in (fp32 I/O, identity base, a scene of <= 16
+ * equal spheres; a collision point the model holds at a constant position is evaluated once per cost model and unit instead of per
+ * sample).  Both compute the same values; trk_last_dispatch answers TRK_DISPATCH_GENERATED for either.
+ * trk_last_plan_specialized: 1 when this thread's latest trk_rollout_cost_grad launch ran a plan-specialised kernel, else 0.
+ * trk_set_plan_specialized (process-wide, default on): 0 keeps every launch on the generic family.  Returns the previous setting. */
+int trk_last_plan_specialized(void);
+int trk_set_plan_specialized(int on);
 /* trk_rollout_is_specialized for trk_rollout_points_cost_grad(ps->model, ps, cm, w, ...) (16-byte aligned point_pos_out assumed). */
 int trk_rollout_points_is_specialized(const TrkPointSet* ps, const TrkCostModel* cm, const TrkRolloutWeights* w);
 /* Strict mode (process-wide; also TRK_STRICT_SPECIALIZED=1 in the environment, read once): the rollout entry points above return

@@ -33,7 +33,7 @@ EXPORTS = [
     "trk_rollout_points_cost_grad", "trk_rollout_collision", "trk_gp_prior_cost_grad", "trk_rollout_cost_grad_f16", "trk_finite_difference", "trk_traj_diff_norm_sum",
     "trk_interpolate_columns", "trk_interpolate_columns_backward", "trk_rollout_collision_via", "trk_rollout_collision_via_flags", "trk_via_partial_flags_bytes", "trk_traj_validate",
     "trk_scale_rows", "trk_jtj", "trk_pack_sums", "trk_pack_sums_scratch_bytes", "trk_rollout_is_specialized", "trk_ik_gn_steps", "trk_rollout_gp_cost_grad",
-    "trk_spec_register_module", "trk_spec_layout_stamp", "trk_last_dispatch", "trk_set_strict_specialized", "trk_rollout_points_is_specialized", "trk_rollout_jacobian_cost_grad",
+    "trk_spec_register_module", "trk_spec_layout_stamp", "trk_last_dispatch", "trk_last_plan_specialized", "trk_set_plan_specialized", "trk_set_strict_specialized", "trk_rollout_points_is_specialized", "trk_rollout_jacobian_cost_grad",
     "trk_handle_kind", "trk_mailbox_create", "trk_mailbox_ipc_handle", "trk_mailbox_connect", "trk_mailbox_send", "trk_mailbox_recv", "trk_mailbox_exchange", "trk_mailbox_status", "trk_mailbox_destroy",
     "trk_scene2d_create", "trk_scene2d_destroy", "trk_scene2d_cost_grad", "trk_scene2d_collision", "trk_scene2d_collision_via",
     "trk_grid2d_precompute", "trk_scene2d_sdf_points", "trk_scene2d_traj_cost_grad", "trk_scene2d_traj_adam_steps",
@@ -142,6 +142,8 @@ def lib():
     L.trk_rollout_jacobian_cost_grad.argtypes = [vp, vp, C.POINTER(_abi.RolloutWeights), vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.trk_rollout_points_is_specialized.argtypes = [vp, vp, C.POINTER(_abi.RolloutWeights)]
     L.trk_set_strict_specialized.argtypes = [i32]
+    L.trk_last_plan_specialized.argtypes = []
+    L.trk_set_plan_specialized.argtypes = [i32]
     L.trk_interpolate_via_points.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp]
     L.trk_debug_set_stamp_buffer.argtypes = [vp]
     L.trk_reduce_sum.argtypes = [vp, i64, vp, vp]

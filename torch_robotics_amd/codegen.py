@@ -694,6 +694,14 @@ class _LinkUnit:
                    for i in _ancestry(kin, [tmpl.ee_link] + self.ee_jac_cols))
         self.jacf_ok = bool(self.ee_jac_cols) and not tmpl.virtual and same
 
+        # Plan-specialised rollout kernels (k_rollout_fx<terms>_bi<IO, NP>): the (terms, pair counts) this unit compiles
+        # ahead of time.  Only the whole-row, four-wavefront units whose collision links are scored in one scene evaluation qualify.
+        fx_terms, fx_nps = FX_AOT.get(ident, ((), ()))
+        fx_fits = (not self.chunked) and (not self.fast_switch) and not tmpl.virtual and 0 < self.NL <= LINK_OBJ_GROUP_MAX
+        self.fx_terms = [int(v) for v in fx_terms] if fx_fits else []
+        self.fx_nps = [int(v) for v in fx_nps] if fx_fits else []
+        self.fx_const: List[Tuple[float, float, float]] = []      # the leading collision links at constant positions (set by the emitter)
+
         # GPT: the fused rollout with the GP prior fused in ("tree" schedule of trk_rollout_gp_cost_grad: the whole tree at once, like
         # k_rollout -- see _gp_segments_kernel for the segment schedule and for what the prior adds).  launch_gp exists exactly when it does.
         self.gpt_ok = (not self.chunked) and not tmpl.virtual and D <= 32
@@ -861,9 +869,9 @@ def _emit_obj_group(E: Emitter, t, grp, first: int, ticks: _Ticks, fast_arg: str
     E.raw("    }")
 
 
-def _emit_self_pairs(E: Emitter, t, pairs) -> None:
-    """pairs: [(index in the template, link a, link b)]"""
-    E.raw("    if (A.w.w_self != 0.0f) {")
+def _emit_self_pairs(E: Emitter, t, pairs, guard: bool = True) -> None:
+    """pairs: [(index in the template, link a, link b)]; guard: behind the run-time test of the weight (else the term is compiled in)"""
+    E.raw("    if (A.w.w_self != 0.0f) {" if guard else "    {")
     for pi, a, b in pairs:
         pa = ", ".join(E.expr(t[a][k]) for k in range(3))
         pb = ", ".join(E.expr(t[b][k]) for k in range(3))
@@ -872,13 +880,14 @@ def _emit_self_pairs(E: Emitter, t, pairs) -> None:
     E.raw("    }")
 
 
-def _emit_ee_terms(E: Emitter, tracked, R, t) -> None:
-    """the tracked links' SE3 costs: position adjoints into tb<i>, rotation adjoints into the 9-float arrays they name"""
+def _emit_ee_terms(E: Emitter, tracked, R, t, guard: bool = True) -> None:
+    """the tracked links' SE3 costs: position adjoints into tb<i>, rotation adjoints into the 9-float arrays they name; guard: behind
+    the run-time test of the weight (else the term is compiled in)"""
     for ee, tgt, rb in tracked:
         E.raw(f"    float {rb}[9] = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}};")
     if not tracked:
         return
-    E.raw("    if (A.w.w_ee != 0.0f) {")
+    E.raw("    if (A.w.w_ee != 0.0f) {" if guard else "    {")
     for ee, tgt, rb in tracked:
         E.raw("      {")
         E.raw(f"        const float eR[9] = {{{', '.join(E.expr(R[ee][r][c]) for r in range(3) for c in range(3))}}};")
@@ -1274,6 +1283,178 @@ def _rollout_kernel(u: _LinkUnit, base_identity: bool, GPT: bool) -> List[str]:
         _emit_fused_jacobian(u, E, R, t)
     E.raw("}")
     return E.lines
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Plan-specialised rollout kernels.  k_rollout_bi decides in every wavefront of every launch what a bound plan (model, cost model,
+# weights, outputs) fixes once: which objective terms exist, which outputs are written, how many sphere pairs the scene has.  This
+# family compiles those in: one TEXT per set of terms (the name carries the mask: an absent term has no text, and its position
+# adjoints are the symbolic zeros the reverse pass folds away), NP a template parameter, identity base, fp32 I/O, no stamps.  The
+# unit's fx_select (host) answers which instantiation serves a launch; everything else stays with the generic kernel.
+# ----------------------------------------------------------------------------------------------------------------------
+FX_OBJ, FX_WS, FX_SELF, FX_EE, FX_POS, FX_SUM = 1, 2, 4, 8, 16, 32
+FX_C2 = FX_OBJ | FX_EE | FX_POS | FX_SUM                  # bench.py's headline: obstacle + EE cost, link positions, per-wavefront sums
+FX_C3 = FX_C2 | FX_WS | FX_SELF                           # configs[2]'s objective stack
+# ahead-of-time instantiations: unit -> (term sets, sphere-pair counts).  EnvSpheres3D (the bundled sphere scene) has 10 spheres = 5 pairs.
+FX_AOT = {"panda": ((FX_C2, FX_C3), (5,))}
+
+
+def _fx_name(terms: int) -> str:
+    return f"k_rollout_fx{terms:02x}_bi"
+
+
+def _rollout_fx_kernel(u: _LinkUnit, terms: int) -> List[str]:
+    """k_rollout_fx<terms>_bi<IO, NP>: k_rollout_bi for one set of objective terms / outputs and exactly NP sphere pairs"""
+    kin, tmpl, L, D, NL = u.kin, u.tmpl, u.L, u.D, u.NL
+    has = lambda bit: bool(terms & bit)
+    assert has(FX_OBJ), "the family exists for the sphere scene's object term"
+    E = Emitter()
+    lds_lane = max(3 * L, D)
+    E.raw("template <class IO, int NP>      // IO: HBM-side type of q / link_pos / gq; NP: the scene's sphere pairs")
+    E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, 4) {_fx_name(terms)}(SpecArgs A) {{")
+    E.raw(f"    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * {lds_lane} + SPEC_WAVES * TRK_LDS_SPHERES * 4];")
+    E.raw("    typedef typename IoTraits<IO>::Q IOQ;")
+    E.raw("    typedef typename IoTraits<IO>::G IOG;")
+    E.raw("    const int lane = __builtin_amdgcn_workitem_id_x() & (TRK_WAVE - 1);")
+    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_workitem_id_x() / TRK_WAVE);")
+    E.raw(f"    float* lds = lds_all + wave * (TRK_WAVE * {lds_lane});")
+    E.raw(f"    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * {lds_lane}) + wave * TRK_LDS_SPHERES;")
+    E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);   // waited for together with the rows below")
+    E.raw("    const int64_t wblock = (int64_t)__builtin_amdgcn_workgroup_id_x() * SPEC_WAVES + wave;")
+    E.raw("    const int64_t base = wblock * TRK_WAVE;")
+    E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
+    E.raw("    float q[D];")
+    E.raw("    spec_load_q<D>(static_cast<const IOQ*>(A.q), base, rows, lane, lds, q);")
+    E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
+    R, t, passv = _root_pose(True)
+    _emit_angles(E, kin)
+    for p in range(1, L):
+        _emit_fk_link(E, kin, u.walk[p], R, t, passv, u.snap)
+    if has(FX_POS):
+        pos_list = ", ".join(E.expr(t[i][k]) for i in range(L) for k in range(3))
+        E.raw(f"    const float pv[{3 * L}] = {{{pos_list}}};")
+        E.raw(f"    const PosFlusher<{3 * L}, IOQ> flush = spec_stage_rows<{3 * L}>(static_cast<IOQ*>(A.link_pos), base, rows, lane, lds, pv);")
+    else:
+        E.raw("    const NoFlush flush{};")
+    ticks = _Ticks()
+    # ---------------- objectives: the terms of this text, unguarded ----------------
+    obj = list(tmpl.obj_links)
+    n_const = 0
+    for i in obj:
+        if all(t[i][k].is_const for k in range(3)):
+            n_const += 1
+        else:
+            break
+    n_const = min(n_const, NL - 1)
+    const_pts = [tuple(float(np.float32(t[i][k].c)) for k in range(3)) for i in obj[:n_const]]
+    assert not u.fx_const or u.fx_const == const_pts
+    u.fx_const = const_pts
+    adj = set(obj)
+    if has(FX_SELF):
+        adj |= {a for pr in tmpl.self_pairs for a in pr}
+    tracked = u.tracked if has(FX_EE) else []
+    adj |= {l for l, _, _ in tracked}
+    adj = sorted(adj)
+    E.raw("    float cost = 0.0f;")
+    for i in adj:
+        E.raw(f"    float tb{i}_0 = 0.0f, tb{i}_1 = 0.0f, tb{i}_2 = 0.0f;")
+    moving = obj[n_const:]
+    for k, nm in enumerate("xyz"):                               # the points that move; gradients for all NL (constant ones first)
+        E.raw(f"    const float p{nm}[{NL - n_const}] = {{{', '.join(E.expr(t[i][k]) for i in moving)}}};")
+    E.raw("    float gx[NL], gy[NL], gz[NL];")
+    E.raw("#pragma unroll")
+    E.raw("    for (int l = 0; l < NL; ++l) { gx[l] = 0.0f; gy[l] = 0.0f; gz[l] = 0.0f; }")
+    c0 = ticks.take(OBJ_TICK_SLOTS)
+    E.raw(f"    const TickFrom<decltype(flush), {c0}> ticks{{flush}};")
+    E.raw(f"    cost += spec_objects_cost_fx<NL, {n_const}, NP, decltype(ticks)>(A.C, A.w.w_obj, A.fx_rec, px, py, pz, gx, gy, gz, ticks, lds_sph);")
+    if has(FX_WS):
+        for k, nm in enumerate("xyz"):
+            E.raw(f"    const float w{nm}[NL] = {{{', '.join(E.expr(t[i][k]) for i in obj)}}};")
+        E.raw('    asm("" : "+v"(cost));')
+        E.raw("#pragma unroll")
+        E.raw('    for (int l = 0; l < NL; ++l) asm("" : "+v"(gx[l]), "+v"(gy[l]), "+v"(gz[l]));      // the object term ends here (see below)')
+        E.raw("    cost += spec_ws_cost<NL>(A.C, A.w.w_ws, wx, wy, wz, gx, gy, gz);")
+    _emit_obj_adjoints(E, obj, "    ")
+    # The unit grants the compiler reassociation (#pragma clang fp).  In the generic kernel every term sits in a guarded block of its
+    # own, which is where the freedom ends; here the terms are one straight line, and the sums that run through them (the cost, the
+    # position adjoints) would be re-ordered across terms: the last bit of a sum then differs from the generic kernel's.  An empty
+    # asm that claims to modify the running sums ends a term the way the block boundary does -- no instruction, same values.
+    touched = set(obj)
+
+    def end_of_term(extra=()):
+        names = ["cost"] + [f"tb{i}_{k}" for i in sorted(touched) for k in range(3)] + list(extra)
+        for k0 in range(0, len(names), 24):
+            ops_ = ", ".join(f'"+v"({n})' for n in names[k0:k0 + 24])
+            E.raw(f'    asm("" : {ops_});')
+    end_of_term()
+    if has(FX_SELF) and tmpl.self_pairs:
+        _emit_self_pairs(E, t, [(pi, a, b) for pi, (a, b) in enumerate(tmpl.self_pairs)], guard=False)
+        touched |= {a for pr in tmpl.self_pairs for a in pr}
+        end_of_term()
+    _emit_ee_terms(E, tracked, R, t, guard=False)
+    if tracked:
+        touched |= {l for l, _, _ in tracked}
+        end_of_term([f"{rb}[{k}]" for _, _, rb in tracked for k in range(9)])
+    E.raw(ticks())
+    E.raw("    if (lane < rows) store_wt_f1(A.cost + base + lane, cost);")
+    if has(FX_SUM):
+        E.raw("    {")
+        E.raw("        const float tot = spec_wave_sum(lane < rows ? cost : 0.0f);")
+        E.raw("        if (lane == 0 && rows > 0) store_wt_f1(A.cost_sum + wblock, tot);")
+        E.raw("    }")
+    gq_expr = _emit_reverse_links(E, kin, R, t, {i: [f"tb{i}_{k}" for k in range(3)] for i in adj if i < L},
+                                  {l: rb for l, _, rb in tracked}, u.masked, tick=ticks, order=u.walk)
+    E.raw(f"    flush.template rest<{ticks.n}>();")
+    E.raw(f"    const float gv[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
+    E.raw("    spec_store_gq<D, IOG, IoTraits<IO>::kScaled>(static_cast<IOG*>(A.gq), base, rows, lane, lds, gv, A.grad_scale);")
+    E.raw("}")
+    return E.lines
+
+
+def _fx_points_kernel(u: _LinkUnit) -> List[str]:
+    """k_fx_points: one wavefront; the record (signed distance, gradient) of the unit's constant collision points -> A.fx_rec"""
+    n = len(u.fx_const)
+    out = ["__global__ void __launch_bounds__(TRK_WAVE) k_fx_points(SpecArgs A) {"]
+    for k, nm in enumerate("xyz"):
+        out.append(f"    const float p{nm}[{n}] = {{{', '.join(flit(p[k]) for p in u.fx_const)}}};")
+    out.append(f"    spec_fx_point_records<{n}>(A.C, px, py, pz, A.fx_rec, (int)__builtin_amdgcn_workitem_id_x());")
+    out.append("}")
+    return out
+
+
+def _fx_device_lines(u: _LinkUnit) -> List[str]:
+    out = ["#ifndef __HIPCC_RTC__          // plan-specialised rollouts (linked / dlopen-ed units only: a code-object unit keeps the generic kernel)"]
+    for terms in u.fx_terms:
+        out += _rollout_fx_kernel(u, terms) + [""]
+    if u.fx_const:
+        out += _fx_points_kernel(u) + [""]
+    out.append("#endif      // !__HIPCC_RTC__")
+    return out
+
+
+def _fx_host_lines(u: _LinkUnit) -> List[str]:
+    """fx_select (which instantiation serves these arguments: index into the unit's (terms, NP) list, or -1), launch_fx (called by
+    `launch` when the C ABI passed the answer on in fx_pick) and launch_fx_points"""
+    combos = [(tm, n) for tm in u.fx_terms for n in u.fx_nps]
+    out = ["static int fx_select(const SpecArgs& a, int base_identity) {",
+           "    if (!base_identity || a.io_f16 != TRK_IO_F32 || a.stamps || !a.gq || a.coll_out || !scene_is_fast(a.C)) return -1;",
+           f"    if (spec_stream_stores(a, {u.L}, {u.D})) return -1;      // beyond the Infinity Cache: the generic kernel's non-temporal instantiation",
+           f"    const int terms = (a.w.w_obj != 0.0f ? {FX_OBJ} : 0) | ((a.w.w_ws != 0.0f && a.C.has_ws) ? {FX_WS} : 0) | (a.w.w_self != 0.0f ? {FX_SELF} : 0) | "
+           f"(a.w.w_ee != 0.0f ? {FX_EE} : 0) | (a.link_pos ? {FX_POS} : 0) | (a.cost_sum ? {FX_SUM} : 0);"]
+    for k, (tm, n) in enumerate(combos):
+        out.append(f"    if (terms == 0x{tm:02x} && a.C.n_sphere_pairs == {n}) return {k};")
+    out += ["    return -1;", "}",
+            "static void launch_fx(const SpecArgs& a, hipStream_t st) {",
+            "    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);",
+            "    switch (a.fx_pick - 1) {"]
+    for k, (tm, n) in enumerate(combos):
+        out.append(f"    case {k}: hipLaunchKernelGGL(({_fx_name(tm)}<float, {n}>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a); break;")
+    out += ["    default: break;", "    }", "}"]
+    if u.fx_const:
+        out += ["static void launch_fx_points(const SpecEntry*, const SpecArgs& a, int, hipStream_t st) {",
+                "    hipLaunchKernelGGL(k_fx_points, dim3(1), dim3(TRK_WAVE), 0, st, a);",
+                "}"]
+    return out
 
 
 def _gp_segments_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
@@ -1986,6 +2167,8 @@ def _rollout_switches(u: _LinkUnit) -> List[str]:
 def _rollout_launcher_lines(u: _LinkUnit) -> List[str]:
     out = ["static void launch(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {",
            "    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);"]
+    if u.fx_terms:
+        out.append("    if (a.fx_pick > 0) { launch_fx(a, st); return; }      // the plan-specialised family (fx_select chose the instantiation)")
     # every (IO, [POS,] [FAST,] [BOX,] base) instantiation: one generic lambda per compile-time switch, in template-parameter order
     switches = _rollout_switches(u)
     n_sw = len(switches)
@@ -2081,6 +2264,8 @@ def _link_host_lines(u: _LinkUnit) -> List[str]:
            f"static const int32_t kSelfPairs[] = {{{pairs}}};",
            f"static const int32_t kVirtualSrc[] = {{{vsrc}}};",
            f"static const float kVirtualW[] = {{{vw}}};"]
+    if u.fx_terms:
+        out += _fx_host_lines(u)
     out += _rollout_launcher_lines(u)
     if u.jacf_ok:
         out += _rjac_launcher_lines(u)
@@ -2116,7 +2301,8 @@ def _link_host_lines(u: _LinkUnit) -> List[str]:
                f"{slot(u.jac_ok, 'launch_jac')}, launch_coll, launch_fkh, {slot(u.fkhbwd_ok, 'launch_fkhbwd')}, "
                f"{slot(u.ik_ok, 'launch_ik')}, launch_fk1, {slot(u.fields_ok, 'launch_fields')}, "
                f"{len(tmpl.virtual)}, kVirtualSrc, kVirtualW, {slot(u.ikgn_ok, 'launch_ikgn')}, {slot(u.gpt_ok, 'launch_gp')}, nullptr, "
-               f"{slot(u.jacf_ok, 'launch_rjac')}, {slot(u.ajac_ok, 'launch_ajac')}}};")
+               f"{slot(u.jacf_ok, 'launch_rjac')}, {slot(u.ajac_ok, 'launch_ajac')}, {slot(bool(u.fx_terms), 'fx_select')}, "
+               f"{slot(bool(u.fx_terms) and bool(u.fx_const), 'launch_fx_points')}, {len(u.fx_const) if u.fx_terms else 0}}};")
     out.append("static struct Reg { Reg() { trk_spec_register(&kEntry); } } reg;")
     out.append("#endif      // !__HIPCC_RTC__")
     return out
@@ -2143,7 +2329,10 @@ def _link_meta(u: _LinkUnit) -> dict:
         names += [f"{ns}k_fields", f"{ns}k_collf"]
     return dict(ident=u.ident, kernels=names, chunked=bool(u.chunked), fast_switch=bool(u.fast_switch), fkhbwd_ok=bool(u.fkhbwd_ok),
                 fields_ok=bool(u.fields_ok), ik_ok=bool(u.ik_ok), ikgn_ok=bool(u.ikgn_ok), jac_ok=bool(u.jac_ok),
-                jac_direct=bool(u.jac_direct), gp_ok=bool(rtc_gp), n_links=u.L, n_dofs=u.D)
+                jac_direct=bool(u.jac_direct), gp_ok=bool(rtc_gp), n_links=u.L, n_dofs=u.D,
+                # the plan-specialised instantiations of the unit's host half (not in `kernels`: a code-object unit has none)
+                fx_kernels=[f"{ns}{_fx_name(tm)}<float, {n}>" for tm in u.fx_terms for n in u.fx_nps],
+                fx_const_points=[list(p) for p in u.fx_const] if u.fx_terms else [])
 
 
 def generate_rollout_source(kin: KinModel, tmpl: CollisionTemplate, ident: str, snap: float = SNAP, meta: Optional[dict] = None) -> str:
@@ -2174,6 +2363,8 @@ def generate_rollout_source(kin: KinModel, tmpl: CollisionTemplate, ident: str, 
         for base_identity in (True, False):
             out.extend(emit(u, base_identity, *args) + [""])
     per_base(_rollout_kernel, False)
+    if u.fx_terms:
+        out.extend(_fx_device_lines(u))
     if u.gpt_ok:
         per_base(_rollout_kernel, True)
     if u.arm_plan is not None:

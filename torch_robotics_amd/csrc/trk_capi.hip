@@ -2,6 +2,7 @@
 // handles (host tables -> device tables, copied once), kernel launches.  No torch types here.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -343,6 +344,10 @@ struct TrkCostModel {
     std::vector<int32_t> virtual_src;    // host copies of the interpolated-column table (a generated unit must bake the same one)
     std::vector<float> virtual_w;
     bool spec_enabled = true;            // trk_cost_model_enable_specialized: may trk_cost_fields use a generated unit's field kernel
+    // plan-specialised rollouts: per unit, the record of its constant collision points in THIS scene (fx_point_record).  The scene
+    // tables and margins of a cost model never change after trk_cost_model_create and the family runs at the identity base only, so
+    // a record holds for the life of the handle.
+    mutable std::vector<std::pair<const SpecEntry*, float*>> fx_recs;
 };
 
 static bool spec_matches(const SpecEntry* e, const TrkCostModel* cm, const TrkRolloutWeights* w) {
@@ -515,6 +520,47 @@ static int spec_launch(Fn fn, const SpecEntry* e, const Args& a, const TrkModel*
     TRK_HIP(last_launch_error());
     return TRK_OK;
 }
+// The plan-specialised rollout family (k_rollout_fx).  The unit's fx_select says which of its instantiations serves the
+// bound arguments (-1: none); the answer travels to the unit's launcher in fx_pick.  A unit with collision points at constant
+// positions reads their signed distance and gradient from a record evaluated ONCE per (cost model, unit): one wavefront of the unit's
+// own k_fx_points, here, the first time the pair is launched, followed by a stream synchronisation -- which a capturing stream
+// cannot take, so a first launch under capture keeps the generic kernel.  trk_set_plan_specialized(0) keeps every launch generic.
+static std::atomic<int> g_fx_enabled{1};
+static thread_local int g_last_fx = 0;
+static std::mutex g_fx_mutex;            // the records of a cost model may be asked for by several threads
+static int fx_point_record(const TrkCostModel* cm, const SpecEntry* e, const SpecArgs& a, int base_identity, hipStream_t st, float** out) {
+    std::lock_guard<std::mutex> lock(g_fx_mutex);
+    for (const auto& r : cm->fx_recs) if (r.first == e) { *out = r.second; return TRK_OK; }
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); *out = nullptr; return TRK_OK; }
+    float* rec = nullptr;
+    TRK_HIP(hipMalloc(&rec, sizeof(float) * 4 * (size_t)e->fx_n_const));
+    SpecArgs b = a;
+    b.fx_rec = rec;
+    e->launch_fx_points(e, b, base_identity, st);
+    hipError_t err = last_launch_error();
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) { (void)hipFree(rec); return hip_fail(err, "constant-point record"); }
+    cm->fx_recs.emplace_back(e, rec);
+    *out = rec;
+    return TRK_OK;
+}
+static int bind_plan_specialized(SpecArgs& a, const SpecEntry* e, const TrkModel* m, const TrkCostModel* cm, trk_stream_t stream) {
+    g_last_fx = 0;
+    if (!e->fx_select || !g_fx_enabled.load(std::memory_order_relaxed)) return TRK_OK;
+    const int bi = base_is_identity(m);
+    const int pick = e->fx_select(a, bi);
+    if (pick < 0) return TRK_OK;
+    if (e->fx_n_const > 0) {
+        if (!e->launch_fx_points) return TRK_OK;
+        if (int rc = fx_point_record(cm, e, a, bi, (hipStream_t)stream, &a.fx_rec)) return rc;
+        if (!a.fx_rec) return TRK_OK;
+    }
+    a.fx_pick = pick + 1;
+    g_last_fx = 1;
+    return TRK_OK;
+}
+
 // the rollout family records which kernel family served the call (trk_last_dispatch); the other entry points do not
 static int served_generated(int rc) {
     if (rc == TRK_OK) g_last_dispatch = TRK_DISPATCH_GENERATED;
@@ -1321,6 +1367,7 @@ void trk_cost_model_destroy(TrkCostModel* cm) {
     live_del(cm);
     if (cm->d_blob) (void)hipFree(cm->d_blob);
     if (cm->d_cells) (void)hipFree(cm->d_cells);
+    for (const auto& r : cm->fx_recs) (void)hipFree(r.second);
     delete cm;
 }
 
@@ -1394,6 +1441,7 @@ int trk_ee_cost(const TrkCostModel* cm, const float* H_ee, int64_t n, int64_t st
 static int rollout_impl(const char* who, const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w, int io_f16, float grad_scale,
                         const void* q, int64_t batch, int32_t horizon, void* link_pos_out, float* cost, void* gq,
                         float* cost_sum, trk_stream_t stream) {
+    g_last_fx = 0;
     int rc = check_rollout_call(who, m, cm, batch, horizon);
     if (rc) return rc;
     const int64_t n = batch * horizon;
@@ -1406,6 +1454,7 @@ static int rollout_impl(const char* who, const TrkModel* m, const TrkCostModel* 
         SpecArgs a;
         spec_args(a, m, cm, w);
         bind_rollout(a, q, n, link_pos_out, cost, gq, cost_sum, io_f16, grad_scale, g_stamps);
+        if ((rc = bind_plan_specialized(a, e, m, cm, stream)) != TRK_OK) return rc;
         return served_generated(spec_launch(e->launch, e, a, m, stream));
     }
     if ((rc = strict_refusal(who, m)) != TRK_OK) return rc;
@@ -1417,6 +1466,8 @@ static int rollout_impl(const char* who, const TrkModel* m, const TrkCostModel* 
 }
 
 int trk_last_dispatch(void) { return g_last_dispatch; }
+int trk_last_plan_specialized(void) { return g_last_fx; }
+int trk_set_plan_specialized(int on) { return g_fx_enabled.exchange(on ? 1 : 0); }
 int trk_set_strict_specialized(int on) {
     const int prev = strict_specialized() ? 1 : 0;
     g_strict = on ? 1 : 0;

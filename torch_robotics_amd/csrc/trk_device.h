@@ -668,6 +668,52 @@ __device__ __forceinline__ void scene_sphere_winners_global(const DevCostHdr& C,
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// The plan-specialised rollout kernels (k_rollout_fx) compile the scene's SHAPE in: the launch guarantees scene_is_fast
+// and n_sphere_pairs == NP.  The ranking is straight-line for exactly NP pairs -- the arithmetic of scene_rank_pairs without its
+// wave-uniform guards -- with the caller's TRK_OBJ_TICK_SLOTS tick slots at the same places (one in front of each of the first trips).
+template <int NL, int NP, int J, class Tick>
+__device__ __forceinline__ void scene_rank_pairs_fixed(const TRK_CAS float* tab, const float (&px)[NL], const float (&py)[NL],
+                                                       const float (&pz)[NL], float (&bk)[NL], const Tick& tick) {
+    if constexpr (J < NP || J < TRK_OBJ_TICK_SLOTS) {
+        if constexpr (J < TRK_OBJ_TICK_SLOTS) tick.template at<J>();
+        if constexpr (J < NP) {
+            const trk_f2 cx = {tab[8 * J + 0], tab[8 * J + 1]}, cy = {tab[8 * J + 2], tab[8 * J + 3]},
+                         cz = {tab[8 * J + 4], tab[8 * J + 5]}, cw = {tab[8 * J + 6], tab[8 * J + 7]};
+#pragma unroll
+            for (int l = 0; l < NL; ++l) {
+                const trk_f2 key = __builtin_elementwise_fma(trk_f2{px[l], px[l]}, cx,
+                                   __builtin_elementwise_fma(trk_f2{py[l], py[l]}, cy,
+                                   __builtin_elementwise_fma(trk_f2{pz[l], pz[l]}, cz, cw)));
+                const float ks = __uint_as_float((__float_as_uint(key.x) & ~15u) | (unsigned)(2 * J));
+                const float kt = __uint_as_float((__float_as_uint(key.y) & ~15u) | (unsigned)(2 * J + 1));
+                bk[l] = __builtin_fminf(bk[l], __builtin_fminf(ks, kt));
+            }
+        }
+        scene_rank_pairs_fixed<NL, NP, J + 1>(tab, px, py, pz, bk, tick);
+    }
+}
+// scene_min_sdf's equal-radius, <= 16-sphere, LDS-copy path for exactly NP sphere pairs: same ranking origin, same keys, same winner.
+template <int NL, int NP, class Tick>
+__device__ __forceinline__ void scene_min_sdf_fixed(const DevCostHdr& C, const float (&px)[NL], const float (&py)[NL],
+                                                    const float (&pz)[NL], float (&s)[NL], float (&gx)[NL], float (&gy)[NL],
+                                                    float (&gz)[NL], const Tick& tick, const float4* lds_spheres) {
+    static_assert(NP >= 1 && 2 * NP <= TRK_LDS_SPHERES, "the LDS copy holds TRK_LDS_SPHERES spheres");
+    float qx[NL], qy[NL], qz[NL], bk[NL];
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+        qx[l] = px[l] - C.sphere_o[0]; qy[l] = py[l] - C.sphere_o[1]; qz[l] = pz[l] - C.sphere_o[2];
+        bk[l] = __builtin_inff();
+    }
+    scene_rank_pairs_fixed<NL, NP, 0>(cptr(C.sphere_pairs), qx, qy, qz, bk, tick);
+    typedef __attribute__((address_space(3))) const float lds_cfloat;
+    lds_cfloat* lp = (lds_cfloat*)reinterpret_cast<const float*>(lds_spheres);
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+        const int bi = (int)(__float_as_uint(bk[l]) & 15u);
+        scene_sphere_winner(C, px[l], py[l], pz[l], lp[4 * bi], lp[4 * bi + 1], lp[4 * bi + 2], s[l], gx[l], gy[l], gz[l]);
+    }
+}
+
 template <int NL, class Tick = NoTick, bool FAST = false, bool GENERAL = true>
 __device__ __forceinline__ void scene_min_sdf(const DevCostHdr& C, const float (&px)[NL], const float (&py)[NL],
                                               const float (&pz)[NL], float (&s)[NL], float (&gx)[NL], float (&gy)[NL],

@@ -79,6 +79,12 @@ struct SpecArgs {
     const void* qd; void* gqd;
     float gp_dt, gp_a, gp_b, gp_c, gp_w;
     int32_t gp_H;
+    // plan-specialised rollout (k_rollout_fx).  fx_pick: 1 + the index of the unit's instantiation that serves this
+    // launch, as the unit's own fx_select answered; 0: the generic kernel (what every zeroed SpecArgs says).  fx_rec: DEVICE
+    // [4 * fx_n_const] (signed distance, unit gradient) of the unit's collision points at constant positions, evaluated once per
+    // (cost model, unit) by launch_fx_points; k_rollout_fx reads it through the scalar cache
+    float* fx_rec;
+    int32_t fx_pick; int32_t _pad_fx;
 };
 
 #ifndef __HIPCC_RTC__          // host side of a unit (launchers, registry): not part of an in-process device compilation
@@ -131,7 +137,7 @@ typedef void (*SpecIkGnLaunchFn)(const SpecEntry* self, const IkGnArgs& args, in
 // Layout version of SpecArgs / SpecEntry / DevCostHdr as seen by a generated unit.  A unit compiled against another layout
 // (a stale on-disk JIT object) must never be dispatched: trk_spec_register refuses it.  Bump on ANY change to these structs,
 // to TrkRolloutWeights or to the TRK_MAX_* limits in include/trk.h.
-#define TRK_SPEC_ABI_VERSION (TRK_ABI_VERSION * 1000 + 25)
+#define TRK_SPEC_ABI_VERSION (TRK_ABI_VERSION * 1000 + 26)
 
 #ifndef __HIPCC_RTC__
 struct SpecEntry {
@@ -175,6 +181,13 @@ struct SpecEntry {
     int (*launch_rjac)(const SpecEntry* self, const SpecArgs& args, int base_identity, hipStream_t stream);
     // analytic Jacobian of every link (trk_fk_analytic_jacobian: d [pos, quat] / d q, [N, L, 7, D] -> args.jac_lin); nullptr if not generated
     SpecLaunchFn launch_ajac;
+    // plan-specialised rollout kernels (k_rollout_fx<IO, NP>, one text per set of objective terms): fx_select answers the index of the
+    // instantiation that serves a launch with these arguments, or -1 (everything the generic kernel decides at run time that this
+    // family compiles in: scene shape and pair count, the weights' zero pattern, the outputs, no stamps, identity base, fp32 I/O);
+    // launch_fx_points writes args.fx_rec for the fx_n_const collision points the unit knows to be constant; nullptr / 0 if not generated
+    int (*fx_select)(const SpecArgs& args, int base_identity);
+    SpecLaunchFn launch_fx_points;
+    int32_t fx_n_const;
 };
 
 // Does this launch take the F32Stream instantiation (non-temporal output stores)?  Its working set -- q in, positions, cost and
@@ -1229,6 +1242,52 @@ __device__ __forceinline__ float spec_objects_cost(const DevCostHdr& C, float w,
         gx[l] = fmaf(-w, ax[l], gx[l]); gy[l] = fmaf(-w, ay[l], gy[l]); gz[l] = fmaf(-w, az[l], gz[l]);
     }
     return w * cost;
+}
+
+// The same for the plan-specialised kernels (k_rollout_fx): NP sphere pairs compiled in, and the first NC of the NL collision points
+// at constant positions -- their signed distance and gradient come from the record `rec` ([4 * NC], wave-uniform: scalar loads)
+// instead of a per-lane ranking; p* hold the other NL - NC points, g* all NL.  The hinge loop is spec_objects_cost's, term for term.
+template <int NL, int NC, int NP, class Tick>
+__device__ __forceinline__ float spec_objects_cost_fx(const DevCostHdr& C, float w, const float* rec, const float (&px)[NL - NC],
+                                                      const float (&py)[NL - NC], const float (&pz)[NL - NC], float (&gx)[NL],
+                                                      float (&gy)[NL], float (&gz)[NL], const Tick& tick, const float4* lds_spheres) {
+    float s[NL], ax[NL], ay[NL], az[NL];
+    {
+        float sm[NL - NC], am[NL - NC], bm[NL - NC], cm[NL - NC];
+        scene_min_sdf_fixed<NL - NC, NP, Tick>(C, px, py, pz, sm, am, bm, cm, tick, lds_spheres);
+#pragma unroll
+        for (int l = 0; l < NC; ++l) { s[l] = cptr(rec)[4 * l]; ax[l] = cptr(rec)[4 * l + 1]; ay[l] = cptr(rec)[4 * l + 2]; az[l] = cptr(rec)[4 * l + 3]; }
+#pragma unroll
+        for (int l = NC; l < NL; ++l) { s[l] = sm[l - NC]; ax[l] = am[l - NC]; ay[l] = bm[l - NC]; az[l] = cm[l - NC]; }
+    }
+    float cost = 0.0f;
+    if (C.clamp_fields & TRK_FIELD_OBJECTS) {                                  // wave-uniform: the hinge form (clamp_sdf=True)
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+            const float v = cptr(C.obj_link_margin)[l] - s[l];
+            const float wl = v > 0.0f ? w : 0.0f;
+            cost += __builtin_fmaxf(v, 0.0f);
+            gx[l] = fmaf(-wl, ax[l], gx[l]); gy[l] = fmaf(-wl, ay[l], gy[l]); gz[l] = fmaf(-wl, az[l], gz[l]);
+        }
+        return w * cost;
+    }
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+        cost += cptr(C.obj_link_margin)[l] - s[l];
+        gx[l] = fmaf(-w, ax[l], gx[l]); gy[l] = fmaf(-w, ay[l], gy[l]); gz[l] = fmaf(-w, az[l], gz[l]);
+    }
+    return w * cost;
+}
+// launch_fx_points' kernel body: the record of NC constant points, by the per-lane path's own functions (ranking, winner)
+template <int NC>
+__device__ __forceinline__ void spec_fx_point_records(const DevCostHdr& C, const float (&px)[NC], const float (&py)[NC], const float (&pz)[NC],
+                                                      float* rec, int lane) {
+    float s[NC], ax[NC], ay[NC], az[NC];
+    scene_min_sdf<NC, NoTick, true, false>(C, px, py, pz, s, ax, ay, az);
+    if (lane == 0) {
+#pragma unroll
+        for (int l = 0; l < NC; ++l) { rec[4 * l] = s[l]; rec[4 * l + 1] = ax[l]; rec[4 * l + 2] = ay[l]; rec[4 * l + 3] = az[l]; }
+    }
 }
 
 // Arm-per-lane kernels (k_rollout_gpa): lanes 2s / 2s + 1 of a wavefront hold the two ISOMORPHIC arms of sample s, each with the NL

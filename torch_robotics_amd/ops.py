@@ -929,6 +929,18 @@ def last_dispatch() -> str:
     return DISPATCH_NAMES[int(lib().trk_last_dispatch())]
 
 
+def last_plan_specialized() -> bool:
+    """Did this thread's latest `trk_rollout_cost_grad` launch run a plan-specialised kernel (`k_rollout_fx`: objective terms, outputs
+    and sphere-pair count compiled in)?  `last_dispatch()` says 'generated' for both generated families."""
+    return bool(lib().trk_last_plan_specialized())
+
+
+def set_plan_specialized(on: bool) -> bool:
+    """`trk_set_plan_specialized`: False keeps every rollout launch on the generic generated kernel (process-wide; tests compare the two
+    families on the same inputs with it).  Returns the previous setting."""
+    return bool(lib().trk_set_plan_specialized(1 if on else 0))
+
+
 def set_strict_specialized(on: bool) -> bool:
     """Strict mode (`trk_set_strict_specialized`; TRK_STRICT_SPECIALIZED=1 sets it from the environment): a rollout call on a model
     that HAS generated kernels raises NotImplementedError instead of silently taking the 10 - 30 x slower table-driven kernel when
