@@ -1035,9 +1035,58 @@ def builddef_goldens(trees=None):
     np.savez_compressed(GOLD / "ik_gn_panda.npz", **out)
 
 
+def grid3d_aniso_golden():
+    """tests/golden/cost_grid3d_aniso.npz: the reference's own GridMapSDF on a NON-CUBIC, off-centre grid (15 x 9 x 11 cells of 0.1 m)
+    over a synthetic scene of posed objects -- a translated and rotated sphere object and a rounded-box object rotated about a tilted
+    axis --, with get_sdf values and gradients at 500 seeded points, some of them outside the limits on every side.  The scene
+    travels as data in scene_arrays' layout (tests/helpers.objects_from_golden reads it).  Written with a fixed time stamp."""
+    import zipfile
+    from torch_robotics.environments.grid_map_sdf import GridMapSDF
+    from torch_robotics.environments.primitives import MultiBoxField, MultiSphereField, ObjectField
+
+    def unit(q):
+        q = np.asarray(q, np.float64)
+        return torch.tensor(q / np.linalg.norm(q), **TA)
+
+    limits = torch.tensor([[-0.6, -0.4, 0.0], [0.9, 0.5, 1.1]], **TA)
+    spheres = MultiSphereField(np.array([[0.0, 0.0, 0.0], [0.35, 0.1, 0.2], [-0.2, 0.3, 0.45], [0.5, -0.25, 0.6]], np.float32),
+                               np.array([0.12, 0.08, 0.15, 0.1], np.float32), tensor_args=TA)
+    boxes = MultiBoxField(np.array([[0.0, 0.0, 0.0], [0.3, 0.05, -0.2]], np.float32),
+                          np.array([[0.3, 0.16, 0.22], [0.12, 0.2, 0.1]], np.float32), tensor_args=TA)
+    objs = [ObjectField([spheres], "posed_spheres", pos=torch.tensor([-0.15, -0.1, 0.25], **TA), ori=unit([0.9, 0.1, -0.3, 0.2])),
+            ObjectField([boxes], "tilted_boxes", pos=torch.tensor([0.45, 0.2, 0.7], **TA), ori=unit([0.8, 0.35, 0.4, -0.25]))]
+    grid = quiet(GridMapSDF, limits, 0.1, objs, tensor_args=TA)
+
+    class _Env:                                           # what scene_arrays reads
+        obj_fixed_list, obj_extra_list = objs, None
+    _Env.limits = limits
+    out = scene_arrays(_Env)
+    gen = torch.Generator().manual_seed(515)
+    ext = limits[1] - limits[0]
+    pts = limits[0] - 0.15 * ext + torch.rand(500, 3, generator=gen) * 1.3 * ext        # a 15 % rim outside the limits on every side
+    x = pts.clone().requires_grad_(True)
+    val = grid.get_sdf(x)
+    (gval,) = torch.autograd.grad(val.sum(), x)
+    out.update(cell=np.float32(0.1), cmap_dim=grid.cmap_dim.numpy().astype(np.int32), sdf=grid.sdf_tensor.numpy(),
+               grad=grid.grad_sdf_tensor.numpy(), pts=pts.numpy(), pts_sdf=val.detach().numpy(), pts_grad=gval.numpy())
+    with zipfile.ZipFile(GOLD / "cost_grid3d_aniso.npz", "w", zipfile.ZIP_DEFLATED) as zf:
+        for k, v in out.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            zf.writestr(info, buf.getvalue())
+    inside = ((pts >= limits[0]) & (pts <= limits[1])).all(-1)
+    print(f"cost_grid3d_aniso: cmap_dim {out['cmap_dim'].tolist()}, {int((~inside).sum())} of 500 points outside the limits, "
+          f"{(GOLD / 'cost_grid3d_aniso.npz').stat().st_size / 1024:.0f} kB")
+
+
 def main():
     GOLD.mkdir(parents=True, exist_ok=True)
     URDF_OUT.mkdir(parents=True, exist_ok=True)
+    if sys.argv[1:] == ["grid3d"]:
+        grid3d_aniso_golden()
+        return
     if sys.argv[1:] == ["points"]:
         points_goldens()
         return
@@ -1104,6 +1153,7 @@ def main():
     tree_cost_goldens(trees)
     builddef_goldens(trees)
     originals_golden()
+    grid3d_aniso_golden()
     total = sum(p.stat().st_size for p in GOLD.glob("*.npz"))
     print(f"golden dir: {len(list(GOLD.glob('*.npz')))} files, {total/1024:.0f} kB")
 

@@ -949,9 +949,10 @@ void FN(orc_grid_precompute)(const TrkCostModelDesc* c, const int32_t* dims, con
                 int id[3] = {ix, iy, iz};
                 REAL x[3];
                 for (int k = 0; k < 3; ++k) {
-                    /* torch.linspace(start, end, steps): start + i*step for the first half, end - (steps-1-i)*step after */
+                    /* torch.linspace(start, end, steps): start + i*step for the first half, end - (steps-1-i)*step after;
+                     * a single node is the START, torch.linspace(lo, hi, 1) = [lo] */
                     REAL step = dims[k] > 1 ? (lim_max[k] - lim_min[k]) / (REAL)(dims[k] - 1) : 0;
-                    x[k] = id[k] < dims[k] / 2 ? lim_min[k] + step * id[k] : lim_max[k] - step * (dims[k] - 1 - id[k]);
+                    x[k] = (dims[k] == 1 || id[k] < dims[k] / 2) ? lim_min[k] + step * id[k] : lim_max[k] - step * (dims[k] - 1 - id[k]);
                 }
                 REAL best = 0, gb[3] = {0, 0, 0};
                 int first = 1;

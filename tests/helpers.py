@@ -288,12 +288,95 @@ def quat_rot64(ori):
                      [dc * (x * z - y * w), dc * (y * z + x * w), 1 - dc * (x * x + y * y)]], np.float64)
 
 
-def planar_grid_index(q32, lo, md, dims):
-    """GridMapSDF.get_sdf's own fp32 index arithmetic (grid_map_sdf.py:84-93): floor((X - lim_min) / map_dim * cmap_dim), clamped."""
-    q32 = np.asarray(q32, np.float32).reshape(-1, 2)
-    f = np.floor((q32 - np.asarray(lo, np.float32)) / np.asarray(md, np.float32) * np.asarray(dims).astype(np.float32))
-    f = np.clip(np.nan_to_num(f, nan=0.0, posinf=1e9, neginf=-1e9), 0, np.asarray(dims, np.float64) - 1)
+def grid_index_unclamped(q32, lo, md, dims):
+    """floor((X - lim_min) / map_dim * cmap_dim) of GridMapSDF.get_sdf (grid_map_sdf.py:93) in numpy fp32, before the clamp: (n, D) fp32,
+    D = len(dims).  Every operation rounds to fp32 on its own, as the reference's tensor expression does."""
+    dims = np.asarray(dims).reshape(-1)
+    q32 = np.asarray(q32, np.float32).reshape(-1, len(dims))
+    return np.floor((q32 - np.asarray(lo, np.float32)) / np.asarray(md, np.float32) * dims.astype(np.float32))
+
+
+def grid_index(q32, lo, md, dims):
+    """GridMapSDF.get_sdf's own fp32 index arithmetic (grid_map_sdf.py:84-97), 2-D or 3-D: the cell of each point, clamped to the grid."""
+    f = grid_index_unclamped(q32, lo, md, dims)
+    f = np.clip(np.nan_to_num(f, nan=0.0, posinf=1e9, neginf=-1e9), 0, np.asarray(dims, np.float64).reshape(-1) - 1)
     return f.astype(np.int64)
+
+
+def planar_grid_index(q32, lo, md, dims):
+    """grid_index of 2-D points"""
+    return grid_index(np.asarray(q32, np.float32).reshape(-1, 2), lo, md, dims)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the 3-D voxel grid: nodes of the precompute and the bounds its results are held to
+# ---------------------------------------------------------------------------------------------------------------------------
+# the 27 points of a 2e-6 m neighbourhood: where a gradient differs from the fp64 one, one of them must have it (a branch switch)
+KINK_PROBES = 2e-6 * np.array([[0, 0, 0]] + [[sx, sy, sz] for sx in (-1, 0, 1) for sy in (-1, 0, 1) for sz in (-1, 0, 1)
+                                            if (sx, sy, sz) != (0, 0, 0)], np.float64)
+
+
+def linspace_nodes(dims, lo, hi):
+    """The reference's voxel nodes (grid_map_sdf.py:34-45): torch.linspace(lo_k, hi_k, dims_k) per axis in fp32 -- an axis of one node
+    is [lo_k] --, as a meshgrid (n0, n1, n2, 3) fp32."""
+    import torch
+    axes = [torch.linspace(float(np.float32(lo[k])), float(np.float32(hi[k])), int(dims[k]), dtype=torch.float32).numpy() for k in range(3)]
+    return np.stack(np.meshgrid(*axes, indexing="ij"), -1).astype(np.float32)
+
+
+def scene_min64(orc, pts):
+    """GridMapSDF.compute_signed_distance_raw at `pts` in fp64 through the oracle's per-object distances (Oracle.sdf_points): the
+    minimum over the objects and the arg-min object's gradient -> (sdf (n,), grad (n, 3))."""
+    s, g = orc.sdf_points(np.asarray(pts, np.float64).reshape(-1, 3), "f64")
+    a = np.argmin(s, axis=1)
+    r = np.arange(len(s))
+    return s[r, a], g[r, a]
+
+
+def grid_precompute_check(sdf, grad, ref_sdf, ref_grad, nodes, orc, what=""):
+    """The bounds of test_gpu_parity.test_grid_precompute_and_sdf_points on a precomputed grid: value within 2e-6 m of the reference
+    at every node; gradient within 1e-5 at 99.5 % of the nodes at least, and at every other node either the fp64 gradient of some point
+    of the node's 2e-6 m neighbourhood (a branch switch: arg-min object or primitive, face / edge / corner of a box) or inside the
+    envelope of the fp64 gradients over the node's rounding neighbourhood (an ill-conditioned normal just inside a rounded edge).
+    `orc`: an Oracle of the analytic scene.  Returns (worst value error, worst gradient error, nodes explained by the kink rule)."""
+    sdf, grad = np.asarray(sdf, np.float64).reshape(-1), np.asarray(grad, np.float64).reshape(-1, 3)
+    ref_sdf, ref_grad = np.asarray(ref_sdf, np.float64).reshape(-1), np.asarray(ref_grad, np.float64).reshape(-1, 3)
+    nodes = np.asarray(nodes, np.float64).reshape(-1, 3)
+    assert sdf.shape == ref_sdf.shape and grad.shape == ref_grad.shape and len(nodes) == len(sdf), what
+    ev = np.abs(sdf - ref_sdf)
+    d = np.abs(grad - ref_grad).max(-1)
+    print(f"grid precompute {what}: worst |sdf - ref| {ev.max():.3g}, worst |grad - ref| {d.max():.3g}, {int((d >= 1e-5).sum())} of {len(d)} nodes to explain")
+    assert ev.max() < 2e-6, (what, float(ev.max()), int(np.argmax(ev)))
+    assert (d < 1e-5).mean() >= 0.995, (what, float((d < 1e-5).mean()))
+    for n in np.flatnonzero(d >= 1e-5):
+        _, gp = scene_min64(orc, nodes[n] + KINK_PROBES)
+        if np.abs(gp - grad[n]).max(-1).min() < 1e-5:
+            continue
+        _, gn = scene_min64(orc, nodes[n] + 0.125 * KINK_PROBES)
+        lo, hi = gn.min(0) - 1e-5, gn.max(0) + 1e-5
+        assert ((grad[n] >= lo) & (grad[n] <= hi)).all(), (what, int(n), grad[n], ref_grad[n])
+    return float(ev.max()), float(d.max()), int((d >= 1e-5).sum())
+
+
+def posed_scene_objects():
+    """Analytic objects that are NOT at the origin: a sphere object, translated, and a rounded-box object, translated and rotated about
+    a tilted axis (25 degrees about (1, 2, -1))."""
+    a = np.array([1.0, 2.0, -1.0]) / np.sqrt(6.0)
+    t = np.deg2rad(25.0)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    R = np.eye(3) + np.sin(t) * K + (1 - np.cos(t)) * K @ K
+    spheres = make_object(sphere_prims(np.array([[0.0, 0.0, 0.0], [0.4, 0.1, -0.3], [-0.3, 0.35, 0.2]]), np.array([0.15, 0.1, 0.2], np.float32)),
+                          pos=np.array([0.2, 0.5, -0.4], np.float32))
+    boxes = make_object(box_prims(np.array([[0.0, 0.0, 0.0], [0.25, -0.1, 0.3]]), np.array([[0.4, 0.2, 0.3], [0.15, 0.25, 0.1]]), rounded=True),
+                        pos=np.array([-0.2, 0.7, -0.6], np.float32), R=R.astype(np.float32))
+    return [spheres, boxes]
+
+
+def scene_only_spec(objects):
+    """A cost model that holds nothing but a scene (no collision links): what the precompute and sdf_points read."""
+    spec = CostModelSpec(n_links_in=11, objects=list(objects))
+    spec.validate()
+    return spec
 
 
 def planar_object_sdf64(x, obj):
@@ -478,3 +561,176 @@ def _nearest_exact(objects, q64, ws):
         faces = np.concatenate([q64 - np.asarray(ws[0], np.float64), np.asarray(ws[1], np.float64) - q64], -1)
         d = np.minimum(d, faces.min(-1))
     return d
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# "address" grids: voxel grids whose stored values say which cell was read (tests/test_gpu_grid3d_edges.py)
+# ---------------------------------------------------------------------------------------------------------------------------
+ADDRESS_DIMS = [(5, 6, 7), (4, 8, 12), (7, 4, 9), (2, 3, 130), (1, 5, 9), (9, 1, 3), (3, 7, 1), (1, 1, 1), (20, 20, 20)]   # the last: control
+ADDRESS_LO, ADDRESS_HI = np.array([-0.6, 0.0, -1.1], np.float32), np.array([0.9, 0.8, 0.2], np.float32)   # anisotropic, off-centre, one limit 0
+ADDRESS_MARGIN = np.float32(0.1)
+ADDRESS_VMAX = 1.0
+
+
+def address_grid(dims, lo, hi, seed=0, vlo=-ADDRESS_VMAX, vhi=ADDRESS_VMAX, margin=ADDRESS_MARGIN):
+    """dict(dims, lim_min, map_dim, sdf, grad) of a grid whose every cell stores a distance and a gradient of its own.  The distances
+    are a seeded permutation of an evenly spaced ladder over [vlo, vhi], moved so that `margin` lies midway between two rungs: two cells
+    differ by at least (vhi - vlo) / n_cells and none is nearer than half of that, and 1.25e-4, to the margin.  The gradients are an injective
+    affine function of (i, j, k); they are not unit vectors and need not be.  map_dim = |hi - lo| in fp32, as the callers form it."""
+    dims = np.asarray(dims, np.int32)
+    n = int(np.prod(dims))
+    step = (vhi - vlo) / n
+    t = (float(margin) - vlo) / step - 0.5
+    ladder = vlo + (np.arange(n) + 0.5) * step + (t - np.floor(t) - 0.5) * step
+    gap = max(0.0, 2.5e-4 - step)                        # many cells: the rungs either side of the margin move apart, 1.25e-4 from it each
+    ladder = np.where(ladder > float(margin), ladder + 0.5 * gap, ladder - 0.5 * gap)
+    sdf = ladder[np.random.default_rng(seed).permutation(n)].astype(np.float32).reshape(dims)
+    ijk = np.stack(np.meshgrid(*[np.arange(d) for d in dims], indexing="ij"), -1).astype(np.float64)
+    A = np.array([[0.05, -0.021, 0.0013], [0.017, 0.033, -0.0021], [-0.009, 0.013, 0.0047]])
+    grad = (ijk @ A.T + np.array([0.3, -0.4, 0.1])).astype(np.float32)
+    lo, hi = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
+    return dict(dims=dims, lim_min=lo, map_dim=np.abs(hi - lo), sdf=sdf, grad=grad)
+
+
+def address_points(dims, lo, hi, seed=1):
+    """Query points (n, 3) fp32 for an address grid: the centre of every cell; every cell face of every axis -- the two limits
+    included -- formed in fp32 as lo + f * (map_dim / dims), with its fp32 neighbours one ulp either side; -0.0 and +0.0 on every axis
+    whose limits include 0; and points outside the limits on both sides of every axis, from one ulp to 1000 m out, corners included.
+    The coordinates a group leaves free are those of seeded cell centres."""
+    rng = np.random.default_rng(seed)
+    dims = np.asarray(dims, np.int64)
+    lo, hi = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
+    md = np.abs(hi - lo)
+    idx = np.stack(np.meshgrid(*[np.arange(d) for d in dims], indexing="ij"), -1).reshape(-1, 3)
+    centres = (lo.astype(np.float64) + (idx + 0.5) * md.astype(np.float64) / dims).astype(np.float32)
+    groups = [centres]
+
+    def with_axis(k, values, per=4):
+        values = np.asarray(values, np.float32)
+        p = centres[rng.integers(len(centres), size=len(values) * per)].copy()
+        p[:, k] = np.repeat(values, per)
+        return p
+
+    up, dn = np.float32(np.inf), np.float32(-np.inf)
+    for k in range(3):
+        cw = np.float32(md[k] / np.float32(dims[k]))
+        faces = [np.float32(lo[k] + np.float32(f) * cw) for f in range(int(dims[k]) + 1)] + [hi[k]]
+        groups.append(with_axis(k, [u for v in faces for u in (v, np.nextafter(v, up), np.nextafter(v, dn))]))
+        if lo[k] <= 0 <= hi[k]:
+            groups.append(with_axis(k, [np.float32(-0.0), np.float32(0.0)]))
+        out = [1e-6, 1e-4, 1e-2, 0.1, 1.0, 10.0, 100.0, 1000.0]
+        groups.append(with_axis(k, [np.nextafter(lo[k], dn)] + [np.float32(lo[k] - np.float32(d)) for d in out], per=2))
+        groups.append(with_axis(k, [np.nextafter(hi[k], up)] + [np.float32(hi[k] + np.float32(d)) for d in out], per=2))
+    sides = np.array([[sx, sy, sz] for sx in (0, 1) for sy in (0, 1) for sz in (0, 1)], bool)
+    groups.append(np.where(sides, hi + np.float32(1000.0), lo - np.float32(1000.0)).astype(np.float32))
+    groups.append(np.where(sides, np.nextafter(hi, up), np.nextafter(lo, dn)).astype(np.float32))
+    pts = np.concatenate(groups).astype(np.float32)
+    assert np.isfinite(pts).all()
+    return pts
+
+
+def address_coverage(pts, grid):
+    """What the address tests assert about their own inputs: every cell is the expected cell of at least one point; every axis of
+    more than one cell has at least 8 points clamped from below and 8 from above; every axis has at least 8 points exactly on a
+    face.  Returns the expected cells (n, 3)."""
+    dims, lo, md = np.asarray(grid["dims"], np.int64), grid["lim_min"], grid["map_dim"]
+    unc, cell = grid_index_unclamped(pts, lo, md, dims), grid_index(pts, lo, md, dims)
+    lin = (cell[:, 0] * dims[1] + cell[:, 1]) * dims[2] + cell[:, 2]
+    assert len(np.unique(lin)) == int(np.prod(dims)), (dims, len(np.unique(lin)))
+    t = (np.asarray(pts, np.float32) - np.asarray(lo, np.float32)) / np.asarray(md, np.float32) * dims.astype(np.float32)
+    on_face = (t == np.floor(t)) & (t >= 0) & (t <= dims)
+    for k in range(3):
+        if dims[k] > 1:
+            assert (unc[:, k] < 0).sum() >= 8 and (unc[:, k] > dims[k] - 1).sum() >= 8, (dims, k)
+        assert on_face[:, k].sum() >= 8, (dims, k, int(on_face[:, k].sum()))
+    return cell
+
+
+def address_spec(grid, extra_objects=(), full=False, margin=ADDRESS_MARGIN):
+    """The Panda's object-collision links (every margin = `margin`) on a scene that holds `grid` and `extra_objects`, as
+    tests/test_gpu_edges._spec builds its scenes; full: also the workspace box of the grid's limits, the Panda's self-collision pairs
+    and the recorded end-effector target, for rollouts with all four weights."""
+    robot = gold("panda_robot")
+    spec = CostModelSpec(n_links_in=11)
+    spec.obj_link_idx = robot["obj_link_idxs"]
+    spec.obj_link_margin = np.full(len(robot["obj_link_idxs"]), margin, np.float32)
+    spec.objects = [grid_object()] + list(extra_objects)
+    spec.grid = dict(grid)
+    if full:
+        spec.ws_min, spec.ws_max = grid["lim_min"], (grid["lim_min"] + grid["map_dim"]).astype(np.float32)
+        spec.self_link_idx, spec.self_pairs, spec.self_margin = robot["self_link_idxs"], robot["self_pairs"], robot["self_margins"]
+        spec.ee_link, spec.ee_target = 10, gold("rollout_panda")["target"]
+    spec.validate()
+    return spec
+
+
+def address_spheres(lo, hi):
+    """Two spheres of one object inside the limits, for the minimum over a grid and an analytic object: (centres (2, 3), radii (2,))"""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    return (np.stack([lo + np.array([0.3, 0.35, 0.3]) * (hi - lo), lo + np.array([0.7, 0.6, 0.75]) * (hi - lo)]).astype(np.float32),
+            np.array([0.05, 0.08], np.float32))
+
+
+def sphere_dists64(p, c, r):
+    """fp64 signed distances (n, n_spheres) and unit gradients (n, n_spheres, 3) of fp32 points to fp32 spheres"""
+    v = np.asarray(p, np.float32).astype(np.float64)[:, None, :] - np.asarray(c, np.float32).astype(np.float64)[None]
+    d = np.linalg.norm(v, axis=-1)
+    return d - np.asarray(r, np.float32).astype(np.float64)[None], v / d[..., None]
+
+
+# the fused rollouts on a grid: limits that cover most of the Panda's reach and leave its base, its first links and its far reach outside
+ROLLOUT_GRID_DIMS = [(5, 6, 7), (2, 3, 130)]
+ROLLOUT_LO, ROLLOUT_HI = np.array([-0.5, -0.7, 0.14], np.float32), np.array([0.8, 0.4, 0.93], np.float32)
+ROLLOUT_NS = (1, 63, 65, 1000)
+ROLLOUT_BASES = {"identity": None, "moved": [0.1234, -0.2345, 0.0567, 0.9659258, 0.0, 0.0, 0.2588190]}   # xyz + wxyz, as KinModel.set_base_pose
+FACE_BAND = 1e-5
+
+
+def panda_q(n, seed):
+    """q (n, 7) fp32 uniform in the Panda's joint limits"""
+    lim = gold("panda_robot")["q_limits"].astype(np.float64)
+    lim = lim if lim.shape[0] == 2 else lim.T
+    return np.random.default_rng(seed).uniform(lim[0], lim[1], (n, 7)).astype(np.float32)
+
+
+def off_face_rows(pos64, grid, band=FACE_BAND):
+    """Samples whose link positions (n, L, 3) fp64 all lie at least `band` from every cell face of `grid` (the faces of an axis are
+    lim_min + f * map_dim / dims, f = 0 .. dims; beyond the limits the index is clamped and there is no face): there the fp32 kernel
+    and the fp64 oracle read the same cell."""
+    dims = np.asarray(grid["dims"], np.float64)
+    t = (np.asarray(pos64, np.float64) - grid["lim_min"].astype(np.float64)) / grid["map_dim"].astype(np.float64) * dims
+    near = np.abs(t - np.round(t)) * grid["map_dim"].astype(np.float64) / dims < band
+    near &= (np.round(t) >= 0) & (np.round(t) <= dims)
+    return ~near.any(axis=(1, 2))
+
+
+def address_sphere_case(dims, margin=ADDRESS_MARGIN):
+    """An address grid with distances in [0.02, 0.9] next to address_spheres: (grid, centres, radii, points, the expected cell's stored
+    distance (n,), fp64 sphere distances (n, 2) and unit gradients (n, 2, 3)).  The sphere distances are continuous and the test cannot
+    choose them, so points within 1e-4 of a tie between grid and spheres, or where a winning sphere is within 1e-4 of the margin, are
+    left out; a cell that loses its only point that way gets another point of its interior."""
+    grid = address_grid(dims, ADDRESS_LO, ADDRESS_HI, seed=3, vlo=0.02, vhi=0.9, margin=margin)
+    cw, r = address_spheres(ADDRESS_LO, ADDRESS_HI)
+    d3 = np.asarray(dims, np.int64)
+
+    def look(p):
+        c = grid_index(p, grid["lim_min"], grid["map_dim"], dims)
+        sg = grid["sdf"][c[:, 0], c[:, 1], c[:, 2]].astype(np.float64)
+        ds, us = sphere_dists64(p, cw, r)
+        keep = (np.abs(ds.min(1) - sg) > 1e-4) & ((np.abs(ds.min(1) - float(margin)) > 1e-4) | (sg < ds.min(1)))
+        return c, sg, ds, us, keep
+
+    pts = address_points(dims, ADDRESS_LO, ADDRESS_HI, seed=4)
+    c, _, _, _, keep = look(pts)
+    hit = np.zeros(tuple(d3), bool)
+    hit[c[keep, 0], c[keep, 1], c[keep, 2]] = True
+    rng = np.random.default_rng(6)
+    extra = []
+    for cell in np.argwhere(~hit):
+        cand = (ADDRESS_LO.astype(np.float64) + (cell + rng.uniform(0.2, 0.8, (32, 3))) * grid["map_dim"].astype(np.float64) / d3).astype(np.float32)
+        ok = look(cand)[4]
+        extra.append(cand[np.flatnonzero(ok)[0]])
+    pts = np.concatenate([pts[keep]] + ([np.array(extra, np.float32)] if extra else []))
+    c, sg, ds, us, keep = look(pts)
+    assert keep.all()
+    return grid, cw, r, pts, sg, ds, us

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import ROBOTS, gold, grad_close, grad_close_kinks, kink_rows_ok, model, panda_cost_spec, rel_err
+from helpers import KINK_PROBES, ROBOTS, gold, grad_close, grad_close_kinks, kink_rows_ok, model, panda_cost_spec, rel_err
 from torch_robotics_amd._abi import FIELD_OBJECTS, FIELD_SELF, FIELD_WS
 
 pytestmark = pytest.mark.gpu
@@ -297,10 +297,6 @@ def _voxel_centres(dims, lim):
     return np.stack(np.meshgrid(*axes, indexing="ij"), -1)
 
 
-_KINK_PROBES = 2e-6 * np.array([[0, 0, 0]] + [[sx, sy, sz] for sx in (-1, 0, 1) for sy in (-1, 0, 1) for sz in (-1, 0, 1)
-                                            if (sx, sy, sz) != (0, 0, 0)], np.float64)
-
-
 def test_grid_precompute_and_sdf_points(ops, oracle_lib):
     """SDF values everywhere to 2e-6; gradients to 1e-5 everywhere EXCEPT on kinks of the distance function, where fp32 and the
     reference may pick different branches -- and there the result must be the gradient of one of the tied branches (no
@@ -335,13 +331,13 @@ def test_grid_precompute_and_sdf_points(ops, oracle_lib):
         d = np.abs(gr - g64).max(-1)
         assert (d < 1e-5).mean() > 0.995
         for n, ob in np.argwhere(d >= 1e-5):
-            _, gp = o.sdf_points(pts[n].astype(np.float64) + _KINK_PROBES, "f64")
+            _, gp = o.sdf_points(pts[n].astype(np.float64) + KINK_PROBES, "f64")
             if np.abs(gp[:, ob] - gr[n, ob]).max(-1).min() < 1e-5:
                 continue
             # not a branch switch: an ill-conditioned normal.  Just inside a rounded edge / corner region the normal is r / |r| with |r|
             # small, and the fp32 rounding of the point's offsets (~6e-8) turns it by 6e-8 / |r| (found by the seed soak: 1.7e-5 at
             # |r| = 3e-3).  The result must then lie inside the envelope of the fp64 gradients over the point's rounding neighbourhood.
-            _, gn = o.sdf_points(pts[n].astype(np.float64) + 0.125 * _KINK_PROBES, "f64")
+            _, gn = o.sdf_points(pts[n].astype(np.float64) + 0.125 * KINK_PROBES, "f64")
             lo, hi = gn[:, ob].min(0) - 1e-5, gn[:, ob].max(0) + 1e-5
             assert ((gr[n, ob] >= lo) & (gr[n, ob] <= hi)).all(), (env, n, ob, gr[n, ob], lo, hi)
 

@@ -506,3 +506,63 @@ def test_gauss_newton_step_against_reference_jacobian_golden(oracle_lib, prec):
         assert (np.abs(q_new - g[f"q_new_{tag}"]) <= 2e-5 + 2e-3 * dq).all(), tag
         assert rel_err(err, g[f"err_{tag}"]) < 2e-5, tag
     assert (np.abs(g["q_new_a"] - g["q0"]).max(1) > 1e-2).sum() >= 30           # the steps are real steps, not clamped no-ops
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the voxel grid off the cubic, origin-centred case
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dims", [(1, 5, 3), (4, 1, 2), (3, 2, 1)])
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_grid_precompute_at_linspace_nodes_with_an_axis_of_one(oracle_lib, dims, prec):
+    """orc_grid_precompute against the reference's OWN nodes, torch.linspace(lo, hi, n) per axis -- an axis of one node is [lo], not
+    [hi] --, on posed objects and off-centre limits.  The reference values are the fp64 per-object distances at those nodes
+    (orc_sdf_points, which has no node rule), minimum over the objects with the arg-min object's gradient."""
+    from helpers import ADDRESS_HI, ADDRESS_LO, grid_precompute_check, linspace_nodes, posed_scene_objects, scene_min64, scene_only_spec
+    o = oracle_lib.Oracle(model("panda_arm_no_gripper"), scene_only_spec(posed_scene_objects()))
+    nodes = linspace_nodes(dims, ADDRESS_LO, ADDRESS_HI)
+    for k in range(3):
+        if dims[k] == 1:
+            assert (nodes[..., k] == ADDRESS_LO[k]).all()
+    ref_s, ref_g = scene_min64(o, nodes)
+    sdf, grad = o.grid_precompute(dims, ADDRESS_LO, ADDRESS_HI, prec)
+    assert sdf.shape == tuple(dims) and grad.shape == tuple(dims) + (3,)
+    grid_precompute_check(sdf, grad, ref_s, ref_g, nodes, o, f"oracle {prec} {dims}")
+
+
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_grid3d_aniso_fixture(oracle_lib, prec):
+    """tests/golden/cost_grid3d_aniso.npz, the reference's GridMapSDF on a 15 x 9 x 11 grid over posed objects: the oracle's
+    precompute of the recorded scene against the recorded grid, and (fp32: the reference's own arithmetic) its lookups at the 500
+    recorded points, array_equal."""
+    from helpers import grid_precompute_check, linspace_nodes, objects_from_golden, scene_only_spec
+    from torch_robotics_amd.costmodel import CostModelSpec, grid_object
+    g = gold("cost_grid3d_aniso")
+    lim, dims = g["limits"], g["cmap_dim"]
+    assert tuple(dims) == (15, 9, 11) and g["sdf"].shape == (15, 9, 11) and len(set(dims.tolist())) == 3
+    inside = ((g["pts"] >= lim[0]) & (g["pts"] <= lim[1])).all(-1)
+    assert 100 <= inside.sum() <= 400                                       # points inside and outside the limits
+    o = oracle_lib.Oracle(model("panda_arm_no_gripper"), scene_only_spec(objects_from_golden(g, "fixed")))
+    sdf, grad = o.grid_precompute(dims, lim[0], lim[1], prec)
+    grid_precompute_check(sdf, grad, g["sdf"], g["grad"], linspace_nodes(dims, lim[0], lim[1]), o, f"oracle {prec} recorded grid")
+    if prec == "f32":
+        spec = CostModelSpec(n_links_in=11, objects=[grid_object()])
+        spec.grid = dict(dims=dims, lim_min=lim[0], map_dim=np.abs(lim[1] - lim[0]), sdf=g["sdf"], grad=g["grad"])
+        s, gr = oracle_lib.Oracle(model("panda_arm_no_gripper"), spec).sdf_points(g["pts"], "f32")
+        np.testing.assert_array_equal(s[:, 0], g["pts_sdf"])
+        np.testing.assert_array_equal(gr[:, 0], g["pts_grad"])
+
+
+def test_address_grid_inputs_and_oracle_lookup(oracle_lib):
+    """The inputs of tests/test_gpu_grid3d_edges.py checked without a GPU: the coverage its address points must have on every grid, and
+    the fp32 oracle's lookup reading exactly the cell of GridMapSDF.get_sdf's fp32 index arithmetic on them."""
+    from helpers import ADDRESS_DIMS, ADDRESS_HI, ADDRESS_LO, address_coverage, address_grid, address_points
+    from torch_robotics_amd.costmodel import CostModelSpec, grid_object
+    for dims in ADDRESS_DIMS:
+        grid = address_grid(dims, ADDRESS_LO, ADDRESS_HI)
+        pts = address_points(dims, ADDRESS_LO, ADDRESS_HI)
+        c = address_coverage(pts, grid)
+        spec = CostModelSpec(n_links_in=11, objects=[grid_object()])
+        spec.grid = grid
+        s, gr = oracle_lib.Oracle(model("panda_arm_no_gripper"), spec).sdf_points(pts, "f32")
+        np.testing.assert_array_equal(s[:, 0], grid["sdf"][c[:, 0], c[:, 1], c[:, 2]], err_msg=str(dims))
+        np.testing.assert_array_equal(gr[:, 0], grid["grad"][c[:, 0], c[:, 1], c[:, 2]], err_msg=str(dims))

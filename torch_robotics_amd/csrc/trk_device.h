@@ -381,7 +381,11 @@ __host__ __device__ __forceinline__ int64_t grid_record(int nb1, int nb2, int i,
 // grid_map_sdf.py:84-114: nearest-lower cell, stored gradient
 typedef float trk_f3u __attribute__((ext_vector_type(3), aligned(4)));       // a 12-byte gradient record: one dwordx3 load
 // one axis of the lookup: floor((X - lim_min) / map_dim * cmap_dim), clamped to [0, dim - 1] (the 3-D grid and the 2-D one)
+// The reference's operation order, whatever the unit grants: a generated unit's `#pragma clang fp reassociate(on)` turned this into
+// ((p - lim_min) * fdim) / map_dim, which rounds to the next integer for points within an ulp of a cell face (a neighbouring cell read;
+// tests/test_gpu_grid3d_edges.py).  Same instructions, in the other order.
 __device__ __forceinline__ int grid_axis_cell(float p, float lim_min, float map_dim, float fdim, int dim) {
+#pragma clang fp reassociate(off) contract(off) reciprocal(off)
     const float f = floorf((p - lim_min) / map_dim * fdim);
     int v = (int)f;
     v = v < 0 ? 0 : v;

@@ -1480,9 +1480,10 @@ k_grid_precompute(DevCostHdr C, int nx, int ny, int nz, float lo0, float lo1, fl
     const float lo[3] = {lo0, lo1, lo2}, hi[3] = {hi0, hi1, hi2};
     float x[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {   // torch.linspace: start + i*step for the first half, end - (steps-1-i)*step after
+    for (int k = 0; k < 3; ++k) {   // torch.linspace: start + i*step for the first half, end - (steps-1-i)*step after;
+                                    // a single node is the START, torch.linspace(lo, hi, 1) = [lo]
         const float step = dims[k] > 1 ? (hi[k] - lo[k]) / (float)(dims[k] - 1) : 0.0f;
-        x[k] = id[k] < dims[k] / 2 ? lo[k] + step * (float)id[k] : hi[k] - step * (float)(dims[k] - 1 - id[k]);
+        x[k] = (dims[k] == 1 || id[k] < dims[k] / 2) ? lo[k] + step * (float)id[k] : hi[k] - step * (float)(dims[k] - 1 - id[k]);
     }
     float best = 0.0f, bx = 0.0f, by = 0.0f, bz = 0.0f;
     bool first = true;
