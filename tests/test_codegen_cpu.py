@@ -279,3 +279,77 @@ def test_unit_kernel_list_and_registry_entry_name_what_the_unit_defines(ident, s
     for name in re.findall(r"hipLaunchKernelGGL\(\(?(\w+)", src):
         assert name in all_kernels, name
     assert ("launch_gp" in launchers) == any(k.startswith("k_rollout_gp") for k in all_kernels)
+
+
+@__import__("pytest").mark.parametrize("ident", list(codegen.SPEC_POINT_ROBOTS) + ["link:dual_panda"])
+def test_points_unit_kernel_list_and_registry_entry_name_what_the_unit_defines(ident):
+    """The attached-point units under the rule the link units are held to: the kernels a code-object build is asked for are defined
+    where it sees them, with that many template parameters; every launcher of the entry is defined and starts kernels that exist.
+    "link:<robot>": that robot's link unit from the per-link pipeline -- no kernel list (the hipRTC path does not serve it) and an
+    ordinary link unit's entry (no point set)."""
+    from torch_robotics_amd.kinematics import URDF_DIR
+    from torch_robotics_amd.kinmodel import KinModel
+    link_mode = ident.startswith("link:")
+    if link_mode:
+        ident = ident[len("link:"):]
+        kin, tmpl = codegen.template_for(ident)
+        pt = codegen.link_points_template(kin, tmpl)
+    else:
+        urdf, fn = codegen.SPEC_POINT_ROBOTS[ident]
+        kin = KinModel.from_urdf(str(URDF_DIR / urdf))
+        pt = fn(kin)
+    meta = {}
+    src = codegen.generate_points_rollout_source(kin, pt, ident, link_mode=link_mode, meta=meta)
+    listed = [f"spec_{ident}::k_rollout_{b}<{f}, float>" for b in ("bi", "bg") for f in ("true", "false")] + \
+             [f"spec_{ident}::k_posbwd_{b}" for b in ("bi", "bg")]
+    assert meta == ({} if link_mode else {"kernels": listed})
+    rtc_src = re.sub(r"#ifndef __HIPCC_RTC__.*?#endif", "", src, flags=re.S)       # what a code-object build compiles
+    rtc_kernels, all_kernels = _defined_kernels(rtc_src), _defined_kernels(src)
+    assert rtc_kernels == all_kernels == {"k_rollout_bi": (2, 2), "k_rollout_bg": (2, 2), "k_posbwd_bi": (0, 0), "k_posbwd_bg": (0, 0)}
+    for name in listed:
+        m = re.fullmatch(rf"spec_{ident}::(\w+)(?:<(.*)>)?", name)
+        assert m and m.group(1) in rtc_kernels, name
+        assert (len(m.group(2).split(",")) if m.group(2) else 0) == rtc_kernels[m.group(1)][0], name
+    entry = re.search(r"static const SpecEntry kEntry = \{(.*)\};", src).group(1)
+    assert re.findall(r"\blaunch\w*", entry) == ["launch", "launch_posbwd"]
+    for name in ("launch", "launch_posbwd"):
+        assert re.search(rf"^static (?:void|int) {name}\(", src, re.M), name
+    started = re.findall(r"hipLaunchKernelGGL\(\(?(\w+)", src)
+    assert set(started) == set(all_kernels)
+    fields = [f.strip() for f in entry.split(",")]
+    assert fields[9] == f'"{ident}"' and fields[10] == "launch" and fields[13] == "launch_posbwd"
+    n_points, phash = (0, 0) if link_mode else (len(pt.point_link), codegen.points_hash(pt.point_link, pt.point_offset))
+    assert fields[11] == str(n_points) and fields[12] == f"0x{phash:016x}ull"
+
+
+def test_generator_and_runtime_compiler_share_the_column_layout_rule():
+    """jit._points_template_of answers None exactly where generate_points_rollout_source raises: columns out of walk order, collision
+    columns not increasing."""
+    import types
+    import numpy as np
+    import pytest
+    from torch_robotics_amd import jit
+    kin = model("panda_arm_no_gripper")
+    order = [int(v) for v in kin.order]
+    walk = [order[1], order[1], order[3], order[6]]
+    po = np.zeros((4, 3), np.float32)
+    po[1] = (0.0, 0.05, -0.02)
+    cases = [(walk, [0, 1, 3], None),
+             ([walk[0], walk[2], walk[1], walk[3]], [0, 1, 3], "columns must follow the walk order of their links"),
+             (walk, [1, 0, 3], "obj_cols must be increasing")]
+    for pl, obj, error in cases:
+        spec = types.SimpleNamespace(n_links_in=4, obj_link_idx=obj, self_link_idx=[0, 2, 3], self_pairs=[(1, 0), (2, 1)],
+                                     ee_link=walk[3], ee2_link=-1)
+        got = jit._points_template_of(kin, pl, po, spec)
+        pt = codegen.PointsTemplate(point_link=np.asarray(pl, np.int32), point_offset=po, obj_cols=obj, self_pairs=[(2, 0), (3, 2)],
+                                    ee_link=walk[3])
+        msg = codegen.points_layout_error(kin, pl, obj)
+        assert (msg is None) == (error is None) and (error is None or error in msg)
+        if error is None:
+            assert got is not None and list(got.point_link) == pl and got.obj_cols == obj and got.self_pairs == pt.self_pairs
+            assert (got.ee_link, got.ee2_link) == (walk[3], -1)
+            assert codegen.generate_points_rollout_source(kin, got, "ok") == codegen.generate_points_rollout_source(kin, pt, "ok")
+        else:
+            assert got is None
+            with pytest.raises(ValueError, match=error):
+                codegen.generate_points_rollout_source(kin, pt, "bad")

@@ -651,6 +651,56 @@ def _gp_segments(kin: KinModel, tmpl: CollisionTemplate, tracked) -> Tuple[List[
     return segs, cross_pairs
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# The link generator's staging constants and the geometry of its ring staging
+# ----------------------------------------------------------------------------------------------------------------------
+CHUNKED_STAGING_MIN_FLOATS = 80       # link kernels with more position floats per sample than this stream them out in chunks
+LINK_OBJ_GROUP_MAX = 12    # link kernels: up to this many collision links are scored in one scene evaluation (more ILP: dual Panda 5+5 was ~1 us slower) ...
+LINK_OBJ_GROUP = 5         # ... more are split into groups of about this size
+RING_FLOATS = 32           # link kernels with ring staging (RingFlusher in trk_spec_common.h): floats per chunk
+
+
+@dataclass
+class RingPlan:
+    """Geometry of RingFlusher<W, V, ALIGNED, IO> (mirrors its constants; see the comment there)."""
+    W: int
+    V: int
+    aligned: bool
+    hx: int                 # longest head
+    n_full: int
+    tail: int               # floats of a sample's tail + head
+    pieces: int             # store instructions per chunk
+
+    @property
+    def stride(self) -> int:
+        return (64 + self.hx) | 1
+
+    def ready_float(self, c: int) -> int:
+        """chunk c is complete in every lane's ring once this float has been staged"""
+        return self.W - 1 if c >= self.n_full else min(self.W - 1, RING_FLOATS * c + RING_FLOATS - 1 + self.hx)
+
+    def reuse_float(self, c: int) -> int:
+        """the first float whose staging overwrites chunk c's half of the ring (W if none does)"""
+        return min(self.W, RING_FLOATS * (c + 2))
+
+    def regular(self, f: int) -> bool:
+        """the float's ring slot is the same offset from the lane's row pointer for every head"""
+        return (f & 63) >= self.hx
+
+
+def ring_plan(W: int) -> RingPlan:
+    assert W >= RING_FLOATS
+    g = W % 8
+    hx = 0 if g == 0 else (7 if g % 2 else (4 if g == 4 else 6))
+    n_full = (W - max(hx, 1)) // RING_FLOATS
+    tail = W - RING_FLOATS * n_full
+    if tail + (8 - g if g else 0) <= RING_FLOATS:        # the longest tail unit (tail of row s + head of row s + 1) fits a chunk
+        return RingPlan(W=W, V=2, aligned=True, hx=hx, n_full=n_full, tail=tail, pieces=16)
+    V = 2 if W % 2 == 0 else 1
+    n_full = (W - 1) // RING_FLOATS
+    return RingPlan(W=W, V=V, aligned=False, hx=0, n_full=n_full, tail=W - RING_FLOATS * n_full, pieces=64 // (64 // (RING_FLOATS // V)))
+
+
 class _LinkUnit:
     """Everything generate_rollout_source decides about one unit, decided once: the walk and the staging of its positions, the columns
     that receive adjoints, and which kernel families (and launchers) the unit carries.  The emitters below only read it."""
@@ -2424,452 +2474,421 @@ class PointsTemplate:
     ee2_link: int = -1                      # second tracked LINK (two-arm scenes)
 
 
-CHUNKED_STAGING_MIN_FLOATS = 80       # link kernels with more position floats per sample than this stream them out in chunks
-LINK_OBJ_GROUP_MAX = 12    # link kernels: up to this many collision links are scored in one scene evaluation (more ILP: dual Panda 5+5 was ~1 us slower) ...
-LINK_OBJ_GROUP = 5         # ... more are split into groups of about this size
 # The fused point rollout stages 64 floats per sample and chunk (256 B: one store instruction writes whole 256-byte segments of 4 / 2 / 1
 # samples, and the lane -> (sample, vector) map is a shift).  Same-box A/B (profiles/r05_ab_chunk_floats.txt), 36 -> 64 floats: 45 spheres 67.0 -> 60.9 us, grasped box 44.6 -> 41.9, both 98.1 -> 86.3; positions only 36.2 -> 30.5, 25.0 -> 21.2,
 # 61.1 -> 46.5 (a row's 144-byte pieces were partial lines for two instructions each).  17.4 KB of LDS per wavefront: still two workgroups per CU.
 ROLLOUT_CHUNK_FLOATS = 64
-RING_FLOATS = 32           # link kernels with ring staging (RingFlusher in trk_spec_common.h): floats per chunk
-@dataclass
-class RingPlan:
-    """Geometry of RingFlusher<W, V, ALIGNED, IO> (mirrors its constants; see the comment there)."""
-    W: int
-    V: int
-    aligned: bool
-    hx: int                 # longest head
-    n_full: int
-    tail: int               # floats of a sample's tail + head
-    pieces: int             # store instructions per chunk
-
-    @property
-    def stride(self) -> int:
-        return (64 + self.hx) | 1
-
-    def ready_float(self, c: int) -> int:
-        """chunk c is complete in every lane's ring once this float has been staged"""
-        return self.W - 1 if c >= self.n_full else min(self.W - 1, RING_FLOATS * c + RING_FLOATS - 1 + self.hx)
-
-    def reuse_float(self, c: int) -> int:
-        """the first float whose staging overwrites chunk c's half of the ring (W if none does)"""
-        return min(self.W, RING_FLOATS * (c + 2))
-
-    def regular(self, f: int) -> bool:
-        """the float's ring slot is the same offset from the lane's row pointer for every head"""
-        return (f & 63) >= self.hx
-
-
-def ring_plan(W: int) -> RingPlan:
-    assert W >= RING_FLOATS
-    g = W % 8
-    hx = 0 if g == 0 else (7 if g % 2 else (4 if g == 4 else 6))
-    n_full = (W - max(hx, 1)) // RING_FLOATS
-    tail = W - RING_FLOATS * n_full
-    if tail + (8 - g if g else 0) <= RING_FLOATS:        # the longest tail unit (tail of row s + head of row s + 1) fits a chunk
-        return RingPlan(W=W, V=2, aligned=True, hx=hx, n_full=n_full, tail=tail, pieces=16)
-    V = 2 if W % 2 == 0 else 1
-    n_full = (W - 1) // RING_FLOATS
-    return RingPlan(W=W, V=V, aligned=False, hx=0, n_full=n_full, tail=W - RING_FLOATS * n_full, pieces=64 // (64 // (RING_FLOATS // V)))
 
 
 OBJ_GROUP = 6       # points evaluated against the scene together (register arrays of this size; 4 / 8 / 12: within the noise, r05_ab_obj_group.txt)
 
 
+def points_layout_error(kin: KinModel, point_link, obj_cols) -> Optional[str]:
+    """Why the attached-point generator cannot take this column layout (None: it can).  The generator's two layout rules, stated
+    once: _PointsUnit raises with the answer, jit._points_template_of returns None where there is one."""
+    pos_of = {int(kin.order[p]): p for p in range(kin.n_links)}
+    rank = [pos_of[int(i)] for i in point_link]
+    if any(rank[k] > rank[k + 1] for k in range(len(rank) - 1)):
+        return "generate_points_rollout_source: columns must follow the walk order of their links"
+    if sorted(obj_cols) != list(obj_cols):
+        return "generate_points_rollout_source: obj_cols must be increasing (margins are read in groups)"
+    return None
+
+
+class _PointsUnit:
+    """Everything the attached-point generator decides about one unit, decided once: the column tables, where the walk scores each
+    self pair, the joints and what moves them, the chunk geometry of both kernels and what the registry entry carries.  The emitters
+    below only read it.
+
+    link_mode: the columns are exactly the links in file order with zero offsets and the unit registers as an ordinary link kernel
+    (n_points = 0)."""
+
+    def __init__(self, kin: KinModel, pt: PointsTemplate, ident: str, snap: float = SNAP, link_mode: bool = False):
+        if link_mode:
+            assert [int(v) for v in pt.point_link] == list(range(kin.n_links)) and not np.asarray(pt.point_offset).any()
+        self.kin, self.pt, self.ident, self.snap, self.link_mode = kin, pt, ident, snap, link_mode
+        L, D, P = self.L, self.D, self.P = kin.n_links, kin.n_dofs, len(pt.point_link)
+        W = self.W = 3 * P
+        self.V = 4 if W % 4 == 0 else (2 if W % 2 == 0 else 1)
+        pl = self.pl = [int(v) for v in pt.point_link]
+        self.po = np.asarray(pt.point_offset, np.float32).reshape(-1, 3)
+        err = points_layout_error(kin, pl, pt.obj_cols)
+        if err:
+            raise ValueError(err)
+        pos_of = self.pos_of = {int(kin.order[p]): p for p in range(L)}
+        walk_rank = self.walk_rank = [pos_of[i] for i in pl]
+        self.cols_of_link: Dict[int, List[int]] = {i: [c for c in range(P) if pl[c] == i] for i in range(L)}
+        self.obj_rank = {c: k for k, c in enumerate(pt.obj_cols)}
+        # a pair is scored when the walk reaches its later column; pairs_at[link] = [(pair index, late col, early col, late_is_a)]
+        self.pairs_at: Dict[int, List[Tuple[int, int, int, bool]]] = {i: [] for i in range(L)}
+        for pi, (a, b) in enumerate(pt.self_pairs):
+            late_is_a = (walk_rank[a], a) >= (walk_rank[b], b)
+            late, early = (a, b) if late_is_a else (b, a)
+            self.pairs_at[pl[late]].append((pi, late, early, late_is_a))
+        self.masked = _masked_factory(kin)
+        # the rollout's chunk: NF floats of every sample's row leave together; LS = the per-lane stride of the staging buffer (a multiple of
+        # 4 floats for the 16-byte reads, and NOT a multiple of 32: the per-lane row writes would all hit one bank)
+        self.NF = ROLLOUT_CHUNK_FLOATS
+        self.LS = self.NF if self.NF % 32 else self.NF + 4
+        self.lds_per_lane = max(self.LS, D)
+        # the reverse mode's chunk of adjoints, same geometry (36 -> 64 floats measured 43.7 -> 42.8, 21.3 -> 19.9, 66.7 -> 47.5 us)
+        self.BNF = ROLLOUT_CHUNK_FLOATS
+        self.BLS = self.BNF if self.BNF % 32 else self.BNF + 4
+        # the joints, the sign each gradient takes (0: the joint cannot move anything), and where the walk leaves each one's subtree
+        self.joint_links = [i for i in range(1, L) if int(kin.joint_type[i]) != JOINT_FIXED]
+        self.sign = {i: 1.0 if int(kin.joint_type[i]) == JOINT_PRISMATIC else float(kin.rot_sign[i]) for i in self.joint_links}
+        self.ends_at = {p: [j for j in self.joint_links if int(kin.subtree_end[pos_of[j]]) == p + 1 and self.sign[j] != 0.0]
+                        for p in range(L)}
+        self.ancestors: Dict[int, List[int]] = {}
+        for i in range(L):
+            chain, a = [], i
+            while a > 0:
+                if int(kin.joint_type[a]) != JOINT_FIXED:
+                    chain.append(a)
+                a = int(kin.parent[a])
+            self.ancestors[i] = chain                   # links whose joints move link i (incl. i itself)
+        # the registry entry: a link-mode unit is an ordinary link unit to the dispatcher
+        self.n_points = 0 if link_mode else P
+
+    @property
+    def points_hash(self) -> int:
+        return 0 if self.link_mode else points_hash(self.pt.point_link, self.pt.point_offset)
+
+    @property
+    def kernels(self) -> List[str]:
+        """what a code-object (hipRTC) build of this unit must contain: the name expressions of its kernels (jit.py,
+        trk_spec_register_module)"""
+        return [f"spec_{self.ident}::k_rollout_{b}<{f}, float>" for b in ("bi", "bg") for f in ("true", "false")] + \
+               [f"spec_{self.ident}::k_posbwd_{b}" for b in ("bi", "bg")]
+
+
+class _WrenchWalk:
+    """The reverse mode both attached-point kernels share, as the walk meets it.  A force g at world point p enters ONE running
+    wrench (pf, pt) = (sum g, sum p x g) about the world origin.  In walk order a joint's subtree is a contiguous range, so its
+    gradient is the prefix-sum form of the transposed geometric Jacobian: the functional z . (Pt - t x Pf) (prismatic:
+    (R_parent axis) . Pf) is sampled when the walk enters the joint's link, and the joint takes the difference when its subtree's
+    range ends.  The constructor emits nothing; `declare` writes the wrench's declaration where the kernel wants it."""
+
+    def __init__(self, u: _PointsUnit, E: Emitter, base_identity: bool):
+        self.u, self.E = u, E
+        self.R, self.t, self.passv = _root_pose(base_identity)
+        self.PF = [S(1.0, f"pf{k}") for k in range(3)]
+        self.PT = [S(1.0, f"pt{k}") for k in range(3)]
+        self.snap_c: Dict[int, S] = {}
+        self.pos: Dict[int, List[S]] = {}                # column -> world position, once the walk has produced it
+
+    def declare(self) -> None:
+        self.E.raw("    float pf0 = 0.0f, pf1 = 0.0f, pf2 = 0.0f, pt0 = 0.0f, pt1 = 0.0f, pt2 = 0.0f;   // running wrench of the links visited so far")
+
+    def slide_dir(self, i: int) -> List[S]:
+        """world direction of prismatic joint i"""
+        kin, par = self.u.kin, int(self.u.kin.parent[i])
+        return [self.E.lincomb([(self.R[par][r][k], S(float(kin.axis[i][k]))) for k in range(3)]) for r in range(3)]
+
+    def spin_axis(self, i: int) -> List[S]:
+        """world axis of revolute joint i"""
+        ax = int(self.u.kin.rot_axis[i])
+        return [self.R[i][r][ax] for r in range(3)]
+
+    def functional(self, i: int) -> S:
+        """z_i . (Pt - t_i x Pf) with the CURRENT running wrench (prismatic: (R_parent axis) . Pf)"""
+        E = self.E
+        if int(self.u.kin.joint_type[i]) == JOINT_PRISMATIC:
+            return E.dot(self.slide_dir(i), self.PF)
+        z = self.spin_axis(i)
+        cr = E.cross(self.t[i], self.PF)
+        return E.dot(z, [E.lincomb([(self.PT[k], ONE), (cr[k], S(-1.0))]) for k in range(3)])
+
+    def enter(self, i: int) -> None:
+        """the walk steps onto link i: its pose, and its joint's sample of the running wrench BEFORE the subtree -- a COPY (pf / pt are
+        mutable; the expression may be a bare alias)"""
+        u, E = self.u, self.E
+        _emit_fk_link(E, u.kin, i, self.R, self.t, self.passv, u.snap)
+        if int(u.kin.joint_type[i]) != JOINT_FIXED:
+            self.snap_c[i] = S(1.0, E.tmp(E.expr(self.functional(i))))
+
+    def difference(self, j: int) -> S:
+        """joint j's subtree is complete: its share of the running wrench"""
+        return self.E.lincomb([(self.functional(j), ONE), (self.snap_c[j], S(-1.0))])
+
+    def colpos(self, i: int, c: int) -> List[S]:
+        """world position of column c, a point of link i: R_i off + t_i (a zero offset is the link origin itself)"""
+        E = self.E
+        off = [S(snap_const(self.u.po[c][k], 0.0)) for k in range(3)]
+        self.pos[c] = self.t[i] if all(o.is_zero for o in off) else \
+            [E.named(E.lincomb([(self.R[i][r][k], off[k]) for k in range(3)], self.t[i][r])) for r in range(3)]
+        return self.pos[c]
+
+    def push(self, p: List[S], g: List[str]) -> None:
+        """force g (C expressions) at world point p on the link the walk stands on -> running wrench"""
+        px, py, pz = (self.E.expr(v) for v in p)
+        self.E.raw(f"    pf0 += {g[0]}; pf1 += {g[1]}; pf2 += {g[2]};")
+        self.E.raw(f"    pt0 += {py} * {g[2]} - {pz} * {g[1]}; pt1 += {pz} * {g[0]} - {px} * {g[2]}; pt2 += {px} * {g[1]} - {py} * {g[0]};")
+
+
+def _points_posbwd_kernel(u: _PointsUnit, base_identity: bool, w_expr: str = "W") -> List[str]:
+    """k_posbwd_bi / k_posbwd_bg: explicit reverse mode of point (or link) positions, d sum(gpos . pos) / dq, for columns in walk order
+    (trk_fk_points_backward).  FK again, the adjoint rows arrive through a chunk buffer in column order (spec_load_chunk:
+    ROLLOUT_CHUNK_FLOATS floats of every sample's row per trip), each adjoint g at point p joins the running wrench (_WrenchWalk).
+    17 KB of LDS per wavefront whatever the row length and no per-sample adjoint array in registers: also what the many-link robots'
+    trk_fk_positions_backward runs (their whole-row tile was 92 KB per workgroup = one wavefront per SIMD: UR10 + Allegro 34.1 us =
+    0.51 of the roofline).  w_expr: the row length as the text names it (the link units, which have no W, pass the number)."""
+    kin, L, D, W, BNF, BLS = u.kin, u.L, u.D, u.W, u.BNF, u.BLS
+    E = Emitter()
+    _kernel_head(E, "k_posbwd_bi" if base_identity else "k_posbwd_bg", 2, max(BLS, D))
+    E.raw("    const float* gpos = static_cast<const float*>(A.link_pos);")
+    E.raw("    float q[D];")
+    E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
+    E.raw(f"    const float* row = lds + lane * {BLS};")
+    w = _WrenchWalk(u, E, base_identity)
+    _emit_angles(E, kin)
+    w.declare()
+    gq_expr: Dict[int, S] = {}
+    chunk_start = -1
+    for p in range(L):
+        i = int(kin.order[p])
+        if p > 0:
+            w.enter(i)
+        for c in u.cols_of_link[i]:
+            # the three floats of a column may straddle two chunks: fetch component by component
+            comp = []
+            for f in range(3 * c, 3 * c + 3):
+                cs = (f // BNF) * BNF
+                if cs != chunk_start:
+                    E.raw(f"    spec_load_chunk<{w_expr}, {min(BNF, W - cs)}, {BLS}, {u.V}>(gpos, base, {cs}, rows, lane, lds);")
+                    chunk_start = cs
+                comp.append(E.tmp(f"row[{f - cs}]"))
+            if p > 0:                               # (the root does not move with q)
+                w.push(w.colpos(i, c), comp)
+        for j in u.ends_at[p]:
+            g, d = w.difference(j), int(kin.dof_idx[j])
+            gq_expr[d] = u.masked(E, j, d, S(g.c * u.sign[j], g.n))
+    E.raw(f"    const float gv[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
+    E.raw("    spec_store_gq<D>(static_cast<float*>(A.gq), base, rows, lane, lds, gv);")
+    E.raw("}")
+    return E.lines
+
+
 def _chunked_posbwd_lines(kin: KinModel, point_link, point_offset, snap: float = SNAP, w_expr: Optional[str] = None) -> List[str]:
-    """k_posbwd_bi / k_posbwd_bg: explicit reverse mode of point (or link) positions, d sum(gpos . pos) / dq, for columns in walk order.
-    FK again, the adjoint rows arrive through a chunk buffer in column order (spec_load_chunk: ROLLOUT_CHUNK_FLOATS floats of every
-    sample's row per trip), each adjoint g at point p joins the running wrench (g, p x g); a joint's gradient is the prefix-sum form
-    s z . ((Pt1 - Pt0) - t x (Pf1 - Pf0)) over its subtree's range of the walk.  17 KB of LDS per wavefront whatever the row length and
-    no per-sample adjoint array in registers: also what the many-link robots' trk_fk_positions_backward runs (their whole-row tile was
-    92 KB per workgroup = one wavefront per SIMD: UR10 + Allegro 34.1 us = 0.51 of the roofline)."""
-    L, D, P = kin.n_links, kin.n_dofs, len(point_link)
-    W = 3 * P
-    Wx = w_expr or "W"
-    V = 4 if W % 4 == 0 else (2 if W % 2 == 0 else 1)
-    pl = [int(v) for v in point_link]
-    po = np.asarray(point_offset, np.float32).reshape(-1, 3)
-    pos_of = {int(kin.order[p]): p for p in range(L)}
-    cols_of_link: Dict[int, List[int]] = {i: [c for c in range(P) if pl[c] == i] for i in range(L)}
-    masked = _masked_factory(kin)
-    BNF = ROLLOUT_CHUNK_FLOATS      # 36 -> 64 measured 43.7 -> 42.8, 21.3 -> 19.9, 66.7 -> 47.5 us
-    BLS = BNF if BNF % 32 else BNF + 4
-    out: List[str] = []
-    # ---- explicit reverse mode of the point positions (trk_fk_points_backward): FK again, the adjoint rows arrive through
-    # the chunk buffer in column order, each adjoint g at point p joins the running wrench (g, p x g); prefix-sum gradients
-    for base_identity in (True, False):
-        E = Emitter()
-        kname = "k_posbwd_bi" if base_identity else "k_posbwd_bg"
-        E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, 2) {kname}(SpecArgs A) {{")
-        E.raw(f"    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * {max(BLS, D)}];")
-        E.raw("    const int lane = __builtin_amdgcn_workitem_id_x() & (TRK_WAVE - 1);")
-        E.raw("    const int wave = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_workitem_id_x() / TRK_WAVE);")
-        E.raw(f"    float* lds = lds_all + wave * (TRK_WAVE * {max(BLS, D)});")
-        E.raw("    const int64_t wblock = (int64_t)__builtin_amdgcn_workgroup_id_x() * SPEC_WAVES + wave;")
-        E.raw("    const int64_t base = wblock * TRK_WAVE;")
-        E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
-        E.raw("    const float* gpos = static_cast<const float*>(A.link_pos);")
-        E.raw("    float q[D];")
-        E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
-        E.raw(f"    const float* row = lds + lane * {BLS};")
-        R = {}; t = {}; passv = {}
-        if base_identity:
-            R[0] = [[ONE if r == c else ZERO for c in range(3)] for r in range(3)]
-            t[0] = [ZERO, ZERO, ZERO]
+    """k_posbwd_bi and k_posbwd_bg of a column set on its own: what the many-link link units take for their position reverse mode.
+    The columns must follow the walk order of their links (ValueError otherwise, as in generate_points_rollout_source): the link
+    units call it only when their file order is the walk (_LinkUnit.posbwd_chunked)."""
+    u = _PointsUnit(kin, PointsTemplate(point_link=point_link, point_offset=point_offset, obj_cols=[]), "", snap)
+    return [line for base_identity in (True, False) for line in _points_posbwd_kernel(u, base_identity, w_expr or "W") + [""]]
+
+
+def _points_stage_positions(u: _PointsUnit, E: Emitter, w: _WrenchWalk, i: int, chunk_start: int) -> int:
+    """positions of link i's columns, staged for output; a chunk leaves as soon as it is full.  Returns the first float of the chunk
+    being filled."""
+    for c in u.cols_of_link[i]:
+        pc = w.colpos(i, c)
+        for k in range(3):
+            f = 3 * c + k
+            E.raw(f"    row[{f - chunk_start}] = {E.expr(pc[k])};")
+            if f + 1 - chunk_start == u.NF or f + 1 == u.W:
+                nf = f + 1 - chunk_start
+                # vector width V of this chunk's stores: the row's (wider stores at 4- / 8-byte alignment for the odd row lengths
+                # are legal on this chip and measured the same time)
+                E.raw(f"    if (pos_out) spec_flush_chunk<W, {nf}, {u.LS}, {u.V}, IO, false>(pos_out, base, {chunk_start}, rows, lane, lds);")
+                chunk_start = f + 1
+    return chunk_start
+
+
+def _points_obj_groups(u: _PointsUnit, E: Emitter, w: _WrenchWalk, i: int) -> None:
+    """objects / workspace box on link i's collision columns, OBJ_GROUP at a time"""
+    ocols = [c for c in u.cols_of_link[i] if c in u.obj_rank]
+    for g0 in range(0, len(ocols), OBJ_GROUP):
+        grp = ocols[g0:g0 + OBJ_GROUP]
+        n = len(grp)
+        mb = u.obj_rank[grp[0]]
+        assert [u.obj_rank[c] for c in grp] == list(range(mb, mb + n))
+        E.raw("    {")
+        for k, nm in enumerate("xyz"):
+            E.raw(f"        const float p{nm}[{n}] = {{{', '.join(E.expr(w.pos[c][k]) for c in grp)}}};")
+        E.raw(f"        float gx[{n}], gy[{n}], gz[{n}];")
+        E.raw("#pragma unroll")
+        E.raw(f"        for (int l = 0; l < {n}; ++l) {{ gx[l] = 0.0f; gy[l] = 0.0f; gz[l] = 0.0f; }}")
+        E.raw(f"        if (A.w.w_obj != 0.0f) cost += spec_objects_cost<{n}, NoTick, FAST>(A.C, A.w.w_obj, px, py, pz, gx, gy, gz, notick, lds_sph, {mb});")
+        E.raw(f"        if (A.w.w_ws != 0.0f && A.C.has_ws) cost += spec_ws_cost<{n}>(A.C, A.w.w_ws, px, py, pz, gx, gy, gz, {mb});")
+        E.raw("#pragma unroll")
+        E.raw(f"        for (int l = 0; l < {n}; ++l) {{")
+        E.raw("            pf0 += gx[l]; pf1 += gy[l]; pf2 += gz[l];")
+        E.raw("            pt0 += py[l] * gz[l] - pz[l] * gy[l]; pt1 += pz[l] * gx[l] - px[l] * gz[l]; pt2 += px[l] * gy[l] - py[l] * gx[l];")
+        E.raw("        }")
+        E.raw("    }")
+
+
+def _points_late_force(u: _PointsUnit, E: Emitter, w: _WrenchWalk, link: int, p: List[S], g: List[str]) -> None:
+    """force g at world point p on an EARLIER link (the far side of a self-collision pair): instead of entering the running sums it goes
+    straight onto the joints that move that link, s z_j . ((p - t_j) x g)"""
+    gS = [S(1.0, x) for x in g]
+    for j in u.ancestors[link]:
+        if u.sign[j] == 0.0:
+            continue
+        if int(u.kin.joint_type[j]) == JOINT_PRISMATIC:
+            val = E.dot(w.slide_dir(j), gS)
         else:
-            R[0] = [[S(1.0, f"A.base_R[{3 * r + c}]") for c in range(3)] for r in range(3)]
-            t[0] = [S(1.0, f"A.base_t[{r}]") for r in range(3)]
-        _emit_angles(E, kin)
-        E.raw("    float pf0 = 0.0f, pf1 = 0.0f, pf2 = 0.0f, pt0 = 0.0f, pt1 = 0.0f, pt2 = 0.0f;")
-        PF = [S(1.0, f"pf{k}") for k in range(3)]
-        PT = [S(1.0, f"pt{k}") for k in range(3)]
-        snap_c = {}; gq_expr = {}
-    
-        def functional(i: int) -> S:
-            jt = int(kin.joint_type[i])
-            if jt == JOINT_PRISMATIC:
-                par = int(kin.parent[i])
-                dirw = [E.lincomb([(R[par][r][k], S(float(kin.axis[i][k]))) for k in range(3)]) for r in range(3)]
-                return E.dot(dirw, PF)
-            ax = int(kin.rot_axis[i])
-            z = [R[i][r][ax] for r in range(3)]
-            cr = E.cross(t[i], PF)
-            return E.dot(z, [E.lincomb([(PT[k], ONE), (cr[k], S(-1.0))]) for k in range(3)])
-    
-        chunk_start = -1
-        for p in range(L):
-            i = int(kin.order[p])
-            if p > 0:
-                _emit_fk_link(E, kin, i, R, t, passv, snap)
-                if int(kin.joint_type[i]) != JOINT_FIXED:
-                    snap_c[i] = S(1.0, E.tmp(E.expr(functional(i))))
-            for c in cols_of_link[i]:
-                f0 = 3 * c
-                # the three floats of a column may straddle two chunks: fetch component by component
-                comp = []
-                for k in range(3):
-                    f = f0 + k
-                    cs = (f // BNF) * BNF
-                    if cs != chunk_start:
-                        nf = min(BNF, W - cs)
-                        E.raw(f"    spec_load_chunk<{Wx}, {nf}, {BLS}, {V}>(gpos, base, {cs}, rows, lane, lds);")
-                        chunk_start = cs
-                    comp.append(E.tmp(f"row[{f - cs}]"))
-                if p == 0:
-                    continue                        # the root does not move with q
-                off = [S(snap_const(po[c][k], 0.0)) for k in range(3)]
-                pc = t[i] if all(o.is_zero for o in off) else \
-                    [E.named(E.lincomb([(R[i][r][k], off[k]) for k in range(3)], t[i][r])) for r in range(3)]
-                px, py, pz = (E.expr(v) for v in pc)
-                E.raw(f"    pf0 += {comp[0]}; pf1 += {comp[1]}; pf2 += {comp[2]};")
-                E.raw(f"    pt0 += {py} * {comp[2]} - {pz} * {comp[1]}; pt1 += {pz} * {comp[0]} - {px} * {comp[2]}; "
-                      f"pt2 += {px} * {comp[1]} - {py} * {comp[0]};")
-            for j in [j for j in range(1, L) if int(kin.joint_type[j]) != JOINT_FIXED]:
-                if int(kin.subtree_end[pos_of[j]]) == p + 1:
-                    d = int(kin.dof_idx[j]); jt = int(kin.joint_type[j])
-                    sg = 1.0 if jt == JOINT_PRISMATIC else float(kin.rot_sign[j])
-                    if sg == 0.0:
-                        gq_expr[d] = ZERO
-                    else:
-                        g = E.lincomb([(functional(j), ONE), (snap_c[j], S(-1.0))])
-                        gq_expr[d] = masked(E, j, d, S(g.c * sg, g.n))
-        E.raw(f"    const float gv[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
-        E.raw("    spec_store_gq<D>(static_cast<float*>(A.gq), base, rows, lane, lds, gv);")
-        E.raw("}")
-        out.extend(E.lines)
-        out.append("")
-    return out
+            arm = [E.lincomb([(p[k], ONE), (w.t[j][k], S(-1.0))]) for k in range(3)]
+            val = E.dot(w.spin_axis(j), E.cross(arm, gS))
+        if not val.is_zero:
+            E.raw(f"    late{int(u.kin.dof_idx[j])} += {E.expr(val)};")
 
 
-def generate_points_rollout_source(kin: KinModel, pt: PointsTemplate, ident: str, snap: float = SNAP,
-                                   link_mode: bool = False, meta: Optional[dict] = None) -> str:
-    """Fused FK + objectives + gradient with the collision fields on attached points.  Differences to the link kernel:
+def _points_self_pairs(u: _PointsUnit, E: Emitter, w: _WrenchWalk, i: int) -> None:
+    """self-collision pairs whose later column belongs to link i.  Round 5: the force on a point is ACCUMULATED over its pairs (a pair
+    hands back s = w / ||d|| and d = p_late - p_early: one FMA per component and side) and enters the running wrench ONCE per point (9
+    instructions) instead of once per pair and side.  The grasped-box model has 66 pairs on 14 + 4 points: 2061 of the kernel's 5532
+    static vector instructions were this phase (tools/isa_valu_count.sh).  (First built as S = sum s, V = sum s p_e, force = V - p S: a
+    few instructions fewer, but it cancels when the points are close and far from the origin -- spec_self_pair_sd's comment.)"""
+    if not u.pairs_at[i]:
+        return
+    E.raw("    if (A.w.w_self != 0.0f) {")
+    E.raw("        const bool sclamp = (A.C.clamp_fields & TRK_FIELD_SELF) != 0;")
+    earlies = sorted({early for _, _, early, _ in u.pairs_at[i]})
+    lates = sorted({late for _, late, _, _ in u.pairs_at[i]})
+    for e in earlies:             # all pairs of one earlier column push on the same point
+        E.raw(f"        float ge{e}_0 = 0.0f, ge{e}_1 = 0.0f, ge{e}_2 = 0.0f;")
+    for c in lates:
+        E.raw("        {")
+        E.raw("        float gl0 = 0.0f, gl1 = 0.0f, gl2 = 0.0f;")
+        pc = [E.expr(w.pos[c][k]) for k in range(3)]
+        for pi, late, early, _late_is_a in u.pairs_at[i]:
+            if late != c:
+                continue
+            pe = [E.expr(w.pos[early][k]) for k in range(3)]
+            E.raw(f"        {{ float d0_, d1_, d2_; const float s_ = spec_self_pair_sd(A.w.w_self, cptr(A.C.self_margin)[{pi}], {', '.join(pc)}, {', '.join(pe)}, sclamp, cost, d0_, d1_, d2_);")
+            E.raw(f"          gl0 = fmaf(-s_, d0_, gl0); gl1 = fmaf(-s_, d1_, gl1); gl2 = fmaf(-s_, d2_, gl2); "
+                  f"ge{early}_0 = fmaf(s_, d0_, ge{early}_0); ge{early}_1 = fmaf(s_, d1_, ge{early}_1); ge{early}_2 = fmaf(s_, d2_, ge{early}_2); }}")
+        w.push(w.pos[c], ["gl0", "gl1", "gl2"])
+        E.raw("        }")
+    for e in earlies:
+        g = [f"ge{e}_0", f"ge{e}_1", f"ge{e}_2"]
+        if u.pl[e] == i:
+            w.push(w.pos[e], g)
+        else:
+            _points_late_force(u, E, w, u.pl[e], w.pos[e], g)
+    E.raw("    }")
 
-    * each link's points are produced, scored against the scene and folded into ONE running wrench (f, p x f about the
-      world origin) as soon as the link's pose exists -- no position or adjoint tile in LDS, no per-link accumulators;
-    * reverse mode is the prefix-sum form of the transposed geometric Jacobian (the table-driven kernels' idea, in
-      registers): in walk order a joint's subtree is a contiguous range, so its gradient is
-      s z_j . ((Pt1 - Pt0) - t_j x (Pf1 - Pf0)) with the running wrench sampled at the range's start and end;
-      a force that lands on an EARLIER link (the far side of a self-collision pair) is applied directly to that link's
-      ancestor joints, s z_j . ((p - t_j) x f), instead of entering the running sums;
+
+def _points_ee_term(u: _PointsUnit, E: Emitter, w: _WrenchWalk, i: int) -> None:
+    """end-effector tracking when the walk stands on a tracked link"""
+    if i < 0 or i not in (u.pt.ee_link, u.pt.ee2_link):
+        return
+    tgt_name = "A.C.ee_target" if i == u.pt.ee_link else "A.C.ee2_target"
+    E.raw("    if (A.w.w_ee != 0.0f) {")
+    E.raw(f"        const float eR[9] = {{{', '.join(E.expr(w.R[i][r][c]) for r in range(3) for c in range(3))}}};")
+    E.raw(f"        const float et[3] = {{{', '.join(E.expr(w.t[i][k]) for k in range(3))}}};")
+    E.raw("        float gR[9], gt[3];")
+    E.raw(f"        const float ce = ee_cost_eval(eR, et, {tgt_name}, A.C.ee_w_pos, A.C.ee_w_rot, A.C.ee_square, gR, gt);")
+    E.raw("        cost = fmaf(A.w.w_ee, ce, cost);")
+    E.raw("        gt[0] *= A.w.w_ee; gt[1] *= A.w.w_ee; gt[2] *= A.w.w_ee;")
+    E.raw("        pf0 += gt[0]; pf1 += gt[1]; pf2 += gt[2];")
+    # torque = t x gt + axial(Rbar R^T), Rbar = w gR
+    E.raw("        float M[9];")
+    E.raw("#pragma unroll")
+    E.raw("        for (int a = 0; a < 3; ++a)")
+    E.raw("#pragma unroll")
+    E.raw("            for (int b = 0; b < 3; ++b) M[3 * a + b] = A.w.w_ee * (gR[3 * a] * eR[3 * b] + gR[3 * a + 1] * eR[3 * b + 1] + gR[3 * a + 2] * eR[3 * b + 2]);")
+    E.raw("        pt0 += et[1] * gt[2] - et[2] * gt[1] + (M[7] - M[5]);")
+    E.raw("        pt1 += et[2] * gt[0] - et[0] * gt[2] + (M[2] - M[6]);")
+    E.raw("        pt2 += et[0] * gt[1] - et[1] * gt[0] + (M[3] - M[1]);")
+    E.raw("    }")
+
+
+def _points_finish_joints(u: _PointsUnit, E: Emitter, w: _WrenchWalk, p: int, gfin: Dict[int, S]) -> None:
+    """joints whose subtree ends with walk position p: their share of the running wrench is final.  `late` forces may still arrive (a
+    pair whose later column sits in ANOTHER branch of a tree), so they are added at the very end."""
+    for j in u.ends_at[p]:
+        gfin[j] = S(1.0, E.tmp(E.expr(E.named(w.difference(j)))))
+
+
+def _points_rollout_kernel(u: _PointsUnit, base_identity: bool) -> List[str]:
+    """k_rollout_bi / k_rollout_bg: fused FK + objectives + gradient with the collision fields on attached points.  Differences to the
+    link kernel:
+
+    * each link's points are produced, scored against the scene and folded into ONE running wrench (_WrenchWalk) as soon as the
+      link's pose exists -- no position or adjoint tile in LDS, no per-link accumulators;
+    * a force that lands on an EARLIER link (the far side of a self-collision pair) is applied directly to that link's ancestor
+      joints (_points_late_force) instead of entering the running sums;
     * positions leave through one 64-float chunk buffer per wavefront (spec_flush_chunk; ROLLOUT_CHUNK_FLOATS).
 
     The kernel needs the full 256-VGPR budget (2 wavefronts per SIMD).  A two-sweep variant for serial chains (root->tip
     for the positions, then tip->root stepping the pose back through the inverse joint transforms with a single suffix
     wrench; 168 VGPRs, 3 wavefronts per SIMD) was built and measured: 79 vs 76 us for the 45-sphere Panda -- the kernel
     is bound by its ~6900 VALU instructions per wavefront (SQ_INSTS_VALU), so the recomputation ate what the occupancy
-    gave, and it was dropped.
+    gave, and it was dropped."""
+    kin, D = u.kin, u.D
+    E = Emitter()
+    E.raw("template <bool FAST, class IO>   // FAST: scene_is_fast(A.C) -- only the few-equal-spheres scene path is compiled in")
+    _kernel_head(E, "k_rollout_bi" if base_identity else "k_rollout_bg", 2, u.lds_per_lane, spheres=True)
+    E.raw("    IO* pos_out = static_cast<IO*>(A.link_pos);")
+    E.raw("    float q[D];")
+    E.raw("    spec_load_q<D>(static_cast<const IO*>(A.q), base, rows, lane, lds, q);")
+    E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
+    E.raw(f"    float* row = lds + lane * {u.LS};          // this lane's slice of the chunk buffer")
+    E.raw("    NoTick notick;")
+    w = _WrenchWalk(u, E, base_identity)
+    _emit_angles(E, kin)
+    E.raw("    float cost = 0.0f;")
+    w.declare()
+    for i in u.joint_links:
+        E.raw(f"    float late{int(kin.dof_idx[i])} = 0.0f;")
+    gfin: Dict[int, S] = {}
+    chunk_start = 0                       # first float of the chunk being filled
+    for p in range(u.L):
+        i = int(kin.order[p])
+        if p > 0:
+            w.enter(i)
+        chunk_start = _points_stage_positions(u, E, w, i, chunk_start)
+        _points_obj_groups(u, E, w, i)
+        _points_self_pairs(u, E, w, i)
+        _points_ee_term(u, E, w, i)
+        _points_finish_joints(u, E, w, p, gfin)
+    assert chunk_start == u.W
+    gq_expr: Dict[int, S] = {}
+    for i in [i for i in u.joint_links if i in gfin]:
+        d = int(kin.dof_idx[i])
+        g = E.lincomb([(gfin[i], ONE), (S(1.0, f"late{d}"), ONE)])
+        gq_expr[d] = u.masked(E, i, d, S(g.c * u.sign[i], g.n))
+    E.raw("    if (!A.gq) return;                       // positions only (trk_fk_points): weights are zero, nothing else to write")
+    E.raw("    if (lane < rows) store_wt_f1(A.cost + base + lane, cost);")
+    E.raw("    if (A.cost_sum) {")
+    E.raw("        const float tot = spec_wave_sum(lane < rows ? cost : 0.0f);")
+    E.raw("        if (lane == 0 && rows > 0) store_wt_f1(A.cost_sum + wblock, tot);")
+    E.raw("    }")
+    E.raw(f"    const float gv[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
+    E.raw("    spec_store_gq<D>(static_cast<IO*>(A.gq), base, rows, lane, lds, gv);")
+    E.raw("}")
+    return E.lines
+
+
+def generate_points_rollout_source(kin: KinModel, pt: PointsTemplate, ident: str, snap: float = SNAP,
+                                   link_mode: bool = False, meta: Optional[dict] = None) -> str:
+    """The unit of an attached-point model: the fused rollout (_points_rollout_kernel) and the reverse mode of the point positions
+    (_points_posbwd_kernel), planned once by _PointsUnit.
 
     link_mode: the columns are exactly the links in file order with zero offsets and the unit registers as an ordinary
     link kernel (n_points = 0).  For TREES this pipeline beats generate_rollout_source: a finger's or an arm's joints are
-    finished (and their axes / origins die) when their subtree ends, instead of living until a reverse pass."""
-    if link_mode:
-        assert [int(v) for v in pt.point_link] == list(range(kin.n_links)) and not np.asarray(pt.point_offset).any()
-    L, D, P = kin.n_links, kin.n_dofs, len(pt.point_link)
-    W = 3 * P
-    V = 4 if W % 4 == 0 else (2 if W % 2 == 0 else 1)
-    pl = [int(v) for v in pt.point_link]
-    po = np.asarray(pt.point_offset, np.float32).reshape(-1, 3)
-    pos_of = {int(kin.order[p]): p for p in range(L)}
-    walk_rank = [pos_of[i] for i in pl]
-    if any(walk_rank[k] > walk_rank[k + 1] for k in range(P - 1)):
-        raise ValueError("generate_points_rollout_source: columns must follow the walk order of their links")
-    cols_of_link: Dict[int, List[int]] = {i: [c for c in range(P) if pl[c] == i] for i in range(L)}
-    obj_rank = {c: k for k, c in enumerate(pt.obj_cols)}
-    if sorted(pt.obj_cols) != list(pt.obj_cols):
-        raise ValueError("generate_points_rollout_source: obj_cols must be increasing (margins are read in groups)")
-    # a pair is scored when the walk reaches its later column; pairs_at[link] = [(pair index, late col, early col, late_is_a)]
-    pairs_at: Dict[int, List[Tuple[int, int, int, bool]]] = {i: [] for i in range(L)}
-    for pi, (a, b) in enumerate(pt.self_pairs):
-        late_is_a = (walk_rank[a], a) >= (walk_rank[b], b)
-        late, early = (a, b) if late_is_a else (b, a)
-        pairs_at[pl[late]].append((pi, late, early, late_is_a))
-    masked = _masked_factory(kin)
-    # the rollout's chunk: NF floats of every sample's row leave together; LS = the per-lane stride of the staging buffer (a multiple of
-    # 4 floats for the 16-byte reads, and NOT a multiple of 32: the per-lane row writes would all hit one bank)
-    NF = ROLLOUT_CHUNK_FLOATS
-    LS = NF if NF % 32 else NF + 4
-    lds_per_lane = max(LS, D)
-    joint_links = [i for i in range(1, L) if int(kin.joint_type[i]) != JOINT_FIXED]
-    ancestors: Dict[int, List[int]] = {}
-    for i in range(L):
-        chain, a = [], i
-        while a > 0:
-            if int(kin.joint_type[a]) != JOINT_FIXED:
-                chain.append(a)
-            a = int(kin.parent[a])
-        ancestors[i] = chain                   # links whose joints move link i (incl. i itself)
+    finished (and their axes / origins die) when their subtree ends, instead of living until a reverse pass.
 
-    out: List[str] = []
-    out.append(f"// GENERATED by torch_robotics_amd/codegen.py for model '{kin.name}' ({L} links, {D} DOF) with {P} attached points -- do not edit.")
+    meta (optional): receives the kernels' name expressions, as in generate_rollout_source (not in link mode)."""
+    u = _PointsUnit(kin, pt, ident, snap, link_mode)
+    out: List[str] = [f"// GENERATED by torch_robotics_amd/codegen.py for model '{kin.name}' ({u.L} links, {u.D} DOF) with {u.P} attached points -- do not edit."]
     out.append('#include "trk_spec_common.h"')
     out.append(f"namespace spec_{ident} {{")
-    out.append(f"constexpr int L = {L}, D = {D}, P = {P}, W = {W};")
-    for base_identity in (True, False):
-        E = Emitter()
-        kname = "k_rollout_bi" if base_identity else "k_rollout_bg"
-        E.raw("template <bool FAST, class IO>   // FAST: scene_is_fast(A.C) -- only the few-equal-spheres scene path is compiled in")
-        E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, 2) {kname}(SpecArgs A) {{")
-        E.raw(f"    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * {lds_per_lane} + SPEC_WAVES * TRK_LDS_SPHERES * 4];")
-        E.raw("    const int lane = __builtin_amdgcn_workitem_id_x() & (TRK_WAVE - 1);")
-        E.raw("    const int wave = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_workitem_id_x() / TRK_WAVE);   // wave-uniform -> SGPR")
-        E.raw(f"    float* lds = lds_all + wave * (TRK_WAVE * {lds_per_lane});")
-        E.raw(f"    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * {lds_per_lane}) + wave * TRK_LDS_SPHERES;")
-        E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);   // waited for together with the rows below")
-        E.raw("    const int64_t wblock = (int64_t)__builtin_amdgcn_workgroup_id_x() * SPEC_WAVES + wave;")
-        E.raw("    const int64_t base = wblock * TRK_WAVE;")
-        E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
-        E.raw("    IO* pos_out = static_cast<IO*>(A.link_pos);")
-        E.raw("    float q[D];")
-        E.raw("    spec_load_q<D>(static_cast<const IO*>(A.q), base, rows, lane, lds, q);")
-        E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
-        E.raw(f"    float* row = lds + lane * {LS};          // this lane's slice of the chunk buffer")
-        E.raw("    NoTick notick;")
-        R: Dict[int, List[List[S]]] = {}
-        t: Dict[int, List[S]] = {}
-        passv: Dict[int, S] = {}
-        if base_identity:
-            R[0] = [[ONE if r == c else ZERO for c in range(3)] for r in range(3)]
-            t[0] = [ZERO, ZERO, ZERO]
-        else:
-            R[0] = [[S(1.0, f"A.base_R[{3 * r + c}]") for c in range(3)] for r in range(3)]
-            t[0] = [S(1.0, f"A.base_t[{r}]") for r in range(3)]
-        _emit_angles(E, kin)
-        E.raw("    float cost = 0.0f;")
-        E.raw("    float pf0 = 0.0f, pf1 = 0.0f, pf2 = 0.0f, pt0 = 0.0f, pt1 = 0.0f, pt2 = 0.0f;   // running wrench of the links visited so far")
-        for i in joint_links:
-            E.raw(f"    float late{int(kin.dof_idx[i])} = 0.0f;")
-        PF = [S(1.0, f"pf{k}") for k in range(3)]
-        PT = [S(1.0, f"pt{k}") for k in range(3)]
-        colpos: Dict[int, List[S]] = {}
-        snap_c: Dict[int, S] = {}
-        gq_expr: Dict[int, S] = {}
-        chunk_start = 0                       # first float of the chunk being filled
-
-        def joint_functional(i: int) -> S:
-            """z_i . (Pt - t_i x Pf) with the CURRENT running wrench (prismatic: (R_parent axis) . Pf)"""
-            jt = int(kin.joint_type[i])
-            if jt == JOINT_PRISMATIC:
-                par = int(kin.parent[i])
-                dirw = [E.lincomb([(R[par][r][k], S(float(kin.axis[i][k]))) for k in range(3)]) for r in range(3)]
-                return E.dot(dirw, PF)
-            ax = int(kin.rot_axis[i])
-            z = [R[i][r][ax] for r in range(3)]
-            cr = E.cross(t[i], PF)
-            return E.dot(z, [E.lincomb([(PT[k], ONE), (cr[k], S(-1.0))]) for k in range(3)])
-
-        def in_order(p: List[S], g: List[str]):
-            """force g (C expressions) at world point p on the link the walk stands on -> running wrench"""
-            px, py, pz = (E.expr(v) for v in p)
-            E.raw(f"    pf0 += {g[0]}; pf1 += {g[1]}; pf2 += {g[2]};")
-            E.raw(f"    pt0 += {py} * {g[2]} - {pz} * {g[1]}; pt1 += {pz} * {g[0]} - {px} * {g[2]}; pt2 += {px} * {g[1]} - {py} * {g[0]};")
-
-        def late_force(link: int, p: List[S], g: List[str]):
-            """force g at world point p on an EARLIER link: straight onto the joints that move that link"""
-            gS = [S(1.0, x) for x in g]
-            for j in ancestors[link]:
-                d = int(kin.dof_idx[j]); jt = int(kin.joint_type[j])
-                if jt == JOINT_PRISMATIC:
-                    par = int(kin.parent[j])
-                    dirw = [E.lincomb([(R[par][r][k], S(float(kin.axis[j][k]))) for k in range(3)]) for r in range(3)]
-                    val = E.dot(dirw, gS)
-                else:
-                    if float(kin.rot_sign[j]) == 0.0:
-                        continue
-                    ax = int(kin.rot_axis[j])
-                    z = [R[j][r][ax] for r in range(3)]
-                    arm = [E.lincomb([(p[k], ONE), (t[j][k], S(-1.0))]) for k in range(3)]
-                    val = E.dot(z, E.cross(arm, gS))
-                if not val.is_zero:
-                    E.raw(f"    late{d} += {E.expr(val)};")
-
-        gfin: Dict[int, S] = {}
-
-        def finish_joint(i: int):
-            """subtree of joint i complete: its share of the running wrench is final.  `late` forces may still arrive
-            (a pair whose later column sits in ANOTHER branch of a tree), so they are added at the very end."""
-            d = int(kin.dof_idx[i]); jt = int(kin.joint_type[i])
-            sg = 1.0 if jt == JOINT_PRISMATIC else float(kin.rot_sign[i])
-            if sg == 0.0:
-                return
-            end = joint_functional(i)
-            gfin[i] = S(1.0, E.tmp(E.expr(E.named(E.lincomb([(end, ONE), (snap_c[i], S(-1.0))])))))
-
-        for p in range(L):
-            i = int(kin.order[p])
-            if p > 0:
-                _emit_fk_link(E, kin, i, R, t, passv, snap)
-                if int(kin.joint_type[i]) != JOINT_FIXED:
-                    # running wrench BEFORE this link's subtree: a COPY (pf/pt are mutable; the expression may be a bare alias)
-                    snap_c[i] = S(1.0, E.tmp(E.expr(joint_functional(i))))
-            cols = cols_of_link[i]
-            # ---- positions of this link's columns, staged for output
-            for c in cols:
-                off = [S(snap_const(po[c][k], 0.0)) for k in range(3)]
-                if all(o.is_zero for o in off):
-                    colpos[c] = t[i]
-                else:
-                    colpos[c] = [E.named(E.lincomb([(R[i][r][k], off[k]) for k in range(3)], t[i][r])) for r in range(3)]
-                for k in range(3):
-                    f = 3 * c + k
-                    E.raw(f"    row[{f - chunk_start}] = {E.expr(colpos[c][k])};")
-                    if f + 1 - chunk_start == NF or f + 1 == W:
-                        nf = f + 1 - chunk_start
-                        # vector width V of this chunk's stores: the row's (wider stores at 4- / 8-byte alignment for the odd row lengths
-                        # are legal on this chip and measured the same time)
-                        E.raw(f"    if (pos_out) spec_flush_chunk<W, {nf}, {LS}, {V}, IO, false>(pos_out, base, {chunk_start}, rows, lane, lds);")
-                        chunk_start = f + 1
-            # ---- objects / workspace box on this link's collision columns, a few at a time
-            ocols = [c for c in cols if c in obj_rank]
-            for g0 in range(0, len(ocols), OBJ_GROUP):
-                grp = ocols[g0:g0 + OBJ_GROUP]
-                n = len(grp)
-                mb = obj_rank[grp[0]]
-                assert [obj_rank[c] for c in grp] == list(range(mb, mb + n))
-                E.raw("    {")
-                for k, nm in enumerate("xyz"):
-                    E.raw(f"        const float p{nm}[{n}] = {{{', '.join(E.expr(colpos[c][k]) for c in grp)}}};")
-                E.raw(f"        float gx[{n}], gy[{n}], gz[{n}];")
-                E.raw("#pragma unroll")
-                E.raw(f"        for (int l = 0; l < {n}; ++l) {{ gx[l] = 0.0f; gy[l] = 0.0f; gz[l] = 0.0f; }}")
-                E.raw(f"        if (A.w.w_obj != 0.0f) cost += spec_objects_cost<{n}, NoTick, FAST>(A.C, A.w.w_obj, px, py, pz, gx, gy, gz, notick, lds_sph, {mb});")
-                E.raw(f"        if (A.w.w_ws != 0.0f && A.C.has_ws) cost += spec_ws_cost<{n}>(A.C, A.w.w_ws, px, py, pz, gx, gy, gz, {mb});")
-                E.raw("#pragma unroll")
-                E.raw(f"        for (int l = 0; l < {n}; ++l) {{")
-                E.raw("            pf0 += gx[l]; pf1 += gy[l]; pf2 += gz[l];")
-                E.raw("            pt0 += py[l] * gz[l] - pz[l] * gy[l]; pt1 += pz[l] * gx[l] - px[l] * gz[l]; pt2 += px[l] * gy[l] - py[l] * gx[l];")
-                E.raw("        }")
-                E.raw("    }")
-            # ---- self-collision pairs whose later column belongs to this link.  Round 5: the force on a point is ACCUMULATED over its
-            # pairs (a pair hands back s = w / ||d|| and d = p_late - p_early: one FMA per component and side) and enters the running
-            # wrench ONCE per point (9 instructions) instead of once per pair and side.  The grasped-box model has 66 pairs on 14 + 4
-            # points: 2061 of the kernel's 5532 static vector instructions were this phase (tools/isa_valu_count.sh).  (First built as
-            # S = sum s, V = sum s p_e, force = V - p S: a few instructions fewer, but it cancels when the points are close and far from
-            # the origin -- spec_self_pair_sd's comment.)
-            if pairs_at[i]:
-                E.raw("    if (A.w.w_self != 0.0f) {")
-                E.raw("        const bool sclamp = (A.C.clamp_fields & TRK_FIELD_SELF) != 0;")
-                earlies = sorted({early for _, _, early, _ in pairs_at[i]})
-                lates = sorted({late for _, late, _, _ in pairs_at[i]})
-                for e in earlies:             # all pairs of one earlier column push on the same point
-                    E.raw(f"        float ge{e}_0 = 0.0f, ge{e}_1 = 0.0f, ge{e}_2 = 0.0f;")
-                for c in lates:
-                    E.raw("        {")
-                    E.raw("        float gl0 = 0.0f, gl1 = 0.0f, gl2 = 0.0f;")
-                    pc = [E.expr(colpos[c][k]) for k in range(3)]
-                    for pi, late, early, late_is_a in pairs_at[i]:
-                        if late != c:
-                            continue
-                        pe = [E.expr(colpos[early][k]) for k in range(3)]
-                        E.raw(f"        {{ float d0_, d1_, d2_; const float s_ = spec_self_pair_sd(A.w.w_self, cptr(A.C.self_margin)[{pi}], {', '.join(pc)}, {', '.join(pe)}, sclamp, cost, d0_, d1_, d2_);")
-                        E.raw(f"          gl0 = fmaf(-s_, d0_, gl0); gl1 = fmaf(-s_, d1_, gl1); gl2 = fmaf(-s_, d2_, gl2); "
-                              f"ge{early}_0 = fmaf(s_, d0_, ge{early}_0); ge{early}_1 = fmaf(s_, d1_, ge{early}_1); ge{early}_2 = fmaf(s_, d2_, ge{early}_2); }}")
-                    in_order(colpos[c], ["gl0", "gl1", "gl2"])
-                    E.raw("        }")
-                for e in earlies:
-                    g = [f"ge{e}_0", f"ge{e}_1", f"ge{e}_2"]
-                    if pl[e] == i:
-                        in_order(colpos[e], g)
-                    else:
-                        late_force(pl[e], colpos[e], g)
-                E.raw("    }")
-            # ---- end-effector tracking when the walk stands on the EE link
-            if i in (pt.ee_link, pt.ee2_link) and i >= 0:
-                tgt_name = "A.C.ee_target" if i == pt.ee_link else "A.C.ee2_target"
-                E.raw("    if (A.w.w_ee != 0.0f) {")
-                E.raw(f"        const float eR[9] = {{{', '.join(E.expr(R[i][r][c]) for r in range(3) for c in range(3))}}};")
-                E.raw(f"        const float et[3] = {{{', '.join(E.expr(t[i][k]) for k in range(3))}}};")
-                E.raw("        float gR[9], gt[3];")
-                E.raw(f"        const float ce = ee_cost_eval(eR, et, {tgt_name}, A.C.ee_w_pos, A.C.ee_w_rot, A.C.ee_square, gR, gt);")
-                E.raw("        cost = fmaf(A.w.w_ee, ce, cost);")
-                E.raw("        gt[0] *= A.w.w_ee; gt[1] *= A.w.w_ee; gt[2] *= A.w.w_ee;")
-                E.raw("        pf0 += gt[0]; pf1 += gt[1]; pf2 += gt[2];")
-                # torque = t x gt + axial(Rbar R^T), Rbar = w gR
-                E.raw("        float M[9];")
-                E.raw("#pragma unroll")
-                E.raw("        for (int a = 0; a < 3; ++a)")
-                E.raw("#pragma unroll")
-                E.raw("            for (int b = 0; b < 3; ++b) M[3 * a + b] = A.w.w_ee * (gR[3 * a] * eR[3 * b] + gR[3 * a + 1] * eR[3 * b + 1] + gR[3 * a + 2] * eR[3 * b + 2]);")
-                E.raw("        pt0 += et[1] * gt[2] - et[2] * gt[1] + (M[7] - M[5]);")
-                E.raw("        pt1 += et[2] * gt[0] - et[0] * gt[2] + (M[2] - M[6]);")
-                E.raw("        pt2 += et[0] * gt[1] - et[1] * gt[0] + (M[3] - M[1]);")
-                E.raw("    }")
-            # ---- joints whose subtree ends after this link
-            for j in joint_links:
-                if int(kin.subtree_end[pos_of[j]]) == p + 1:
-                    finish_joint(j)
-        assert chunk_start == W
-        for i in joint_links:
-            d = int(kin.dof_idx[i]); jt = int(kin.joint_type[i])
-            sg = 1.0 if jt == JOINT_PRISMATIC else float(kin.rot_sign[i])
-            if i not in gfin:
-                gq_expr[d] = ZERO
-                continue
-            g = E.lincomb([(gfin[i], ONE), (S(1.0, f"late{d}"), ONE)])
-            gq_expr[d] = masked(E, i, d, S(g.c * sg, g.n))
-        E.raw("    if (!A.gq) return;                       // positions only (trk_fk_points): weights are zero, nothing else to write")
-        E.raw("    if (lane < rows) store_wt_f1(A.cost + base + lane, cost);")
-        E.raw("    if (A.cost_sum) {")
-        E.raw("        const float tot = spec_wave_sum(lane < rows ? cost : 0.0f);")
-        E.raw("        if (lane == 0 && rows > 0) store_wt_f1(A.cost_sum + wblock, tot);")
-        E.raw("    }")
-        E.raw(f"    const float gv[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
-        E.raw("    spec_store_gq<D>(static_cast<IO*>(A.gq), base, rows, lane, lds, gv);")
-        E.raw("}")
-        out.extend(E.lines)
-        out.append("")
-
-    out.extend(_chunked_posbwd_lines(kin, pl, po, snap))
-
+    out.append(f"constexpr int L = {u.L}, D = {u.D}, P = {u.P}, W = {u.W};")
+    for emit in (_points_rollout_kernel, _points_posbwd_kernel):
+        for base_identity in (True, False):
+            out.extend(emit(u, base_identity) + [""])
     if meta is not None and not link_mode:
-        # what a code-object (hipRTC) build of this unit must contain: the name expressions of its kernels (jit.py, trk_spec_register_module)
-        meta["kernels"] = [f"spec_{ident}::k_rollout_{b}<{f}, float>" for b in ("bi", "bg") for f in ("true", "false")] + \
-                          [f"spec_{ident}::k_posbwd_{b}" for b in ("bi", "bg")]
-    out.extend(_points_entry_lines(kin, pt, ident, link_mode))
+        meta["kernels"] = list(u.kernels)
+    out.extend(_points_entry_lines(u))
     return "\n".join(out) + "\n"
 
 
-def _points_entry_lines(kin: KinModel, pt: PointsTemplate, ident: str, link_mode: bool = False) -> List[str]:
+def _points_entry_lines(u: _PointsUnit) -> List[str]:
+    """the unit's host half: launchers and its registry entry"""
+    kin, pt = u.kin, u.pt
     out: List[str] = []
     obj = ", ".join(str(c) for c in pt.obj_cols) or "0"
     pairs = ", ".join(f"{a}, {b}" for a, b in pt.self_pairs) or "0"
@@ -2889,21 +2908,19 @@ def _points_entry_lines(kin: KinModel, pt: PointsTemplate, ident: str, link_mode
     out.append("    }")
     out.append("}")
     out.append("static void launch(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {")
-    if link_mode:
+    if u.link_mode:
         out.append("    if (a.io_f16) launch_io<_Float16>(a, base_identity, st); else launch_io<float>(a, base_identity, st);")
     else:
         out.append("    launch_io<float>(a, base_identity, st);")
     out.append("}")
     out += _launcher_lines("posbwd")
-    n_points = 0 if link_mode else len(pt.point_link)
-    phash = 0 if link_mode else points_hash(pt.point_link, pt.point_offset)
     out.append(f"static const SpecEntry kEntry = {{SPEC_ENTRY_STAMP, 0x{model_hash(kin):016x}ull, {kin.n_links}, {kin.n_dofs}, {len(pt.obj_cols)}, kObjCols, "
-               f"{len(pt.self_pairs)}, kSelfPairs, {pt.ee_link}, \"{ident}\", launch, {n_points}, "
-               f"0x{phash:016x}ull, launch_posbwd, {pt.ee2_link}, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, "
+               f"{len(pt.self_pairs)}, kSelfPairs, {pt.ee_link}, \"{u.ident}\", launch, {u.n_points}, "
+               f"0x{u.points_hash:016x}ull, launch_posbwd, {pt.ee2_link}, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, "
                f"0, nullptr, nullptr}};")
     out.append("static struct Reg { Reg() { trk_spec_register(&kEntry); } } reg;")
     out.append("#endif      // !__HIPCC_RTC__")
-    out.append(f"}}  // namespace spec_{ident}")
+    out.append(f"}}  // namespace spec_{u.ident}")
     return out
 
 

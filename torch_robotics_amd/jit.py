@@ -202,98 +202,69 @@ def _rtc_code_object(source: str, ident: str, kernels) -> tuple:
     return code, lowered
 
 
+def _register_code_object(kin: KinModel, ident: str, source: str, kernels, obj_cols, self_pairs, ee_link: int, ee2_link: int,
+                          **own) -> object:
+    """hipRTC-compile `source` (or take the code object from the cache) and register it with libtrk.so, whose generic launchers play
+    the unit's host half (trk_spec_register_module).  Fills what every unit's descriptor carries; `own` are the descriptor fields
+    only the caller's kind of unit has (an array becomes a pointer to its data)."""
+    code, lowered = _rtc_code_object(source, ident, kernels)
+    L = _lib.lib()
+    from . import _abi
+    stamp = (C.c_int64 * 3)()
+    L.trk_spec_layout_stamp(stamp)
+    d = _abi.ModuleUnitDesc()
+    d.spec_abi_version, d.sizeof_args, d.sizeof_cost_hdr = int(stamp[0]), int(stamp[1]), int(stamp[2])
+    d.ident = ident.encode()
+    d.model_hash = codegen.model_hash(kin)
+    d.n_links, d.n_dofs = kin.n_links, kin.n_dofs
+    obj = np.ascontiguousarray(obj_cols, np.int32)
+    pairs = np.ascontiguousarray(self_pairs, np.int32).reshape(-1)
+    d.n_obj_links, d.n_self_pairs = len(obj), len(pairs) // 2
+    d.ee_link, d.ee2_link = int(ee_link), int(ee2_link)
+    d.n_virtual = 0
+    keep = []
+    fields, pointer_of = dict(d._fields_), {np.dtype(np.int32): C.POINTER(C.c_int32), np.dtype(np.float32): C.POINTER(C.c_float)}
+    for name, v in dict(obj_link_idx=obj, self_pairs=pairs, **own).items():
+        assert name in fields, f"ModuleUnitDesc has no field {name!r}"      # (a ctypes structure takes any attribute name silently)
+        if isinstance(v, np.ndarray):
+            assert fields[name] is pointer_of[v.dtype], f"{name}: {v.dtype} array for a {fields[name].__name__} field"
+            keep.append(v)
+            v = v.ctypes.data_as(fields[name])
+        setattr(d, name, v)
+    buf = C.create_string_buffer(code, len(code))
+    d.code, d.code_size = C.cast(buf, C.c_void_p), len(code)
+    names = (C.c_char_p * len(kernels))(*[k.encode() for k in kernels])
+    lows = (C.c_char_p * len(lowered))(*[k.encode() for k in lowered])
+    d.n_kernels, d.name_exprs, d.lowered_names = len(lowered), names, lows
+    before = L.trk_spec_count()
+    _lib.check(L.trk_spec_register_module(C.byref(d)), "trk_spec_register_module")
+    if L.trk_spec_count() != before + 1:
+        raise _lib.TrkError(f"spec_{ident}: libtrk.so refused the code-object unit")
+    _rtc_keep.append((buf, names, lows, *keep, d))
+    return d
+
+
 def _load_points_unit_rtc(kin: KinModel, pt: "codegen.PointsTemplate", ident: str) -> object:
     """An ATTACHED-POINT unit (link spheres, grasped-object points) without hipcc: its device half compiled in-process, libtrk.so's
     generic launchers as its host half (trk_spec_register_module with n_points > 0)."""
     meta: dict = {}
     source = codegen.generate_points_rollout_source(kin, pt, ident, meta=meta)
-    code, lowered = _rtc_code_object(source, ident, meta["kernels"])
-    L = _lib.lib()
-    from . import _abi
-    stamp = (C.c_int64 * 3)()
-    L.trk_spec_layout_stamp(stamp)
-    d = _abi.ModuleUnitDesc()
-    d.spec_abi_version, d.sizeof_args, d.sizeof_cost_hdr = int(stamp[0]), int(stamp[1]), int(stamp[2])
-    d.ident = ident.encode()
-    d.model_hash = codegen.model_hash(kin)
-    d.n_links, d.n_dofs = kin.n_links, kin.n_dofs
-    obj = np.ascontiguousarray(pt.obj_cols, np.int32)
-    pairs = np.ascontiguousarray(pt.self_pairs, np.int32).reshape(-1)
-    i32p = C.POINTER(C.c_int32)
-    d.n_obj_links, d.obj_link_idx = len(obj), obj.ctypes.data_as(i32p)
-    d.n_self_pairs, d.self_pairs = len(pairs) // 2, pairs.ctypes.data_as(i32p)
-    d.ee_link, d.ee2_link = int(pt.ee_link), int(pt.ee2_link)
-    d.n_virtual = 0
-    d.n_points, d.points_hash = len(pt.point_link), codegen.points_hash(pt.point_link, pt.point_offset)
-    buf = C.create_string_buffer(code, len(code))
-    d.code, d.code_size = C.cast(buf, C.c_void_p), len(code)
-    names = (C.c_char_p * len(meta["kernels"]))(*[k.encode() for k in meta["kernels"]])
-    lows = (C.c_char_p * len(lowered))(*[k.encode() for k in lowered])
-    d.n_kernels, d.name_exprs, d.lowered_names = len(lowered), names, lows
-    before = L.trk_spec_count()
-    _lib.check(L.trk_spec_register_module(C.byref(d)), "trk_spec_register_module")
-    if L.trk_spec_count() != before + 1:
-        raise _lib.TrkError(f"spec_{ident}: libtrk.so refused the code-object unit")
-    _rtc_keep.append((buf, names, lows, obj, pairs, d))
-    return d
+    return _register_code_object(kin, ident, source, meta["kernels"], pt.obj_cols, pt.self_pairs, pt.ee_link, pt.ee2_link,
+                                 n_points=len(pt.point_link), points_hash=codegen.points_hash(pt.point_link, pt.point_offset))
 
 
 def _load_unit_rtc(kin: KinModel, tmpl: codegen.CollisionTemplate, ident: str) -> object:
     """generate + hipRTC-compile (or take from the cache) + register the code object with libtrk.so"""
-    import json
-    JIT_DIR.mkdir(parents=True, exist_ok=True)
-    co, js = JIT_DIR / f"spec_{ident}.hsaco", JIT_DIR / f"spec_{ident}.rtc.json"
     meta: dict = {}
     source = codegen.generate_link_kernel_source(kin, tmpl, ident, meta=meta)
     if not meta:
         raise _lib.TrkError("this robot's link unit comes from the per-link pipeline generator, which the hipRTC fall-back does not serve")
-    want = _rtc_stamp()
-    code = lowered = None
-    if co.exists() and js.exists():
-        try:
-            rec = json.loads(js.read_text())
-            if rec.get("stamp") == want and rec.get("kernels") == meta["kernels"]:
-                code, lowered = co.read_bytes(), rec["lowered"]
-        except (OSError, ValueError):
-            pass
-    if code is None:
-        code, lowered = _rtc_compile(source, ident, meta["kernels"])
-        tag = f".tmp{os.getpid()}"
-        (JIT_DIR / f"spec_{ident}{tag}.hsaco").write_bytes(code)
-        os.replace(JIT_DIR / f"spec_{ident}{tag}.hsaco", co)
-        (JIT_DIR / f"spec_{ident}{tag}.json").write_text(json.dumps({"stamp": want, "kernels": meta["kernels"], "lowered": lowered}))
-        os.replace(JIT_DIR / f"spec_{ident}{tag}.json", js)
-    L = _lib.lib()
-    from . import _abi
-    stamp = (C.c_int64 * 3)()
-    L.trk_spec_layout_stamp(stamp)
-    d = _abi.ModuleUnitDesc()
-    d.spec_abi_version, d.sizeof_args, d.sizeof_cost_hdr = int(stamp[0]), int(stamp[1]), int(stamp[2])
-    d.ident = ident.encode()
-    d.model_hash = codegen.model_hash(kin)
-    d.n_links, d.n_dofs = kin.n_links, kin.n_dofs
-    obj = np.ascontiguousarray(tmpl.obj_links, np.int32)
-    pairs = np.ascontiguousarray(tmpl.self_pairs, np.int32).reshape(-1)
-    vsrc = np.ascontiguousarray([r[:2] for r in tmpl.virtual], np.int32).reshape(-1)
-    vw = np.ascontiguousarray([r[2:] for r in tmpl.virtual], np.float32).reshape(-1)
-    i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
-    d.n_obj_links, d.obj_link_idx = len(obj), obj.ctypes.data_as(i32p)
-    d.n_self_pairs, d.self_pairs = len(pairs) // 2, pairs.ctypes.data_as(i32p)
-    d.ee_link, d.ee2_link = int(tmpl.ee_link), int(tmpl.ee2_link)
-    d.n_virtual, d.virtual_src, d.virtual_w = len(tmpl.virtual), vsrc.ctypes.data_as(i32p), vw.ctypes.data_as(f32p)
-    for k in ("chunked", "fast_switch", "fkhbwd_ok", "fields_ok", "ik_ok", "ikgn_ok", "jac_ok", "jac_direct", "gp_ok"):
-        setattr(d, k, int(bool(meta[k])))
-    buf = C.create_string_buffer(code, len(code))
-    d.code, d.code_size = C.cast(buf, C.c_void_p), len(code)
-    names = (C.c_char_p * len(meta["kernels"]))(*[k.encode() for k in meta["kernels"]])
-    lows = (C.c_char_p * len(lowered))(*[k.encode() for k in lowered])
-    d.n_kernels, d.name_exprs, d.lowered_names = len(lowered), names, lows
-    before = L.trk_spec_count()
-    _lib.check(L.trk_spec_register_module(C.byref(d)), "trk_spec_register_module")
-    if L.trk_spec_count() != before + 1:
-        raise _lib.TrkError(f"spec_{ident}: libtrk.so refused the code-object unit")
-    _rtc_keep.append((buf, names, lows, obj, pairs, vsrc, vw, d))
-    return d
+    traits = {k: int(bool(meta[k])) for k in ("chunked", "fast_switch", "fkhbwd_ok", "fields_ok", "ik_ok", "ikgn_ok", "jac_ok",
+                                              "jac_direct", "gp_ok")}
+    return _register_code_object(kin, ident, source, meta["kernels"], tmpl.obj_links, tmpl.self_pairs, tmpl.ee_link, tmpl.ee2_link,
+                                 n_virtual=len(tmpl.virtual),
+                                 virtual_src=np.ascontiguousarray([r[:2] for r in tmpl.virtual], np.int32).reshape(-1),
+                                 virtual_w=np.ascontiguousarray([r[2:] for r in tmpl.virtual], np.float32).reshape(-1), **traits)
 
 
 def unit_ident(kin: KinModel, tmpl: codegen.CollisionTemplate, pipeline: bool = False) -> str:
@@ -337,21 +308,24 @@ def _virtual_rows(spec):
     return [(int(a), int(b), float(wa), float(wb)) for (a, b), (wa, wb) in zip(src, w)]
 
 
+def _spec_self_pairs(spec):
+    """the cost model's self pairs as (column, column): its pairs index the table of self-collision columns"""
+    sl = np.asarray(spec.self_link_idx, np.int32)
+    return [(int(sl[a]), int(sl[b])) for a, b in np.asarray(spec.self_pairs, np.int32).reshape(-1, 2)]
+
+
 def generatable(spec, points: bool = False) -> bool:
     """False for cost models only the table-driven kernels evaluate (the dispatcher's rule, trk_capi.hip: spec_matches): the
     single-link self distance (a degenerate pair) and -- for attached-point units -- interpolated (virtual) position columns."""
     if points and _virtual_rows(spec):
         return False
-    sl = np.asarray(spec.self_link_idx, np.int32)
-    return not any(int(sl[a]) == int(sl[b]) for a, b in np.asarray(spec.self_pairs, np.int32).reshape(-1, 2))
+    return not any(a == b for a, b in _spec_self_pairs(spec))
 
 
 def _template_of(kin: KinModel, spec) -> Optional[codegen.CollisionTemplate]:
     if spec.n_links_in != kin.n_links or not generatable(spec):
         return None
-    sl = np.asarray(spec.self_link_idx, np.int32)
-    pairs = [(int(sl[a]), int(sl[b])) for a, b in np.asarray(spec.self_pairs, np.int32).reshape(-1, 2)]
-    return codegen.CollisionTemplate(obj_links=[int(i) for i in spec.obj_link_idx], self_pairs=pairs,
+    return codegen.CollisionTemplate(obj_links=[int(i) for i in spec.obj_link_idx], self_pairs=_spec_self_pairs(spec),
                                      ee_link=int(spec.ee_link), ee2_link=int(spec.ee2_link), virtual=_virtual_rows(spec))
 
 
@@ -385,12 +359,10 @@ def has_matching_unit(kin: KinModel, spec) -> bool:
 
 def specialize_for_cost_spec(kin: KinModel, spec, verbose: bool = False) -> Optional[str]:
     """Template from a CostModelSpec whose columns are the links (no attached points)."""
-    if spec.n_links_in != kin.n_links or not generatable(spec):
+    tmpl = _template_of(kin, spec)
+    if tmpl is None:
         return None
-    sl = np.asarray(spec.self_link_idx, np.int32)
-    pairs = [(int(sl[a]), int(sl[b])) for a, b in np.asarray(spec.self_pairs, np.int32).reshape(-1, 2)]
-    return specialize(kin, [int(i) for i in spec.obj_link_idx], pairs, int(spec.ee_link), verbose, ee2_link=int(spec.ee2_link),
-                      virtual=_virtual_rows(spec))
+    return specialize(kin, tmpl.obj_links, tmpl.self_pairs, tmpl.ee_link, verbose, ee2_link=tmpl.ee2_link, virtual=tmpl.virtual)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -401,15 +373,11 @@ def _points_template_of(kin: KinModel, point_link, point_offset, spec) -> Option
     po = np.ascontiguousarray(point_offset, np.float32).reshape(-1, 3)
     if spec.n_links_in != len(pl) or not generatable(spec, points=True):
         return None
-    pos_of = {int(kin.order[p]): p for p in range(kin.n_links)}
-    rank = [pos_of[int(i)] for i in pl]
     obj = [int(c) for c in spec.obj_link_idx]
-    if any(rank[k] > rank[k + 1] for k in range(len(rank) - 1)) or sorted(obj) != obj:
+    if codegen.points_layout_error(kin, pl, obj) is not None:
         return None                                # the generator needs walk-ordered columns / increasing collision columns
-    sl = np.asarray(spec.self_link_idx, np.int32)
-    pairs = [(int(sl[a]), int(sl[b])) for a, b in np.asarray(spec.self_pairs, np.int32).reshape(-1, 2)]
-    return codegen.PointsTemplate(point_link=pl, point_offset=po, obj_cols=obj, self_pairs=pairs, ee_link=int(spec.ee_link),
-                                  ee2_link=int(spec.ee2_link))
+    return codegen.PointsTemplate(point_link=pl, point_offset=po, obj_cols=obj, self_pairs=_spec_self_pairs(spec),
+                                  ee_link=int(spec.ee_link), ee2_link=int(spec.ee2_link))
 
 
 def _points_template_hash(pt: codegen.PointsTemplate) -> str:
