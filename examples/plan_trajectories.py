@@ -8,7 +8,10 @@ where every cost / gradient evaluation is ONE launch of `trk_rollout_gp_cost_gra
 with the GP prior fused in: `task.rollout_gp_plan`); the result is validated the way the reference does it after planning
 (`get_trajs_collision_and_free`: 5 via points per segment, fused FK + boolean fields).  Needs the MI355X: there is no CPU path.
 
-    python examples/plan_trajectories.py [--batch 256] [--horizon 64] [--iters 200]
+    python examples/plan_trajectories.py [--batch 256] [--horizon 64] [--iters 200] [--fused]
+
+--fused runs the same problem with the whole loop on the chip (`task.rollout_adam_plan(...).step(32)`, `trk_rollout_gp_adam_steps`):
+trajectories and Adam's state stay in registers, one launch per 32 iterations (horizons that are a power of two up to 64).
 """
 import argparse
 import sys
@@ -23,7 +26,7 @@ import torch_robotics_amd as tra
 from torch_robotics_amd import ops
 
 
-def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0):
+def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0, fused=False, stats=None):
     torch.manual_seed(seed)
     ta = dict(device=torch.device(device), dtype=torch.float32)
     robot = tra.RobotPanda(tensor_args=ta)
@@ -39,6 +42,8 @@ def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0
     qd = ((q_goal - q_start) / T).expand(batch, horizon, -1).contiguous()
 
     w_obj, sigma_gp, lr = 50.0, 2.0, 1e-2
+    if fused:
+        return _main_fused(task, q, qd, q_start + s * (q_goal - q_start), dt, sigma_gp, w_obj, lr, iters, verbose, stats)
     # pre-bound launch: reads q, qd in place; cost = w_obj * (self + object + workspace hinges) + the prior's factor costs
     plan = task.rollout_gp_plan(q, qd, dt, sigma_gp, gp_weight=1.0, w_self=w_obj, w_obj=w_obj, w_ws=w_obj)
     free_mask = torch.ones(1, horizon, 1, **ta)
@@ -71,11 +76,41 @@ def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0
     return q, n_free, coll0
 
 
+def _main_fused(task, q, qd, q_lines, dt, sigma_gp, w_obj, lr, iters, verbose, stats):
+    """the same objective, pins and Adam, `iters` iterations in launches of 32: plan.step(n) returns the cost of the state it started from"""
+    batch, horizon = q.shape[:2]
+    plan = task.rollout_adam_plan(q, qd, dt, sigma_gp, gp_weight=1.0, w_self=w_obj, w_obj=w_obj, w_ws=w_obj, lr=lr)      # start and goal pinned
+    probe = task.rollout_adam_plan(q, qd, dt, sigma_gp, gp_weight=0.0, w_self=w_obj, w_obj=w_obj, w_ws=w_obj, lr=0.0)   # collision cost only
+    cost0 = float(probe.step(1).sum(1).mean()) / w_obj
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    done = 0
+    while done < iters:
+        n = min(32, iters - done)
+        plan.step(n)
+        done += n
+    torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+    cost1 = float(probe.step(1).sum(1).mean()) / w_obj
+    coll0 = task.compute_collision(q_lines).any(1).float().mean().item()
+    trajs_coll, trajs_free = task.get_trajs_collision_and_free(q, num_interpolation=5)
+    n_free = 0 if trajs_free is None else trajs_free.shape[0]
+    if stats is not None:
+        stats.update(cost_before=cost0, cost_after=cost1, elapsed=elapsed)
+    if verbose:
+        print(f"mean collision cost per trajectory {cost0:9.4f} -> {cost1:9.4f}")
+        print(f"{iters} fused iterations x {batch * horizon} configurations in {elapsed * 1e3:.1f} ms "
+              f"({batch * horizon * iters / elapsed:.3g} FK+cost+grad+Adam evaluations/s)")
+        print(f"straight lines in collision: {coll0 * 100:.0f} %   collision-free after optimisation: {n_free}/{batch}")
+    return q, n_free, coll0
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--horizon", type=int, default=64)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--fused", action="store_true", help="the whole loop in one kernel (rollout_adam_plan)")
     a = ap.parse_args()
-    main(a.batch, a.horizon, a.iters, a.device)
+    main(a.batch, a.horizon, a.iters, a.device, fused=a.fused)

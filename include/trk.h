@@ -858,6 +858,27 @@ int trk_scene2d_traj_adam_steps(const TrkScene2D* scene, const TrkPlanarObjectiv
                                 float* qd, float* adam_m, float* adam_v, int64_t batch, int32_t horizon, float* cost,
                                 trk_stream_t stream);
 
+/* The arm's planning loop on the chip: n_steps iterations of Adam (the arithmetic and bias terms of trk_scene2d_traj_adam_steps, above)
+ * on the objective of trk_rollout_gp_cost_grad -- the collision and EE terms of trk_rollout_cost_grad under `w` plus the
+ * constant-velocity GP prior -- with the trajectories and the optimiser's state in registers: q, qd [batch, horizon, dof] fp32 and
+ * adam_m, adam_v [batch, horizon, 2 dof] = [q part | qd part] per sample are read once and written once per launch, at most 32
+ * iterations per launch (more = several launches inside the call; the result does not depend on how the iterations are grouped into
+ * calls).  pin: TrkPlanarAdam's bits.  cost (nullable) [batch, horizon]: the objective of the state as passed in, the prior's factor
+ * t -> t+1 attributed to sample t.  lr = 0 (or n_steps = 0) only evaluates: nothing but cost is written.
+ * Served by a generated kernel only (k_traj_adam: link-column units of robots up to 8 DOF); TRK_ERR_UNSUPPORTED when the horizon is
+ * not a power of two <= TRK_TRAJ_ADAM_MAX_HORIZON (a wavefront owns whole trajectories), when no unit of the model carries the
+ * kernel, when none matches the cost model, or when trk_model_enable_specialized is off.  No host synchronisation: capturable. */
+#define TRK_TRAJ_ADAM_MAX_HORIZON 64
+typedef struct TrkTrajAdam {
+    float lr;                   /* finite */
+    int32_t pin;                /* 0 .. 15 */
+    int32_t first_step;         /* >= 1 */
+    int32_t n_steps;            /* >= 0 */
+} TrkTrajAdam;
+int trk_rollout_gp_adam_steps(const TrkModel* model, const TrkCostModel* cm, const TrkRolloutWeights* weights, const TrkGpPrior* gp,
+                              const TrkTrajAdam* adam, float* q, float* qd, float* adam_m, float* adam_v, int64_t batch,
+                              int32_t horizon, float* cost, trk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,13 @@ class PlanarAdam(C.Structure):          # TrkPlanarAdam
     _fields_ = [("lr", C.c_float), ("pin", C.c_int32), ("first_step", C.c_int32), ("n_steps", C.c_int32)]
 
 
+TRK_TRAJ_ADAM_MAX_HORIZON = 64
+
+
+class TrajAdam(C.Structure):            # TrkTrajAdam
+    _fields_ = [("lr", C.c_float), ("pin", C.c_int32), ("first_step", C.c_int32), ("n_steps", C.c_int32)]
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 

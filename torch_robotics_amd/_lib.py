@@ -37,6 +37,7 @@ EXPORTS = [
     "trk_handle_kind", "trk_mailbox_create", "trk_mailbox_ipc_handle", "trk_mailbox_connect", "trk_mailbox_send", "trk_mailbox_recv", "trk_mailbox_exchange", "trk_mailbox_status", "trk_mailbox_destroy",
     "trk_scene2d_create", "trk_scene2d_destroy", "trk_scene2d_cost_grad", "trk_scene2d_collision", "trk_scene2d_collision_via",
     "trk_grid2d_precompute", "trk_scene2d_sdf_points", "trk_scene2d_traj_cost_grad", "trk_scene2d_traj_adam_steps",
+    "trk_rollout_gp_adam_steps",
 ]
 
 
@@ -193,6 +194,8 @@ def lib():
     L.trk_scene2d_sdf_points.argtypes = [vp, vp, i64, vp, vp, vp]
     L.trk_scene2d_traj_cost_grad.argtypes = [vp, C.POINTER(_abi.PlanarObjective), vp, vp, i64, i32, vp, vp, vp, vp]
     L.trk_scene2d_traj_adam_steps.argtypes = [vp, C.POINTER(_abi.PlanarObjective), C.POINTER(_abi.PlanarAdam), vp, vp, vp, vp, i64, i32, vp, vp]
+    L.trk_rollout_gp_adam_steps.argtypes = [vp, vp, C.POINTER(_abi.RolloutWeights), C.POINTER(_abi.GpPrior), C.POINTER(_abi.TrajAdam),
+                                            vp, vp, vp, vp, i64, i32, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)        # AttributeError here = the library does not export the ABI
         if name not in ("trk_last_error", "trk_model_destroy", "trk_cost_model_destroy", "trk_point_set_destroy",

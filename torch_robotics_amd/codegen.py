@@ -782,6 +782,9 @@ class _LinkUnit:
         # registers; UR10+Allegro, 22 DOF: 377) and those robots keep the table-driven kernel
         self.ik_ok = tmpl.ee_link >= 0 and D <= 9
         self.ikgn_ok = tmpl.ee_link >= 0 and D <= 9 and len(self.ee_jac_cols) > 0
+        # the planning loop in one kernel (k_traj_adam): the whole-row, four-wavefront units -- on top of the rollout's registers the
+        # loop keeps qd, m and v (5 D); the two-wavefront units' rollout already takes 217
+        self.traj_adam_ok = self.gpt_ok and D <= 8
         # k_jac.  Small arms: the lane writes its columns straight into two [64][3D] output tiles (static offsets; non-ancestor columns
         # stay zero), finishes z x (p_link - p_joint) in place, and the read-out is a contiguous 16-byte copy.  The record scheme
         # needs less LDS when the target link has few ancestors among many joints (a finger tip of UR10+Allegro: 10 of 22), but its
@@ -2012,6 +2015,122 @@ def _ikgn_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     return E.lines
 
 
+# Wavefronts per SIMD k_traj_adam runs at: the rollout's registers + qd, m, v (5 D) + the loop-invariant scene scalars the compiler parks
+# in VGPR lanes come to 218 - 229 VGPRs for the Panda (three wavefronts = 168: 148 - 264 bytes of scratch per lane).  The kernel states
+# only its block size: with the explicit bound `, 2` the allocator leaves two instantiations a dead 20 - 36 byte private segment.
+TRAJ_ADAM_OCCUPANCY = 2
+
+
+def _traj_adam_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
+    """k_traj_adam_bi / _bg<BOX>: the arm's planning loop (trk_rollout_gp_adam_steps) -- n_steps iterations of Adam on the objective of
+    trk_rollout_gp_cost_grad (collision + EE terms + constant-velocity GP prior) with (q, qd, m, v) of a sample in its lane's registers.
+    One lane per sample, fp32; the horizon is a power of two <= 64, so a wavefront owns 64 / H whole trajectories and the prior's
+    neighbours in time are the neighbouring lanes (two DPP wavefront shifts per value, as k_rollout_gpt's): nothing crosses a
+    wavefront, no LDS exchange, no barrier.  The iteration is k_rollout's text (same emitters, same scene switch BOX) without
+    positions -- NoFlush: the tick slots are empty -- followed by the prior on the register copies and trk_ik_step's Adam update."""
+    kin, L, D = u.kin, u.L, u.D
+    E = Emitter()
+    kname = "k_traj_adam_bi" if base_identity else "k_traj_adam_bg"
+    E.raw("template <bool BOX>      // the scene switch of k_rollout (scene_is_general): boxes and / or a voxel grid")
+    E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK) {kname}(TrajAdamArgs A) {{      // {TRAJ_ADAM_OCCUPANCY} wavefronts per SIMD (TRAJ_ADAM_OCCUPANCY)")
+    E.raw("    constexpr int LDS_LANE = 2 * D;        // the transposes of q, qd [64][D] and of m, v [64][2D]")
+    E.raw("    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * LDS_LANE + SPEC_WAVES * (TRK_LDS_SPHERES * 4 + (BOX ? TRK_LDS_PRIMS * 8 : 0))];")
+    E.raw("    const int lane = __builtin_amdgcn_workitem_id_x() & (TRK_WAVE - 1);")
+    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_workitem_id_x() / TRK_WAVE);")
+    E.raw("    float* lds = lds_all + wave * (TRK_WAVE * LDS_LANE);")
+    E.raw("    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * LDS_LANE) + wave * (TRK_LDS_SPHERES + (BOX ? 2 * TRK_LDS_PRIMS : 0));")
+    E.raw("    float4* lds_prm = BOX ? lds_sph + TRK_LDS_SPHERES : nullptr;")
+    E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);")
+    E.raw("    const SpheresInFlight prm = BOX ? spec_load_prims_issue(A.C, lane) : sph;")
+    E.raw("    const int64_t wblock = (int64_t)__builtin_amdgcn_workgroup_id_x() * SPEC_WAVES + wave;")
+    E.raw("    const int64_t base = wblock * TRK_WAVE;")
+    E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));      // lanes beyond: clamped loads, no stores")
+    E.raw("    const bool update = A.update != 0;")
+    E.raw("    float q[D], qd[D], am[2 * D], av[2 * D];")
+    E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
+    E.raw("    spec_load_q<D>(static_cast<const float*>(A.qd), base, rows, lane, lds, qd);")
+    E.raw("    if (update) {")
+    E.raw("        spec_load_q<2 * D>(static_cast<const float*>(A.adam_m), base, rows, lane, lds, am);")
+    E.raw("        spec_load_q<2 * D>(static_cast<const float*>(A.adam_v), base, rows, lane, lds, av);")
+    E.raw("    } else {")
+    E.raw("#pragma unroll")
+    E.raw("        for (int d = 0; d < 2 * D; ++d) { am[d] = 0.0f; av[d] = 0.0f; }")
+    E.raw("    }")
+    E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
+    E.raw("    if constexpr (BOX) spec_load_spheres_finish(lds_prm, lane, prm);")
+    E.raw("    const NoFlush flush{};                 // this kernel writes no positions")
+    E.raw("    // time step: 64 is a multiple of the horizon, so a wavefront starts at step 0 of a trajectory")
+    E.raw("    const int tl = lane & (A.gp_H - 1);")
+    E.raw("    const bool t_first = tl == 0, t_last = tl == A.gp_H - 1;")
+    E.raw("    const bool pin_q = ((A.pin & 1) && t_first) || ((A.pin & 2) && t_last);        // a pinned component's gradient is taken as zero")
+    E.raw("    const bool pin_qd = ((A.pin & 4) && t_first) || ((A.pin & 8) && t_last);")
+    E.raw("    const float wm = (lane < rows && !t_last) ? A.gp_w : 0.0f;       // the factor t -> t + 1 exists")
+    E.raw("    const float dt = A.gp_dt, gaw = wm * A.gp_a, gbw = wm * A.gp_b, gcw = wm * A.gp_c;")
+    E.raw("    float cost0 = 0.0f;")
+    E.raw("#pragma nounroll")
+    E.raw("    for (int it = 0; it < A.n_steps; ++it) {")
+    # ---------------- forward, objectives, reverse: k_rollout's ----------------
+    R, t, passv = _root_pose(base_identity)
+    _emit_angles(E, kin)
+    for p in range(1, L):
+        _emit_fk_link(E, kin, u.walk[p], R, t, passv, u.snap)
+    ticks = _Ticks()
+    _emit_collision_objectives(u, E, t, ticks, fast_arg=", decltype(ticks), false, BOX", prims_ptr="lds_prm")
+    _emit_ee_terms(E, u.tracked, R, t)
+    E.raw(ticks())
+    gq_expr = _emit_reverse_links(E, kin, R, t, {i: [f"tb{i}_{k}" for k in range(3)] for i in u.real_adj},
+                                  {l: rb for l, _, rb in u.tracked}, u.masked, tick=ticks, order=u.walk)
+    E.raw(f"    const float gc[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
+    # ---------------- the prior on the register copies (_emit_gpt_prior's expressions) ----------------
+    E.raw("    // the prior: e_t = (p_t + dt v_t - p_t+1, v_t - v_t+1), r = w Q^-1 e; the next sample's (p, v) come by wave_shl:1, the finished")
+    E.raw("    // factor goes to the next lane by wave_shr:1.  A lane at the last step has weight 0, so a lane at step 0 receives 0; lanes 63 / 0")
+    E.raw("    // have no source and keep the shift's `old` operand: their own value (weight 0) / 0.")
+    E.raw("    float gpv[D], gvv[D], accg = 0.0f;")
+    E.raw("#pragma unroll")
+    E.raw("    for (int d = 0; d < D; ++d) {")
+    E.raw("        const float p0 = q[d], v0 = qd[d];")
+    E.raw("        const float pn = trk_dpp_from_next(p0, p0), vn = trk_dpp_from_next(v0, v0);")
+    E.raw("        const float ep = fmaf(dt, v0, p0) - pn, ev = v0 - vn;")
+    E.raw("        const float rp = fmaf(gaw, ep, gbw * ev), rv_ = fmaf(gbw, ep, gcw * ev);")
+    E.raw("        accg = fmaf(ep, rp, fmaf(ev, rv_, accg));")
+    E.raw("        gpv[d] = rp - trk_dpp_from_prev(0.0f, rp);")
+    E.raw("        gvv[d] = fmaf(dt, rp, rv_) - trk_dpp_from_prev(0.0f, rv_);")
+    E.raw("    }")
+    E.raw("    if (it == 0) cost0 = fmaf(0.5f, accg, cost);      // the state as passed in; the factor t -> t + 1 attributed to sample t")
+    E.raw("    if (update) {")
+    E.raw("        const float step = spec_adam_step_size(A.lr, A.sched.bc1[it]), rs = A.sched.rsqrt_bc2[it];")
+    E.raw("#pragma unroll")
+    E.raw("        for (int d = 0; d < D; ++d) {")
+    E.raw("            spec_adam_component(pin_q ? 0.0f : gc[d] + gpv[d], step, rs, q[d], am[d], av[d]);")
+    E.raw("            spec_adam_component(pin_qd ? 0.0f : gvv[d], step, rs, qd[d], am[D + d], av[D + d]);")
+    E.raw("        }")
+    E.raw("    }")
+    E.raw("    }")
+    E.raw("    if (A.cost && lane < rows) store_wt_f1(A.cost + base + lane, cost0);")
+    E.raw("    if (update) {")
+    E.raw("        spec_store_gq<D>(A.q, base, rows, lane, lds, q);")
+    E.raw("        spec_store_gq<D>(A.qd, base, rows, lane, lds, qd);")
+    E.raw("        spec_store_gq<2 * D>(A.adam_m, base, rows, lane, lds, am);")
+    E.raw("        spec_store_gq<2 * D>(A.adam_v, base, rows, lane, lds, av);")
+    E.raw("    }")
+    E.raw("}")
+    return E.lines
+
+
+def _traj_adam_launcher_lines(u: _LinkUnit) -> List[str]:
+    out = ["static void launch_traj_adam(const SpecEntry*, const TrajAdamArgs& a, int base_identity, hipStream_t st) {",
+           "    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);",
+           f"    if ({u.scene_switch}) {{",
+           "        if (base_identity) hipLaunchKernelGGL((k_traj_adam_bi<true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+           "        else hipLaunchKernelGGL((k_traj_adam_bg<true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+           "    } else {",
+           "        if (base_identity) hipLaunchKernelGGL((k_traj_adam_bi<false>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+           "        else hipLaunchKernelGGL((k_traj_adam_bg<false>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+           "    }",
+           "}"]
+    return out
+
+
 def _jac_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     """k_jac_bi / _bg: stateful FK + geometric Jacobian of ONE link (trk_fk_jacobian; robot_tree.py:136-190, 218-248): the walk unrolled
     with the stateful path's quirks (clamp wherever limits exist, rotation about the axis with its sign ignored); every joint that can
@@ -2354,6 +2473,9 @@ def _link_host_lines(u: _LinkUnit) -> List[str]:
                f"{slot(u.jacf_ok, 'launch_rjac')}, {slot(u.ajac_ok, 'launch_ajac')}, {slot(bool(u.fx_terms), 'fx_select')}, "
                f"{slot(bool(u.fx_terms) and bool(u.fx_const), 'launch_fx_points')}, {len(u.fx_const) if u.fx_terms else 0}}};")
     out.append("static struct Reg { Reg() { trk_spec_register(&kEntry); } } reg;")
+    if u.traj_adam_ok:
+        out += _traj_adam_launcher_lines(u)
+        out.append("static struct RegTrajAdam { RegTrajAdam() { trk_spec_register_traj_adam(&kEntry, (uint32_t)sizeof(TrajAdamArgs), launch_traj_adam); } } reg_traj_adam;")
     out.append("#endif      // !__HIPCC_RTC__")
     return out
 
@@ -2440,6 +2562,10 @@ def generate_rollout_source(kin: KinModel, tmpl: CollisionTemplate, ident: str, 
     if u.ajac_ok:
         out.append("#ifndef __HIPCC_RTC__          // (linked / dlopen-ed units only: a code-object unit keeps the table-driven kernel)")
         per_base(_ajac_kernel)
+        out.append("#endif      // !__HIPCC_RTC__")
+    if u.traj_adam_ok:
+        out.append("#ifndef __HIPCC_RTC__          // (linked / dlopen-ed units only: libtrk.so has no generic launcher for it)")
+        per_base(_traj_adam_kernel)
         out.append("#endif      // !__HIPCC_RTC__")
     out += _link_host_lines(u)
     out.append(f"}}  // namespace spec_{ident}")

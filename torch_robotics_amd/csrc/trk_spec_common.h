@@ -134,6 +134,48 @@ struct IkGnArgs {
 typedef void (*SpecIkGnLaunchFn)(const SpecEntry* self, const IkGnArgs& args, int base_identity, hipStream_t stream);
 #endif
 
+// Arguments of the generated planning-loop kernel (k_traj_adam; trk_rollout_gp_adam_steps): the cost header, weights and base pose
+// under the names SpecArgs gives them (the objective emitters read A.C / A.w / A.base_*), the prior as launch_gp forms it, Adam's
+// parameters and the bias terms of the launch's iterations by value.  Its own struct for the reason IkArgs is one.
+struct TrajAdamArgs {
+    DevCostHdr C;
+    TrkRolloutWeights w;
+    float base_R[9];
+    float base_t[3];
+    float* q; float* qd;          // [N, D], in place
+    float* adam_m; float* adam_v; // [N, 2D] = [q part | qd part], in place
+    float* cost;                  // nullable [N]: the objective of the state as passed in
+    int64_t n;
+    float gp_dt, gp_a, gp_b, gp_c, gp_w;
+    int32_t gp_H;                 // a power of two <= TRK_WAVE: a wavefront owns whole trajectories
+    float lr;
+    int32_t pin;                  // bits as TrkPlanarAdam
+    int32_t n_steps;              // <= TRK_IK_MAX_STEPS
+    int32_t update;               // 0: evaluate only (cost), nothing else is written
+    IkSchedule sched;
+};
+#ifndef __HIPCC_RTC__
+typedef void (*SpecTrajAdamLaunchFn)(const SpecEntry* self, const TrajAdamArgs& args, int base_identity, hipStream_t stream);
+// a unit that carries k_traj_adam announces its launcher after its entry (a registry of its own: SpecEntry keeps its layout);
+// refused like trk_spec_register when the unit was compiled against another TrajAdamArgs
+int trk_spec_register_traj_adam(const SpecEntry* e, uint32_t sizeof_args, SpecTrajAdamLaunchFn fn);
+#endif
+
+// trk_ik_step's Adam on one component with every operation rounded once, whatever FP freedoms the unit grants its other code: the
+// update is specified operation by operation (include/trk.h) and k_planar_traj_adam computes exactly this
+__device__ __forceinline__ void spec_adam_component(float g, float step, float rsqrt_bc2, float& x, float& m, float& v) {
+#pragma clang fp reassociate(off) contract(off) reciprocal(off)
+    const float m1 = fmaf(0.9f, m, 0.1f * g);
+    const float v1 = fmaf(0.999f, v, 0.001f * g * g);
+    m = m1; v = v1;
+    const float denom = fmaf(sqrtf(v1), rsqrt_bc2, 1e-8f);
+    x = x - step * (m1 / denom);
+}
+__device__ __forceinline__ float spec_adam_step_size(float lr, float bc1) {
+#pragma clang fp reassociate(off) contract(off) reciprocal(off)
+    return lr / bc1;
+}
+
 // Layout version of SpecArgs / SpecEntry / DevCostHdr as seen by a generated unit.  A unit compiled against another layout
 // (a stale on-disk JIT object) must never be dispatched: trk_spec_register refuses it.  Bump on ANY change to these structs,
 // to TrkRolloutWeights or to the TRK_MAX_* limits in include/trk.h.

@@ -1612,6 +1612,46 @@ class PlanarAdamPlan(_Plan):
         return self.cost
 
 
+class ArmAdamPlan(_Plan):
+    """Adam on RolloutGpPlan's objective with the trajectories and the optimiser's state on the chip (include/trk.h:
+    trk_rollout_gp_adam_steps; generated kernel k_traj_adam, robots up to 8 DOF).  Pre-bound: `step(n)` runs the next n iterations on
+    the caller's q, qd (B,H,D) fp32 IN PLACE -- one launch per 32 iterations -- and returns the (B,H) cost of the state it started
+    from.  The plan owns `m`, `v` (B,H,2D) = [q part | qd part] and the iteration counter `t`.  H must be a power of two <= 64.
+    pin_*: the start / goal position (velocity) keeps its value.  lr = 0 only evaluates."""
+
+    def __init__(self, model: ModelHandle, cm: CostHandle, weights, q: torch.Tensor, qd: torch.Tensor, dt: float, sigma: float,
+                 gp_weight: float = 1.0, lr: float = 1e-2, pin_start: bool = True, pin_goal: bool = True, pin_start_vel: bool = False,
+                 pin_goal_vel: bool = False):
+        B, H, D = _gp_args(model, q, qd, "ArmAdamPlan")
+        if q.dtype != torch.float32:
+            raise ValueError("ArmAdamPlan: q, qd must be float32 (the planning-loop kernel has no fp16 I/O)")
+        if H > _abi.TRK_TRAJ_ADAM_MAX_HORIZON or H & (H - 1):
+            raise NotImplementedError(f"ArmAdamPlan: horizon {H} is not a power of two <= {_abi.TRK_TRAJ_ADAM_MAX_HORIZON} (a wavefront of the "
+                                      f"planning-loop kernel owns whole trajectories; RolloutGpPlan serves any horizon)")
+        self.model, self.cm, self.q, self.qd, self.device, self.B, self.H = model, cm, q, qd, q.device, B, H
+        self.m = torch.zeros((B, H, 2 * D), device=q.device, dtype=torch.float32)
+        self.v = torch.zeros((B, H, 2 * D), device=q.device, dtype=torch.float32)
+        self.cost = torch.empty((B, H), device=q.device, dtype=torch.float32)
+        self.t = 0                              # iterations done
+        self.pin = 1 * bool(pin_start) | 2 * bool(pin_goal) | 4 * bool(pin_start_vel) | 8 * bool(pin_goal_vel)
+        self._w = _weights_struct(weights)
+        self._gp = _abi.GpPrior(float(dt), float(sigma), float(gp_weight))
+        self._adam = _abi.TrajAdam(float(lr), self.pin, 1, 0)
+        self._fn = lib().trk_rollout_gp_adam_steps
+        self._args = (model._h, cm._h, C.byref(self._w), C.byref(self._gp), C.byref(self._adam), q.data_ptr(), qd.data_ptr(),
+                      self.m.data_ptr(), self.v.data_ptr(), B, H, self.cost.data_ptr())
+
+    def step(self, n: int = 1, stream: Optional[int] = None) -> torch.Tensor:
+        n = int(n)
+        if n < 0:
+            raise ValueError("ArmAdamPlan.step: n must be >= 0")
+        self._adam.first_step, self._adam.n_steps = self.t + 1, n
+        self._launch(stream)
+        if self._adam.lr != 0.0:
+            self.t += n
+        return self.cost
+
+
 def reduce_sum(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Deterministic sum of a float32 device vector (fixed association order)."""
     x = _dev_f32(x, "reduce_sum(x)").reshape(-1)

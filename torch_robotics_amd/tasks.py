@@ -252,6 +252,25 @@ class PlanningTask(Task):
         return ops.RolloutGpPlan(model, cm, (w_self, w_obj, w_ws, w_ee), q, qd, dt, sigma_gp, gp_weight, want_pos=want_pos,
                                  grad_dtype=grad_dtype, grad_scale=grad_scale, strict=os.environ.get("TRK_ALLOW_TABLE_DRIVEN", "0") != "1")
 
+    def rollout_adam_plan(self, q, qd, dt, sigma_gp, gp_weight=1.0, w_self=1.0, w_obj=1.0, w_ws=1.0, w_ee=0.0, lr=1e-2,
+                          **pins) -> "ops.ArmAdamPlan":
+        """A small arm's planning loop on the chip (`trk_rollout_gp_adam_steps`): Adam on `rollout_gp_plan`'s objective with q, qd
+        (B,H,D) fp32 and the optimiser's state in registers.  `plan.step(n)` improves q, qd in place and returns the (B,H) cost they
+        started from; pins: pin_start / pin_goal (default True), pin_start_vel / pin_goal_vel (default False).  For link-column
+        cost models of robots up to 8 DOF (a robot without a bundled unit compiles one on first use -- with hipcc: a unit that the
+        hipRTC fall-back loads as a code object has no planning-loop kernel, and the plan's first step raises NotImplementedError) and
+        horizons that are a power of two <= 64."""
+        if getattr(self.robot, "has_extra_points", False):
+            raise NotImplementedError("rollout_adam_plan is for link-column cost models (no grasped object / link spheres)")
+        if not self._has_tree:
+            raise NotImplementedError("rollout_adam_plan needs a robot with a kinematic tree (the 2-D point mass has trajectory_optimizer)")
+        H = int(q.shape[1]) if q.dim() == 3 else 0
+        if q.dim() == 3 and (H < 1 or H > 64 or H & (H - 1)):          # before _fused_handles, which may compile a unit
+            raise NotImplementedError(f"rollout_adam_plan: horizon {H} is not a power of two <= 64 (a wavefront of the planning-loop "
+                                      f"kernel owns whole trajectories; rollout_gp_plan serves any horizon)")
+        model, cm = self._fused_handles(q.device)
+        return ops.ArmAdamPlan(model, cm, (w_self, w_obj, w_ws, w_ee), q, qd, dt, sigma_gp, gp_weight, lr, **pins)
+
     def trajectory_optimizer(self, q, qd, dt, sigma_gp, w_obj=1.0, gp_weight=1.0, lr=5e-3, **pins) -> "ops.PlanarAdamPlan":
         """The 2-D point mass's planning loop on the chip (`trk_scene2d_traj_adam_steps`): Adam on w_obj x this task's collision hinge
         (its scene, its clamp_sdf) + the constant-velocity GP prior.  `plan.step(n)` improves q, qd (B,H,2) in place and returns the
