@@ -74,12 +74,13 @@ def dof_limits(kin):
     return lo, hi
 
 
-def inputs(kin, B, H):
+def inputs(kin, B, H, seed=None):
+    """the walks of a shape, drawn once per robot (seed: another draw than the shape's own 1000 B + H)"""
     if not hasattr(kin, "lower_dof"):
         kin.lower_dof, kin.upper_dof = dof_limits(kin)
-    key = ("in", kin.name, B, H)
+    key = ("in", kin.name, B, H, seed)
     if key not in _cache:
-        _cache[key] = walks(kin, B, H, seed=1000 * B + H)
+        _cache[key] = walks(kin, B, H, seed=1000 * B + H if seed is None else seed)
     return _cache[key]
 
 
@@ -96,8 +97,8 @@ def cost_bound(ref):
     return TOL_COST * np.abs(ref["hinge"]).max() + TOL_COST * np.abs(ref["prior"]).max()
 
 
-def plan_of(h, cm, q, qd, lr=LR, pin=3, w=W, gpw=GPW):
-    return ops.ArmAdamPlan(h, cm, w, q, qd, DT, SIGMA, gpw, lr, pin_start=bool(pin & 1), pin_goal=bool(pin & 2),
+def plan_of(h, cm, q, qd, lr=LR, pin=3, w=W, gpw=GPW, dt=DT, sigma=SIGMA):
+    return ops.ArmAdamPlan(h, cm, w, q, qd, dt, sigma, gpw, lr, pin_start=bool(pin & 1), pin_goal=bool(pin & 2),
                            pin_start_vel=bool(pin & 4), pin_goal_vel=bool(pin & 8))
 
 
@@ -110,25 +111,29 @@ def pin_masks(pin, B, H, D):
     return m
 
 
-def check_gradient(o, oracle_lib, got_q, got_qd, ref, q, qd, what):
+def check_gradient(o, oracle_lib, got_q, got_qd, ref, q, qd, what, w=W, rows=None):
     """DESIGN section 2's gradient tolerance (rel 1e-4 and the per-element bound, helpers.grad_close) on gq and on gqd; for gq, whose
     collision half has kinks, on every ordinary row, with kink_rows_ok (its own cap of 3 rows) for the rest; at least half the batch
-    ordinary.  The prior is smooth: gqd has no kinks, and at H = 1 there is no factor -- it is exactly zero."""
+    ordinary.  The prior is smooth: gqd has no kinks, and at H = 1 there is no factor -- it is exactly zero.  w: the weights `ref` was
+    formed with; rows: boolean (B H,), the samples whose gq is judged (default: all).  Returns the number of rows at a kink."""
     B, H, D = q.shape
-    n = B * H
-    g, r = got_q.reshape(n, D).astype(np.float64), ref["gq"].reshape(n, D)
+    keep = np.ones(B * H, bool) if rows is None else np.asarray(rows, bool).reshape(B * H)
+    n = int(keep.sum())
+    g, r = got_q.reshape(B * H, D).astype(np.float64)[keep], ref["gq"].reshape(B * H, D)[keep]
+    q = q.reshape(B * H, D)[keep]
     bound = hp.GRAD_RTOL * np.abs(r) + hp.GRAD_ATOL * max(1e-30, np.abs(r).max())
     bad = (np.abs(g - r) > bound).any(-1)
     print(f"{what}: {int(bad.sum())} of {n} rows at a kink; rel err of the rest {rel_err(g[~bad], r[~bad]) if (~bad).any() else 0.0:.2e}; "
           f"gqd excess {hp.grad_excess(got_qd, ref['gqd']) if H > 1 else 0.0:.3f}")
     assert 2 * int((~bad).sum()) >= n, what
     assert hp.grad_close(g[~bad], r[~bad], 1e-4, np.abs(r).max() / max(1e-30, np.abs(r[~bad]).max())), what
-    prior_q = (ref["gq"] - ref["gc"]).reshape(n, D)
-    assert hp.kink_rows_ok(g, r, q.reshape(n, D), lambda qp: o.rollout(qp, W, "f64")[2] + prior_q[rows_of(qp, q.reshape(n, D))], bad), what
+    prior_q = (ref["gq"] - ref["gc"]).reshape(B * H, D)[keep]
+    assert hp.kink_rows_ok(g, r, q.reshape(n, D), lambda qp: o.rollout(qp, w, "f64")[2] + prior_q[rows_of(qp, q.reshape(n, D))], bad), what
     if H > 1:
         assert hp.grad_close(got_qd, ref["gqd"], 1e-4), what
     else:
         assert not np.asarray(got_qd).any(), what
+    return int(bad.sum())
 
 
 def rows_of(qp, q):
@@ -176,7 +181,7 @@ def test_evaluation_gradient_and_update(scene, clamp, base, oracle_lib):
         check_update(2, x1, m1, v1, g1, x2, host(plan.m), host(plan.v))
 
 
-def check_update(step, x0, m0, v0, g, x1, m1, v1):
+def check_update(step, x0, m0, v0, g, x1, m1, v1, lr=LR):
     """test_gpu_planar_traj.check_adam_step for 2 D components: m1 = 0.9 m0 + 0.1 g and v1 = 0.999 v0 + 0.001 g^2 within what the
     gradient tolerance d = 1e-4 |g| + 5e-6 max|g| allows (0.1 d; 0.001 (2 |g| d + d^2)) plus the roundings of the fma and the product,
     then the update formula on the returned moments"""
@@ -185,7 +190,7 @@ def check_update(step, x0, m0, v0, g, x1, m1, v1):
     em = np.abs(m1 - (0.9 * m0 + 0.1 * g)) / (0.1 * d + 2.0 ** -22 * np.abs(m1))
     ev = np.abs(v1 - (0.999 * v0 + 0.001 * g * g)) / (0.001 * (2.0 * np.abs(g) * d + d * d) + 2.0 ** -22 * np.abs(v1) + 1e-300)
     bc1, rs = ops.planar_adam_bias_terms(step)
-    upd = (float(np.float32(LR)) / bc1) * m1 / (np.sqrt(v1) * rs + 1e-8)
+    upd = (float(np.float32(lr)) / bc1) * m1 / (np.sqrt(v1) * rs + 1e-8)
     bound = 0.5 * np.spacing(np.abs(x1).astype(np.float32)).astype(np.float64) + 2.0 * pt.ADAM_ROUNDINGS * 2.0 ** -24 * np.abs(upd)
     err = np.abs(x1 - (x0 - upd))
     print(f"adam step {step}: worst m / v recurrence error / bound {float(em.max()):.3f} / {float(ev.max()):.3f}, "
