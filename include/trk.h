@@ -449,7 +449,7 @@ int trk_rollout_jacobian_cost_grad(const TrkModel* model, const TrkCostModel* cm
 int trk_rollout_is_specialized(const TrkModel* model, const TrkCostModel* cm, const TrkRolloutWeights* w);
 
 /* Which kernel family served the CALLING THREAD's latest rollout call (trk_rollout_cost_grad[_f16], trk_rollout_gp_cost_grad,
- * trk_rollout_points_cost_grad, trk_rollout_collision[_via]).  No reference counterpart: the reference has one code path
+ * trk_rollout_points_cost_grad, trk_rollout_collision[_via], trk_rollout_points_collision[_via]).  No reference counterpart: the reference has one code path
  * (tasks.py:139-232); here a cost model whose link sets no generated unit bakes is served by the table-driven kernels, 10 - 30 x slower. */
 enum {
     TRK_DISPATCH_NONE = 0,                  /* no rollout call yet on this thread (or a call that had nothing to launch) */
@@ -590,6 +590,27 @@ int trk_rollout_collision_via_flags(const TrkModel* model, const TrkCostModel* c
                                     int32_t horizon, int32_t state_dim, int32_t n_interp, const float* alpha, const float* beta,
                                     float margin_override, const float* q_min, const float* q_max, uint8_t* in_collision,
                                     uint8_t* partial_flags, trk_stream_t stream);
+
+/* trk_rollout_collision for a cost model whose columns are the attached points of `ps` (link spheres, grasped-object points; the model
+ * is ps's): FK + the OR of the selected fields' tests in ONE launch, one byte per sample out, no point position reaches HBM.
+ * reference: PlanningTask.compute_collision tasks.py:131-133 with such a robot.  Same validation and margin rule as
+ * trk_rollout_collision; a field with nothing to test is dropped from the mask.  Served by the boolean kernels of a generated
+ * attached-point unit (compiled ahead of time or by hipcc at run time; a unit loaded as a code object has none).  Without one: the
+ * two launches trk_fk_points + trk_collision_fields through point_pos_ws [batch*horizon, n_points, 3] (TRK_ERR_INVALID_ARG when it is
+ * NULL; TRK_ERR_UNSUPPORTED in strict mode when the point set has generated kernels).  trk_last_dispatch tells which. */
+int trk_rollout_points_collision(const TrkPointSet* ps, const TrkCostModel* cm, int32_t fields, const float* q, int64_t batch,
+                                 int32_t horizon, float margin_override, uint8_t* in_collision, float* point_pos_ws,
+                                 trk_stream_t stream);
+
+/* trk_rollout_collision_via / _via_flags for such a cost model: the via points are interpolated in the kernel (reference:
+ * PlanningTask.get_trajs_collision_and_free tasks.py:244-251).  traj_flags, q_min and q_max are given together (the per-wavefront
+ * partial flags of trk_rollout_collision_via_flags, trk_via_partial_flags_bytes(n_traj, horizon, n_interp) bytes, ready for
+ * trk_traj_validate) or all NULL.  Served by the generated boolean kernels only: TRK_ERR_UNSUPPORTED when none serves the point
+ * set / cost model -- the caller then runs trk_interpolate_via_points + trk_rollout_points_collision. */
+int trk_rollout_points_collision_via(const TrkPointSet* ps, const TrkCostModel* cm, int32_t fields, const float* x, int64_t n_traj,
+                                     int32_t horizon, int32_t state_dim, int32_t n_interp, const float* alpha, const float* beta,
+                                     float margin_override, const float* q_min, const float* q_max, uint8_t* in_collision,
+                                     uint8_t* traj_flags, trk_stream_t stream);
 
 /* The rest of get_trajs_collision_and_free (tasks.py:253-299) on the device: three launches, no host round trip (two when
  * `waypoint_collisions` is the partial_flags buffer of trk_rollout_collision_via_flags and n_waypoints = -(samples per trajectory):

@@ -38,6 +38,7 @@ EXPORTS = [
     "trk_scene2d_create", "trk_scene2d_destroy", "trk_scene2d_cost_grad", "trk_scene2d_collision", "trk_scene2d_collision_via",
     "trk_grid2d_precompute", "trk_scene2d_sdf_points", "trk_scene2d_traj_cost_grad", "trk_scene2d_traj_adam_steps",
     "trk_rollout_gp_adam_steps",
+    "trk_rollout_points_collision", "trk_rollout_points_collision_via",
 ]
 
 
@@ -196,6 +197,8 @@ def lib():
     L.trk_scene2d_traj_adam_steps.argtypes = [vp, C.POINTER(_abi.PlanarObjective), C.POINTER(_abi.PlanarAdam), vp, vp, vp, vp, i64, i32, vp, vp]
     L.trk_rollout_gp_adam_steps.argtypes = [vp, vp, C.POINTER(_abi.RolloutWeights), C.POINTER(_abi.GpPrior), C.POINTER(_abi.TrajAdam),
                                             vp, vp, vp, vp, i64, i32, vp, vp]
+    L.trk_rollout_points_collision.argtypes = [vp, vp, i32, vp, i64, i32, f32, vp, vp, vp]
+    L.trk_rollout_points_collision_via.argtypes = [vp, vp, i32, vp, i64, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)        # AttributeError here = the library does not export the ABI
         if name not in ("trk_last_error", "trk_model_destroy", "trk_cost_model_destroy", "trk_point_set_destroy",

@@ -3050,6 +3050,95 @@ def _points_entry_lines(u: _PointsUnit) -> List[str]:
     return out
 
 
+# Wavefronts per SIMD k_pcoll states (__launch_bounds__): the walk keeps one pose chain (12 registers per link that still has
+# children to come), the positions of the earlier columns of pending self pairs (the grasped box: four link origins) and one group of
+# OBJ_GROUP points with its keys -- no wrench, no gradients, no staging row.  Measured per unit and base: DESIGN 4.5.
+POINTS_COLL_OCCUPANCY = 4
+
+
+def _points_coll_kernel(u: _PointsUnit, base_identity: bool) -> List[str]:
+    """k_pcoll_bi / k_pcoll_bg: boolean mode of an attached-point model (trk_rollout_points_collision, ..._via) -- the twin of
+    _points_rollout_kernel that k_coll is of k_rollout.  k_coll's head (q through the LDS transpose, or interpolated from the way
+    points in via mode), then the walk: a link's collision columns are scored against objects / workspace box in groups of at most
+    OBJ_GROUP as soon as the link's pose exists, a self pair at the link that owns its later column (the earlier column's position
+    is still a named value).  `hit` ORs every test; one byte per sample leaves, plus the per-trajectory partial flags in via mode.
+    No wrench, no staged positions, no position stores: a column that no test reads is never computed."""
+    kin, L = u.kin, u.L
+    E = Emitter()
+    _kernel_head(E, "k_pcoll_bi" if base_identity else "k_pcoll_bg", POINTS_COLL_OCCUPANCY, "D", spheres=True)
+    E.raw("    float q[D];")
+    E.raw("    unsigned via_slot = 0u;")
+    E.raw("    int64_t via_traj0 = 0;")
+    E.raw("    bool via_outside = false;")
+    E.raw("    if (A.via_n > 0) spec_load_q_via<D>(A, base, rows, lane, q, via_slot, via_traj0, via_outside);     // trajectory validation: interpolate the via points here")
+    E.raw("    else spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
+    E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
+    w = _WrenchWalk(u, E, base_identity)          # for the pose tables and colpos (the column arithmetic of the cost rollout); no wrench is declared
+    _emit_angles(E, kin)
+    E.raw("    bool hit = false;")
+    E.raw("    const bool test_scene = (A.coll_fields & (TRK_FIELD_OBJECTS | TRK_FIELD_WS)) != 0, test_self = (A.coll_fields & TRK_FIELD_SELF) != 0;      // wave-uniform")
+    in_pair = {c for pr in u.pt.self_pairs for c in pr}
+    for p in range(L):
+        i = int(kin.order[p])
+        if p > 0:
+            _emit_fk_link(E, kin, i, w.R, w.t, w.passv, u.snap)
+        for c in u.cols_of_link[i]:
+            if c in u.obj_rank or c in in_pair:
+                w.colpos(i, c)
+                if c in in_pair:                        # a pair's column outlives its link: a named value, not an expression
+                    w.pos[c] = [E.named(v) for v in w.pos[c]]
+        ocols = [c for c in u.cols_of_link[i] if c in u.obj_rank]
+        for g0 in range(0, len(ocols), OBJ_GROUP):
+            grp = ocols[g0:g0 + OBJ_GROUP]
+            n, mb = len(grp), u.obj_rank[grp[0]]
+            assert [u.obj_rank[c] for c in grp] == list(range(mb, mb + n))          # one run of margins per group
+            E.raw("    if (test_scene) {")
+            for k, nm in enumerate("xyz"):
+                E.raw(f"        const float p{nm}[{n}] = {{{', '.join(E.expr(w.pos[c][k]) for c in grp)}}};")
+            E.raw(f"        hit |= spec_collision_links<{n}>(A.C, A.coll_fields, A.coll_margin, A.coll_use_default, px, py, pz, lds_sph, {mb});")
+            E.raw("    }")
+        if u.pairs_at[i]:
+            E.raw("    if (test_self) {")
+            for pi, late, early, late_is_a in u.pairs_at[i]:
+                a, b = (late, early) if late_is_a else (early, late)
+                pa = ", ".join(E.expr(w.pos[a][k]) for k in range(3))
+                pb = ", ".join(E.expr(w.pos[b][k]) for k in range(3))
+                E.raw(f"        hit |= spec_self_hit(A.coll_use_default ? cptr(A.C.self_margin)[{pi}] : A.coll_margin, {pa}, {pb});")
+            E.raw("    }")
+    E.raw("    if (lane < rows) A.coll_out[base + lane] = hit ? 1 : 0;")
+    E.raw("    if (A.via_n > 0 && A.via_partial) spec_via_partial_flags(A, wblock, via_traj0, via_slot, hit, via_outside, lane < rows, lane);     // wave-uniform")
+    E.raw("}")
+    return E.lines
+
+
+def points_collision_kernels(ident: str) -> List[str]:
+    """the kernels a spec_<ident>_coll unit defines"""
+    return [f"spec_{ident}::k_pcoll_{b}" for b in ("bi", "bg")]
+
+
+def generate_points_collision_source(kin: KinModel, pt: PointsTemplate, ident: str, snap: float = SNAP) -> str:
+    """spec_<ident>_coll.hip: the boolean kernels of an attached-point model (_points_coll_kernel), a translation unit of its own next
+    to generate_points_rollout_source's -- same namespace, same _PointsUnit plan, nothing shared but the headers.  The main unit's
+    registry entry has no slot for it: the unit announces its launcher under the main unit's ident and hashes
+    (trk_spec_register_points_coll), and trk_rollout_points_collision looks it up by those of the entry that serves the cost model.
+    Linked / dlopen-ed units only: a code-object (hipRTC) build of the model carries no boolean kernel."""
+    u = _PointsUnit(kin, pt, ident, snap)
+    out: List[str] = [f"// GENERATED by torch_robotics_amd/codegen.py for model '{kin.name}' ({u.L} links, {u.D} DOF) with {u.P} attached points: "
+                      f"boolean collision kernels -- do not edit."]
+    out.append('#include "trk_spec_common.h"')
+    out.append(f"namespace spec_{ident} {{")
+    out.append(f"constexpr int L = {u.L}, D = {u.D}, P = {u.P};")
+    for base_identity in (True, False):
+        out.extend(_points_coll_kernel(u, base_identity) + [""])
+    out.append("#ifndef __HIPCC_RTC__          // the unit's host half: its launcher, announced under the main unit's ident and hashes")
+    out += _launcher_lines("pcoll")
+    out.append(f"static struct RegPointsColl {{ RegPointsColl() {{ trk_spec_register_points_coll(\"{ident}\", 0x{model_hash(kin):016x}ull, "
+               f"0x{u.points_hash:016x}ull, (uint32_t)sizeof(SpecArgs), launch_pcoll); }} }} reg_points_coll;")
+    out.append("#endif      // !__HIPCC_RTC__")
+    out.append(f"}}  // namespace spec_{ident}")
+    return "\n".join(out) + "\n"
+
+
 def link_points_template(kin: KinModel, tmpl: CollisionTemplate) -> PointsTemplate:
     """a CollisionTemplate expressed as a point set: every link origin, file order (requires file order == walk order)"""
     if [int(v) for v in kin.order] != list(range(kin.n_links)):
@@ -3240,6 +3329,13 @@ def generate_all(out_dir) -> List[str]:
         kin = KinModel.from_urdf(str(URDF_DIR / urdf))
         src = generate_points_rollout_source(kin, tmpl_fn(kin), ident)
         path = out_dir / f"spec_{ident}.hip"
+        if not path.exists() or path.read_text() != src:
+            path.write_text(src)
+        written.append(path.name)
+    for ident, (urdf, tmpl_fn) in SPEC_POINT_ROBOTS.items():           # their boolean kernels: units of their own, after the main ones
+        kin = KinModel.from_urdf(str(URDF_DIR / urdf))
+        src = generate_points_collision_source(kin, tmpl_fn(kin), ident)
+        path = out_dir / f"spec_{ident}_coll.hip"
         if not path.exists() or path.read_text() != src:
             path.write_text(src)
         written.append(path.name)

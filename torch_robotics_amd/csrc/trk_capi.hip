@@ -122,6 +122,33 @@ int trk_spec_register_traj_adam(const SpecEntry* e, uint32_t sizeof_args, SpecTr
     traj_adam_registry().emplace_back(e, fn);
     return 0;
 }
+// the boolean kernels of the attached-point units (k_pcoll): translation units of their own, which name the main unit they belong to
+// by its ident and hashes.  Nothing here depends on which of the two registered first.
+namespace {
+struct PointsCollUnit { std::string ident; uint64_t model_hash, points_hash; SpecLaunchFn fn; };
+std::vector<PointsCollUnit>& points_coll_registry() { static std::vector<PointsCollUnit> r; return r; }
+// a run-time unit registers from the thread that loads it (jit.specialize_points) while other threads may be dispatching
+std::mutex& points_coll_mutex() { static std::mutex m; return m; }
+SpecLaunchFn points_coll_launcher(const SpecEntry* e) {
+    if (!e->name || e->module_ctx) return nullptr;          // (a code-object unit has no boolean kernel)
+    std::lock_guard<std::mutex> lock(points_coll_mutex());
+    for (const auto& r : points_coll_registry())
+        if (r.model_hash == e->model_hash && r.points_hash == e->points_hash && r.ident == e->name) return r.fn;
+    return nullptr;
+}
+}  // namespace
+int trk_spec_register_points_coll(const char* ident, uint64_t model_hash, uint64_t points_hash, uint32_t sizeof_args, SpecLaunchFn fn) {
+    if (!ident || !fn || sizeof_args != sizeof(SpecArgs)) {
+        fprintf(stderr, "libtrk: refusing a generated unit's boolean point kernels (compiled against another SpecArgs layout) -- they "
+                        "will not be dispatched\n");
+        return TRK_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lock(points_coll_mutex());
+    for (auto& r : points_coll_registry())
+        if (r.model_hash == model_hash && r.points_hash == points_hash && r.ident == ident) { r.fn = fn; return 0; }
+    points_coll_registry().push_back(PointsCollUnit{ident, model_hash, points_hash, fn});
+    return 0;
+}
 int trk_spec_layout_stamp(int64_t* out) {
     if (!out) return TRK_ERR_INVALID_ARG;
     out[0] = TRK_SPEC_ABI_VERSION; out[1] = (int64_t)(sizeof(SpecArgs) + sizeof(IkArgs) + sizeof(IkGnArgs)); out[2] = (int64_t)sizeof(DevCostHdr);
@@ -1812,6 +1839,105 @@ int trk_rollout_points_cost_grad(const TrkModel* m, const TrkPointSet* ps, const
     trk_launch_rollout_generic(m->hdr, m->d_links, m->d_fin, &ps->dev, cm->hdr, *w, 0, 1.0f, q, n, point_pos_out, cost, gq, cost_sum, (hipStream_t)stream);
     TRK_HIP(last_launch_error());
     return TRK_OK;
+}
+
+// Boolean mode of the attached-point models.  What both entry points check alike, in this order (nothing of a handle beyond its own
+// header is read before the arguments are sound): the handles, the mask, the sizes -- then that the point set is a live one of a
+// supported model and that the cost model's columns are its points.
+static int check_points_collision_call(const char* who, const TrkPointSet* ps, const TrkCostModel* cm, int32_t fields, int64_t batch,
+                                       int32_t horizon, int32_t min_horizon) {
+    if (!ps) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null point set");
+    if (!cm) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null cost model");
+    if ((fields & ~7) || !fields) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": bad fields");
+    if (batch < 0 || horizon < min_horizon) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": bad batch/horizon");
+    return TRK_OK;
+}
+static int check_points_collision_handles(const char* who, const TrkPointSet* ps, const TrkCostModel* cm) {
+    if (!ps->model) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": the point set belongs to no model");
+    if (int rc = check_model(ps->model, who)) return rc;
+    if (cm->hdr.n_links_in != ps->dev.n_points) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": cost model n_links_in != number of points");
+    return TRK_OK;
+}
+// the unit that serves (ps, cm, effective mask) and its boolean launcher; both null when there is none
+static SpecLaunchFn points_coll_for(const TrkPointSet* ps, const TrkCostModel* cm, const TrkRolloutWeights* w, const SpecEntry** e) {
+    *e = ps->model->spec_enabled ? points_spec_for(ps, cm, w) : nullptr;      // also: the unit bakes the cost model's column sets for these fields
+    return *e ? points_coll_launcher(*e) : nullptr;
+}
+
+int trk_rollout_points_collision(const TrkPointSet* ps, const TrkCostModel* cm, int32_t fields, const float* q, int64_t batch,
+                                 int32_t horizon, float margin_override, uint8_t* in_collision, float* point_pos_ws, trk_stream_t stream) {
+    const char* who = "trk_rollout_points_collision";
+    int rc = check_points_collision_call(who, ps, cm, fields, batch, horizon, 1);
+    if (rc) return rc;
+    const int64_t n = batch * horizon;
+    if (n > 0 && (!q || !in_collision)) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_points_collision: null q / in_collision");
+    if ((rc = check_points_collision_handles(who, ps, cm)) != TRK_OK) return rc;
+    if (n == 0) return TRK_OK;
+    const TrkModel* m = ps->model;
+    const int32_t eff = effective_fields(cm, fields);
+    if (!eff) {                                 // nothing to test: nobody collides
+        TRK_HIP(hipMemsetAsync(in_collision, 0, (size_t)n, (hipStream_t)stream));
+        g_last_dispatch = TRK_DISPATCH_NONE;
+        return TRK_OK;
+    }
+    const TrkRolloutWeights w = field_weights(eff, true);
+    const SpecEntry* e = nullptr;
+    if (SpecLaunchFn fn = points_coll_for(ps, cm, &w, &e)) {
+        SpecArgs a;
+        spec_args(a, m, cm, &w);
+        a.q = q; a.n = n;
+        bind_collision(a, in_collision, eff, margin_override);
+        return served_generated(spec_launch(fn, e, a, m, stream));
+    }
+    if (strict_specialized() && m->spec_enabled && points_spec(ps))
+        return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_points_collision: strict mode: the point set has generated kernels but no boolean kernel that bakes this "
+                                         "cost model's columns for the fields asked for -- the call would take the two-launch path");
+    g_last_dispatch = TRK_DISPATCH_TABLE;
+    // the two launches: every point's position into the caller's scratch, then the field kernel on them (the mask as given, like a
+    // caller of trk_fk_points + trk_collision_fields)
+    if (!point_pos_ws) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_points_collision: no generated boolean kernel serves this point set / cost model and no point_pos_ws scratch given");
+    if ((rc = trk_fk_points(m, ps, q, n, point_pos_ws, stream)) != TRK_OK) return rc;
+    return trk_collision_fields(cm, fields, point_pos_ws, n, margin_override, in_collision, stream);
+}
+
+int trk_rollout_points_collision_via(const TrkPointSet* ps, const TrkCostModel* cm, int32_t fields, const float* x, int64_t n_traj,
+                                     int32_t horizon, int32_t state_dim, int32_t n_interp, const float* alpha, const float* beta,
+                                     float margin_override, const float* q_min, const float* q_max, uint8_t* in_collision,
+                                     uint8_t* traj_flags, trk_stream_t stream) {
+    const char* who = "trk_rollout_points_collision_via";
+    int rc = check_points_collision_call(who, ps, cm, fields, n_traj, horizon, 2);
+    if (rc) return rc;
+    if (n_interp < 1 || state_dim < 1 || !alpha || !beta) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_points_collision_via: bad n_interp / state_dim / alpha / beta");
+    if ((traj_flags != nullptr) != (q_min != nullptr) || (traj_flags != nullptr) != (q_max != nullptr))
+        return fail(TRK_ERR_INVALID_ARG, "trk_rollout_points_collision_via: traj_flags (trk_via_partial_flags_bytes), q_min and q_max are given together or not at all");
+    const int64_t hi = (int64_t)(horizon - 1) * n_interp;
+    if (hi > 0x7fffffff - 64) return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_points_collision_via: (horizon - 1) * n_interp too large");
+    const int64_t n = n_traj * hi;
+    if (n > 0 && (!x || !in_collision)) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_points_collision_via: null x / in_collision");
+    if ((rc = check_points_collision_handles(who, ps, cm)) != TRK_OK) return rc;
+    const TrkModel* m = ps->model;
+    if (state_dim < m->hdr.n_dofs) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_points_collision_via: state_dim < the model's DOF");
+    if (n == 0) return TRK_OK;
+    const int32_t eff = effective_fields(cm, fields);
+    // (the fused flags need the generated kernel even when no field has anything to test: the joint limits are looked at there)
+    if (!eff && !traj_flags) {
+        TRK_HIP(hipMemsetAsync(in_collision, 0, (size_t)n, (hipStream_t)stream));
+        g_last_dispatch = TRK_DISPATCH_NONE;
+        return TRK_OK;
+    }
+    const TrkRolloutWeights w = field_weights(eff, true);
+    const SpecEntry* e = nullptr;
+    SpecLaunchFn fn = points_coll_for(ps, cm, &w, &e);
+    if (!fn)
+        return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_points_collision_via: no generated boolean kernel serves this point set / cost model "
+                                         "(use trk_interpolate_via_points + trk_rollout_points_collision)");
+    SpecArgs a;
+    spec_args(a, m, cm, &w);
+    a.q = x; a.n = n;
+    bind_collision(a, in_collision, eff, margin_override);
+    a.via_alpha = alpha; a.via_beta = beta; a.via_n = n_interp; a.via_H = horizon; a.via_S = state_dim;
+    if (traj_flags) { a.via_partial = traj_flags; a.via_slots = trk_via_slots(hi); a.via_qmin = q_min; a.via_qmax = q_max; }
+    return served_generated(spec_launch(fn, e, a, m, stream));
 }
 
 int trk_interpolate_via_points(const float* x, int64_t n_traj, int32_t horizon, int32_t dim, int32_t n_interp,

@@ -159,6 +159,10 @@ typedef void (*SpecTrajAdamLaunchFn)(const SpecEntry* self, const TrajAdamArgs& 
 // a unit that carries k_traj_adam announces its launcher after its entry (a registry of its own: SpecEntry keeps its layout);
 // refused like trk_spec_register when the unit was compiled against another TrajAdamArgs
 int trk_spec_register_traj_adam(const SpecEntry* e, uint32_t sizeof_args, SpecTrajAdamLaunchFn fn);
+// the boolean kernels of an attached-point unit (k_pcoll; trk_rollout_points_collision) live in a translation unit of their own,
+// spec_<ident>_coll, which cannot see the main unit's entry: it announces its launcher under the main unit's ident and hashes, and
+// the dispatcher looks it up by those of the entry points_spec_for chose.  Refused when compiled against another SpecArgs.
+int trk_spec_register_points_coll(const char* ident, uint64_t model_hash, uint64_t points_hash, uint32_t sizeof_args, SpecLaunchFn fn);
 #endif
 
 // trk_ik_step's Adam on one component with every operation rounded once, whatever FP freedoms the unit grants its other code: the

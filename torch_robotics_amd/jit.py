@@ -246,7 +246,8 @@ def _register_code_object(kin: KinModel, ident: str, source: str, kernels, obj_c
 
 def _load_points_unit_rtc(kin: KinModel, pt: "codegen.PointsTemplate", ident: str) -> object:
     """An ATTACHED-POINT unit (link spheres, grasped-object points) without hipcc: its device half compiled in-process, libtrk.so's
-    generic launchers as its host half (trk_spec_register_module with n_points > 0)."""
+    generic launchers as its host half (trk_spec_register_module with n_points > 0).  The fused rollout and the position reverse
+    mode only: no boolean kernel (k_pcoll) -- trk_rollout_points_collision takes its two launches, ..._via declines."""
     meta: dict = {}
     source = codegen.generate_points_rollout_source(kin, pt, ident, meta=meta)
     return _register_code_object(kin, ident, source, meta["kernels"], pt.obj_cols, pt.self_pairs, pt.ee_link, pt.ee2_link,
@@ -417,7 +418,9 @@ def has_matching_points_unit(kin: KinModel, point_link, point_offset, spec) -> b
 
 def specialize_points(kin: KinModel, point_link, point_offset, spec, verbose: bool = False) -> Optional[str]:
     """Generated fused kernel for a robot whose collision columns are attached points (RobotPanda with another sphere
-    table, another grasped object ...).  Returns None when the column layout is not one the generator handles."""
+    table, another grasped object ...).  Returns None when the column layout is not one the generator handles.
+    With hipcc the unit's boolean kernels (codegen.generate_points_collision_source) are compiled and loaded next to it; the hipRTC
+    fall-back carries none: such a robot keeps the two-step boolean path (fk_points + collision_fields)."""
     pt = _points_template_of(kin, point_link, point_offset, spec)
     if pt is None:
         return None
@@ -430,6 +433,12 @@ def specialize_points(kin: KinModel, point_link, point_offset, spec, verbose: bo
         if not (so.exists() and stamp.exists() and stamp.read_text() == _generator_stamp()):
             so = _compile_unit(codegen.generate_points_rollout_source(kin, pt, ident), ident, verbose)
         _loaded[ident] = _load_unit(so, ident)
+        # the unit's boolean kernels (k_pcoll: ops.rollout_points_collision[_via]): a unit of their own, spec_<ident>_coll, cached under
+        # the same stamp; its initialiser announces the launcher under the main unit's ident (trk_spec_register_points_coll)
+        cso, cstamp = JIT_DIR / f"spec_{ident}_coll.so", JIT_DIR / f"spec_{ident}_coll.stamp"
+        if not (cso.exists() and cstamp.exists() and cstamp.read_text() == _generator_stamp()):
+            cso = _compile_unit(codegen.generate_points_collision_source(kin, pt, ident), f"{ident}_coll", verbose)
+        _loaded[f"{ident}_coll"] = C.CDLL(str(cso))
     else:           # no compiler driver on this box: the unit's device half through hipRTC (round 5: attached-point units too)
         _loaded[ident] = _load_points_unit_rtc(kin, pt, ident)
     _loaded_point_templates[ident] = (codegen.model_hash(kin), pt)

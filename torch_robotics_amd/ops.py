@@ -1004,6 +1004,61 @@ def rollout_points_cost_grad(ps: PointSetHandle, cm: CostHandle, weights, q: tor
     return None if pos is None else pos.reshape(lead + (P, 3)), cost.reshape(lead), gq.reshape(lead + (D,))
 
 
+def rollout_points_collision(ps: PointSetHandle, cm: CostHandle, fields: int, q: torch.Tensor, margin: Optional[float] = None) -> torch.Tensor:
+    """`rollout_collision` for a cost model whose columns are the attached points of `ps` (link spheres, grasped-object points):
+    q (B,H,D) or (N,D) -> bool (B,H) / (N,).  One launch of the unit's boolean kernel (k_pcoll), one byte per sample out, no point
+    position stored; `margin=None` uses the fields' own margins.  Where no generated boolean kernel serves the call (no unit for the
+    point set, or one loaded as a code object by the hipRTC fall-back) the library runs `fk_points` + `collision_fields` through a
+    scratch tensor allocated here; `last_dispatch()` tells which."""
+    model = ps.model
+    q = _dev_f32(q, "rollout_points_collision(q)")
+    _check_q_dofs(q, model.n_dofs, "rollout_points_collision(q)")
+    q, lead, B, Hh = _lead_batch_horizon(q, model.n_dofs)
+    n = B * Hh
+    out = torch.empty((n,), device=q.device, dtype=torch.bool)      # the kernel writes 0 / 1 bytes
+    m = float("nan") if margin is None else float(margin)
+    with _on(q.device):
+        rc = lib().trk_rollout_points_collision(ps._h, cm._h, int(fields), q.data_ptr(), B, Hh, m, out.data_ptr(), None, _stream(q))
+        if rc == _abi.TRK_ERR_INVALID_ARG and n > 0:       # no boolean kernel serves the call: the two launches need scratch (as rollout_collision)
+            ws = torch.empty((n, ps.n_points, 3), device=q.device, dtype=torch.float32)
+            rc = lib().trk_rollout_points_collision(ps._h, cm._h, int(fields), q.data_ptr(), B, Hh, m, out.data_ptr(), ws.data_ptr(), _stream(q))
+        check(rc, "trk_rollout_points_collision")
+    return out.reshape(lead)
+
+
+def rollout_points_collision_via(ps: PointSetHandle, cm: CostHandle, fields: int, trajs: torch.Tensor, num_interpolation: int,
+                                 margin: Optional[float] = None, limits=None):
+    """`rollout_collision_via` for a cost model whose columns are the attached points of `ps`, same return contract: bool
+    (T, (H-1) * num_interpolation) -- with limits=(q_min, q_max): (bool tensor, flags buffer for `traj_validate(..., flags=...)`) --
+    or None when no generated boolean kernel serves the point set / cost model (a unit loaded by the hipRTC fall-back has none): the
+    caller then interpolates first."""
+    model = ps.model
+    x = _dev_f32(trajs, "rollout_points_collision_via(trajs)")
+    T, H, S = (int(v) for v in x.shape)
+    if S < model.n_dofs:
+        raise ValueError(f"rollout_points_collision_via: way points have {S} columns, the model has {model.n_dofs} DOF")
+    n = int(num_interpolation)
+    alpha, beta = via_point_weights(n, x.device)
+    out = torch.empty((T, (H - 1) * n), device=x.device, dtype=torch.bool)
+    m = float("nan") if margin is None else float(margin)
+    small, qmin_p, qmax_p, flags_p = None, None, None, None
+    if limits is not None:
+        q_min, q_max = limits
+        _check_buffer(q_min, model.n_dofs, torch.float32, x.device, "rollout_points_collision_via(q_min)")
+        _check_buffer(q_max, model.n_dofs, torch.float32, x.device, "rollout_points_collision_via(q_max)")
+        # [counts 16 B | pad 16 B | flags T, padded to 16 | per-wavefront partial flags]: the layout traj_validate carries on with
+        nb = int(lib().trk_via_partial_flags_bytes(T, H, n))
+        small = torch.empty(32 + (T + 15) // 16 * 16 + nb, device=x.device, dtype=torch.uint8)
+        qmin_p, qmax_p, flags_p = q_min.data_ptr(), q_max.data_ptr(), small.data_ptr() + 32 + (T + 15) // 16 * 16
+    with _on(x.device):
+        rc = lib().trk_rollout_points_collision_via(ps._h, cm._h, int(fields), x.data_ptr(), T, H, S, n, alpha.data_ptr(), beta.data_ptr(),
+                                                    m, qmin_p, qmax_p, out.data_ptr(), flags_p, _stream(x))
+    if rc == _abi.TRK_ERR_UNSUPPORTED:
+        return None
+    check(rc, "trk_rollout_points_collision_via")
+    return out if limits is None else (out, (small, (H - 1) * n))
+
+
 def gp_prior_cost_grad(q: torch.Tensor, qd: torch.Tensor, dt: float, sigma: float, weight: float = 1.0,
                        accumulate_into=None, grad_dtype=None, grad_scale: float = 1.0):
     """Constant-velocity GP prior over (B,H,D) trajectories (build-defined; include/trk.h): -> (cost (B,), gq, gqd).

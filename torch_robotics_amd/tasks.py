@@ -324,6 +324,11 @@ class PlanningTask(Task):
         if field_type == "occupancy":
             if ps is None:                                    # FK + boolean fields in one launch, one byte per sample out
                 return ops.rollout_collision(model, cm, fields, q.detach(), margin=kwargs.get("margin", None))
+            if _points_collision_fused(ps, "compute_collision"):       # the same for attached points (k_pcoll); declined: strict mode without a boolean kernel
+                try:
+                    return ops.rollout_points_collision(ps, cm, fields, q.detach(), margin=kwargs.get("margin", None))
+                except NotImplementedError:
+                    pass
             pos = ops.fk_points(ps, q.detach())
             return ops.collision_fields(cm, fields, pos, margin=kwargs.get("margin", None)).reshape(q.shape[:-1])
         w = (1.0 if self.df_collision_self is not None else 0.0, 1.0, 1.0, 0.0)
@@ -353,11 +358,15 @@ class PlanningTask(Task):
             # 2-D point mass: interpolation and the boolean test in one launch, the via points never stored
             wp = ops.planar_collision_via(self._planar_handles(flat.device)[0], flat, num_interpolation, margin=0.)
             return wp if limits is None else (wp, None)
-        if self._has_tree and self._points(flat.device) is None and num_interpolation > 0 and flat.shape[1] >= 2:
+        ps = self._points(flat.device) if self._has_tree else None
+        if self._has_tree and (ps is None or _points_collision_fused(ps, "validation")) and num_interpolation > 0 and flat.shape[1] >= 2:
             model, cm = self._fused_handles(flat.device)
             fields = FIELD_OBJECTS | FIELD_WS | (FIELD_SELF if self.df_collision_self is not None else 0)
-            res = ops.rollout_collision_via(model, cm, fields, flat, num_interpolation, margin=0.,
-                                            limits=limits if (limits is not None and limits[0].numel() == model.n_dofs) else None)
+            lim = limits if (limits is not None and limits[0].numel() == model.n_dofs) else None
+            if ps is None:
+                res = ops.rollout_collision_via(model, cm, fields, flat, num_interpolation, margin=0., limits=lim)
+            else:                                           # attached points: k_pcoll's via mode; None where no boolean kernel serves the model
+                res = ops.rollout_points_collision_via(ps, cm, fields, flat, num_interpolation, margin=0., limits=lim)
             if res is not None:
                 if limits is None:
                     return res
@@ -413,6 +422,22 @@ class PlanningTask(Task):
     def compute_success_free_trajs(self, trajs, **kwargs):
         _, trajs_free = self.get_trajs_collision_and_free(trajs)
         return 1 if (trajs_free is not None and trajs_free.nelement() >= 1) else 0
+
+
+# (columns of the point set, call) for which the fused boolean kernel did NOT beat the two-step routing by more than the spread of the
+# measurement's windows (tools/bench_points_collision.py): those stay on the two-step routing unless the switch asks
+POINTS_COLLISION_TWO_STEP_BY_DEFAULT = frozenset()
+
+
+def _points_collision_fused(ps, call: str) -> bool:
+    """Attached-point models (link spheres, grasped object): does `call` ("compute_collision" / "validation") take the fused boolean
+    kernel (ops.rollout_points_collision[_via])?  TRK_POINTS_COLLISION_FUSED=0 keeps the two-step routing -- fk_points +
+    collision_fields, the via points materialised first -- and =1 takes the fused kernel: the A/B switch, read per call.  Unset: by
+    what was measured for the model and call."""
+    env = os.environ.get("TRK_POINTS_COLLISION_FUSED")
+    if env is not None:
+        return env != "0"
+    return (ps.n_points, call) not in POINTS_COLLISION_TWO_STEP_BY_DEFAULT
 
 
 class GraphedCostBackward:
