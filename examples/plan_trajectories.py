@@ -8,10 +8,14 @@ where every cost / gradient evaluation is ONE launch of `trk_rollout_gp_cost_gra
 with the GP prior fused in: `task.rollout_gp_plan`); the result is validated the way the reference does it after planning
 (`get_trajs_collision_and_free`: 5 via points per segment, fused FK + boolean fields).  Needs the MI355X: there is no CPU path.
 
-    python examples/plan_trajectories.py [--batch 256] [--horizon 64] [--iters 200] [--fused]
+    python examples/plan_trajectories.py [--batch 256] [--horizon 64] [--iters 200] [--fused] [--via-cost N]
 
 --fused runs the same problem with the whole loop on the chip (`task.rollout_adam_plan(...).step(32)`, `trk_rollout_gp_adam_steps`):
 trajectories and Adam's state stay in registers, one launch per 32 iterations (horizons that are a power of two up to 64).
+--via-cost N (eager loop, horizons up to 64) adds the collision cost at N via points per segment -- the configurations the
+validation judges and the optimiser otherwise never sees -- through one more launch per iteration (`task.rollout_via_plan`,
+`trk_rollout_via_cost_grad`: its gradient arrives at the way points), and prints the collision-free count of both runs (the problem
+is solved twice for that); it cannot be combined with --fused.
 """
 import argparse
 import sys
@@ -26,7 +30,11 @@ import torch_robotics_amd as tra
 from torch_robotics_amd import ops
 
 
-def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0, fused=False, stats=None):
+def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0, fused=False, stats=None, via_cost=0):
+    if via_cost > 0 and fused:
+        raise ValueError("--via-cost belongs to the eager loop: the planning-loop kernel of --fused has no via-point term")
+    if via_cost > 0:                       # the same problem (same seed) without the via-point term first, for the comparison
+        n_free_plain = main(batch, horizon, iters, device, False, seed)[1]
     torch.manual_seed(seed)
     ta = dict(device=torch.device(device), dtype=torch.float32)
     robot = tra.RobotPanda(tensor_args=ta)
@@ -46,6 +54,8 @@ def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0
         return _main_fused(task, q, qd, q_start + s * (q_goal - q_start), dt, sigma_gp, w_obj, lr, iters, verbose, stats)
     # pre-bound launch: reads q, qd in place; cost = w_obj * (self + object + workspace hinges) + the prior's factor costs
     plan = task.rollout_gp_plan(q, qd, dt, sigma_gp, gp_weight=1.0, w_self=w_obj, w_obj=w_obj, w_ws=w_obj)
+    # the collision hinges at via_cost via points per segment, same weights: one more launch, its gradient lands on the way points
+    via = task.rollout_via_plan(q, via_cost, w_self=w_obj, w_obj=w_obj, w_ws=w_obj) if via_cost > 0 else None
     free_mask = torch.ones(1, horizon, 1, **ta)
     free_mask[:, 0] = 0.0
     free_mask[:, -1] = 0.0                                               # start and goal stay fixed
@@ -59,7 +69,11 @@ def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0
             # the prior's share of plan.cost, from the SAME q / qd the launch read (before the step moves them in place)
             c_gp = ops.gp_prior_cost_grad(q, qd, dt, sigma_gp)[0]
             hist.append((it, float((plan.cost.sum(1) - c_gp).mean()) / w_obj, float(c_gp.mean())))
-        q.grad = free_mask * plan.gq                                     # gradients come from the kernel, not from autograd
+        if via is not None:
+            via.launch()
+            q.grad = free_mask * (plan.gq + via.gq)
+        else:
+            q.grad = free_mask * plan.gq                                 # gradients come from the kernel, not from autograd
         qd.grad = plan.gqd
         opt.step()                                                       # in place: the plan keeps reading q's and qd's buffers
     torch.cuda.synchronize()
@@ -73,6 +87,8 @@ def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0
         print(f"{iters} iterations x {batch * horizon} configurations in {elapsed * 1e3:.1f} ms "
               f"({batch * horizon * iters / elapsed:.3g} FK+cost+grad evaluations/s incl. the Python loop)")
         print(f"straight lines in collision: {coll0 * 100:.0f} %   collision-free after optimisation: {n_free}/{batch}")
+        if via is not None:
+            print(f"collision-free without the via-point cost: {n_free_plain}/{batch}   with it ({via_cost} per segment): {n_free}/{batch}")
     return q, n_free, coll0
 
 
@@ -112,5 +128,6 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--fused", action="store_true", help="the whole loop in one kernel (rollout_adam_plan)")
+    ap.add_argument("--via-cost", type=int, default=0, help="N > 0: add the collision cost at N via points per segment (eager loop)")
     a = ap.parse_args()
-    main(a.batch, a.horizon, a.iters, a.device, fused=a.fused)
+    main(a.batch, a.horizon, a.iters, a.device, fused=a.fused, via_cost=a.via_cost)

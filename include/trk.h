@@ -449,14 +449,15 @@ int trk_rollout_jacobian_cost_grad(const TrkModel* model, const TrkCostModel* cm
 int trk_rollout_is_specialized(const TrkModel* model, const TrkCostModel* cm, const TrkRolloutWeights* w);
 
 /* Which kernel family served the CALLING THREAD's latest rollout call (trk_rollout_cost_grad[_f16], trk_rollout_gp_cost_grad,
- * trk_rollout_points_cost_grad, trk_rollout_collision[_via], trk_rollout_points_collision[_via]).  No reference counterpart: the reference has one code path
+ * trk_rollout_points_cost_grad, trk_rollout_collision[_via], trk_rollout_points_collision[_via], trk_rollout_via_cost_grad).  No reference counterpart: the reference has one code path
  * (tasks.py:139-232); here a cost model whose link sets no generated unit bakes is served by the table-driven kernels, 10 - 30 x slower. */
 enum {
     TRK_DISPATCH_NONE = 0,                  /* no rollout call yet on this thread (or a call that had nothing to launch) */
     TRK_DISPATCH_GENERATED = 1,             /* one launch of a generated (model-specialised) kernel */
     TRK_DISPATCH_TABLE = 2,                 /* the table-driven kernels */
-    TRK_DISPATCH_GENERATED_PLUS_PRIOR = 3   /* trk_rollout_gp_cost_grad: generated rollout, the GP prior as launches of its own;
+    TRK_DISPATCH_GENERATED_PLUS_PRIOR = 3,  /* trk_rollout_gp_cost_grad: generated rollout, the GP prior as launches of its own;
                                              * trk_rollout_jacobian_cost_grad: generated rollout, the Jacobian as a launch of its own */
+    TRK_DISPATCH_GENERATED_VIA_COST = 4     /* trk_rollout_via_cost_grad: one launch of the generated via-point cost kernel */
 };
 int trk_last_dispatch(void);
 /* The generated rollout kernels come in two families: the generic one, and a plan-specialised one that has the objective terms with
@@ -899,6 +900,28 @@ typedef struct TrkTrajAdam {
 int trk_rollout_gp_adam_steps(const TrkModel* model, const TrkCostModel* cm, const TrkRolloutWeights* weights, const TrkGpPrior* gp,
                               const TrkTrajAdam* adam, float* q, float* qd, float* adam_m, float* adam_v, int64_t batch,
                               int32_t horizon, float* cost, trk_stream_t stream);
+
+/* The collision / EE objective of trk_rollout_cost_grad at the via points BETWEEN the way points of a batch of trajectories, and its
+ * gradient with respect to the way points, in one launch: nothing is materialised in between (reference:
+ * interpolate_traj_via_points trajectory/utils.py:37-50 followed by the collision cost, differentiated through the interpolation).
+ * x [n_traj, horizon, dof] fp32, contiguous (positions only).  Via point a of segment i is
+ *   v[t, i, a] = x[t, i] * alpha[a] + x[t, i + 1] * beta[a],   0 <= i < horizon - 1, 0 <= a < n_interp,
+ * each product and the sum rounded once (no FMA); alpha, beta: DEVICE [n_interp] (alpha = linspace(0, 1, n + 2)[1 : n + 1],
+ * beta = 1 - alpha; a = 0 is the via point nearest x[t, i + 1]).
+ *   cost (nullable) [n_traj, (horizon - 1) * n_interp]   cost[t, i * n_interp + a] = the objective at v[t, i, a]
+ *   gq [n_traj, horizon, dof]                            gq[t, i] = sum_a seed[t, i, a] alpha[a] g(v[t, i, a])
+ *                                                                 + sum_a seed[t, i - 1, a] beta[a] g(v[t, i - 1, a]),
+ * g = the rollout's gradient with respect to the configuration; seed (nullable) [n_traj, (horizon - 1) * n_interp]: the upstream
+ * gradient of every via point's cost, NULL = ones.  Every element of gq is written (no zeroing needed); the way points' own cost is
+ * not part of this call (trk_rollout_cost_grad).  Bit-identical from run to run and however a batch is split into calls.
+ * Validated before any device work; horizon < 2 or n_interp < 1: TRK_ERR_INVALID_ARG.  Served by a generated kernel only
+ * (k_via_cost: link-column units of robots up to 8 DOF); TRK_ERR_UNSUPPORTED when horizon > TRK_VIA_COST_MAX_HORIZON (a wavefront owns
+ * whole trajectories), when no unit of the model carries the kernel, when none matches the cost model, or when
+ * trk_model_enable_specialized is off.  n_traj = 0: TRK_OK without a launch.  No host synchronisation: capturable. */
+#define TRK_VIA_COST_MAX_HORIZON 64
+int trk_rollout_via_cost_grad(const TrkModel* model, const TrkCostModel* cm, const TrkRolloutWeights* weights, const float* x,
+                              int64_t n_traj, int32_t horizon, int32_t n_interp, const float* alpha, const float* beta,
+                              const float* seed, float* cost, float* gq, trk_stream_t stream);
 
 #ifdef __cplusplus
 }

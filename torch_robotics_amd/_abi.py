@@ -132,6 +132,7 @@ class PlanarAdam(C.Structure):          # TrkPlanarAdam
 
 
 TRK_TRAJ_ADAM_MAX_HORIZON = 64
+TRK_VIA_COST_MAX_HORIZON = 64
 
 
 class TrajAdam(C.Structure):            # TrkTrajAdam

@@ -39,6 +39,7 @@ EXPORTS = [
     "trk_grid2d_precompute", "trk_scene2d_sdf_points", "trk_scene2d_traj_cost_grad", "trk_scene2d_traj_adam_steps",
     "trk_rollout_gp_adam_steps",
     "trk_rollout_points_collision", "trk_rollout_points_collision_via",
+    "trk_rollout_via_cost_grad",
 ]
 
 
@@ -199,6 +200,7 @@ def lib():
                                             vp, vp, vp, vp, i64, i32, vp, vp]
     L.trk_rollout_points_collision.argtypes = [vp, vp, i32, vp, i64, i32, f32, vp, vp, vp]
     L.trk_rollout_points_collision_via.argtypes = [vp, vp, i32, vp, i64, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp]
+    L.trk_rollout_via_cost_grad.argtypes = [vp, vp, C.POINTER(_abi.RolloutWeights), vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)        # AttributeError here = the library does not export the ABI
         if name not in ("trk_last_error", "trk_model_destroy", "trk_cost_model_destroy", "trk_point_set_destroy",

@@ -2131,6 +2131,153 @@ def _traj_adam_launcher_lines(u: _LinkUnit) -> List[str]:
     return out
 
 
+# Wavefronts per SIMD k_via_cost runs at.  The estimate is the rollout's registers + 3 D (the way point, its successor and the two
+# gradient accumulators, less the q the rollout keeps anyway); what the compiler reports (-Rpass-analysis=kernel-resource-usage, DESIGN
+# 4.9) decides.  Stating only its block size, the Panda's kernels take 145 (bi) / 162 (bg) VGPRs on sphere scenes -- three wavefronts --
+# and 198 / 205 in the general-scene instantiation -- two --, none with scratch; iiwa7 128 / 130 / 164 / 170, UR10 111 / 109 / 148 / 152.
+# The constant is what every instantiation of every unit reaches; a bound of four (128 registers) would make the Panda's spill.
+VIA_COST_OCCUPANCY = 2
+
+
+def template_identity(tmpl: CollisionTemplate) -> int:
+    """FNV-1a (64 bit) over a link-column template without interpolated columns: (n_obj, obj_links, n_pairs, self_pairs, ee_link,
+    ee2_link) as int32 -- the same bytes trk_capi.hip hashes from a unit's SpecEntry (via_template_identity)."""
+    words = [len(tmpl.obj_links), *tmpl.obj_links, len(tmpl.self_pairs), *(v for p in tmpl.self_pairs for v in p), tmpl.ee_link,
+             tmpl.ee2_link]
+    h = 0xcbf29ce484222325
+    for b in np.asarray(words, np.int32).tobytes():
+        h = ((h ^ b) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def via_cost_ok(kin: KinModel, tmpl: CollisionTemplate, ident: str = "", snap: float = SNAP) -> bool:
+    """does the robot's link unit get a spec_<ident>_via unit?  The whole-row four-wavefront units: the ones that carry k_traj_adam"""
+    u = _LinkUnit(kin, tmpl, ident, snap)
+    return (not u.chunked) and not tmpl.virtual and u.D <= 8
+
+
+def _via_cost_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
+    """k_via_cost_bi / _bg<BOX>: the collision / EE objective of trk_rollout_cost_grad at the n via points of every segment of a batch
+    of trajectories (trk_rollout_via_cost_grad), and its gradient with respect to the WAY points.  One lane per way point, fp32; a
+    wavefront owns 64 / H whole trajectories (any 2 <= H <= 64), so lane (t, i) gets x[t, i + 1] from the next lane by one DPP
+    wavefront shift per joint and hands the gradient's share of x[t, i + 1] back by one shift the other way: nothing crosses a
+    wavefront, no atomics, no barrier, the output is not zeroed first.  Lanes beyond (64 / H) H and beyond the batch run on zeros and
+    store nothing (a wavefront without any row returns at once); a lane without a segment is taken out of the sums by a select.  The run-time loop over the via points of the lane's segment interpolates (each product and the sum rounded once,
+    as spec_load_q_via), runs k_rollout's iteration (same emitters, same scene switch BOX) without positions -- NoFlush -- stores the
+    via point's cost and accumulates the two way points' shares of its gradient in registers."""
+    kin, L, D = u.kin, u.L, u.D
+    E = Emitter()
+    kname = "k_via_cost_bi" if base_identity else "k_via_cost_bg"
+    E.raw("template <bool BOX>      // the scene switch of k_rollout (scene_is_general): boxes and / or a voxel grid")
+    E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK) {kname}(ViaCostArgs A) {{      // {VIA_COST_OCCUPANCY} wavefronts per SIMD (VIA_COST_OCCUPANCY)")
+    E.raw("    constexpr int LDS_LANE = D;            // the transposes of x and gq [64][D]")
+    E.raw("    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * LDS_LANE + SPEC_WAVES * (TRK_LDS_SPHERES * 4 + (BOX ? TRK_LDS_PRIMS * 8 : 0))];")
+    E.raw("    const int lane = __builtin_amdgcn_workitem_id_x() & (TRK_WAVE - 1);")
+    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_workitem_id_x() / TRK_WAVE);")
+    E.raw("    float* lds = lds_all + wave * (TRK_WAVE * LDS_LANE);")
+    E.raw("    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * LDS_LANE) + wave * (TRK_LDS_SPHERES + (BOX ? 2 * TRK_LDS_PRIMS : 0));")
+    E.raw("    float4* lds_prm = BOX ? lds_sph + TRK_LDS_SPHERES : nullptr;")
+    E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);")
+    E.raw("    const SpheresInFlight prm = BOX ? spec_load_prims_issue(A.C, lane) : sph;")
+    E.raw("    // the wavefront's trajectories: 64 / H whole ones, their way points in lanes 0 .. rows - 1 (wave-uniform)")
+    E.raw("    const int64_t wblock = (int64_t)__builtin_amdgcn_workgroup_id_x() * SPEC_WAVES + wave;")
+    E.raw("    const int tpw = TRK_WAVE / A.H;")
+    E.raw("    const int64_t traj0 = wblock * tpw;")
+    E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)tpw, A.T - traj0)) * A.H;      // lanes beyond: zeros, no stores")
+    E.raw("    const int64_t base = traj0 * A.H;")
+    E.raw("    if (rows == 0) return;                 // a wavefront beyond the batch (the last workgroup's): wave-uniform, nothing to shift with")
+    E.raw("    float x[D], xn[D], g_lo[D], g_hi[D];")
+    E.raw("    spec_load_q<D>(A.x, base, rows, lane, lds, x);")
+    E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
+    E.raw("    if constexpr (BOX) spec_load_spheres_finish(lds_prm, lane, prm);")
+    E.raw("    const NoFlush flush{};                 // this kernel writes no positions")
+    E.raw("    // lane (t, i) owns the segment i -> i + 1; a lane at the last way point of a trajectory (or without one) has none: weight 0")
+    E.raw("    const int ti = lane / A.H, tl = lane - ti * A.H;")
+    E.raw("    const bool on = lane < rows && tl != A.H - 1;")
+    E.raw("    const int64_t seg = ((traj0 + ti) * (A.H - 1) + tl) * A.n;        // the segment's first via point in cost / seed")
+    E.raw("#pragma unroll")
+    E.raw("    for (int d = 0; d < D; ++d) {")
+    E.raw("        xn[d] = trk_dpp_from_next(x[d], x[d]);      // lane 63 has no source and keeps its own value (weight 0)")
+    E.raw("        g_lo[d] = 0.0f; g_hi[d] = 0.0f;")
+    E.raw("    }")
+    E.raw("#pragma nounroll")
+    E.raw("    for (int a = 0; a < A.n; ++a) {")
+    E.raw("    const float fa = cptr(A.alpha)[a], fb = cptr(A.beta)[a];")
+    E.raw("    float sd = on ? 1.0f : 0.0f;")
+    E.raw("    if (A.seed) sd = on ? A.seed[seg + a] : 0.0f;       // wave-uniform test")
+    E.raw("    float q[D];")
+    E.raw("#pragma unroll")
+    E.raw("    for (int d = 0; d < D; ++d) q[d] = __fadd_rn(__fmul_rn(x[d], fa), __fmul_rn(xn[d], fb));")
+    # ---------------- forward, objectives, reverse: k_rollout's ----------------
+    R, t, passv = _root_pose(base_identity)
+    _emit_angles(E, kin)
+    for p in range(1, L):
+        _emit_fk_link(E, kin, u.walk[p], R, t, passv, u.snap)
+    ticks = _Ticks()
+    _emit_collision_objectives(u, E, t, ticks, fast_arg=", decltype(ticks), false, BOX", prims_ptr="lds_prm")
+    _emit_ee_terms(E, u.tracked, R, t)
+    E.raw(ticks())
+    gq_expr = _emit_reverse_links(E, kin, R, t, {i: [f"tb{i}_{k}" for k in range(3)] for i in u.real_adj},
+                                  {l: rb for l, _, rb in u.tracked}, u.masked, tick=ticks, order=u.walk)
+    E.raw(f"    const float gc[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
+    E.raw("    if (A.cost && on) store_wt_f1(A.cost + seg + a, cost);")
+    E.raw("    const float sa = sd * fa, sb = sd * fb;")
+    E.raw("#pragma unroll")
+    E.raw("    // a lane without a segment contributes by SELECT, not by its zero weight: its via point is formed with the next trajectory's first")
+    E.raw("    // way point (or zeros), and 0 * (a non-finite gradient) must not reach its neighbours' rows")
+    E.raw("    for (int d = 0; d < D; ++d) { const float gd = on ? gc[d] : 0.0f; g_lo[d] = fmaf(sa, gd, g_lo[d]); g_hi[d] = fmaf(sb, gd, g_hi[d]); }")
+    E.raw("    }")
+    E.raw("    // x[t, i]'s gradient: its own segment's share + the previous segment's, which the previous lane holds.  A lane at the last way")
+    E.raw("    // point holds 0, so a lane at step 0 receives 0; lane 0 has no source and takes the shift's `old` operand, 0.")
+    E.raw("    float gv[D];")
+    E.raw("#pragma unroll")
+    E.raw("    for (int d = 0; d < D; ++d) gv[d] = g_lo[d] + trk_dpp_from_prev(0.0f, g_hi[d]);")
+    E.raw("    spec_store_gq<D>(A.gq, base, rows, lane, lds, gv);")
+    E.raw("}")
+    return E.lines
+
+
+def via_cost_kernels(ident: str) -> List[str]:
+    """the kernels a spec_<ident>_via unit defines"""
+    return [f"spec_{ident}::k_via_cost_{b}<{v}>" for b in ("bi", "bg") for v in ("false", "true")]
+
+
+def generate_via_cost_source(kin: KinModel, tmpl: CollisionTemplate, ident: str, snap: float = SNAP) -> str:
+    """spec_<ident>_via.hip: the via-point cost kernels of a link-column unit (_via_cost_kernel), a translation unit of its own next to
+    generate_rollout_source's -- same namespace, same _LinkUnit plan, the same FP freedoms, nothing shared but the headers.  The main
+    unit's registry entry has no slot for it: the unit announces its launcher under the main unit's ident, model hash and template
+    identity (trk_spec_register_via_cost), and trk_rollout_via_cost_grad looks it up by those of the entry that serves the cost model.
+    Linked / dlopen-ed units only: a code-object (hipRTC) build of the model carries none."""
+    u = _LinkUnit(kin, tmpl, ident, snap)
+    assert (not u.chunked) and not tmpl.virtual and u.D <= 8, "the via-point cost kernel exists for the whole-row four-wavefront units"
+    out: List[str] = [f"// GENERATED by torch_robotics_amd/codegen.py for model '{kin.name}' ({u.L} links, {u.D} DOF): via-point cost "
+                      f"kernels -- do not edit."]
+    out.append("#pragma clang fp reassociate(on) contract(fast) reciprocal(on)")
+    out.append('#include "trk_spec_common.h"')
+    out.append(f"namespace spec_{ident} {{")
+    out.append(f"constexpr int L = {u.L}, D = {u.D}, NL = {u.NL};")
+    out.append(f'static_assert(TRK_OBJ_TICK_SLOTS == {OBJ_TICK_SLOTS}, "chunk numbering of this unit assumes another TRK_OBJ_TICK_SLOTS");')
+    for base_identity in (True, False):
+        out.extend(_via_cost_kernel(u, base_identity) + [""])
+    out.append("#ifndef __HIPCC_RTC__          // the unit's host half: its launcher, announced under the main unit's ident, hash and template")
+    out += ["static void launch_via_cost(const ViaCostArgs& a, int base_identity, hipStream_t st) {",
+            "    const int64_t waves = (a.T + TRK_WAVE / a.H - 1) / (TRK_WAVE / a.H);          // 64 / H whole trajectories per wavefront",
+            "    const unsigned grid = (unsigned)((waves + SPEC_WAVES - 1) / SPEC_WAVES);",
+            f"    if ({u.scene_switch}) {{",
+            "        if (base_identity) hipLaunchKernelGGL((k_via_cost_bi<true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+            "        else hipLaunchKernelGGL((k_via_cost_bg<true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+            "    } else {",
+            "        if (base_identity) hipLaunchKernelGGL((k_via_cost_bi<false>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+            "        else hipLaunchKernelGGL((k_via_cost_bg<false>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+            "    }",
+            "}"]
+    out.append(f"static struct RegViaCost {{ RegViaCost() {{ trk_spec_register_via_cost(\"{ident}\", 0x{model_hash(kin):016x}ull, "
+               f"0x{template_identity(tmpl):016x}ull, (uint32_t)sizeof(ViaCostArgs), launch_via_cost); }} }} reg_via_cost;")
+    out.append("#endif      // !__HIPCC_RTC__")
+    out.append(f"}}  // namespace spec_{ident}")
+    return "\n".join(out) + "\n"
+
+
 def _jac_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     """k_jac_bi / _bg: stateful FK + geometric Jacobian of ONE link (trk_fk_jacobian; robot_tree.py:136-190, 218-248): the walk unrolled
     with the stateful path's quirks (clamp wherever limits exist, rotation about the axis with its sign ignored); every joint that can
@@ -3329,6 +3476,16 @@ def generate_all(out_dir) -> List[str]:
         kin = KinModel.from_urdf(str(URDF_DIR / urdf))
         src = generate_points_rollout_source(kin, tmpl_fn(kin), ident)
         path = out_dir / f"spec_{ident}.hip"
+        if not path.exists() or path.read_text() != src:
+            path.write_text(src)
+        written.append(path.name)
+    for ident, (urdf, tmpl_fn) in SPEC_ROBOTS.items():                 # the via-point cost kernels of the small arms: units of their own
+        kin = KinModel.from_urdf(str(URDF_DIR / urdf))
+        tmpl = tmpl_fn(kin)
+        if not via_cost_ok(kin, tmpl, ident):
+            continue
+        src = generate_via_cost_source(kin, tmpl, ident)
+        path = out_dir / f"spec_{ident}_via.hip"
         if not path.exists() or path.read_text() != src:
             path.write_text(src)
         written.append(path.name)

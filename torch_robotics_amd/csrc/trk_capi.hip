@@ -149,6 +149,41 @@ int trk_spec_register_points_coll(const char* ident, uint64_t model_hash, uint64
     points_coll_registry().push_back(PointsCollUnit{ident, model_hash, points_hash, fn});
     return 0;
 }
+// the via-point cost kernels of the small link-column units (k_via_cost): translation units of their own, like the boolean point
+// kernels above, which name the main unit they belong to by its ident, model hash and template identity
+namespace {
+struct ViaCostUnit { std::string ident; uint64_t model_hash, template_identity; SpecViaCostLaunchFn fn; };
+std::vector<ViaCostUnit>& via_cost_registry() { static std::vector<ViaCostUnit> r; return r; }
+std::mutex& via_cost_mutex() { static std::mutex m; return m; }       // (a run-time unit registers from the thread that loads it)
+// must hash the same bytes, in the same order, as torch_robotics_amd/codegen.py: template_identity
+uint64_t via_template_identity(const SpecEntry* e) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    h = fnv1a(h, &e->n_obj_links, 4); h = fnv1a(h, e->obj_link_idx, 4 * (size_t)e->n_obj_links);
+    h = fnv1a(h, &e->n_self_pairs, 4); h = fnv1a(h, e->self_pairs, 8 * (size_t)e->n_self_pairs);
+    h = fnv1a(h, &e->ee_link, 4); h = fnv1a(h, &e->ee2_link, 4);
+    return h;
+}
+SpecViaCostLaunchFn via_cost_launcher(const SpecEntry* e) {
+    if (!e->name || e->module_ctx || e->n_points != 0 || e->n_virtual != 0) return nullptr;      // (a code-object unit has none)
+    const uint64_t id = via_template_identity(e);
+    std::lock_guard<std::mutex> lock(via_cost_mutex());
+    for (const auto& r : via_cost_registry())
+        if (r.model_hash == e->model_hash && r.template_identity == id && r.ident == e->name) return r.fn;
+    return nullptr;
+}
+}  // namespace
+int trk_spec_register_via_cost(const char* ident, uint64_t model_hash, uint64_t template_identity, uint32_t sizeof_args, SpecViaCostLaunchFn fn) {
+    if (!ident || !fn || sizeof_args != sizeof(ViaCostArgs)) {
+        fprintf(stderr, "libtrk: refusing a generated unit's via-point cost kernels (compiled against another ViaCostArgs layout) -- they "
+                        "will not be dispatched\n");
+        return TRK_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lock(via_cost_mutex());
+    for (auto& r : via_cost_registry())
+        if (r.model_hash == model_hash && r.template_identity == template_identity && r.ident == ident) { r.fn = fn; return 0; }
+    via_cost_registry().push_back(ViaCostUnit{ident, model_hash, template_identity, fn});
+    return 0;
+}
 int trk_spec_layout_stamp(int64_t* out) {
     if (!out) return TRK_ERR_INVALID_ARG;
     out[0] = TRK_SPEC_ABI_VERSION; out[1] = (int64_t)(sizeof(SpecArgs) + sizeof(IkArgs) + sizeof(IkGnArgs)); out[2] = (int64_t)sizeof(DevCostHdr);
@@ -1805,6 +1840,58 @@ int trk_rollout_gp_adam_steps(const TrkModel* m, const TrkCostModel* cm, const T
         if ((rc = spec_launch(fn, e, a, m, stream)) != TRK_OK) return rc;
     }
     return served_generated(TRK_OK);
+}
+
+int trk_rollout_via_cost_grad(const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w, const float* x, int64_t n_traj,
+                              int32_t horizon, int32_t n_interp, const float* alpha, const float* beta, const float* seed, float* cost,
+                              float* gq, trk_stream_t stream) {
+    const char* who = "trk_rollout_via_cost_grad";
+    int rc = check_model(m, who);
+    if (rc) return rc;
+    if (!cm) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null cost model");
+    if (!w) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null weights");
+    if (n_traj < 0 || horizon < 2) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": bad n_traj/horizon (a trajectory has at least one segment)");
+    if (n_interp < 1) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": n_interp must be >= 1");
+    if (!std::isfinite(w->w_self) || !std::isfinite(w->w_obj) || !std::isfinite(w->w_ws) || !std::isfinite(w->w_ee))
+        return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": the weights must be finite");
+    if (!alpha || !beta) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null alpha / beta");
+    if (n_traj > 0 && (!x || !gq)) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null x / gq");
+    if (cm->hdr.n_links_in != m->hdr.n_links) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": cost model n_links_in != model n_links");
+    if (horizon > TRK_VIA_COST_MAX_HORIZON)
+        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": the horizon must be <= TRK_VIA_COST_MAX_HORIZON (64): a wavefront owns whole "
+                                         "trajectories and a way point's successor is the next lane; trk_interpolate_via_points + "
+                                         "trk_rollout_cost_grad serve any horizon");
+    if (n_traj == 0 || m->hdr.n_dofs == 0) return TRK_OK;
+    // only the generated kernel serves this call (no table-driven twin, like trk_rollout_gp_adam_steps)
+    if (!m->spec_enabled)
+        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": generated kernels are switched off for this model (trk_model_enable_specialized) "
+                                         "and the via-point cost has no table-driven form");
+    const TrkRolloutWeights we = effective_weights(cm, *w);
+    SpecViaCostLaunchFn fn = nullptr;
+    bool any = false;
+    for (const SpecEntry* c : spec_registry()) {
+        if (c->n_points != 0 || c->model_hash != m->hash || c->n_links != m->hdr.n_links || c->n_dofs != m->hdr.n_dofs) continue;
+        SpecViaCostLaunchFn f = via_cost_launcher(c);
+        if (!f) continue;
+        any = true;
+        if (spec_matches(c, cm, &we)) { fn = f; break; }
+    }
+    if (!any)
+        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": no generated unit of this model carries the via-point cost kernel (k_via_cost: "
+                                         "link-column units of robots up to 8 DOF, built ahead of time or by hipcc at run time; a unit "
+                                         "loaded as a code object through the hipRTC fall-back has none)");
+    if (!fn)
+        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": no generated unit with the via-point cost kernel bakes this cost model's link "
+                                         "sets for the non-zero weights");
+    ViaCostArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.C = cm->hdr; a.w = we;
+    set_base_pose(a, m);
+    a.x = x; a.seed = seed; a.cost = cost; a.gq = gq; a.T = n_traj; a.H = horizon; a.n = n_interp; a.alpha = alpha; a.beta = beta;
+    fn(a, base_is_identity(m), (hipStream_t)stream);
+    TRK_HIP(last_launch_error());
+    g_last_dispatch = TRK_DISPATCH_GENERATED_VIA_COST;
+    return TRK_OK;
 }
 
 int trk_rollout_points_cost_grad(const TrkModel* m, const TrkPointSet* ps, const TrkCostModel* cm, const TrkRolloutWeights* w,

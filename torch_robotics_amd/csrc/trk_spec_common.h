@@ -165,6 +165,32 @@ int trk_spec_register_traj_adam(const SpecEntry* e, uint32_t sizeof_args, SpecTr
 int trk_spec_register_points_coll(const char* ident, uint64_t model_hash, uint64_t points_hash, uint32_t sizeof_args, SpecLaunchFn fn);
 #endif
 
+// Arguments of the generated via-point cost kernel (k_via_cost; trk_rollout_via_cost_grad): the cost header, weights and base pose
+// under the names SpecArgs gives them (the objective emitters read A.C / A.w / A.base_*), the way points in, the via points' costs
+// and the way points' gradient out.  Its own struct for the reason IkArgs is one.
+struct ViaCostArgs {
+    DevCostHdr C;
+    TrkRolloutWeights w;
+    float base_R[9];
+    float base_t[3];
+    const float* x;               // [T, H, D] way points
+    const float* seed;            // nullable [T, (H - 1) n]: the upstream gradient of every via point's cost (null: ones)
+    float* cost;                  // nullable [T, (H - 1) n]
+    float* gq;                    // [T, H, D]: d (sum of seed * cost) / d x, every element written
+    int64_t T;
+    int32_t H;                    // 2 .. TRK_WAVE: a wavefront owns TRK_WAVE / H whole trajectories
+    int32_t n;                    // via points per segment (>= 1)
+    const float* alpha; const float* beta;      // DEVICE [n]: via point a of segment i = x[i] * alpha[a] + x[i + 1] * beta[a]
+};
+#ifndef __HIPCC_RTC__
+typedef void (*SpecViaCostLaunchFn)(const ViaCostArgs& args, int base_identity, hipStream_t stream);
+// the via-point cost kernels of a link-column unit live in a translation unit of their own, spec_<ident>_via, which cannot see the
+// main unit's entry: it announces its launcher under the main unit's ident, model hash and template identity (FNV-1a over the baked
+// link sets: codegen.template_identity), and the dispatcher looks it up by those of the entry that serves the cost model.  Refused
+// when compiled against another ViaCostArgs.
+int trk_spec_register_via_cost(const char* ident, uint64_t model_hash, uint64_t template_identity, uint32_t sizeof_args, SpecViaCostLaunchFn fn);
+#endif
+
 // trk_ik_step's Adam on one component with every operation rounded once, whatever FP freedoms the unit grants its other code: the
 // update is specified operation by operation (include/trk.h) and k_planar_traj_adam computes exactly this
 __device__ __forceinline__ void spec_adam_component(float g, float step, float rsqrt_bc2, float& x, float& m, float& v) {

@@ -289,7 +289,11 @@ def build_unit(kin: KinModel, tmpl: codegen.CollisionTemplate, verbose: bool = F
 def specialize(kin: KinModel, obj_links: Sequence[int], self_pairs: Sequence[Tuple[int, int]] = (), ee_link: int = -1,
                verbose: bool = False, pipeline: bool = False, ee2_link: int = -1, virtual=()) -> str:
     """Make sure a generated fused kernel for (kin, collision template) is registered with libtrk.so.  Idempotent.
-    Returns the unit's identifier.  Robots that already have an ahead-of-time unit with the same template need nothing."""
+    Returns the unit's identifier.  Robots that already have an ahead-of-time unit with the same template need nothing.
+    With hipcc a whole-row unit of a robot up to 8 DOF gets its via-point cost kernels (codegen.generate_via_cost_source) compiled
+    and loaded next to it -- a second hipcc run of about the main unit's length on the robot's first use, cached like it;
+    TRK_JIT_VIA_UNITS=0 skips it for callers that never ask for the via-point cost (they keep the two-step route).  The hipRTC
+    fall-back carries none: such a robot keeps the two-step via-point cost."""
     tmpl = codegen.CollisionTemplate(obj_links=[int(i) for i in obj_links],
                                      self_pairs=[(int(a), int(b)) for a, b in self_pairs], ee_link=int(ee_link),
                                      ee2_link=int(ee2_link), virtual=[tuple(r) for r in virtual])
@@ -297,6 +301,13 @@ def specialize(kin: KinModel, obj_links: Sequence[int], self_pairs: Sequence[Tup
     if ident not in _loaded:
         if hipcc_available() or pipeline:
             _loaded[ident] = _load_unit(build_unit(kin, tmpl, verbose, pipeline), ident)
+            if not pipeline and os.environ.get("TRK_JIT_VIA_UNITS", "1") != "0" and codegen.via_cost_ok(kin, tmpl, ident):
+                # the unit's via-point cost kernels (k_via_cost: ops.rollout_via_cost_grad): a unit of their own, spec_<ident>_via, cached
+                # under the same stamp; its initialiser announces the launcher under the main unit's ident (trk_spec_register_via_cost)
+                vso, vstamp = JIT_DIR / f"spec_{ident}_via.so", JIT_DIR / f"spec_{ident}_via.stamp"
+                if not (vso.exists() and vstamp.exists() and vstamp.read_text() == _generator_stamp()):
+                    vso = _compile_unit(codegen.generate_via_cost_source(kin, tmpl, ident), f"{ident}_via", verbose)
+                _loaded[f"{ident}_via"] = C.CDLL(str(vso))
         else:                               # no compiler driver on this box: the in-process fall-back
             _loaded[ident] = _load_unit_rtc(kin, tmpl, ident)
         _loaded_templates[ident] = (codegen.model_hash(kin), tmpl)

@@ -906,7 +906,7 @@ def rollout_is_specialized(model: ModelHandle, cm: CostHandle, weights) -> bool:
     return bool(lib().trk_rollout_is_specialized(model._h, cm._h, C.byref(_weights_struct(weights))))
 
 
-DISPATCH_NAMES = {0: "none", 1: "generated", 2: "table-driven", 3: "generated + prior launches"}
+DISPATCH_NAMES = {0: "none", 1: "generated", 2: "table-driven", 3: "generated + prior launches", 4: "generated via-point cost"}
 
 
 def rollout_points_is_specialized(ps: "PointSetHandle", cm: CostHandle, weights) -> bool:
@@ -925,7 +925,8 @@ def _require_generated(who: str, model: ModelHandle, served: bool) -> None:
 
 def last_dispatch() -> str:
     """Which kernel family served this thread's latest rollout call (`trk_last_dispatch`): 'generated', 'table-driven',
-    'generated + prior launches' (the two-launch form of the GP-fused rollout) or 'none'."""
+    'generated + prior launches' (the two-launch form of the GP-fused rollout), 'generated via-point cost' (the one launch of
+    `rollout_via_cost_grad`; the two-step route of `PlanningTask.compute_collision_cost_via` ends in a rollout and reports that) or 'none'."""
     return DISPATCH_NAMES[int(lib().trk_last_dispatch())]
 
 
@@ -1261,6 +1262,37 @@ def via_point_weights(num_interpolation: int, device) -> tuple:
         alpha = torch.linspace(0, 1, key[0] + 2, dtype=torch.float32)[1:key[0] + 1]
         ab = _via_weights[key] = (alpha.to(device), (1 - alpha).to(device))
     return ab
+
+
+class _InterpolateVia(torch.autograd.Function):
+    """interpolate_traj_via_points under autograd (the two-step route of PlanningTask.compute_collision_cost_via): the kernel forward,
+    the fold of the via points' gradient rows back onto the way points as torch launches."""
+
+    @staticmethod
+    def forward(ctx, x, n):
+        ctx.n = n
+        return interpolate_traj_via_points(x, n)
+
+    @staticmethod
+    def backward(ctx, g):
+        n = ctx.n
+        T, W, D = g.shape
+        alpha, beta = via_point_weights(n, g.device)
+        g4 = g.reshape(T, W // n, n, D)
+        gx = g.new_zeros((T, W // n + 1, D))
+        gx[:, :-1] += (g4 * alpha[None, None, :, None]).sum(2)
+        gx[:, 1:] += (g4 * beta[None, None, :, None]).sum(2)
+        return gx, None
+
+
+def interpolate_traj_via_points_ad(trajs: torch.Tensor, num_interpolation: int) -> torch.Tensor:
+    """`interpolate_traj_via_points` for trajs (T, H, D) with the gradient flowing back to the way points."""
+    x = _dev_f32(trajs, "interpolate_traj_via_points_ad(trajs)")
+    if x.dim() != 3 or num_interpolation <= 0:
+        raise ValueError("interpolate_traj_via_points_ad: trajs must be (T, H, D) and num_interpolation >= 1")
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _InterpolateVia.apply(x, int(num_interpolation))
+    return interpolate_traj_via_points(x, num_interpolation)
 
 
 def rollout_collision_via(model: ModelHandle, cm: CostHandle, fields: int, trajs: torch.Tensor, num_interpolation: int,
@@ -1944,6 +1976,123 @@ def rollout_ad(model: ModelHandle, cm: CostHandle, weights, q: torch.Tensor, ps:
                                                       ps.uid if ps is not None else 0)
         return cost, (pos if want_pos else None)
     return _Rollout.apply(_dev_f32(q, "rollout(q)"), model, cm, tuple(float(w) for w in weights), ps, bool(want_pos))
+
+
+def _via_cost_args(model: ModelHandle, x: torch.Tensor, num_interpolation: int, who: str):
+    x = _dev_f32(x, f"{who}(x)")
+    if x.dim() != 3:
+        raise ValueError(f"{who}: x must be (trajectories, horizon, dof)")
+    _check_q_dofs(x, model.n_dofs, f"{who}(x)")
+    n = int(num_interpolation)
+    if n < 1:
+        raise ValueError(f"{who}: num_interpolation must be >= 1")
+    return x, int(x.shape[0]), int(x.shape[1]), n
+
+
+def rollout_via_cost_grad(model: ModelHandle, cm: CostHandle, weights, x: torch.Tensor, num_interpolation: int,
+                          seed: Optional[torch.Tensor] = None, want_cost: bool = True):
+    """The fused rollout's objective at the via points between the way points of x (T, H, D) fp32, and its gradient with respect to
+    the WAY points, in one launch (`trk_rollout_via_cost_grad`; trajectory/utils.py:37-50 + the collision cost, differentiated through
+    the interpolation): -> (cost (T, (H-1) n) or None, gq (T, H, D)), or None when no generated kernel serves the call (H > 64, no
+    unit with the kernel for this model / cost model) -- the caller then interpolates first.  seed (T, (H-1) n): the upstream gradient
+    of every via point's cost (default: ones).  The way points' own cost is `rollout_cost_grad`'s."""
+    x, T, H, n = _via_cost_args(model, x, num_interpolation, "rollout_via_cost_grad")
+    if H < 2:
+        raise ValueError("rollout_via_cost_grad: a trajectory needs at least two way points")
+    if seed is not None:
+        seed = _dev_f32(seed, "rollout_via_cost_grad(seed)")
+        _check_buffer(seed, T * (H - 1) * n, torch.float32, x.device, "rollout_via_cost_grad(seed)")
+    alpha, beta = via_point_weights(n, x.device)
+    cost = torch.empty((T, (H - 1) * n), device=x.device, dtype=torch.float32) if want_cost else None
+    gq = torch.empty((T, H, model.n_dofs), device=x.device, dtype=torch.float32)
+    with _on(x.device):
+        rc = lib().trk_rollout_via_cost_grad(model._h, cm._h, C.byref(_weights_struct(weights)), x.data_ptr(), T, H, n, alpha.data_ptr(),
+                                             beta.data_ptr(), _ptr(seed), _ptr(cost), gq.data_ptr(), _stream(x))
+    if rc == _abi.TRK_ERR_UNSUPPORTED:
+        return None
+    check(rc, "trk_rollout_via_cost_grad")
+    return cost, gq
+
+
+class RolloutViaPlan(_Plan):
+    """Pre-bound `trk_rollout_via_cost_grad` launch on the caller's x (T, H, D) fp32: `launch()` is one ctypes call and fills `cost`
+    (T, (H-1) n) and `gq` (T, H, D) -- no allocation, no host synchronisation, so it can be captured in a graph.  seed: an optional
+    (T, (H-1) n) buffer read at every launch.  `launch()` raises NotImplementedError where the kernel does not serve (model, cost model)."""
+
+    def __init__(self, model: ModelHandle, cm: CostHandle, weights, x: torch.Tensor, num_interpolation: int,
+                 seed: Optional[torch.Tensor] = None, gq_out: Optional[torch.Tensor] = None):
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
+            raise ValueError("RolloutViaPlan: x must be a contiguous float32 tensor on the GPU (the plan binds its storage)")
+        x, T, H, n = _via_cost_args(model, x, num_interpolation, "RolloutViaPlan")
+        if H < 2 or H > _abi.TRK_VIA_COST_MAX_HORIZON:
+            raise NotImplementedError(f"RolloutViaPlan: horizon {H} is outside 2 .. {_abi.TRK_VIA_COST_MAX_HORIZON} (a wavefront of the "
+                                      f"via-point cost kernel owns whole trajectories)")
+        self.model, self.cm, self.x, self.device, self.T, self.H, self.n = model, cm, x, x.device, T, H, n
+        _check_buffer(seed, T * (H - 1) * n, torch.float32, x.device, "RolloutViaPlan(seed)")
+        self.seed = seed
+        self.cost = torch.empty((T, (H - 1) * n), device=x.device, dtype=torch.float32)
+        if gq_out is not None:
+            _check_buffer(gq_out, T * H * model.n_dofs, torch.float32, x.device, "RolloutViaPlan(gq_out)")
+            self.gq = gq_out.view(T, H, model.n_dofs)
+        else:
+            self.gq = torch.empty((T, H, model.n_dofs), device=x.device, dtype=torch.float32)
+        self._alpha, self._beta = via_point_weights(n, x.device)
+        self._w = _weights_struct(weights)        # the plan's own reference: the cache may be cleared
+        self._fn = lib().trk_rollout_via_cost_grad
+        self._args = (model._h, cm._h, C.byref(self._w), x.data_ptr(), T, H, n, self._alpha.data_ptr(), self._beta.data_ptr(),
+                      _ptr(seed), self.cost.data_ptr(), self.gq.data_ptr())
+
+    def launch(self, stream: Optional[int] = None) -> None:
+        self._launch(stream)
+
+
+class _RolloutVia(torch.autograd.Function):
+    """cost (T, (H-1) n) of the via points from the way points x; forward keeps d sum(cost) / d x, which the launch produced anyway.
+    backward: an upstream gradient that is one value expanded over the via points (`.sum()`, `.mean()`) scales the kept gradient on
+    the device (trk_scale_rows reads the value behind the pointer); any other is the seed of a second launch.  Nothing is read on
+    the host."""
+
+    @staticmethod
+    def forward(ctx, x, model, cm, weights, n):
+        res = rollout_via_cost_grad(model, cm, weights, x, n)
+        if res is None:
+            raise NotImplementedError("rollout_via_cost: " + lib().trk_last_error().decode("utf-8", "replace"))
+        cost, gq = res
+        ctx.save_for_backward(x, gq)
+        ctx.model, ctx.cm, ctx.weights, ctx.n = model, cm, weights, n
+        return cost
+
+    @staticmethod
+    def backward(ctx, gcost):
+        x, gq = ctx.saved_tensors
+        if gcost.dtype == torch.float32 and gcost.device == gq.device and not any(gcost.stride()):
+            out = torch.empty_like(gq)
+            D = int(gq.shape[-1])
+            with _on(gq.device):
+                check(lib().trk_scale_rows(gq.data_ptr(), gcost.data_ptr(), 0, gq.numel() // D, D, 0, out.data_ptr(), _stream(gq)),
+                      "trk_scale_rows")
+            return out, None, None, None, None
+        res = rollout_via_cost_grad(ctx.model, ctx.cm, ctx.weights, x, ctx.n, seed=gcost.contiguous(), want_cost=False)
+        if res is None:
+            raise NotImplementedError("rollout_via_cost (backward): " + lib().trk_last_error().decode("utf-8", "replace"))
+        return res[1], None, None, None, None
+
+
+def rollout_via_cost(model: ModelHandle, cm: CostHandle, weights, x: torch.Tensor, num_interpolation: int) -> torch.Tensor:
+    """Differentiable `rollout_via_cost_grad`: the (T, (H-1) n) costs of the via points of x (T, H, D), with the gradient flowing back
+    to the way points.  Raises NotImplementedError where the kernel does not serve the call.  There is
+    no dispatcher (torch.ops.trk.*) twin: the op cannot be traced."""
+    if torch.compiler.is_compiling():
+        raise NotImplementedError("rollout_via_cost has no dispatcher op (torch.ops.trk.*): call it outside torch.compile, or wrap the "
+                                  "caller in torch.compiler.disable")
+    x = _dev_f32(x, "rollout_via_cost(x)")
+    w = tuple(float(v) for v in weights)
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _RolloutVia.apply(x, model, cm, w, int(num_interpolation))
+    res = rollout_via_cost_grad(model, cm, w, x, num_interpolation)
+    if res is None:
+        raise NotImplementedError("rollout_via_cost: " + lib().trk_last_error().decode("utf-8", "replace"))
+    return res[0]
 
 
 class RolloutPlan(_Plan):

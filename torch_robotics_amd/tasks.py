@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import ops
+from . import _abi
 from ._abi import FIELD_OBJECTS, FIELD_SELF, FIELD_WS
 from .costmodel import CostModelSpec
 from .environments import _np, objects_to_spec_parts, planar_scene, scene_version
@@ -271,6 +272,17 @@ class PlanningTask(Task):
         model, cm = self._fused_handles(q.device)
         return ops.ArmAdamPlan(model, cm, (w_self, w_obj, w_ws, w_ee), q, qd, dt, sigma_gp, gp_weight, lr, **pins)
 
+    def rollout_via_plan(self, q, num_interpolation=5, w_self=1.0, w_obj=1.0, w_ws=1.0, w_ee=0.0, seed=None, gq_out=None) -> "ops.RolloutViaPlan":
+        """Pre-bound via-point cost (`trk_rollout_via_cost_grad`): `plan.launch()` fills `plan.cost` (B, (H-1) n), the objective at the n
+        via points of every segment of q (B,H,D) fp32, and `plan.gq` (B,H,D), its gradient with respect to the way points.  q is read
+        in place on every launch.  For link-column cost models of robots up to 8 DOF and horizons up to 64;
+        `compute_collision_cost_via` serves everything else."""
+        if getattr(self.robot, "has_extra_points", False) or not self._has_tree:
+            raise NotImplementedError("rollout_via_plan is for link-column cost models of robots with a kinematic tree "
+                                      "(compute_collision_cost_via serves the others)")
+        model, cm = self._fused_handles(q.device)
+        return ops.RolloutViaPlan(model, cm, (w_self, w_obj, w_ws, w_ee), q, num_interpolation, seed=seed, gq_out=gq_out)
+
     def trajectory_optimizer(self, q, qd, dt, sigma_gp, w_obj=1.0, gp_weight=1.0, lr=5e-3, **pins) -> "ops.PlanarAdamPlan":
         """The 2-D point mass's planning loop on the chip (`trk_scene2d_traj_adam_steps`): Adam on w_obj x this task's collision hinge
         (its scene, its clamp_sdf) + the constant-velocity GP prior.  `plan.step(n)` improves q, qd (B,H,2) in place and returns the
@@ -298,6 +310,59 @@ class PlanningTask(Task):
     @ops.host_round_trip
     def compute_collision_cost(self, x, **kwargs):             # tasks.py:135-137
         return self._compute_collision_or_cost(self.robot.get_position(x), field_type="sdf", **kwargs)
+
+    @ops.host_round_trip
+    def compute_collision_cost_via(self, trajs, num_interpolation=5, **weights):
+        """The collision cost on the interpolated trajectory (the planners' `compute_collision_cost(interpolate_traj_via_points(trajs))`,
+        trajectory/utils.py:37-50): trajs (T, H, >= D) -> (T, (H-1) num_interpolation), differentiable in trajs -- the gradient reaches
+        the WAY points, so an optimiser sees the configurations `get_trajs_collision_and_free` judges.  Columns beyond the joint
+        positions (velocities) are sliced off and receive zero gradient; num_interpolation <= 0 is `compute_collision_cost(trajs)`.
+        weights: w_self / w_obj / w_ws / w_ee of the fused rollout (default: compute_collision_cost's).
+        One launch (`ops.rollout_via_cost`, kernel k_via_cost) for link-column cost models of robots up to 8 DOF and horizons up to
+        64; everywhere else -- longer horizons, link spheres / grasped objects, point masses, larger trees -- the two-step route:
+        the via points materialised, then the rollout on them, the gradient folded back.  `ops.last_dispatch()` names the route and
+        `self.via_cost_declined` says why the kernel did not serve the latest call (None when it did).  Not traceable: under
+        torch.compile the method raises (neither route has a dispatcher op)."""
+        if num_interpolation <= 0:
+            return self.compute_collision_cost(trajs)
+        if trajs.ndim != 3:
+            raise ValueError("compute_collision_cost_via: trajs must be (trajectories, horizon, state)")
+        bad = sorted(set(weights) - {"w_self", "w_obj", "w_ws", "w_ee"})
+        if bad:
+            raise TypeError(f"compute_collision_cost_via: unexpected keyword(s) {bad}")
+        q = self.robot.get_position(trajs)
+        n, H = int(num_interpolation), int(q.shape[1])
+        if H < 2:
+            raise ValueError("compute_collision_cost_via: a trajectory needs at least two way points")
+        tree = self._has_tree
+        if not tree and weights:
+            raise NotImplementedError("compute_collision_cost_via: the weights belong to the fused rollout of a robot with a kinematic tree")
+        w = (float(weights.get("w_self", 1.0 if self.df_collision_self is not None else 0.0)), float(weights.get("w_obj", 1.0)),
+             float(weights.get("w_ws", 1.0)), float(weights.get("w_ee", 0.0)))
+        if ops._dispatch():
+            raise NotImplementedError("compute_collision_cost_via has no dispatcher op (torch.ops.trk.*) on either route: call it outside "
+                                      "torch.compile, or wrap the caller in torch.compiler.disable")
+        self.via_cost_declined = None           # why the latest call took the two-step route (None: the kernel served it)
+        if not tree or getattr(self.robot, "has_extra_points", False):
+            self.via_cost_declined = "the cost model's columns are not the links of a kinematic tree"
+        elif H > _abi.TRK_VIA_COST_MAX_HORIZON:
+            self.via_cost_declined = f"horizon {H} > {_abi.TRK_VIA_COST_MAX_HORIZON}"
+        else:
+            model, cm = self._fused_handles(q.device)
+            try:
+                return ops.rollout_via_cost(model, cm, w, q, n)
+            except NotImplementedError as e:    # no unit with the kernel serves this model / cost model (more than 8 DOF, a code-object unit)
+                self.via_cost_declined = str(e)
+        v = ops.interpolate_traj_via_points_ad(q, n)
+        if not tree:
+            return self.compute_collision_cost(v)
+        model, cm = self._fused_handles(v.device)
+        ps = self._points(v.device)
+        if torch.is_grad_enabled() and v.requires_grad:
+            return ops.rollout_ad(model, cm, w, v, ps, want_pos=False)[0]
+        if ps is not None:
+            return ops.rollout_points_cost_grad(ps, cm, w, v, want_pos=False)[1]
+        return ops.rollout_cost_grad(model, cm, w, v, want_pos=False)[1]
 
     def _compute_collision_or_cost(self, q, field_type="occupancy", **kwargs):   # tasks.py:139-232
         if q.ndim == 1:
