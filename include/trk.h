@@ -880,6 +880,30 @@ int trk_scene2d_traj_adam_steps(const TrkScene2D* scene, const TrkPlanarObjectiv
                                 float* qd, float* adam_m, float* adam_v, int64_t batch, int32_t horizon, float* cost,
                                 trk_stream_t stream);
 
+/* The same objective with the collision hinge ALSO at the via points that trajectory validation tests (trk_scene2d_collision_via):
+ * v[b,i,a] = q[b,i] * alpha[a] + q[b,i+1] * beta[a] per coordinate, each product and the sum rounded once as in
+ * trk_interpolate_via_points; alpha, beta DEVICE [n_interp].  With h, g the cost and gradient of trk_scene2d_cost_grad at a point:
+ *   C[b,t] = sum_a h(v[b,t,a]),  L[b,t] = sum_a alpha[a] g(v[b,t,a]),  U[b,t] = sum_a beta[a] g(v[b,t,a])   (0 at t = horizon-1)
+ *   cost[b,t] = (cost of trk_scene2d_traj_cost_grad) + w_via * C[b,t]           -- the segment t -> t+1 attributed to sample t
+ *   gq[b,t]   = (gq of trk_scene2d_traj_cost_grad) + w_via * (L[b,t] + U[b,t-1]),  U[b,-1] = 0;   gqd is unchanged.
+ * C adds in ascending a from 0, L and U are fmaf(weight, g, sum) in ascending a, then cost = fmaf(w_via, C, cost) and
+ * gq = fmaf(w_via, L + U, gq): at w_via = 0, and at horizon 1 (no segment), the results are trk_scene2d_traj_cost_grad's.
+ * One lane per sample, a workgroup owns whole trajectories: 1 <= horizon <= TRK_PLANAR_MAX_HORIZON for BOTH calls,
+ * TRK_ERR_UNSUPPORTED above.  Everything else -- shapes, alignment, gq / gqd nullable together, cost nullable in the loop, pin,
+ * first_step, 32 iterations per launch, lr = 0 -- is as in the two calls above.  No host synchronisation: capturable. */
+typedef struct TrkPlanarViaObjective {
+    TrkPlanarObjective base;    /* as trk_scene2d_traj_cost_grad validates it */
+    float w_via;                /* finite */
+    int32_t n_interp;           /* >= 1 */
+    const float* alpha;         /* DEVICE [n_interp] */
+    const float* beta;          /* DEVICE [n_interp] */
+} TrkPlanarViaObjective;
+int trk_scene2d_traj_via_cost_grad(const TrkScene2D* scene, const TrkPlanarViaObjective* objective, const float* q, const float* qd,
+                                   int64_t batch, int32_t horizon, float* cost, float* gq, float* gqd, trk_stream_t stream);
+int trk_scene2d_traj_via_adam_steps(const TrkScene2D* scene, const TrkPlanarViaObjective* objective, const TrkPlanarAdam* adam,
+                                    float* q, float* qd, float* adam_m, float* adam_v, int64_t batch, int32_t horizon, float* cost,
+                                    trk_stream_t stream);
+
 /* The arm's planning loop on the chip: n_steps iterations of Adam (the arithmetic and bias terms of trk_scene2d_traj_adam_steps, above)
  * on the objective of trk_rollout_gp_cost_grad -- the collision and EE terms of trk_rollout_cost_grad under `w` plus the
  * constant-velocity GP prior -- with the trajectories and the optimiser's state in registers: q, qd [batch, horizon, dof] fp32 and

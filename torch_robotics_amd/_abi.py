@@ -127,6 +127,10 @@ class PlanarObjective(C.Structure):     # TrkPlanarObjective
     _fields_ = [("w_obj", C.c_float), ("clamp", C.c_int32), ("gp", GpPrior)]
 
 
+class PlanarViaObjective(C.Structure):  # TrkPlanarViaObjective
+    _fields_ = [("base", PlanarObjective), ("w_via", C.c_float), ("n_interp", C.c_int32), ("alpha", C.c_void_p), ("beta", C.c_void_p)]
+
+
 class PlanarAdam(C.Structure):          # TrkPlanarAdam
     _fields_ = [("lr", C.c_float), ("pin", C.c_int32), ("first_step", C.c_int32), ("n_steps", C.c_int32)]
 

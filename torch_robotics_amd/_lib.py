@@ -40,6 +40,7 @@ EXPORTS = [
     "trk_rollout_gp_adam_steps",
     "trk_rollout_points_collision", "trk_rollout_points_collision_via",
     "trk_rollout_via_cost_grad",
+    "trk_scene2d_traj_via_cost_grad", "trk_scene2d_traj_via_adam_steps",
 ]
 
 
@@ -196,6 +197,9 @@ def lib():
     L.trk_scene2d_sdf_points.argtypes = [vp, vp, i64, vp, vp, vp]
     L.trk_scene2d_traj_cost_grad.argtypes = [vp, C.POINTER(_abi.PlanarObjective), vp, vp, i64, i32, vp, vp, vp, vp]
     L.trk_scene2d_traj_adam_steps.argtypes = [vp, C.POINTER(_abi.PlanarObjective), C.POINTER(_abi.PlanarAdam), vp, vp, vp, vp, i64, i32, vp, vp]
+    L.trk_scene2d_traj_via_cost_grad.argtypes = [vp, C.POINTER(_abi.PlanarViaObjective), vp, vp, i64, i32, vp, vp, vp, vp]
+    L.trk_scene2d_traj_via_adam_steps.argtypes = [vp, C.POINTER(_abi.PlanarViaObjective), C.POINTER(_abi.PlanarAdam), vp, vp, vp, vp, i64, i32,
+                                                  vp, vp]
     L.trk_rollout_gp_adam_steps.argtypes = [vp, vp, C.POINTER(_abi.RolloutWeights), C.POINTER(_abi.GpPrior), C.POINTER(_abi.TrajAdam),
                                             vp, vp, vp, vp, i64, i32, vp, vp]
     L.trk_rollout_points_collision.argtypes = [vp, vp, i32, vp, i64, i32, f32, vp, vp, vp]

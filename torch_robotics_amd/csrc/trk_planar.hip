@@ -333,6 +333,114 @@ k_planar_traj_adam(P2Hdr S, TrajPar P, AdamPar A, float2* __restrict__ q, float2
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The via-point term (include/trk.h, trk_scene2d_traj_via_cost_grad): the hinge at the n interpolated points of the segment t -> t+1,
+// attributed to sample t like the prior's factor.
+// ---------------------------------------------------------------------------------------------------------------------------
+struct ViaPar { float w_via; int32_t n; const float* alpha; const float* beta; };      // alpha, beta: device [n], the same for every lane
+
+// The segment from x to xn: v[a] = x * alpha[a] + xn * beta[a], each product and the sum rounded once (k_planar_collision_via's
+// arithmetic) -> c = sum_a h(v[a]), l = sum_a alpha[a] g(v[a]) (the segment's gradient on its own sample), u = sum_a beta[a] g(v[a])
+// (on the next one); ascending a from 0.0f, c by plain adds, l and u by fmaf.  A run-time loop: the hinge's code is there once.
+template <bool GRID, bool ANALYTIC, bool WS, bool CLAMP>
+__device__ __forceinline__ void via_segment(const P2Hdr& S, const ViaPar& V, const float4& x, const float4& xn, float& c, float2& l,
+                                            float2& u) {
+    c = 0.0f; l = make_float2(0.0f, 0.0f); u = l;
+    const TRK_CAS float* al = cptr(V.alpha);
+    const TRK_CAS float* be = cptr(V.beta);
+#pragma nounroll
+    for (int a = 0; a < V.n; ++a) {
+        const float wa = al[a], wb = be[a];
+        const float px = __fadd_rn(__fmul_rn(x.x, wa), __fmul_rn(xn.x, wb));
+        const float py = __fadd_rn(__fmul_rn(x.y, wa), __fmul_rn(xn.y, wb));
+        float gx, gy;
+        c = c + hinge_term<GRID, ANALYTIC, WS, CLAMP>(S, make_float2(px, py), gx, gy);
+        l.x = fmaf(wa, gx, l.x); l.y = fmaf(wa, gy, l.y);
+        u.x = fmaf(wb, gx, u.x); u.y = fmaf(wb, gy, u.y);
+    }
+}
+
+// k_planar_traj_adam with the via term in the objective; it serves both entry points (trk_scene2d_traj_via_cost_grad is one
+// evaluation, update == 0, that also stores the gradient).  The layout and the first exchange are k_planar_traj_adam's.  After it a
+// lane with a segment (t < H - 1) walks the segment's n via points with (c, l, u) in registers, and u goes to lane t + 1:
+//   WAVE: two more DPP shifts;
+//   otherwise: one float2 per lane through LDS, ONE buffer and a second barrier per iteration.  A lane that writes uch for iteration
+//   k + 1 has passed the first barrier of iteration k + 1, which every lane reaches only after its read of uch in iteration k; a
+//   lane that reads uch in iteration k has passed the second barrier of iteration k, which every lane reaches only after its write.
+//   With two barriers per iteration xch's two buffers are more than the first exchange needs; they stay as in k_planar_traj_adam.
+// Idle lanes (beyond the workgroup's whole trajectories, or beyond the batch) reach every barrier.  The lane without a segment and
+// the lane without a predecessor have their shares removed by a select: what lane tid - 1 of another trajectory wrote never enters.
+template <bool GRID, bool ANALYTIC, bool WS, bool CLAMP, bool WAVE>
+__global__ void __launch_bounds__(256)
+k_planar_traj_via(P2Hdr S, TrajPar P, ViaPar V, AdamPar A, float2* __restrict__ q, float2* __restrict__ qd, float4* __restrict__ mom,
+                  float4* __restrict__ vel, int64_t B, int H, float* __restrict__ cost, float2* __restrict__ gq,
+                  float2* __restrict__ gqd) {
+    __shared__ float4 xch[WAVE ? 1 : 2][WAVE ? 1 : 256];
+    __shared__ float2 uch[WAVE ? 1 : 256];
+    const int tid = threadIdx.x;
+    const int per_wg = WAVE ? 4 : 256 / H;
+    const int tl = WAVE ? tid >> 6 : tid / H;                      // the lane's trajectory within the workgroup
+    const int t = WAVE ? tid & 63 : tid - tl * H;
+    const int64_t traj = (int64_t)blockIdx.x * per_wg + tl;
+    const bool active = tl < per_wg && traj < B;
+    if (WAVE && !active) return;                                   // a whole wavefront: the DPP shifts below see all 64 lanes
+    const int64_t s = traj * H + t;
+    const bool has_prev = t > 0, has_next = t + 1 < H;
+    const bool update = A.update != 0;
+    float4 x = make_float4(0.0f, 0.0f, 0.0f, 0.0f), m = x, v = x;
+    if (active) {
+        const float2 a = q[s], b = qd[s];
+        x = make_float4(a.x, a.y, b.x, b.y);
+        if (update) { m = mom[s]; v = vel[s]; }
+    }
+    const bool pin_q = ((A.pin & 1) && t == 0) || ((A.pin & 2) && t == H - 1);
+    const bool pin_qd = ((A.pin & 4) && t == 0) || ((A.pin & 8) && t == H - 1);
+    for (int it = 0; it < A.n_steps; ++it) {
+        float4 xm = x, xn = x;
+        if (WAVE) {
+            xm.x = trk_dpp_from_prev(x.x, x.x); xm.y = trk_dpp_from_prev(x.y, x.y);
+            xm.z = trk_dpp_from_prev(x.z, x.z); xm.w = trk_dpp_from_prev(x.w, x.w);
+            xn.x = trk_dpp_from_next(x.x, x.x); xn.y = trk_dpp_from_next(x.y, x.y);
+            xn.z = trk_dpp_from_next(x.z, x.z); xn.w = trk_dpp_from_next(x.w, x.w);
+        } else {
+            xch[it & 1][tid] = x;
+            __syncthreads();
+            if (active && has_prev) xm = xch[it & 1][tid - 1];
+            if (active && has_next) xn = xch[it & 1][tid + 1];
+        }
+        float vc = 0.0f;
+        float2 vl = make_float2(0.0f, 0.0f), vu = vl, up = vl;
+        if (active && has_next) via_segment<GRID, ANALYTIC, WS, CLAMP>(S, V, x, xn, vc, vl, vu);
+        if (WAVE) {
+            up.x = trk_dpp_from_prev(0.0f, vu.x); up.y = trk_dpp_from_prev(0.0f, vu.y);
+        } else {
+            uch[tid] = vu;
+            __syncthreads();
+            if (active && has_prev) up = uch[tid - 1];
+        }
+        if (!has_prev) up = make_float2(0.0f, 0.0f);
+        if (active) {
+            float g[4];
+            float c = traj_objective<GRID, ANALYTIC, WS, CLAMP>(S, P, has_prev, has_next, x, xm, xn, g);
+            c = fmaf(V.w_via, vc, c);
+            g[0] = fmaf(V.w_via, vl.x + up.x, g[0]); g[1] = fmaf(V.w_via, vl.y + up.y, g[1]);
+            if (it == 0 && cost) cost[s] = c;
+            if (it == 0 && gq) { gq[s] = make_float2(g[0], g[1]); gqd[s] = make_float2(g[2], g[3]); }
+            if (update) {
+                const float step = A.lr / A.bc1[it], rs = A.rsqrt_bc2[it];
+                adam_component(pin_q ? 0.0f : g[0], step, rs, x.x, m.x, v.x);
+                adam_component(pin_q ? 0.0f : g[1], step, rs, x.y, m.y, v.y);
+                adam_component(pin_qd ? 0.0f : g[2], step, rs, x.z, m.z, v.z);
+                adam_component(pin_qd ? 0.0f : g[3], step, rs, x.w, m.w, v.w);
+            }
+        }
+    }
+    if (active && update) {
+        q[s] = make_float2(x.x, x.y); qd[s] = make_float2(x.z, x.w);
+        mom[s] = m; vel[s] = v;
+    }
+}
+
 template <bool GRID, bool ANALYTIC, bool WS>
 __global__ void __launch_bounds__(256)
 k_planar_collision(P2Hdr S, const float2* __restrict__ q, int64_t n, float m, uint8_t* __restrict__ out) {
@@ -461,6 +569,20 @@ struct TrajAdamGo {
         const int per_wg = WV ? 4 : 256 / H;
         hipLaunchKernelGGL((k_planar_traj_adam<G, A, W, C, WV>), dim3((unsigned)((B + per_wg - 1) / per_wg)), dim3(256), 0, st, S, P, Ad,
                            q, qd, m, v, B, H, cost);
+    }
+    template <bool G, bool A, bool W> void go() {
+        if (clamp) { if (wave) launch<G, A, W, true, true>(); else launch<G, A, W, true, false>(); }
+        else { if (wave) launch<G, A, W, false, true>(); else launch<G, A, W, false, false>(); }
+    }
+};
+
+struct TrajViaGo {
+    const P2Hdr& S; const TrajPar& P; const ViaPar& V; const AdamPar& Ad; float2* q; float2* qd; float4* m; float4* v; int64_t B; int H;
+    bool clamp, wave; float* cost; float2* gq; float2* gqd; hipStream_t st;
+    template <bool G, bool A, bool W, bool C, bool WV> void launch() {
+        const int per_wg = WV ? 4 : 256 / H;
+        hipLaunchKernelGGL((k_planar_traj_via<G, A, W, C, WV>), dim3((unsigned)((B + per_wg - 1) / per_wg)), dim3(256), 0, st, S, P, V, Ad,
+                           q, qd, m, v, B, H, cost, gq, gqd);
     }
     template <bool G, bool A, bool W> void go() {
         if (clamp) { if (wave) launch<G, A, W, true, true>(); else launch<G, A, W, true, false>(); }
@@ -713,6 +835,88 @@ int trk_scene2d_traj_adam_steps(const TrkScene2D* s, const TrkPlanarObjective* o
         dispatch3(s->hdr.has_grid != 0, s->hdr.n_objects > 0, s->has_ws != 0, f);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return trk_hip_fail((int)e, "k_planar_traj_adam");
+    }
+    return TRK_OK;
+}
+
+// What both via entry points ask on top of check_traj_call, before anything is dereferenced or launched; fills P and V.
+static int check_via_call(const char* who, const TrkScene2D* s, const TrkPlanarViaObjective* o, int64_t batch, int32_t horizon, TrajPar& P,
+                          ViaPar& V) {
+    static thread_local char msg[200];
+    if (!o) { snprintf(msg, sizeof(msg), "%s: null TrkPlanarViaObjective", who); return trk_fail(TRK_ERR_INVALID_ARG, msg); }
+    int rc = check_traj_call(who, s, &o->base, batch, horizon, P);
+    if (rc) return rc;
+    if (!std::isfinite(o->w_via) || o->n_interp < 1 || !o->alpha || !o->beta) {
+        snprintf(msg, sizeof(msg), "%s: w_via must be finite, n_interp >= 1 and alpha, beta device arrays of n_interp weights", who);
+        return trk_fail(TRK_ERR_INVALID_ARG, msg);
+    }
+    if (horizon > TRK_PLANAR_MAX_HORIZON) {
+        snprintf(msg, sizeof(msg), "%s: horizon above TRK_PLANAR_MAX_HORIZON (256): a workgroup owns whole trajectories", who);
+        return trk_fail(TRK_ERR_UNSUPPORTED, msg);
+    }
+    V = ViaPar{o->w_via, o->n_interp, o->alpha, o->beta};
+    return TRK_OK;
+}
+
+// H == 64 runs the WAVE form; TRK_PLANAR_ADAM_LDS64=1 runs the LDS form there too, as in trk_scene2d_traj_adam_steps
+static bool via_wave_form(int32_t horizon) {
+    static const bool lds64 = [] { const char* v = getenv("TRK_PLANAR_ADAM_LDS64"); return v && v[0] == '1'; }();
+    return horizon == 64 && !lds64;
+}
+
+int trk_scene2d_traj_via_cost_grad(const TrkScene2D* s, const TrkPlanarViaObjective* o, const float* q, const float* qd, int64_t batch,
+                                   int32_t horizon, float* cost, float* gq, float* gqd, trk_stream_t stream) {
+    const char* who = "trk_scene2d_traj_via_cost_grad";
+    TrajPar P;
+    ViaPar V;
+    if ((batch > 0 && (!q || !qd || !cost)) || (gq == nullptr) != (gqd == nullptr))
+        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_via_cost_grad: null q / qd / cost, or only one of gq / gqd");
+    int rc = check_via_call(who, s, o, batch, horizon, P, V);
+    if (rc) return rc;
+    if (!aligned_to(q, 8) || !aligned_to(qd, 8) || !aligned_to(gq, 8) || !aligned_to(gqd, 8))
+        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_via_cost_grad: q, qd, gq and gqd must be 8-byte aligned (one float2 per sample)");
+    if (batch == 0) return TRK_OK;
+    AdamPar A{};                                        // one evaluation: update == 0, nothing but cost, gq and gqd is written
+    A.n_steps = 1;
+    TrajViaGo f{s->hdr, P, V, A, (float2*)q, (float2*)qd, nullptr, nullptr, batch, horizon, o->base.clamp != 0, via_wave_form(horizon),
+                cost, (float2*)gq, (float2*)gqd, (hipStream_t)stream};
+    dispatch3(s->hdr.has_grid != 0, s->hdr.n_objects > 0, s->has_ws != 0, f);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? TRK_OK : trk_hip_fail((int)e, "k_planar_traj_via");
+}
+
+int trk_scene2d_traj_via_adam_steps(const TrkScene2D* s, const TrkPlanarViaObjective* o, const TrkPlanarAdam* ad, float* q, float* qd,
+                                    float* adam_m, float* adam_v, int64_t batch, int32_t horizon, float* cost, trk_stream_t stream) {
+    const char* who = "trk_scene2d_traj_via_adam_steps";
+    TrajPar P;
+    ViaPar V;
+    if (!ad) return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_via_adam_steps: null TrkPlanarAdam");
+    if (ad->n_steps < 0 || ad->first_step < 1 || !std::isfinite(ad->lr) || ad->pin < 0 || ad->pin > 15)
+        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_via_adam_steps: n_steps >= 0, first_step >= 1, lr finite and pin in 0 .. 15");
+    int rc = check_via_call(who, s, o, batch, horizon, P, V);
+    if (rc) return rc;
+    const bool update = ad->lr != 0.0f && ad->n_steps > 0;
+    if (batch > 0 && (!q || !qd || (update && (!adam_m || !adam_v))))
+        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_via_adam_steps: null q / qd / adam_m / adam_v");
+    if (!aligned_to(q, 8) || !aligned_to(qd, 8) || !aligned_to(adam_m, 16) || !aligned_to(adam_v, 16))
+        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_via_adam_steps: q, qd must be 8-byte and adam_m, adam_v 16-byte aligned");
+    if (batch == 0 || (!update && !cost)) return TRK_OK;
+    // at most PLANAR_ADAM_MAX_STEPS iterations per launch; the cost comes from the first launch (the state as the caller passed it)
+    const int32_t total = update ? ad->n_steps : 1;
+    for (int32_t done = 0; done < total; done += PLANAR_ADAM_MAX_STEPS) {
+        AdamPar A{};
+        A.lr = ad->lr; A.pin = ad->pin; A.update = update ? 1 : 0;
+        A.n_steps = std::min<int32_t>(PLANAR_ADAM_MAX_STEPS, total - done);
+        for (int32_t i = 0; i < A.n_steps; ++i) {
+            const double k = (double)ad->first_step + (double)done + (double)i;
+            A.bc1[i] = (float)(1.0 - std::pow(0.9, k));
+            A.rsqrt_bc2[i] = (float)(1.0 / std::sqrt(1.0 - std::pow(0.999, k)));
+        }
+        TrajViaGo f{s->hdr, P, V, A, (float2*)q, (float2*)qd, (float4*)adam_m, (float4*)adam_v, batch, horizon, o->base.clamp != 0,
+                    via_wave_form(horizon), done == 0 ? cost : nullptr, nullptr, nullptr, (hipStream_t)stream};
+        dispatch3(s->hdr.has_grid != 0, s->hdr.n_objects > 0, s->has_ws != 0, f);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return trk_hip_fail((int)e, "k_planar_traj_via");
     }
     return TRK_OK;
 }

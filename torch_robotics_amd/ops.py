@@ -1657,6 +1657,31 @@ def planar_traj_cost_grad(scene: Scene2DHandle, q: torch.Tensor, qd: torch.Tenso
     return cost, gq, gqd
 
 
+def _planar_via_objective(dt, sigma, gp_weight, w_obj, clamp, w_via, num_interpolation, device):
+    """-> (TrkPlanarViaObjective, (alpha, beta)): the struct points into the cached device weights, which the caller keeps alive"""
+    n = int(num_interpolation)
+    if n < 1:
+        raise ValueError(f"the via-point term needs num_interpolation >= 1, got {n}")
+    ab = via_point_weights(n, device)
+    return _abi.PlanarViaObjective(_planar_objective(dt, sigma, gp_weight, w_obj, clamp), float(w_via), n, ab[0].data_ptr(), ab[1].data_ptr()), ab
+
+
+def planar_traj_via_cost_grad(scene: Scene2DHandle, q: torch.Tensor, qd: torch.Tensor, dt: float, sigma: float, gp_weight: float = 1.0,
+                              w_obj: float = 1.0, w_via: float = 1.0, num_interpolation: int = 5, clamp: bool = False,
+                              want_grad: bool = True):
+    """planar_traj_cost_grad's objective + w_via x the collision hinge at the num_interpolation via points of every segment -- the
+    points trajectory validation tests -- in one launch (include/trk.h: trk_scene2d_traj_via_cost_grad).  q, qd (B,H,2), H <= 256 ->
+    (cost (B,H) with the segment t -> t+1 at sample t, gq, gqd), the gradients None without want_grad."""
+    B, H = _planar_traj_args(q, qd, "planar_traj_via_cost_grad")
+    obj, _keep = _planar_via_objective(dt, sigma, gp_weight, w_obj, clamp, w_via, num_interpolation, q.device)
+    cost = torch.empty((B, H), device=q.device, dtype=torch.float32)
+    gq, gqd = (torch.empty_like(q), torch.empty_like(q)) if want_grad else (None, None)
+    with _on(q.device):
+        check(lib().trk_scene2d_traj_via_cost_grad(scene._h, C.byref(obj), q.data_ptr(), qd.data_ptr(), B, H, cost.data_ptr(), _ptr(gq),
+                                                   _ptr(gqd), _stream(q)), "trk_scene2d_traj_via_cost_grad")
+    return cost, gq, gqd
+
+
 def planar_adam_bias_terms(step: int):
     """(bc1, 1 / sqrt(bc2)) of Adam's 1-based iteration `step` as trk_scene2d_traj_adam_steps passes them to its kernel: formed in
     double, rounded once to fp32."""
@@ -1667,11 +1692,13 @@ class PlanarAdamPlan(_Plan):
     """Adam on planar_traj_cost_grad's objective with the trajectories and the optimiser's state on the chip (include/trk.h:
     trk_scene2d_traj_adam_steps).  Pre-bound: `step(n)` runs the next n iterations on the caller's q, qd (B,H,2) IN PLACE -- one
     launch per 32 iterations -- and returns the (B,H) cost of the state it started from.  The plan owns `m`, `v` (B,H,4) and the
-    iteration counter `t`.  pin_*: the start / goal position (velocity) keeps its value.  lr = 0 only evaluates."""
+    iteration counter `t`.  pin_*: the start / goal position (velocity) keeps its value.  lr = 0 only evaluates.
+    With num_interpolation > 0 and w_via != 0 the objective is planar_traj_via_cost_grad's (trk_scene2d_traj_via_adam_steps): the
+    hinge also at the via points that trajectory validation tests."""
 
     def __init__(self, scene: Scene2DHandle, q: torch.Tensor, qd: torch.Tensor, dt: float, sigma: float, gp_weight: float = 1.0,
                  w_obj: float = 1.0, clamp: bool = False, lr: float = 5e-3, pin_start: bool = True, pin_goal: bool = True,
-                 pin_start_vel: bool = False, pin_goal_vel: bool = False):
+                 pin_start_vel: bool = False, pin_goal_vel: bool = False, w_via: float = 0.0, num_interpolation: int = 0):
         B, H = _planar_traj_args(q, qd, "PlanarAdamPlan")
         if H > _abi.TRK_PLANAR_MAX_HORIZON:
             raise NotImplementedError(f"PlanarAdamPlan: horizon {H} is above the {_abi.TRK_PLANAR_MAX_HORIZON} samples a workgroup of the "
@@ -1682,11 +1709,21 @@ class PlanarAdamPlan(_Plan):
         self.cost = torch.empty((B, H), device=q.device, dtype=torch.float32)
         self.t = 0                              # iterations done
         self.pin = 1 * bool(pin_start) | 2 * bool(pin_goal) | 4 * bool(pin_start_vel) | 8 * bool(pin_goal_vel)
-        self._obj = _planar_objective(dt, sigma, gp_weight, w_obj, clamp)
+        self._objective = (dt, sigma, gp_weight, w_obj, clamp)
+        self.w_via, self.num_interpolation = float(w_via), int(num_interpolation)
         self._adam = _abi.PlanarAdam(float(lr), self.pin, 1, 0)
-        self._fn = lib().trk_scene2d_traj_adam_steps
-        self._args = (scene._h, C.byref(self._obj), C.byref(self._adam), q.data_ptr(), qd.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                      B, H, self.cost.data_ptr())
+        self._bind(via=self.num_interpolation > 0 and self.w_via != 0.0)
+
+    def _bind(self, via: bool) -> None:
+        """the entry point and its arguments: the via loop only where the via term is on, otherwise exactly the plain loop"""
+        if via:
+            self._obj, self._weights = _planar_via_objective(*self._objective, self.w_via, self.num_interpolation, self.device)
+            self._fn = lib().trk_scene2d_traj_via_adam_steps
+        else:
+            self._obj = _planar_objective(*self._objective)
+            self._fn = lib().trk_scene2d_traj_adam_steps
+        self._args = (self.scene._h, C.byref(self._obj), C.byref(self._adam), self.q.data_ptr(), self.qd.data_ptr(), self.m.data_ptr(),
+                      self.v.data_ptr(), self.B, self.H, self.cost.data_ptr())
 
     def step(self, n: int = 1, stream: Optional[int] = None) -> torch.Tensor:
         n = int(n)

@@ -283,17 +283,21 @@ class PlanningTask(Task):
         model, cm = self._fused_handles(q.device)
         return ops.RolloutViaPlan(model, cm, (w_self, w_obj, w_ws, w_ee), q, num_interpolation, seed=seed, gq_out=gq_out)
 
-    def trajectory_optimizer(self, q, qd, dt, sigma_gp, w_obj=1.0, gp_weight=1.0, lr=5e-3, **pins) -> "ops.PlanarAdamPlan":
+    def trajectory_optimizer(self, q, qd, dt, sigma_gp, w_obj=1.0, gp_weight=1.0, lr=5e-3, w_via=0.0, num_interpolation=0,
+                             **pins) -> "ops.PlanarAdamPlan":
         """The 2-D point mass's planning loop on the chip (`trk_scene2d_traj_adam_steps`): Adam on w_obj x this task's collision hinge
         (its scene, its clamp_sdf) + the constant-velocity GP prior.  `plan.step(n)` improves q, qd (B,H,2) in place and returns the
-        (B,H) cost they started from; pins: pin_start / pin_goal (default True), pin_start_vel / pin_goal_vel (default False)."""
+        (B,H) cost they started from; pins: pin_start / pin_goal (default True), pin_start_vel / pin_goal_vel (default False).
+        With num_interpolation > 0 and w_via != 0 the objective also carries w_via x the hinge at the num_interpolation via points of
+        every segment, the points `get_trajs_collision_and_free` tests (`trk_scene2d_traj_via_adam_steps`)."""
         if not self._planar:
             raise NotImplementedError("trajectory_optimizer serves the 2-D point mass (RobotPointMass in a 2-D scene); other robots "
                                       "optimise on rollout_gp_plan's gradients")
         if self.df_collision_self is not None:
             raise NotImplementedError("2-D point mass: a self-collision field is outside the 2-D kernels")
         scene, clamp = self._planar_handles(q.device)
-        return ops.PlanarAdamPlan(scene, q, qd, dt, sigma_gp, gp_weight, w_obj, clamp, lr, **pins)
+        return ops.PlanarAdamPlan(scene, q, qd, dt, sigma_gp, gp_weight, w_obj, clamp, lr, w_via=w_via, num_interpolation=num_interpolation,
+                                  **pins)
 
     def capture_cost_backward(self, x, reduce=torch.sum, warmup: int = 3) -> "GraphedCostBackward":
         """`reduce(task.compute_collision_cost(x)).backward()` captured ONCE as a hipGraph (a planner's inner loop calls it with
