@@ -12,10 +12,12 @@ with the GP prior fused in: `task.rollout_gp_plan`); the result is validated the
 
 --fused runs the same problem with the whole loop on the chip (`task.rollout_adam_plan(...).step(32)`, `trk_rollout_gp_adam_steps`):
 trajectories and Adam's state stay in registers, one launch per 32 iterations (horizons that are a power of two up to 64).
---via-cost N (eager loop, horizons up to 64) adds the collision cost at N via points per segment -- the configurations the
-validation judges and the optimiser otherwise never sees -- through one more launch per iteration (`task.rollout_via_plan`,
-`trk_rollout_via_cost_grad`: its gradient arrives at the way points), and prints the collision-free count of both runs (the problem
-is solved twice for that); it cannot be combined with --fused.
+--via-cost N (horizons up to 64) adds the collision cost at N via points per segment -- the configurations the validation judges
+and the optimiser otherwise never sees -- and prints the collision-free count of both runs (the problem is solved twice for that).
+In the eager loop it is one more launch per iteration (`task.rollout_via_plan`, `trk_rollout_via_cost_grad`: its gradient arrives
+at the way points, same weight as the way points' own cost).  With --fused the term is part of the planning-loop kernel
+(`task.rollout_adam_plan(..., w_via=1 / N, num_interpolation=N)`, `trk_rollout_gp_via_adam_steps`): the N via points of a segment
+together weigh as much as one way point.
 """
 import argparse
 import sys
@@ -31,10 +33,8 @@ from torch_robotics_amd import ops
 
 
 def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0, fused=False, stats=None, via_cost=0):
-    if via_cost > 0 and fused:
-        raise ValueError("--via-cost belongs to the eager loop: the planning-loop kernel of --fused has no via-point term")
     if via_cost > 0:                       # the same problem (same seed) without the via-point term first, for the comparison
-        n_free_plain = main(batch, horizon, iters, device, False, seed)[1]
+        n_free_plain = main(batch, horizon, iters, device, False, seed, fused=fused)[1]
     torch.manual_seed(seed)
     ta = dict(device=torch.device(device), dtype=torch.float32)
     robot = tra.RobotPanda(tensor_args=ta)
@@ -51,7 +51,14 @@ def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0
 
     w_obj, sigma_gp, lr = 50.0, 2.0, 1e-2
     if fused:
-        return _main_fused(task, q, qd, q_start + s * (q_goal - q_start), dt, sigma_gp, w_obj, lr, iters, verbose, stats)
+        res = _main_fused(task, q, qd, q_start + s * (q_goal - q_start), dt, sigma_gp, w_obj, lr, iters, verbose, stats, via_cost)
+        if via_cost > 0:
+            if stats is not None:
+                stats.update(n_free_plain=n_free_plain, n_free_via=res[1])
+            if verbose:
+                print(f"collision-free without the via-point cost: {n_free_plain}/{batch}   with it ({via_cost} per segment, "
+                      f"w_via = 1/{via_cost}): {res[1]}/{batch}")
+        return res
     # pre-bound launch: reads q, qd in place; cost = w_obj * (self + object + workspace hinges) + the prior's factor costs
     plan = task.rollout_gp_plan(q, qd, dt, sigma_gp, gp_weight=1.0, w_self=w_obj, w_obj=w_obj, w_ws=w_obj)
     # the collision hinges at via_cost via points per segment, same weights: one more launch, its gradient lands on the way points
@@ -92,10 +99,11 @@ def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0
     return q, n_free, coll0
 
 
-def _main_fused(task, q, qd, q_lines, dt, sigma_gp, w_obj, lr, iters, verbose, stats):
+def _main_fused(task, q, qd, q_lines, dt, sigma_gp, w_obj, lr, iters, verbose, stats, via_cost=0):
     """the same objective, pins and Adam, `iters` iterations in launches of 32: plan.step(n) returns the cost of the state it started from"""
     batch, horizon = q.shape[:2]
-    plan = task.rollout_adam_plan(q, qd, dt, sigma_gp, gp_weight=1.0, w_self=w_obj, w_obj=w_obj, w_ws=w_obj, lr=lr)      # start and goal pinned
+    via = dict(w_via=1.0 / via_cost, num_interpolation=via_cost) if via_cost > 0 else {}
+    plan = task.rollout_adam_plan(q, qd, dt, sigma_gp, gp_weight=1.0, w_self=w_obj, w_obj=w_obj, w_ws=w_obj, lr=lr, **via)   # start and goal pinned
     probe = task.rollout_adam_plan(q, qd, dt, sigma_gp, gp_weight=0.0, w_self=w_obj, w_obj=w_obj, w_ws=w_obj, lr=0.0)   # collision cost only
     cost0 = float(probe.step(1).sum(1).mean()) / w_obj
     torch.cuda.synchronize()
@@ -128,6 +136,6 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--fused", action="store_true", help="the whole loop in one kernel (rollout_adam_plan)")
-    ap.add_argument("--via-cost", type=int, default=0, help="N > 0: add the collision cost at N via points per segment (eager loop)")
+    ap.add_argument("--via-cost", type=int, default=0, help="N > 0: add the collision cost at N via points per segment")
     a = ap.parse_args()
     main(a.batch, a.horizon, a.iters, a.device, fused=a.fused, via_cost=a.via_cost)

@@ -449,7 +449,7 @@ int trk_rollout_jacobian_cost_grad(const TrkModel* model, const TrkCostModel* cm
 int trk_rollout_is_specialized(const TrkModel* model, const TrkCostModel* cm, const TrkRolloutWeights* w);
 
 /* Which kernel family served the CALLING THREAD's latest rollout call (trk_rollout_cost_grad[_f16], trk_rollout_gp_cost_grad,
- * trk_rollout_points_cost_grad, trk_rollout_collision[_via], trk_rollout_points_collision[_via], trk_rollout_via_cost_grad).  No reference counterpart: the reference has one code path
+ * trk_rollout_points_cost_grad, trk_rollout_collision[_via], trk_rollout_points_collision[_via], trk_rollout_via_cost_grad, trk_rollout_gp_via_adam_steps).  No reference counterpart: the reference has one code path
  * (tasks.py:139-232); here a cost model whose link sets no generated unit bakes is served by the table-driven kernels, 10 - 30 x slower. */
 enum {
     TRK_DISPATCH_NONE = 0,                  /* no rollout call yet on this thread (or a call that had nothing to launch) */
@@ -457,7 +457,8 @@ enum {
     TRK_DISPATCH_TABLE = 2,                 /* the table-driven kernels */
     TRK_DISPATCH_GENERATED_PLUS_PRIOR = 3,  /* trk_rollout_gp_cost_grad: generated rollout, the GP prior as launches of its own;
                                              * trk_rollout_jacobian_cost_grad: generated rollout, the Jacobian as a launch of its own */
-    TRK_DISPATCH_GENERATED_VIA_COST = 4     /* trk_rollout_via_cost_grad: one launch of the generated via-point cost kernel */
+    TRK_DISPATCH_GENERATED_VIA_COST = 4,    /* trk_rollout_via_cost_grad: one launch of the generated via-point cost kernel */
+    TRK_DISPATCH_GENERATED_VIA_ADAM = 5     /* trk_rollout_gp_via_adam_steps: the generated planning-loop kernel with the via-point term */
 };
 int trk_last_dispatch(void);
 /* The generated rollout kernels come in two families: the generic one, and a plan-specialised one that has the objective terms with
@@ -946,6 +947,38 @@ int trk_rollout_gp_adam_steps(const TrkModel* model, const TrkCostModel* cm, con
 int trk_rollout_via_cost_grad(const TrkModel* model, const TrkCostModel* cm, const TrkRolloutWeights* weights, const float* x,
                               int64_t n_traj, int32_t horizon, int32_t n_interp, const float* alpha, const float* beta,
                               const float* seed, float* cost, float* gq, trk_stream_t stream);
+
+/* trk_rollout_gp_adam_steps with the collision / EE objective ALSO at the via points that trajectory validation tests: the arm's
+ * planning loop with the term of trk_rollout_via_cost_grad inside the kernel.  With h, g the weighted objective of
+ * trk_rollout_cost_grad and its gradient at a configuration (the SAME `weights` at way points and via points) and
+ *   v[b,t,a] = q[b,t] * alpha[a] + q[b,t+1] * beta[a]   (each product and the sum rounded once, as trk_rollout_via_cost_grad's),
+ * the objective of an iteration is trk_rollout_gp_adam_steps' plus
+ *   cost[b,t] += w_via * sum_a h(v[b,t,a])      -- the segment t -> t+1 attributed to sample t, 0 at t = horizon-1
+ *   gq[b,t]   += w_via * (sum_a alpha[a] g(v[b,t,a]) + sum_a beta[a] g(v[b,t-1,a]));   gqd is unchanged.
+ * The fold, operation by operation, every operation rounded once (fp32, fused multiply-add where one is written):
+ *   C = h(q[b,t]);  L[d] = g(q[b,t])[d];  U[d] = 0
+ *   for a = 0 .. n_interp-1, only where the segment t -> t+1 exists:
+ *       wa = w_via * alpha[a];  wb = w_via * beta[a]
+ *       C = fma(w_via, h(v[b,t,a]), C);  L[d] = fma(wa, g(v[b,t,a])[d], L[d]);  U[d] = fma(wb, g(v[b,t,a])[d], U[d])
+ *   gc[b,t][d] = L[b,t][d] + U[b,t-1][d]   (U[b,-1] = 0)
+ * after which C and gc take the place of the rollout's cost and gradient in trk_rollout_gp_adam_steps: cost = fma(0.5, prior, C), the
+ * gradient of q is gc + the prior's, a pinned component's gradient is zero, Adam as there.  A sample without a segment (t =
+ * horizon-1) leaves the sums by a select, not by a zero weight, and the prior's factor of a missing segment is zero by a select: a
+ * non-finite trajectory does not reach another trajectory's rows.  At horizon 1 (no segment) gc = g(q) exactly.
+ * alpha, beta: DEVICE [n_interp].  Validation (before any device work): everything trk_rollout_gp_adam_steps checks; null via /
+ * alpha / beta, n_interp < 1 or a non-finite w_via: TRK_ERR_INVALID_ARG.  TRK_ERR_UNSUPPORTED as there (horizon not a power of two <=
+ * TRK_TRAJ_ADAM_MAX_HORIZON; no unit of the model carries k_traj_via_adam; none matches the cost model; generated kernels off).
+ * batch = 0: TRK_OK without a launch.  At most 32 iterations per launch, more = several launches inside the call, the result does
+ * not depend on the grouping.  trk_last_dispatch: TRK_DISPATCH_GENERATED_VIA_ADAM.  No host synchronisation: capturable. */
+typedef struct TrkTrajVia {
+    float w_via;                /* finite */
+    int32_t n_interp;           /* >= 1 */
+    const float* alpha;         /* DEVICE [n_interp] */
+    const float* beta;          /* DEVICE [n_interp] */
+} TrkTrajVia;
+int trk_rollout_gp_via_adam_steps(const TrkModel* model, const TrkCostModel* cm, const TrkRolloutWeights* weights, const TrkGpPrior* gp,
+                                  const TrkTrajVia* via, const TrkTrajAdam* adam, float* q, float* qd, float* adam_m, float* adam_v,
+                                  int64_t batch, int32_t horizon, float* cost, trk_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -132,19 +132,21 @@ def trace(which, iters, case):
         torch.cuda.synchronize()
 
 
-def summarize(trace_dir, iters, tail):
-    """kernel time per iteration of the last `tail` of `iters` iterations of a --trace run, from rocprofv3's kernel_trace.csv"""
+def summarize(trace_dir, iters, tail, loop_kernels=("k_traj_adam",)):
+    """kernel time per iteration of the last `tail` of `iters` iterations of a --trace run, from rocprofv3's kernel_trace.csv;
+    loop_kernels: the names that mark a trace of a fused loop (tools/bench_arm_traj_via.py adds its own)"""
     import csv
     rows = []
     for f in Path(trace_dir).rglob("*kernel_trace.csv"):
         rows += list(csv.DictReader(f.open()))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     names = [r["Kernel_Name"] for r in rows]
-    fused = any("k_traj_adam" in n for n in names[-20:])
+    is_loop = lambda n: any(k in n for k in loop_kernels)
+    fused = any(is_loop(n) for n in names[-20:])
     per_launch = 32 if fused else 1                                                 # the fused loop: 32 iterations per launch
     groups = tail // per_launch
     if fused:                                                                       # one kernel per 32 iterations: its last launches, by name
-        loop = [r for r in rows if "k_traj_adam" in r["Kernel_Name"]][-groups:]
+        loop = [r for r in rows if is_loop(r["Kernel_Name"])][-groups:]
         ns = sum(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in loop)
         out = dict(trace=str(trace_dir), kernels_per_iteration=1 / per_launch, kernel_us_per_iteration=round(ns / 1e3 / (len(loop) * per_launch), 3),
                    kernels={loop[-1]["Kernel_Name"][:90]: 1})

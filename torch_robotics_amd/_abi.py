@@ -143,6 +143,10 @@ class TrajAdam(C.Structure):            # TrkTrajAdam
     _fields_ = [("lr", C.c_float), ("pin", C.c_int32), ("first_step", C.c_int32), ("n_steps", C.c_int32)]
 
 
+class TrajVia(C.Structure):             # TrkTrajVia
+    _fields_ = [("w_via", C.c_float), ("n_interp", C.c_int32), ("alpha", C.c_void_p), ("beta", C.c_void_p)]
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 

@@ -41,6 +41,7 @@ EXPORTS = [
     "trk_rollout_points_collision", "trk_rollout_points_collision_via",
     "trk_rollout_via_cost_grad",
     "trk_scene2d_traj_via_cost_grad", "trk_scene2d_traj_via_adam_steps",
+    "trk_rollout_gp_via_adam_steps",
 ]
 
 
@@ -205,6 +206,8 @@ def lib():
     L.trk_rollout_points_collision.argtypes = [vp, vp, i32, vp, i64, i32, f32, vp, vp, vp]
     L.trk_rollout_points_collision_via.argtypes = [vp, vp, i32, vp, i64, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp]
     L.trk_rollout_via_cost_grad.argtypes = [vp, vp, C.POINTER(_abi.RolloutWeights), vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.trk_rollout_gp_via_adam_steps.argtypes = [vp, vp, C.POINTER(_abi.RolloutWeights), C.POINTER(_abi.GpPrior), C.POINTER(_abi.TrajVia),
+                                                C.POINTER(_abi.TrajAdam), vp, vp, vp, vp, i64, i32, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)        # AttributeError here = the library does not export the ABI
         if name not in ("trk_last_error", "trk_model_destroy", "trk_cost_model_destroy", "trk_point_set_destroy",

@@ -2278,6 +2278,187 @@ def generate_via_cost_source(kin: KinModel, tmpl: CollisionTemplate, ident: str,
     return "\n".join(out) + "\n"
 
 
+# Wavefronts per SIMD k_traj_via_adam runs at: what every instantiation of every unit reaches.  On top of k_traj_adam's
+# registers the kernel keeps the next sample's position and the two gradient accumulators (3 D) -- not a second rollout body: the way
+# point is one more pass of the loop over the via points.  Stating only its block size, as k_traj_adam does, the Panda's kernels take
+# 207 (bi) / 211 (bg) VGPRs on sphere scenes and 237 / 243 in the general-scene instantiation, iiwa7 194 / 199 / 198 / 204, UR10
+# 171 / 168 / 177 / 181, none with scratch.
+TRAJ_VIA_ADAM_OCCUPANCY = 2
+
+
+def via_adam_ok(kin: KinModel, tmpl: CollisionTemplate, ident: str = "", snap: float = SNAP) -> bool:
+    """does the robot's link unit get a spec_<ident>_vadam unit?  The units that carry k_traj_adam: whole-row staging, no virtual
+    columns, up to 8 DOF (_LinkUnit.traj_adam_ok)"""
+    u = _LinkUnit(kin, tmpl, ident, snap)
+    return u.traj_adam_ok
+
+
+def _traj_via_adam_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
+    """k_traj_via_adam_bi / _bg<BOX>: k_traj_adam's planning loop (trk_rollout_gp_via_adam_steps) with the collision / EE objective
+    also at the n via points of every segment, as k_via_cost evaluates them.  The layout is k_traj_adam's: one lane per sample, fp32,
+    the horizon a power of two <= 64, (q, qd, m, v) in the lane's registers across the launch's iterations, neighbours in time by
+    DPP wavefront shifts; nothing crosses a wavefront, no atomics, no barrier, no positions (NoFlush).  The way point is one more pass
+    of the run-time loop over the via points: pass a = -1 evaluates q itself and starts the sums, passes 0 .. n - 1 evaluate
+    q alpha[a] + q_next beta[a] (each product and the sum rounded once) and fold cost and gradient with the weight w_via, so the
+    rollout body (same emitters, same scene switch BOX) is emitted once.  A lane without a segment leaves the via passes by a select."""
+    kin, L, D = u.kin, u.L, u.D
+    E = Emitter()
+    kname = "k_traj_via_adam_bi" if base_identity else "k_traj_via_adam_bg"
+    E.raw("template <bool BOX>      // the scene switch of k_rollout (scene_is_general): boxes and / or a voxel grid")
+    E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK) {kname}(TrajViaAdamArgs A) {{      // {TRAJ_VIA_ADAM_OCCUPANCY} wavefronts per SIMD (TRAJ_VIA_ADAM_OCCUPANCY)")
+    E.raw("    constexpr int LDS_LANE = 2 * D;        // the transposes of q, qd [64][D] and of m, v [64][2D]")
+    E.raw("    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * LDS_LANE + SPEC_WAVES * (TRK_LDS_SPHERES * 4 + (BOX ? TRK_LDS_PRIMS * 8 : 0))];")
+    E.raw("    const int lane = __builtin_amdgcn_workitem_id_x() & (TRK_WAVE - 1);")
+    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_workitem_id_x() / TRK_WAVE);")
+    E.raw("    float* lds = lds_all + wave * (TRK_WAVE * LDS_LANE);")
+    E.raw("    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * LDS_LANE) + wave * (TRK_LDS_SPHERES + (BOX ? 2 * TRK_LDS_PRIMS : 0));")
+    E.raw("    float4* lds_prm = BOX ? lds_sph + TRK_LDS_SPHERES : nullptr;")
+    E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);")
+    E.raw("    const SpheresInFlight prm = BOX ? spec_load_prims_issue(A.C, lane) : sph;")
+    E.raw("    const int64_t wblock = (int64_t)__builtin_amdgcn_workgroup_id_x() * SPEC_WAVES + wave;")
+    E.raw("    const int64_t base = wblock * TRK_WAVE;")
+    E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));      // lanes beyond: clamped loads, no stores")
+    E.raw("    const bool update = A.update != 0;")
+    E.raw("    float x[D], qd[D], am[2 * D], av[2 * D];")
+    E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, x);")
+    E.raw("    spec_load_q<D>(static_cast<const float*>(A.qd), base, rows, lane, lds, qd);")
+    E.raw("    if (update) {")
+    E.raw("        spec_load_q<2 * D>(static_cast<const float*>(A.adam_m), base, rows, lane, lds, am);")
+    E.raw("        spec_load_q<2 * D>(static_cast<const float*>(A.adam_v), base, rows, lane, lds, av);")
+    E.raw("    } else {")
+    E.raw("#pragma unroll")
+    E.raw("        for (int d = 0; d < 2 * D; ++d) { am[d] = 0.0f; av[d] = 0.0f; }")
+    E.raw("    }")
+    E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
+    E.raw("    if constexpr (BOX) spec_load_spheres_finish(lds_prm, lane, prm);")
+    E.raw("    const NoFlush flush{};                 // this kernel writes no positions")
+    E.raw("    // time step: 64 is a multiple of the horizon, so a wavefront starts at step 0 of a trajectory")
+    E.raw("    const int tl = lane & (A.gp_H - 1);")
+    E.raw("    const bool t_first = tl == 0, t_last = tl == A.gp_H - 1;")
+    E.raw("    const bool pin_q = ((A.pin & 1) && t_first) || ((A.pin & 2) && t_last);        // a pinned component's gradient is taken as zero")
+    E.raw("    const bool pin_qd = ((A.pin & 4) && t_first) || ((A.pin & 8) && t_last);")
+    E.raw("    const bool on = lane < rows && !t_last;                          // the segment t -> t + 1 exists: via points and the prior's factor")
+    E.raw("    const float wm = on ? A.gp_w : 0.0f;")
+    E.raw("    const float dt = A.gp_dt, gaw = wm * A.gp_a, gbw = wm * A.gp_b, gcw = wm * A.gp_c;")
+    E.raw("    float cost0 = 0.0f;")
+    E.raw("#pragma nounroll")
+    E.raw("    for (int it = 0; it < A.n_steps; ++it) {")
+    E.raw("    // the next sample's position: the via points' other end and the prior's p_t+1.  A lane without a segment keeps its own value:")
+    E.raw("    // neither the next trajectory's first way point nor lane 63's missing source is read anywhere")
+    E.raw("    float xn[D], g_lo[D], g_hi[D], csum = 0.0f;")
+    E.raw("#pragma unroll")
+    E.raw("    for (int d = 0; d < D; ++d) {")
+    E.raw("        const float nx = trk_dpp_from_next(x[d], x[d]);")
+    E.raw("        xn[d] = on ? nx : x[d];")
+    E.raw("        g_lo[d] = 0.0f; g_hi[d] = 0.0f;")
+    E.raw("    }")
+    E.raw("    // pass -1: the way point itself (weight 1, starts the sums); passes 0 .. n_via - 1: the via points of the lane's segment")
+    E.raw("#pragma nounroll")
+    E.raw("    for (int a = -1; a < A.n_via; ++a) {")
+    E.raw("    const bool way = a < 0;                // wave-uniform")
+    E.raw("    const float fa = cptr(A.alpha)[way ? 0 : a], fb = cptr(A.beta)[way ? 0 : a];")
+    E.raw("    float q[D];")
+    E.raw("#pragma unroll")
+    E.raw("    for (int d = 0; d < D; ++d) q[d] = way ? x[d] : __fadd_rn(__fmul_rn(x[d], fa), __fmul_rn(xn[d], fb));")
+    # ---------------- forward, objectives, reverse: k_rollout's ----------------
+    R, t, passv = _root_pose(base_identity)
+    _emit_angles(E, kin)
+    for p in range(1, L):
+        _emit_fk_link(E, kin, u.walk[p], R, t, passv, u.snap)
+    ticks = _Ticks()
+    _emit_collision_objectives(u, E, t, ticks, fast_arg=", decltype(ticks), false, BOX", prims_ptr="lds_prm")
+    _emit_ee_terms(E, u.tracked, R, t)
+    E.raw(ticks())
+    gq_expr = _emit_reverse_links(E, kin, R, t, {i: [f"tb{i}_{k}" for k in range(3)] for i in u.real_adj},
+                                  {l: rb for l, _, rb in u.tracked}, u.masked, tick=ticks, order=u.walk)
+    E.raw(f"    const float gc[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
+    E.raw("    // the fold of include/trk.h, every operation rounded once.  A lane without a segment leaves the via passes by SELECT, not by a")
+    E.raw("    // zero weight: 0 * (a non-finite gradient) must not reach its neighbours' rows (as k_via_cost)")
+    E.raw("    const float wa = __fmul_rn(A.w_via, fa), wb = __fmul_rn(A.w_via, fb);")
+    E.raw("    csum = way ? cost : (on ? __fmaf_rn(A.w_via, cost, csum) : csum);")
+    E.raw("#pragma unroll")
+    E.raw("    for (int d = 0; d < D; ++d) {")
+    E.raw("        g_lo[d] = way ? gc[d] : (on ? __fmaf_rn(wa, gc[d], g_lo[d]) : g_lo[d]);")
+    E.raw("        g_hi[d] = (on && !way) ? __fmaf_rn(wb, gc[d], g_hi[d]) : g_hi[d];")
+    E.raw("    }")
+    E.raw("    }")
+    # ---------------- the prior on the register copies (k_traj_adam's expressions) ----------------
+    E.raw("    // the prior: e_t = (p_t + dt v_t - p_t+1, v_t - v_t+1), r = w Q^-1 e; the finished factor goes to the next lane by wave_shr:1.")
+    E.raw("    // A lane without a segment has weight 0 AND sends 0 by a select, so a lane at step 0 receives 0 whatever its neighbour holds;")
+    E.raw("    // lane 0 has no source and keeps the shift's `old` operand, 0.  The previous lane's share of the via gradient comes the same way.")
+    E.raw("    float gqv[D], gvv[D], accg = 0.0f;")
+    E.raw("#pragma unroll")
+    E.raw("    for (int d = 0; d < D; ++d) {")
+    E.raw("        const float p0 = x[d], v0 = qd[d];")
+    E.raw("        const float vs = trk_dpp_from_next(v0, v0);")
+    E.raw("        const float pn = xn[d], vn = on ? vs : v0;")
+    E.raw("        const float ep = fmaf(dt, v0, p0) - pn, ev = v0 - vn;")
+    E.raw("        const float rp = on ? fmaf(gaw, ep, gbw * ev) : 0.0f, rv_ = on ? fmaf(gbw, ep, gcw * ev) : 0.0f;")
+    E.raw("        accg = fmaf(ep, rp, fmaf(ev, rv_, accg));")
+    E.raw("        const float gcd = __fadd_rn(g_lo[d], trk_dpp_from_prev(0.0f, g_hi[d]));")
+    E.raw("        gqv[d] = gcd + (rp - trk_dpp_from_prev(0.0f, rp));")
+    E.raw("        gvv[d] = fmaf(dt, rp, rv_) - trk_dpp_from_prev(0.0f, rv_);")
+    E.raw("    }")
+    E.raw("    if (it == 0) cost0 = fmaf(0.5f, accg, csum);      // the state as passed in; the segment t -> t + 1 attributed to sample t")
+    E.raw("    if (update) {")
+    E.raw("        const float step = spec_adam_step_size(A.lr, A.sched.bc1[it]), rs = A.sched.rsqrt_bc2[it];")
+    E.raw("#pragma unroll")
+    E.raw("        for (int d = 0; d < D; ++d) {")
+    E.raw("            spec_adam_component(pin_q ? 0.0f : gqv[d], step, rs, x[d], am[d], av[d]);")
+    E.raw("            spec_adam_component(pin_qd ? 0.0f : gvv[d], step, rs, qd[d], am[D + d], av[D + d]);")
+    E.raw("        }")
+    E.raw("    }")
+    E.raw("    }")
+    E.raw("    if (A.cost && lane < rows) store_wt_f1(A.cost + base + lane, cost0);")
+    E.raw("    if (update) {")
+    E.raw("        spec_store_gq<D>(A.q, base, rows, lane, lds, x);")
+    E.raw("        spec_store_gq<D>(A.qd, base, rows, lane, lds, qd);")
+    E.raw("        spec_store_gq<2 * D>(A.adam_m, base, rows, lane, lds, am);")
+    E.raw("        spec_store_gq<2 * D>(A.adam_v, base, rows, lane, lds, av);")
+    E.raw("    }")
+    E.raw("}")
+    return E.lines
+
+
+def via_adam_kernels(ident: str) -> List[str]:
+    """the kernels a spec_<ident>_vadam unit defines"""
+    return [f"spec_{ident}::k_traj_via_adam_{b}<{v}>" for b in ("bi", "bg") for v in ("false", "true")]
+
+
+def generate_via_adam_source(kin: KinModel, tmpl: CollisionTemplate, ident: str, snap: float = SNAP) -> str:
+    """spec_<ident>_vadam.hip: the planning-loop kernels with the via-point term (_traj_via_adam_kernel), a translation unit of its
+    own like generate_via_cost_source's -- same namespace, same _LinkUnit plan, the same FP freedoms, nothing shared but the headers.
+    The unit announces its launcher under the main unit's ident, model hash and template identity (trk_spec_register_via_adam), and
+    trk_rollout_gp_via_adam_steps looks it up by those of the entry that serves the cost model.  Linked / dlopen-ed units only."""
+    u = _LinkUnit(kin, tmpl, ident, snap)
+    assert u.traj_adam_ok, "the planning-loop kernel exists for the whole-row four-wavefront units"
+    out: List[str] = [f"// GENERATED by torch_robotics_amd/codegen.py for model '{kin.name}' ({u.L} links, {u.D} DOF): planning-loop "
+                      f"kernels with the via-point term -- do not edit."]
+    out.append("#pragma clang fp reassociate(on) contract(fast) reciprocal(on)")
+    out.append('#include "trk_spec_common.h"')
+    out.append(f"namespace spec_{ident} {{")
+    out.append(f"constexpr int L = {u.L}, D = {u.D}, NL = {u.NL};")
+    out.append(f'static_assert(TRK_OBJ_TICK_SLOTS == {OBJ_TICK_SLOTS}, "chunk numbering of this unit assumes another TRK_OBJ_TICK_SLOTS");')
+    for base_identity in (True, False):
+        out.extend(_traj_via_adam_kernel(u, base_identity) + [""])
+    out.append("#ifndef __HIPCC_RTC__          // the unit's host half: its launcher, announced under the main unit's ident, hash and template")
+    out += ["static void launch_via_adam(const TrajViaAdamArgs& a, int base_identity, hipStream_t st) {",
+            "    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);",
+            f"    if ({u.scene_switch}) {{",
+            "        if (base_identity) hipLaunchKernelGGL((k_traj_via_adam_bi<true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+            "        else hipLaunchKernelGGL((k_traj_via_adam_bg<true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+            "    } else {",
+            "        if (base_identity) hipLaunchKernelGGL((k_traj_via_adam_bi<false>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+            "        else hipLaunchKernelGGL((k_traj_via_adam_bg<false>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+            "    }",
+            "}"]
+    out.append(f"static struct RegViaAdam {{ RegViaAdam() {{ trk_spec_register_via_adam(\"{ident}\", 0x{model_hash(kin):016x}ull, "
+               f"0x{template_identity(tmpl):016x}ull, (uint32_t)sizeof(TrajViaAdamArgs), launch_via_adam); }} }} reg_via_adam;")
+    out.append("#endif      // !__HIPCC_RTC__")
+    out.append(f"}}  // namespace spec_{ident}")
+    return "\n".join(out) + "\n"
+
+
 def _jac_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     """k_jac_bi / _bg: stateful FK + geometric Jacobian of ONE link (trk_fk_jacobian; robot_tree.py:136-190, 218-248): the walk unrolled
     with the stateful path's quirks (clamp wherever limits exist, rotation about the axis with its sign ignored); every joint that can
@@ -3476,6 +3657,16 @@ def generate_all(out_dir) -> List[str]:
         kin = KinModel.from_urdf(str(URDF_DIR / urdf))
         src = generate_points_rollout_source(kin, tmpl_fn(kin), ident)
         path = out_dir / f"spec_{ident}.hip"
+        if not path.exists() or path.read_text() != src:
+            path.write_text(src)
+        written.append(path.name)
+    for ident, (urdf, tmpl_fn) in SPEC_ROBOTS.items():                 # the planning loop with the via-point term: units of their own
+        kin = KinModel.from_urdf(str(URDF_DIR / urdf))
+        tmpl = tmpl_fn(kin)
+        if not via_adam_ok(kin, tmpl, ident):
+            continue
+        src = generate_via_adam_source(kin, tmpl, ident)
+        path = out_dir / f"spec_{ident}_vadam.hip"
         if not path.exists() or path.read_text() != src:
             path.write_text(src)
         written.append(path.name)

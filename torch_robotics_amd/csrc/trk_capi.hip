@@ -184,6 +184,33 @@ int trk_spec_register_via_cost(const char* ident, uint64_t model_hash, uint64_t 
     via_cost_registry().push_back(ViaCostUnit{ident, model_hash, template_identity, fn});
     return 0;
 }
+// the planning-loop kernels with the via-point term (k_traj_via_adam): translation units of their own, spec_<ident>_vadam, announced
+// like the via-point cost kernels above
+namespace {
+struct ViaAdamUnit { std::string ident; uint64_t model_hash, template_identity; SpecViaAdamLaunchFn fn; };
+std::vector<ViaAdamUnit>& via_adam_registry() { static std::vector<ViaAdamUnit> r; return r; }
+std::mutex& via_adam_mutex() { static std::mutex m; return m; }       // (a run-time unit registers from the thread that loads it)
+SpecViaAdamLaunchFn via_adam_launcher(const SpecEntry* e) {
+    if (!e->name || e->module_ctx || e->n_points != 0 || e->n_virtual != 0) return nullptr;      // (a code-object unit has none)
+    const uint64_t id = via_template_identity(e);
+    std::lock_guard<std::mutex> lock(via_adam_mutex());
+    for (const auto& r : via_adam_registry())
+        if (r.model_hash == e->model_hash && r.template_identity == id && r.ident == e->name) return r.fn;
+    return nullptr;
+}
+}  // namespace
+int trk_spec_register_via_adam(const char* ident, uint64_t model_hash, uint64_t template_identity, uint32_t sizeof_args, SpecViaAdamLaunchFn fn) {
+    if (!ident || !fn || sizeof_args != sizeof(TrajViaAdamArgs)) {
+        fprintf(stderr, "libtrk: refusing a generated unit's planning-loop kernels with the via-point term (compiled against another "
+                        "TrajViaAdamArgs layout) -- they will not be dispatched\n");
+        return TRK_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lock(via_adam_mutex());
+    for (auto& r : via_adam_registry())
+        if (r.model_hash == model_hash && r.template_identity == template_identity && r.ident == ident) { r.fn = fn; return 0; }
+    via_adam_registry().push_back(ViaAdamUnit{ident, model_hash, template_identity, fn});
+    return 0;
+}
 int trk_spec_layout_stamp(int64_t* out) {
     if (!out) return TRK_ERR_INVALID_ARG;
     out[0] = TRK_SPEC_ABI_VERSION; out[1] = (int64_t)(sizeof(SpecArgs) + sizeof(IkArgs) + sizeof(IkGnArgs)); out[2] = (int64_t)sizeof(DevCostHdr);
@@ -1840,6 +1867,78 @@ int trk_rollout_gp_adam_steps(const TrkModel* m, const TrkCostModel* cm, const T
         if ((rc = spec_launch(fn, e, a, m, stream)) != TRK_OK) return rc;
     }
     return served_generated(TRK_OK);
+}
+
+int trk_rollout_gp_via_adam_steps(const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w, const TrkGpPrior* gp,
+                                  const TrkTrajVia* via, const TrkTrajAdam* ad, float* q, float* qd, float* adam_m, float* adam_v,
+                                  int64_t batch, int32_t horizon, float* cost, trk_stream_t stream) {
+    const char* who = "trk_rollout_gp_via_adam_steps";
+    int rc = check_rollout_call(who, m, cm, batch, horizon);
+    if (rc) return rc;
+    if (!w || !gp || !ad) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null weights / prior / TrkTrajAdam");
+    if (!via || !via->alpha || !via->beta) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null TrkTrajVia / alpha / beta");
+    if (via->n_interp < 1 || !std::isfinite(via->w_via))
+        return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": n_interp must be >= 1 and w_via finite");
+    if (!std::isfinite(w->w_self) || !std::isfinite(w->w_obj) || !std::isfinite(w->w_ws) || !std::isfinite(w->w_ee) ||
+        !std::isfinite(gp->weight) || !std::isfinite(gp->dt) || !std::isfinite(gp->sigma) || !(gp->dt > 0.0f) || !(gp->sigma > 0.0f))
+        return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": the weights must be finite, the prior needs finite dt > 0 and sigma > 0");
+    if (ad->n_steps < 0 || ad->first_step < 1 || !std::isfinite(ad->lr) || ad->pin < 0 || ad->pin > 15)
+        return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": n_steps >= 0, first_step >= 1, lr finite and pin in 0 .. 15");
+    const bool update = ad->lr != 0.0f && ad->n_steps > 0;
+    if (batch > 0 && (!q || !qd || (update && (!adam_m || !adam_v))))
+        return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null q / qd / adam_m / adam_v");
+    if (horizon > TRK_TRAJ_ADAM_MAX_HORIZON || (horizon & (horizon - 1)) != 0)
+        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": the horizon must be a power of two <= TRK_TRAJ_ADAM_MAX_HORIZON (64): a wavefront "
+                                         "owns whole trajectories and their neighbours in time are neighbouring lanes; "
+                                         "trk_rollout_gp_cost_grad + trk_rollout_via_cost_grad serve the other horizons");
+    if (batch == 0 || m->hdr.n_dofs == 0) return TRK_OK;
+    // only the generated kernel serves this call (no table-driven twin, like trk_rollout_gp_adam_steps)
+    if (!m->spec_enabled)
+        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": generated kernels are switched off for this model (trk_model_enable_specialized) "
+                                         "and the planning loop has no table-driven form");
+    const TrkRolloutWeights we = effective_weights(cm, *w);
+    SpecViaAdamLaunchFn fn = nullptr;
+    bool any = false;
+    for (const SpecEntry* c : spec_registry()) {
+        if (c->n_points != 0 || c->model_hash != m->hash || c->n_links != m->hdr.n_links || c->n_dofs != m->hdr.n_dofs) continue;
+        SpecViaAdamLaunchFn f = via_adam_launcher(c);
+        if (!f) continue;
+        any = true;
+        if (spec_matches(c, cm, &we)) { fn = f; break; }
+    }
+    if (!any)
+        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": no generated unit of this model carries the planning-loop kernel with the via-point "
+                                         "term (k_traj_via_adam: link-column units of robots up to 8 DOF, built ahead of time or by hipcc at "
+                                         "run time; a unit loaded as a code object through the hipRTC fall-back has none)");
+    if (!fn)
+        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": no generated unit with the planning-loop kernel bakes this cost model's link "
+                                         "sets for the non-zero weights");
+    if (!update && !cost) return TRK_OK;
+    TrajViaAdamArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.C = cm->hdr; a.w = we;
+    set_base_pose(a, m);
+    a.q = q; a.qd = qd; a.adam_m = adam_m; a.adam_v = adam_v; a.n = batch * horizon;
+    const float s2 = 1.0f / (gp->sigma * gp->sigma);
+    a.gp_dt = gp->dt; a.gp_w = gp->weight; a.gp_H = horizon;
+    a.gp_a = 12.0f * s2 / (gp->dt * gp->dt * gp->dt); a.gp_b = -6.0f * s2 / (gp->dt * gp->dt); a.gp_c = 4.0f * s2 / gp->dt;
+    a.lr = ad->lr; a.pin = ad->pin; a.update = update ? 1 : 0;
+    a.alpha = via->alpha; a.beta = via->beta; a.n_via = via->n_interp; a.w_via = via->w_via;
+    // at most TRK_IK_MAX_STEPS iterations per launch; the cost comes from the first launch (the state as the caller passed it)
+    const int32_t total = update ? ad->n_steps : 1;
+    for (int32_t done = 0; done < total; done += TRK_IK_MAX_STEPS) {
+        a.n_steps = std::min<int32_t>(TRK_IK_MAX_STEPS, total - done);
+        a.cost = done == 0 ? cost : nullptr;
+        for (int32_t i = 0; i < a.n_steps; ++i) {
+            const double k = (double)ad->first_step + (double)done + (double)i;
+            a.sched.bc1[i] = (float)(1.0 - std::pow(0.9, k));
+            a.sched.rsqrt_bc2[i] = (float)(1.0 / std::sqrt(1.0 - std::pow(0.999, k)));
+        }
+        fn(a, base_is_identity(m), (hipStream_t)stream);
+        TRK_HIP(last_launch_error());
+    }
+    g_last_dispatch = TRK_DISPATCH_GENERATED_VIA_ADAM;
+    return TRK_OK;
 }
 
 int trk_rollout_via_cost_grad(const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w, const float* x, int64_t n_traj,

@@ -191,6 +191,36 @@ typedef void (*SpecViaCostLaunchFn)(const ViaCostArgs& args, int base_identity, 
 int trk_spec_register_via_cost(const char* ident, uint64_t model_hash, uint64_t template_identity, uint32_t sizeof_args, SpecViaCostLaunchFn fn);
 #endif
 
+// Arguments of the generated planning-loop kernel with the via-point term (k_traj_via_adam; trk_rollout_gp_via_adam_steps):
+// TrajAdamArgs' fields under the same names, plus the interpolation weights of the via points and the term's weight.  Its own
+// struct for the reason IkArgs is one.
+struct TrajViaAdamArgs {
+    DevCostHdr C;
+    TrkRolloutWeights w;
+    float base_R[9];
+    float base_t[3];
+    float* q; float* qd;          // [N, D], in place
+    float* adam_m; float* adam_v; // [N, 2D] = [q part | qd part], in place
+    float* cost;                  // nullable [N]: the objective of the state as passed in
+    int64_t n;
+    float gp_dt, gp_a, gp_b, gp_c, gp_w;
+    int32_t gp_H;                 // a power of two <= TRK_WAVE: a wavefront owns whole trajectories
+    float lr;
+    int32_t pin;                  // bits as TrkPlanarAdam
+    int32_t n_steps;              // <= TRK_IK_MAX_STEPS
+    int32_t update;               // 0: evaluate only (cost), nothing else is written
+    IkSchedule sched;
+    const float* alpha; const float* beta;      // DEVICE [n_via]: via point a of segment t = q[t] * alpha[a] + q[t + 1] * beta[a]
+    int32_t n_via;                // via points per segment (>= 1)
+    float w_via;                  // the via term's weight
+};
+#ifndef __HIPCC_RTC__
+typedef void (*SpecViaAdamLaunchFn)(const TrajViaAdamArgs& args, int base_identity, hipStream_t stream);
+// the kernels live in a translation unit of their own, spec_<ident>_vadam, announced like spec_<ident>_via's: under the main unit's
+// ident, model hash and template identity.  Refused when compiled against another TrajViaAdamArgs.
+int trk_spec_register_via_adam(const char* ident, uint64_t model_hash, uint64_t template_identity, uint32_t sizeof_args, SpecViaAdamLaunchFn fn);
+#endif
+
 // trk_ik_step's Adam on one component with every operation rounded once, whatever FP freedoms the unit grants its other code: the
 // update is specified operation by operation (include/trk.h) and k_planar_traj_adam computes exactly this
 __device__ __forceinline__ void spec_adam_component(float g, float step, float rsqrt_bc2, float& x, float& m, float& v) {

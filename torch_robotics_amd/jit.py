@@ -15,7 +15,7 @@ import hashlib
 import os
 import subprocess
 from pathlib import Path
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -293,7 +293,10 @@ def specialize(kin: KinModel, obj_links: Sequence[int], self_pairs: Sequence[Tup
     With hipcc a whole-row unit of a robot up to 8 DOF gets its via-point cost kernels (codegen.generate_via_cost_source) compiled
     and loaded next to it -- a second hipcc run of about the main unit's length on the robot's first use, cached like it;
     TRK_JIT_VIA_UNITS=0 skips it for callers that never ask for the via-point cost (they keep the two-step route).  The hipRTC
-    fall-back carries none: such a robot keeps the two-step via-point cost."""
+    fall-back carries none: such a robot keeps the two-step via-point cost.  The planning-loop kernels with the via-point term
+    (codegen.generate_via_adam_source) are a third unit under the same rule and the same switch, compiled and loaded on the first
+    request for the term (load_via_adam_units: ops.ArmAdamPlan(..., w_via=, num_interpolation=)), not here: a robot that never asks
+    for the fused via loop keeps its first-use cost."""
     tmpl = codegen.CollisionTemplate(obj_links=[int(i) for i in obj_links],
                                      self_pairs=[(int(a), int(b)) for a, b in self_pairs], ee_link=int(ee_link),
                                      ee2_link=int(ee2_link), virtual=[tuple(r) for r in virtual])
@@ -308,10 +311,35 @@ def specialize(kin: KinModel, obj_links: Sequence[int], self_pairs: Sequence[Tup
                 if not (vso.exists() and vstamp.exists() and vstamp.read_text() == _generator_stamp()):
                     vso = _compile_unit(codegen.generate_via_cost_source(kin, tmpl, ident), f"{ident}_via", verbose)
                 _loaded[f"{ident}_via"] = C.CDLL(str(vso))
+                if codegen.via_adam_ok(kin, tmpl, ident):
+                    # its planning-loop kernels with the via-point term (k_traj_via_adam) are a third unit, compiled only when a plan
+                    # first asks for the term: load_via_adam_units
+                    _pending_via_adam[ident] = (kin, tmpl)
         else:                               # no compiler driver on this box: the in-process fall-back
             _loaded[ident] = _load_unit_rtc(kin, tmpl, ident)
         _loaded_templates[ident] = (codegen.model_hash(kin), tmpl)
     return ident
+
+
+_pending_via_adam: Dict[str, tuple] = {}       # run-time units whose spec_<ident>_vadam unit has not been asked for yet: ident -> (kin, tmpl)
+
+
+def load_via_adam_units(kin: KinModel, verbose: bool = False) -> List[str]:
+    """Compile (cached under the generator's stamp, like every unit) and load the planning-loop kernels with the via-point term of
+    every run-time unit of this robot that qualifies for them; each unit's initialiser announces its launcher under the main unit's
+    ident (trk_spec_register_via_adam).  Called when a plan binds trk_rollout_gp_via_adam_steps; idempotent, and a no-op for robots
+    served by the bundled units, whose kernels are linked into libtrk.so.  Returns the idents loaded by this call."""
+    h, done = codegen.model_hash(kin), []
+    for ident, (k2, tmpl) in list(_pending_via_adam.items()):
+        if codegen.model_hash(k2) != h:
+            continue
+        aso, astamp = JIT_DIR / f"spec_{ident}_vadam.so", JIT_DIR / f"spec_{ident}_vadam.stamp"
+        if not (aso.exists() and astamp.exists() and astamp.read_text() == _generator_stamp()):
+            aso = _compile_unit(codegen.generate_via_adam_source(k2, tmpl, ident), f"{ident}_vadam", verbose)
+        _loaded[f"{ident}_vadam"] = C.CDLL(str(aso))
+        del _pending_via_adam[ident]
+        done.append(ident)
+    return done
 
 
 def _virtual_rows(spec):

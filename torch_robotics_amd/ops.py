@@ -906,7 +906,8 @@ def rollout_is_specialized(model: ModelHandle, cm: CostHandle, weights) -> bool:
     return bool(lib().trk_rollout_is_specialized(model._h, cm._h, C.byref(_weights_struct(weights))))
 
 
-DISPATCH_NAMES = {0: "none", 1: "generated", 2: "table-driven", 3: "generated + prior launches", 4: "generated via-point cost"}
+DISPATCH_NAMES = {0: "none", 1: "generated", 2: "table-driven", 3: "generated + prior launches", 4: "generated via-point cost",
+                  5: "generated planning loop with the via-point term"}
 
 
 def rollout_points_is_specialized(ps: "PointSetHandle", cm: CostHandle, weights) -> bool:
@@ -1741,11 +1742,14 @@ class ArmAdamPlan(_Plan):
     trk_rollout_gp_adam_steps; generated kernel k_traj_adam, robots up to 8 DOF).  Pre-bound: `step(n)` runs the next n iterations on
     the caller's q, qd (B,H,D) fp32 IN PLACE -- one launch per 32 iterations -- and returns the (B,H) cost of the state it started
     from.  The plan owns `m`, `v` (B,H,2D) = [q part | qd part] and the iteration counter `t`.  H must be a power of two <= 64.
-    pin_*: the start / goal position (velocity) keeps its value.  lr = 0 only evaluates."""
+    pin_*: the start / goal position (velocity) keeps its value.  lr = 0 only evaluates.
+    With num_interpolation > 0 and w_via != 0 the objective also holds w_via x the collision / EE objective at the num_interpolation
+    via points of every segment -- the points trajectory validation tests -- under the same weights (trk_rollout_gp_via_adam_steps,
+    kernel k_traj_via_adam); otherwise the plan is exactly the plain loop."""
 
     def __init__(self, model: ModelHandle, cm: CostHandle, weights, q: torch.Tensor, qd: torch.Tensor, dt: float, sigma: float,
                  gp_weight: float = 1.0, lr: float = 1e-2, pin_start: bool = True, pin_goal: bool = True, pin_start_vel: bool = False,
-                 pin_goal_vel: bool = False):
+                 pin_goal_vel: bool = False, w_via: float = 0.0, num_interpolation: int = 0):
         B, H, D = _gp_args(model, q, qd, "ArmAdamPlan")
         if q.dtype != torch.float32:
             raise ValueError("ArmAdamPlan: q, qd must be float32 (the planning-loop kernel has no fp16 I/O)")
@@ -1761,9 +1765,24 @@ class ArmAdamPlan(_Plan):
         self._w = _weights_struct(weights)
         self._gp = _abi.GpPrior(float(dt), float(sigma), float(gp_weight))
         self._adam = _abi.TrajAdam(float(lr), self.pin, 1, 0)
-        self._fn = lib().trk_rollout_gp_adam_steps
-        self._args = (model._h, cm._h, C.byref(self._w), C.byref(self._gp), C.byref(self._adam), q.data_ptr(), qd.data_ptr(),
-                      self.m.data_ptr(), self.v.data_ptr(), B, H, self.cost.data_ptr())
+        self.w_via, self.num_interpolation = float(w_via), int(num_interpolation)
+        self._bind(via=self.num_interpolation > 0 and self.w_via != 0.0)
+
+    def _bind(self, via: bool) -> None:
+        """the entry point and its arguments: the via loop only where the via term is on, otherwise exactly the plain loop"""
+        tail = (C.byref(self._adam), self.q.data_ptr(), self.qd.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.B, self.H,
+                self.cost.data_ptr())
+        head = (self.model._h, self.cm._h, C.byref(self._w), C.byref(self._gp))
+        if via:
+            from . import jit
+            jit.load_via_adam_units(self.model.kin)      # a run-time unit's k_traj_via_adam is compiled on the first request for it
+            self._weights = via_point_weights(self.num_interpolation, self.device)      # kept alive: the struct points into them
+            self._via = _abi.TrajVia(self.w_via, self.num_interpolation, self._weights[0].data_ptr(), self._weights[1].data_ptr())
+            self._fn = lib().trk_rollout_gp_via_adam_steps
+            self._args = head + (C.byref(self._via),) + tail
+        else:
+            self._fn = lib().trk_rollout_gp_adam_steps
+            self._args = head + tail
 
     def step(self, n: int = 1, stream: Optional[int] = None) -> torch.Tensor:
         n = int(n)

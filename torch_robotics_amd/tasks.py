@@ -254,13 +254,15 @@ class PlanningTask(Task):
                                  grad_dtype=grad_dtype, grad_scale=grad_scale, strict=os.environ.get("TRK_ALLOW_TABLE_DRIVEN", "0") != "1")
 
     def rollout_adam_plan(self, q, qd, dt, sigma_gp, gp_weight=1.0, w_self=1.0, w_obj=1.0, w_ws=1.0, w_ee=0.0, lr=1e-2,
-                          **pins) -> "ops.ArmAdamPlan":
+                          w_via=0.0, num_interpolation=0, **pins) -> "ops.ArmAdamPlan":
         """A small arm's planning loop on the chip (`trk_rollout_gp_adam_steps`): Adam on `rollout_gp_plan`'s objective with q, qd
         (B,H,D) fp32 and the optimiser's state in registers.  `plan.step(n)` improves q, qd in place and returns the (B,H) cost they
         started from; pins: pin_start / pin_goal (default True), pin_start_vel / pin_goal_vel (default False).  For link-column
         cost models of robots up to 8 DOF (a robot without a bundled unit compiles one on first use -- with hipcc: a unit that the
         hipRTC fall-back loads as a code object has no planning-loop kernel, and the plan's first step raises NotImplementedError) and
-        horizons that are a power of two <= 64."""
+        horizons that are a power of two <= 64.  With num_interpolation > 0 and w_via != 0 the objective also holds w_via x the same
+        collision / EE objective at the num_interpolation via points of every segment, the points `get_trajs_collision_and_free`
+        tests (`trk_rollout_gp_via_adam_steps`); otherwise the plan is the plain loop."""
         if getattr(self.robot, "has_extra_points", False):
             raise NotImplementedError("rollout_adam_plan is for link-column cost models (no grasped object / link spheres)")
         if not self._has_tree:
@@ -270,7 +272,8 @@ class PlanningTask(Task):
             raise NotImplementedError(f"rollout_adam_plan: horizon {H} is not a power of two <= 64 (a wavefront of the planning-loop "
                                       f"kernel owns whole trajectories; rollout_gp_plan serves any horizon)")
         model, cm = self._fused_handles(q.device)
-        return ops.ArmAdamPlan(model, cm, (w_self, w_obj, w_ws, w_ee), q, qd, dt, sigma_gp, gp_weight, lr, **pins)
+        return ops.ArmAdamPlan(model, cm, (w_self, w_obj, w_ws, w_ee), q, qd, dt, sigma_gp, gp_weight, lr, w_via=w_via,
+                               num_interpolation=num_interpolation, **pins)
 
     def rollout_via_plan(self, q, num_interpolation=5, w_self=1.0, w_obj=1.0, w_ws=1.0, w_ee=0.0, seed=None, gq_out=None) -> "ops.RolloutViaPlan":
         """Pre-bound via-point cost (`trk_rollout_via_cost_grad`): `plan.launch()` fills `plan.cost` (B, (H-1) n), the objective at the n
