@@ -476,6 +476,55 @@ def test_through_the_task_and_dispatch():
     plan_of(h, cm, e, e.clone(), n, 0.2).step(5)                  # batch = 0
 
 
+def test_the_launch_loop_and_the_dispatch_bookkeeping():
+    """What the two planning-loop entries share on the host and no kernel's text shows: the loop over the launches with its slice of
+    the bias-correction schedule, and trk_last_dispatch.  Panda, sphere scene, 2 x 8: 34 iterations from first_step = 31 in ONE call
+    (launches of 32 + 2) against the same entry called twice, 32 and 2 iterations with first_step advanced by hand -- bit for bit,
+    for either entry; the dispatch value after each entry, and that an early TRK_OK return (an empty batch) leaves it alone."""
+    GENERATED, VIA_COST, VIA_ADAM = 1, 4, 5                       # TRK_DISPATCH_* of include/trk.h
+    kin, spec, h, cm, o, _ = at.setup("spheres", True, "identity")
+    (B, H, n), D, L = (2, 8, 2), kin.n_dofs, lib()
+    q0, qd0 = at.inputs(kin, B, H)
+    stream = torch.cuda.current_stream(DEV).cuda_stream
+    ws, g = _abi.RolloutWeights(*W), _abi.GpPrior(*GP_ON)
+    a, b = ops.via_point_weights(n, DEV)
+    via = _abi.TrajVia(W_VIA[n], n, a.data_ptr(), b.data_ptr())
+
+    def steps(with_via, batch, calls):
+        q, qd = dev(q0), dev(qd0)
+        m, v, cost = (torch.zeros(s, **TA) for s in ((B, H, 2 * D), (B, H, 2 * D), (B, H)))
+        for k, (first, count) in enumerate(calls):
+            ad = _abi.TrajAdam(LR, 3, first, count)
+            head = (h._h, cm._h, C.byref(ws), C.byref(g)) + ((C.byref(via),) if with_via else ())
+            fn = L.trk_rollout_gp_via_adam_steps if with_via else L.trk_rollout_gp_adam_steps
+            # (the cost is that of the state as passed in: the second call of a split run would overwrite it)
+            rc = fn(*head, C.byref(ad), q.data_ptr(), qd.data_ptr(), m.data_ptr(), v.data_ptr(), batch, H, cost.data_ptr() if k == 0 else None,
+                    stream)
+            assert rc == 0, L.trk_last_error()
+            if batch > 0:
+                assert int(L.trk_last_dispatch()) == (VIA_ADAM if with_via else GENERATED)
+        return [host(x).copy() for x in (q, qd, m, v, cost)]
+
+    for with_via in (False, True):
+        one, two = steps(with_via, B, [(31, 34)]), steps(with_via, B, [(31, 32), (63, 2)])
+        for x, y in zip(one, two):
+            assert np.array_equal(x, y), with_via
+        assert not np.array_equal(one[0], q0) and np.isfinite(one[4]).all() and (one[4] > 0).any()
+        assert not np.array_equal(one[0], steps(with_via, B, [(31, 32), (62, 2)])[0])       # ... and the schedule's slice is looked at
+    x = dev(q0)
+    cost, gq = torch.zeros((B, (H - 1) * n), **TA), torch.zeros((B, H, D), **TA)
+
+    def via_cost(n_traj):
+        return L.trk_rollout_via_cost_grad(h._h, cm._h, C.byref(ws), x.data_ptr(), n_traj, H, n, a.data_ptr(), b.data_ptr(), None,
+                                           cost.data_ptr(), gq.data_ptr(), stream)
+
+    assert via_cost(B) == 0 and int(L.trk_last_dispatch()) == VIA_COST
+    assert via_cost(0) == 0 and int(L.trk_last_dispatch()) == VIA_COST
+    for with_via in (False, True):
+        steps(with_via, 0, [(1, 3)])
+        assert int(L.trk_last_dispatch()) == VIA_COST
+
+
 def test_capture_and_replay():
     kin, spec, h, cm, o, _ = at.setup("shelf", True, "identity")
     B, H, n = 5, 64, 5

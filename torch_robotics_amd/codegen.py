@@ -2015,6 +2015,111 @@ def _ikgn_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     return E.lines
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# The trajectory-layout kernels (k_traj_adam, k_via_cost, k_traj_via_adam): a wavefront owns 64 / H whole trajectories, a sample's
+# neighbours in time are the neighbouring lanes.  What they share is emitted once, here; each kernel keeps its row geometry, its
+# loop and its prior.
+# ----------------------------------------------------------------------------------------------------------------------
+def _emit_traj_head(E: Emitter, kname: str, args_type: str, lds_lane_expr: str, lds_comment: str, occupancy_name: str) -> None:
+    """template line, signature (only the block size is stated: see the occupancy constants), the LDS carve-up -- lds_lane_expr floats
+    per lane for the transposes, then the wavefronts' sphere / primitive tables -- and the table loads in flight"""
+    E.raw("template <bool BOX>      // the scene switch of k_rollout (scene_is_general): boxes and / or a voxel grid")
+    E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK) {kname}({args_type} A) {{      // {globals()[occupancy_name]} wavefronts per SIMD ({occupancy_name})")
+    E.raw(f"    constexpr int LDS_LANE = {lds_lane_expr};".ljust(43) + f"// {lds_comment}")
+    E.raw("    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * LDS_LANE + SPEC_WAVES * (TRK_LDS_SPHERES * 4 + (BOX ? TRK_LDS_PRIMS * 8 : 0))];")
+    E.raw("    const int lane = __builtin_amdgcn_workitem_id_x() & (TRK_WAVE - 1);")
+    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_workitem_id_x() / TRK_WAVE);")
+    E.raw("    float* lds = lds_all + wave * (TRK_WAVE * LDS_LANE);")
+    E.raw("    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * LDS_LANE) + wave * (TRK_LDS_SPHERES + (BOX ? 2 * TRK_LDS_PRIMS : 0));")
+    E.raw("    float4* lds_prm = BOX ? lds_sph + TRK_LDS_SPHERES : nullptr;")
+    E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);")
+    E.raw("    const SpheresInFlight prm = BOX ? spec_load_prims_issue(A.C, lane) : sph;")
+
+
+def _emit_traj_tables_finish(E: Emitter) -> None:
+    """the scene tables of _emit_traj_head land in LDS (after the rows' loads were issued); no positions leave these kernels"""
+    E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
+    E.raw("    if constexpr (BOX) spec_load_spheres_finish(lds_prm, lane, prm);")
+    E.raw("    const NoFlush flush{};                 // this kernel writes no positions")
+
+
+def _emit_rollout_iteration(u: _LinkUnit, E: Emitter, base_identity: bool) -> None:
+    """forward, objectives, reverse of the configuration q: k_rollout's text (same emitters, same scene switch BOX) without positions
+    -- the tick slots are empty.  Leaves `cost` and the gradient gc[D]."""
+    kin = u.kin
+    R, t, passv = _root_pose(base_identity)
+    _emit_angles(E, kin)
+    for p in range(1, u.L):
+        _emit_fk_link(E, kin, u.walk[p], R, t, passv, u.snap)
+    ticks = _Ticks()
+    _emit_collision_objectives(u, E, t, ticks, fast_arg=", decltype(ticks), false, BOX", prims_ptr="lds_prm")
+    _emit_ee_terms(E, u.tracked, R, t)
+    E.raw(ticks())
+    gq_expr = _emit_reverse_links(E, kin, R, t, {i: [f"tb{i}_{k}" for k in range(3)] for i in u.real_adj},
+                                  {l: rb for l, _, rb in u.tracked}, u.masked, tick=ticks, order=u.walk)
+    E.raw(f"    const float gc[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(u.D))}}};")
+
+
+def _emit_adam_state_load(E: Emitter, pos: str) -> None:
+    """the Adam kernels' rows (one lane per sample) and (q, qd, m, v) into the lane's registers; the positions are called `pos`"""
+    E.raw("    const int64_t wblock = (int64_t)__builtin_amdgcn_workgroup_id_x() * SPEC_WAVES + wave;")
+    E.raw("    const int64_t base = wblock * TRK_WAVE;")
+    E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));      // lanes beyond: clamped loads, no stores")
+    E.raw("    const bool update = A.update != 0;")
+    E.raw(f"    float {pos}[D], qd[D], am[2 * D], av[2 * D];")
+    E.raw(f"    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, {pos});")
+    E.raw("    spec_load_q<D>(static_cast<const float*>(A.qd), base, rows, lane, lds, qd);")
+    E.raw("    if (update) {")
+    E.raw("        spec_load_q<2 * D>(static_cast<const float*>(A.adam_m), base, rows, lane, lds, am);")
+    E.raw("        spec_load_q<2 * D>(static_cast<const float*>(A.adam_v), base, rows, lane, lds, av);")
+    E.raw("    } else {")
+    E.raw("#pragma unroll")
+    E.raw("        for (int d = 0; d < 2 * D; ++d) { am[d] = 0.0f; av[d] = 0.0f; }")
+    E.raw("    }")
+
+
+def _emit_traj_pins(E: Emitter) -> None:
+    """the lane's time step and which of its components the pin mask holds"""
+    E.raw("    // time step: 64 is a multiple of the horizon, so a wavefront starts at step 0 of a trajectory")
+    E.raw("    const int tl = lane & (A.gp_H - 1);")
+    E.raw("    const bool t_first = tl == 0, t_last = tl == A.gp_H - 1;")
+    E.raw("    const bool pin_q = ((A.pin & 1) && t_first) || ((A.pin & 2) && t_last);        // a pinned component's gradient is taken as zero")
+    E.raw("    const bool pin_qd = ((A.pin & 4) && t_first) || ((A.pin & 8) && t_last);")
+
+
+def _emit_adam_loop_open(E: Emitter) -> None:
+    """the prior's coefficients times the lane's weight wm, and the launch's loop over its iterations"""
+    E.raw("    const float dt = A.gp_dt, gaw = wm * A.gp_a, gbw = wm * A.gp_b, gcw = wm * A.gp_c;")
+    E.raw("    float cost0 = 0.0f;")
+    E.raw("#pragma nounroll")
+    E.raw("    for (int it = 0; it < A.n_steps; ++it) {")
+
+
+def _emit_adam_update(E: Emitter, pos: str, grad_q: str) -> None:
+    """trk_ik_step's Adam update of (pos, qd) with the gradients (grad_q, gvv[d]), and the end of the iteration"""
+    E.raw("    if (update) {")
+    E.raw("        const float step = spec_adam_step_size(A.lr, A.sched.bc1[it]), rs = A.sched.rsqrt_bc2[it];")
+    E.raw("#pragma unroll")
+    E.raw("        for (int d = 0; d < D; ++d) {")
+    E.raw(f"            spec_adam_component(pin_q ? 0.0f : {grad_q}, step, rs, {pos}[d], am[d], av[d]);")
+    E.raw("            spec_adam_component(pin_qd ? 0.0f : gvv[d], step, rs, qd[d], am[D + d], av[D + d]);")
+    E.raw("        }")
+    E.raw("    }")
+    E.raw("    }")
+
+
+def _emit_adam_state_store(E: Emitter, pos: str) -> None:
+    """the cost of the state as passed in, and (q, qd, m, v) back -- the end of an Adam kernel"""
+    E.raw("    if (A.cost && lane < rows) store_wt_f1(A.cost + base + lane, cost0);")
+    E.raw("    if (update) {")
+    E.raw(f"        spec_store_gq<D>(A.q, base, rows, lane, lds, {pos});")
+    E.raw("        spec_store_gq<D>(A.qd, base, rows, lane, lds, qd);")
+    E.raw("        spec_store_gq<2 * D>(A.adam_m, base, rows, lane, lds, am);")
+    E.raw("        spec_store_gq<2 * D>(A.adam_v, base, rows, lane, lds, av);")
+    E.raw("    }")
+    E.raw("}")
+
+
 # Wavefronts per SIMD k_traj_adam runs at: the rollout's registers + qd, m, v (5 D) + the loop-invariant scene scalars the compiler parks
 # in VGPR lanes come to 218 - 229 VGPRs for the Panda (three wavefronts = 168: 148 - 264 bytes of scratch per lane).  The kernel states
 # only its block size: with the explicit bound `, 2` the allocator leaves two instantiations a dead 20 - 36 byte private segment.
@@ -2026,61 +2131,17 @@ def _traj_adam_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     trk_rollout_gp_cost_grad (collision + EE terms + constant-velocity GP prior) with (q, qd, m, v) of a sample in its lane's registers.
     One lane per sample, fp32; the horizon is a power of two <= 64, so a wavefront owns 64 / H whole trajectories and the prior's
     neighbours in time are the neighbouring lanes (two DPP wavefront shifts per value, as k_rollout_gpt's): nothing crosses a
-    wavefront, no LDS exchange, no barrier.  The iteration is k_rollout's text (same emitters, same scene switch BOX) without
-    positions -- NoFlush: the tick slots are empty -- followed by the prior on the register copies and trk_ik_step's Adam update."""
-    kin, L, D = u.kin, u.L, u.D
+    wavefront, no LDS exchange, no barrier.  The iteration is k_rollout's text (_emit_rollout_iteration) followed by the prior on
+    the register copies and trk_ik_step's Adam update."""
     E = Emitter()
-    kname = "k_traj_adam_bi" if base_identity else "k_traj_adam_bg"
-    E.raw("template <bool BOX>      // the scene switch of k_rollout (scene_is_general): boxes and / or a voxel grid")
-    E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK) {kname}(TrajAdamArgs A) {{      // {TRAJ_ADAM_OCCUPANCY} wavefronts per SIMD (TRAJ_ADAM_OCCUPANCY)")
-    E.raw("    constexpr int LDS_LANE = 2 * D;        // the transposes of q, qd [64][D] and of m, v [64][2D]")
-    E.raw("    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * LDS_LANE + SPEC_WAVES * (TRK_LDS_SPHERES * 4 + (BOX ? TRK_LDS_PRIMS * 8 : 0))];")
-    E.raw("    const int lane = __builtin_amdgcn_workitem_id_x() & (TRK_WAVE - 1);")
-    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_workitem_id_x() / TRK_WAVE);")
-    E.raw("    float* lds = lds_all + wave * (TRK_WAVE * LDS_LANE);")
-    E.raw("    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * LDS_LANE) + wave * (TRK_LDS_SPHERES + (BOX ? 2 * TRK_LDS_PRIMS : 0));")
-    E.raw("    float4* lds_prm = BOX ? lds_sph + TRK_LDS_SPHERES : nullptr;")
-    E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);")
-    E.raw("    const SpheresInFlight prm = BOX ? spec_load_prims_issue(A.C, lane) : sph;")
-    E.raw("    const int64_t wblock = (int64_t)__builtin_amdgcn_workgroup_id_x() * SPEC_WAVES + wave;")
-    E.raw("    const int64_t base = wblock * TRK_WAVE;")
-    E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));      // lanes beyond: clamped loads, no stores")
-    E.raw("    const bool update = A.update != 0;")
-    E.raw("    float q[D], qd[D], am[2 * D], av[2 * D];")
-    E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
-    E.raw("    spec_load_q<D>(static_cast<const float*>(A.qd), base, rows, lane, lds, qd);")
-    E.raw("    if (update) {")
-    E.raw("        spec_load_q<2 * D>(static_cast<const float*>(A.adam_m), base, rows, lane, lds, am);")
-    E.raw("        spec_load_q<2 * D>(static_cast<const float*>(A.adam_v), base, rows, lane, lds, av);")
-    E.raw("    } else {")
-    E.raw("#pragma unroll")
-    E.raw("        for (int d = 0; d < 2 * D; ++d) { am[d] = 0.0f; av[d] = 0.0f; }")
-    E.raw("    }")
-    E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
-    E.raw("    if constexpr (BOX) spec_load_spheres_finish(lds_prm, lane, prm);")
-    E.raw("    const NoFlush flush{};                 // this kernel writes no positions")
-    E.raw("    // time step: 64 is a multiple of the horizon, so a wavefront starts at step 0 of a trajectory")
-    E.raw("    const int tl = lane & (A.gp_H - 1);")
-    E.raw("    const bool t_first = tl == 0, t_last = tl == A.gp_H - 1;")
-    E.raw("    const bool pin_q = ((A.pin & 1) && t_first) || ((A.pin & 2) && t_last);        // a pinned component's gradient is taken as zero")
-    E.raw("    const bool pin_qd = ((A.pin & 4) && t_first) || ((A.pin & 8) && t_last);")
+    _emit_traj_head(E, "k_traj_adam_bi" if base_identity else "k_traj_adam_bg", "TrajAdamArgs", "2 * D",
+                    "the transposes of q, qd [64][D] and of m, v [64][2D]", "TRAJ_ADAM_OCCUPANCY")
+    _emit_adam_state_load(E, "q")
+    _emit_traj_tables_finish(E)
+    _emit_traj_pins(E)
     E.raw("    const float wm = (lane < rows && !t_last) ? A.gp_w : 0.0f;       // the factor t -> t + 1 exists")
-    E.raw("    const float dt = A.gp_dt, gaw = wm * A.gp_a, gbw = wm * A.gp_b, gcw = wm * A.gp_c;")
-    E.raw("    float cost0 = 0.0f;")
-    E.raw("#pragma nounroll")
-    E.raw("    for (int it = 0; it < A.n_steps; ++it) {")
-    # ---------------- forward, objectives, reverse: k_rollout's ----------------
-    R, t, passv = _root_pose(base_identity)
-    _emit_angles(E, kin)
-    for p in range(1, L):
-        _emit_fk_link(E, kin, u.walk[p], R, t, passv, u.snap)
-    ticks = _Ticks()
-    _emit_collision_objectives(u, E, t, ticks, fast_arg=", decltype(ticks), false, BOX", prims_ptr="lds_prm")
-    _emit_ee_terms(E, u.tracked, R, t)
-    E.raw(ticks())
-    gq_expr = _emit_reverse_links(E, kin, R, t, {i: [f"tb{i}_{k}" for k in range(3)] for i in u.real_adj},
-                                  {l: rb for l, _, rb in u.tracked}, u.masked, tick=ticks, order=u.walk)
-    E.raw(f"    const float gc[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
+    _emit_adam_loop_open(E)
+    _emit_rollout_iteration(u, E, base_identity)
     # ---------------- the prior on the register copies (_emit_gpt_prior's expressions) ----------------
     E.raw("    // the prior: e_t = (p_t + dt v_t - p_t+1, v_t - v_t+1), r = w Q^-1 e; the next sample's (p, v) come by wave_shl:1, the finished")
     E.raw("    // factor goes to the next lane by wave_shr:1.  A lane at the last step has weight 0, so a lane at step 0 receives 0; lanes 63 / 0")
@@ -2097,38 +2158,27 @@ def _traj_adam_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     E.raw("        gvv[d] = fmaf(dt, rp, rv_) - trk_dpp_from_prev(0.0f, rv_);")
     E.raw("    }")
     E.raw("    if (it == 0) cost0 = fmaf(0.5f, accg, cost);      // the state as passed in; the factor t -> t + 1 attributed to sample t")
-    E.raw("    if (update) {")
-    E.raw("        const float step = spec_adam_step_size(A.lr, A.sched.bc1[it]), rs = A.sched.rsqrt_bc2[it];")
-    E.raw("#pragma unroll")
-    E.raw("        for (int d = 0; d < D; ++d) {")
-    E.raw("            spec_adam_component(pin_q ? 0.0f : gc[d] + gpv[d], step, rs, q[d], am[d], av[d]);")
-    E.raw("            spec_adam_component(pin_qd ? 0.0f : gvv[d], step, rs, qd[d], am[D + d], av[D + d]);")
-    E.raw("        }")
-    E.raw("    }")
-    E.raw("    }")
-    E.raw("    if (A.cost && lane < rows) store_wt_f1(A.cost + base + lane, cost0);")
-    E.raw("    if (update) {")
-    E.raw("        spec_store_gq<D>(A.q, base, rows, lane, lds, q);")
-    E.raw("        spec_store_gq<D>(A.qd, base, rows, lane, lds, qd);")
-    E.raw("        spec_store_gq<2 * D>(A.adam_m, base, rows, lane, lds, am);")
-    E.raw("        spec_store_gq<2 * D>(A.adam_v, base, rows, lane, lds, av);")
-    E.raw("    }")
-    E.raw("}")
+    _emit_adam_update(E, "q", "gc[d] + gpv[d]")
+    _emit_adam_state_store(E, "q")
     return E.lines
 
 
-def _traj_adam_launcher_lines(u: _LinkUnit) -> List[str]:
-    out = ["static void launch_traj_adam(const SpecEntry*, const TrajAdamArgs& a, int base_identity, hipStream_t st) {",
-           "    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);",
-           f"    if ({u.scene_switch}) {{",
-           "        if (base_identity) hipLaunchKernelGGL((k_traj_adam_bi<true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
-           "        else hipLaunchKernelGGL((k_traj_adam_bg<true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
-           "    } else {",
-           "        if (base_identity) hipLaunchKernelGGL((k_traj_adam_bi<false>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
-           "        else hipLaunchKernelGGL((k_traj_adam_bg<false>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
-           "    }",
-           "}"]
-    return out
+def _scene_switch_lines(u: _LinkUnit, kernel) -> List[str]:
+    """the four launches of a kernel family by scene switch and base pose; kernel(base, box) names the instantiation"""
+    def pair(box: str) -> List[str]:
+        return [f"        if (base_identity) hipLaunchKernelGGL(({kernel('bi', box)}), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+                f"        else hipLaunchKernelGGL(({kernel('bg', box)}), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);"]
+    return [f"    if ({u.scene_switch}) {{", *pair("true"), "    } else {", *pair("false"), "    }"]
+
+
+def _scene_switch_launcher_lines(u: _LinkUnit, name: str, args: str, stem: str, grid_lines: Sequence[str], self_param: bool) -> List[str]:
+    """launch_<name>: k_<stem>_bi / _bg<BOX> over the grid that grid_lines compute (self_param: the launcher of a main unit, which
+    takes its SpecEntry first; a satellite unit's does not)"""
+    return [f"static void launch_{name}({'const SpecEntry*, ' if self_param else ''}const {args}& a, int base_identity, hipStream_t st) {{",
+            *grid_lines, *_scene_switch_lines(u, lambda b, box: f"k_{stem}_{b}<{box}>"), "}"]
+
+
+_GRID_PER_SAMPLE = ["    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);"]
 
 
 # Wavefronts per SIMD k_via_cost runs at.  The estimate is the rollout's registers + 3 D (the way point, its successor and the two
@@ -2151,9 +2201,12 @@ def template_identity(tmpl: CollisionTemplate) -> int:
 
 
 def via_cost_ok(kin: KinModel, tmpl: CollisionTemplate, ident: str = "", snap: float = SNAP) -> bool:
-    """does the robot's link unit get a spec_<ident>_via unit?  The whole-row four-wavefront units: the ones that carry k_traj_adam"""
-    u = _LinkUnit(kin, tmpl, ident, snap)
-    return (not u.chunked) and not tmpl.virtual and u.D <= 8
+    """does the robot's link unit get a spec_<ident>_via unit?  The units that carry k_traj_adam: whole-row staging, no virtual
+    columns, up to 8 DOF (_LinkUnit.traj_adam_ok, the one statement of the rule)"""
+    return _LinkUnit(kin, tmpl, ident, snap).traj_adam_ok
+
+
+via_adam_ok = via_cost_ok         # spec_<ident>_vadam: the same units
 
 
 def _via_cost_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
@@ -2163,22 +2216,11 @@ def _via_cost_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     wavefront shift per joint and hands the gradient's share of x[t, i + 1] back by one shift the other way: nothing crosses a
     wavefront, no atomics, no barrier, the output is not zeroed first.  Lanes beyond (64 / H) H and beyond the batch run on zeros and
     store nothing (a wavefront without any row returns at once); a lane without a segment is taken out of the sums by a select.  The run-time loop over the via points of the lane's segment interpolates (each product and the sum rounded once,
-    as spec_load_q_via), runs k_rollout's iteration (same emitters, same scene switch BOX) without positions -- NoFlush -- stores the
-    via point's cost and accumulates the two way points' shares of its gradient in registers."""
-    kin, L, D = u.kin, u.L, u.D
+    as spec_load_q_via), runs k_rollout's iteration (_emit_rollout_iteration), stores the via point's cost and accumulates the two
+    way points' shares of its gradient in registers."""
     E = Emitter()
-    kname = "k_via_cost_bi" if base_identity else "k_via_cost_bg"
-    E.raw("template <bool BOX>      // the scene switch of k_rollout (scene_is_general): boxes and / or a voxel grid")
-    E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK) {kname}(ViaCostArgs A) {{      // {VIA_COST_OCCUPANCY} wavefronts per SIMD (VIA_COST_OCCUPANCY)")
-    E.raw("    constexpr int LDS_LANE = D;            // the transposes of x and gq [64][D]")
-    E.raw("    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * LDS_LANE + SPEC_WAVES * (TRK_LDS_SPHERES * 4 + (BOX ? TRK_LDS_PRIMS * 8 : 0))];")
-    E.raw("    const int lane = __builtin_amdgcn_workitem_id_x() & (TRK_WAVE - 1);")
-    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_workitem_id_x() / TRK_WAVE);")
-    E.raw("    float* lds = lds_all + wave * (TRK_WAVE * LDS_LANE);")
-    E.raw("    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * LDS_LANE) + wave * (TRK_LDS_SPHERES + (BOX ? 2 * TRK_LDS_PRIMS : 0));")
-    E.raw("    float4* lds_prm = BOX ? lds_sph + TRK_LDS_SPHERES : nullptr;")
-    E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);")
-    E.raw("    const SpheresInFlight prm = BOX ? spec_load_prims_issue(A.C, lane) : sph;")
+    _emit_traj_head(E, "k_via_cost_bi" if base_identity else "k_via_cost_bg", "ViaCostArgs", "D", "the transposes of x and gq [64][D]",
+                    "VIA_COST_OCCUPANCY")
     E.raw("    // the wavefront's trajectories: 64 / H whole ones, their way points in lanes 0 .. rows - 1 (wave-uniform)")
     E.raw("    const int64_t wblock = (int64_t)__builtin_amdgcn_workgroup_id_x() * SPEC_WAVES + wave;")
     E.raw("    const int tpw = TRK_WAVE / A.H;")
@@ -2188,9 +2230,7 @@ def _via_cost_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     E.raw("    if (rows == 0) return;                 // a wavefront beyond the batch (the last workgroup's): wave-uniform, nothing to shift with")
     E.raw("    float x[D], xn[D], g_lo[D], g_hi[D];")
     E.raw("    spec_load_q<D>(A.x, base, rows, lane, lds, x);")
-    E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
-    E.raw("    if constexpr (BOX) spec_load_spheres_finish(lds_prm, lane, prm);")
-    E.raw("    const NoFlush flush{};                 // this kernel writes no positions")
+    _emit_traj_tables_finish(E)
     E.raw("    // lane (t, i) owns the segment i -> i + 1; a lane at the last way point of a trajectory (or without one) has none: weight 0")
     E.raw("    const int ti = lane / A.H, tl = lane - ti * A.H;")
     E.raw("    const bool on = lane < rows && tl != A.H - 1;")
@@ -2208,18 +2248,7 @@ def _via_cost_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     E.raw("    float q[D];")
     E.raw("#pragma unroll")
     E.raw("    for (int d = 0; d < D; ++d) q[d] = __fadd_rn(__fmul_rn(x[d], fa), __fmul_rn(xn[d], fb));")
-    # ---------------- forward, objectives, reverse: k_rollout's ----------------
-    R, t, passv = _root_pose(base_identity)
-    _emit_angles(E, kin)
-    for p in range(1, L):
-        _emit_fk_link(E, kin, u.walk[p], R, t, passv, u.snap)
-    ticks = _Ticks()
-    _emit_collision_objectives(u, E, t, ticks, fast_arg=", decltype(ticks), false, BOX", prims_ptr="lds_prm")
-    _emit_ee_terms(E, u.tracked, R, t)
-    E.raw(ticks())
-    gq_expr = _emit_reverse_links(E, kin, R, t, {i: [f"tb{i}_{k}" for k in range(3)] for i in u.real_adj},
-                                  {l: rb for l, _, rb in u.tracked}, u.masked, tick=ticks, order=u.walk)
-    E.raw(f"    const float gc[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
+    _emit_rollout_iteration(u, E, base_identity)
     E.raw("    if (A.cost && on) store_wt_f1(A.cost + seg + a, cost);")
     E.raw("    const float sa = sd * fa, sb = sd * fb;")
     E.raw("#pragma unroll")
@@ -2242,40 +2271,45 @@ def via_cost_kernels(ident: str) -> List[str]:
     return [f"spec_{ident}::k_via_cost_{b}<{v}>" for b in ("bi", "bg") for v in ("false", "true")]
 
 
-def generate_via_cost_source(kin: KinModel, tmpl: CollisionTemplate, ident: str, snap: float = SNAP) -> str:
-    """spec_<ident>_via.hip: the via-point cost kernels of a link-column unit (_via_cost_kernel), a translation unit of its own next to
-    generate_rollout_source's -- same namespace, same _LinkUnit plan, the same FP freedoms, nothing shared but the headers.  The main
-    unit's registry entry has no slot for it: the unit announces its launcher under the main unit's ident, model hash and template
-    identity (trk_spec_register_via_cost), and trk_rollout_via_cost_grad looks it up by those of the entry that serves the cost model.
-    Linked / dlopen-ed units only: a code-object (hipRTC) build of the model carries none."""
-    u = _LinkUnit(kin, tmpl, ident, snap)
-    assert (not u.chunked) and not tmpl.virtual and u.D <= 8, "the via-point cost kernel exists for the whole-row four-wavefront units"
-    out: List[str] = [f"// GENERATED by torch_robotics_amd/codegen.py for model '{kin.name}' ({u.L} links, {u.D} DOF): via-point cost "
-                      f"kernels -- do not edit."]
-    out.append("#pragma clang fp reassociate(on) contract(fast) reciprocal(on)")
-    out.append('#include "trk_spec_common.h"')
-    out.append(f"namespace spec_{ident} {{")
-    out.append(f"constexpr int L = {u.L}, D = {u.D}, NL = {u.NL};")
-    out.append(f'static_assert(TRK_OBJ_TICK_SLOTS == {OBJ_TICK_SLOTS}, "chunk numbering of this unit assumes another TRK_OBJ_TICK_SLOTS");')
-    for base_identity in (True, False):
-        out.extend(_via_cost_kernel(u, base_identity) + [""])
-    out.append("#ifndef __HIPCC_RTC__          // the unit's host half: its launcher, announced under the main unit's ident, hash and template")
-    out += ["static void launch_via_cost(const ViaCostArgs& a, int base_identity, hipStream_t st) {",
-            "    const int64_t waves = (a.T + TRK_WAVE / a.H - 1) / (TRK_WAVE / a.H);          // 64 / H whole trajectories per wavefront",
-            "    const unsigned grid = (unsigned)((waves + SPEC_WAVES - 1) / SPEC_WAVES);",
-            f"    if ({u.scene_switch}) {{",
-            "        if (base_identity) hipLaunchKernelGGL((k_via_cost_bi<true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
-            "        else hipLaunchKernelGGL((k_via_cost_bg<true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
-            "    } else {",
-            "        if (base_identity) hipLaunchKernelGGL((k_via_cost_bi<false>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
-            "        else hipLaunchKernelGGL((k_via_cost_bg<false>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
-            "    }",
-            "}"]
-    out.append(f"static struct RegViaCost {{ RegViaCost() {{ trk_spec_register_via_cost(\"{ident}\", 0x{model_hash(kin):016x}ull, "
-               f"0x{template_identity(tmpl):016x}ull, (uint32_t)sizeof(ViaCostArgs), launch_via_cost); }} }} reg_via_cost;")
-    out.append("#endif      // !__HIPCC_RTC__")
-    out.append(f"}}  // namespace spec_{ident}")
+def _satellite_unit_source(header_comment: str, ident: str, constants: Sequence[str], fp_pragma: bool, kernels: Sequence[List[str]],
+                           announced_under: str, host_lines: Sequence[str], registrar_line: str) -> str:
+    """A translation unit of its own next to a main unit's (spec_<ident>_via / _vadam / _coll.hip): same namespace, same plan, nothing
+    shared but the headers (fp_pragma: and the link units' FP freedoms).  The main unit's registry entry has no slot for it: its host
+    half is one launcher, which registrar_line announces under the main unit's ident and hashes.  Linked / dlopen-ed units only: a
+    code-object (hipRTC) build of the model carries none."""
+    out = [f"// GENERATED by torch_robotics_amd/codegen.py for model {header_comment} -- do not edit."]
+    if fp_pragma:
+        out.append("#pragma clang fp reassociate(on) contract(fast) reciprocal(on)")
+    out += ['#include "trk_spec_common.h"', f"namespace spec_{ident} {{", *constants]
+    for k in kernels:
+        out.extend(k + [""])
+    out.append(f"#ifndef __HIPCC_RTC__          // the unit's host half: its launcher, announced under the main unit's {announced_under}")
+    out += [*host_lines, registrar_line, "#endif      // !__HIPCC_RTC__", f"}}  // namespace spec_{ident}"]
     return "\n".join(out) + "\n"
+
+
+def _via_unit_source(u: _LinkUnit, what: str, emit_kernel, host_lines: Sequence[str], kind: str, args: str) -> str:
+    """the satellite unit of a link-column unit that carries k_traj_adam; it registers by trk_spec_register_via_<kind>"""
+    assert u.traj_adam_ok, "the trajectory-layout kernels exist for the whole-row four-wavefront units"
+    return _satellite_unit_source(
+        f"'{u.kin.name}' ({u.L} links, {u.D} DOF): {what}", u.ident,
+        [f"constexpr int L = {u.L}, D = {u.D}, NL = {u.NL};",
+         f'static_assert(TRK_OBJ_TICK_SLOTS == {OBJ_TICK_SLOTS}, "chunk numbering of this unit assumes another TRK_OBJ_TICK_SLOTS");'],
+        True, [emit_kernel(u, b) for b in (True, False)], "ident, hash and template", host_lines,
+        f"static struct RegVia{kind.capitalize()} {{ RegVia{kind.capitalize()}() {{ trk_spec_register_via_{kind}(\"{u.ident}\", 0x{model_hash(u.kin):016x}ull, "
+        f"0x{template_identity(u.tmpl):016x}ull, (uint32_t)sizeof({args}), launch_via_{kind}); }} }} reg_via_{kind};")
+
+
+def generate_via_cost_source(kin: KinModel, tmpl: CollisionTemplate, ident: str, snap: float = SNAP) -> str:
+    """spec_<ident>_via.hip: the via-point cost kernels of a link-column unit (_via_cost_kernel), a satellite unit
+    (_satellite_unit_source) of generate_rollout_source's.  It announces its launcher under the main unit's ident, model hash and
+    template identity (trk_spec_register_via_cost), and trk_rollout_via_cost_grad looks it up by those of the entry that serves the
+    cost model."""
+    u = _LinkUnit(kin, tmpl, ident, snap)
+    grid = ["    const int64_t waves = (a.T + TRK_WAVE / a.H - 1) / (TRK_WAVE / a.H);          // 64 / H whole trajectories per wavefront",
+            "    const unsigned grid = (unsigned)((waves + SPEC_WAVES - 1) / SPEC_WAVES);"]
+    return _via_unit_source(u, "via-point cost kernels", _via_cost_kernel,
+                            _scene_switch_launcher_lines(u, "via_cost", "ViaCostArgs", "via_cost", grid, False), "cost", "ViaCostArgs")
 
 
 # Wavefronts per SIMD k_traj_via_adam runs at: what every instantiation of every unit reaches (DESIGN 4.10).  On top of k_traj_adam's
@@ -2286,13 +2320,6 @@ def generate_via_cost_source(kin: KinModel, tmpl: CollisionTemplate, ident: str,
 TRAJ_VIA_ADAM_OCCUPANCY = 2
 
 
-def via_adam_ok(kin: KinModel, tmpl: CollisionTemplate, ident: str = "", snap: float = SNAP) -> bool:
-    """does the robot's link unit get a spec_<ident>_vadam unit?  The units that carry k_traj_adam: whole-row staging, no virtual
-    columns, up to 8 DOF (_LinkUnit.traj_adam_ok)"""
-    u = _LinkUnit(kin, tmpl, ident, snap)
-    return u.traj_adam_ok
-
-
 def _traj_via_adam_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     """k_traj_via_adam_bi / _bg<BOX>: k_traj_adam's planning loop (trk_rollout_gp_via_adam_steps) with the collision / EE objective
     also at the n via points of every segment, as k_via_cost evaluates them.  The layout is k_traj_adam's: one lane per sample, fp32,
@@ -2300,49 +2327,16 @@ def _traj_via_adam_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     DPP wavefront shifts; nothing crosses a wavefront, no atomics, no barrier, no positions (NoFlush).  The way point is one more pass
     of the run-time loop over the via points: pass a = -1 evaluates q itself and starts the sums, passes 0 .. n - 1 evaluate
     q alpha[a] + q_next beta[a] (each product and the sum rounded once) and fold cost and gradient with the weight w_via, so the
-    rollout body (same emitters, same scene switch BOX) is emitted once.  A lane without a segment leaves the via passes by a select."""
-    kin, L, D = u.kin, u.L, u.D
+    rollout body (_emit_rollout_iteration) is emitted once.  A lane without a segment leaves the via passes by a select."""
     E = Emitter()
-    kname = "k_traj_via_adam_bi" if base_identity else "k_traj_via_adam_bg"
-    E.raw("template <bool BOX>      // the scene switch of k_rollout (scene_is_general): boxes and / or a voxel grid")
-    E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK) {kname}(TrajViaAdamArgs A) {{      // {TRAJ_VIA_ADAM_OCCUPANCY} wavefronts per SIMD (TRAJ_VIA_ADAM_OCCUPANCY)")
-    E.raw("    constexpr int LDS_LANE = 2 * D;        // the transposes of q, qd [64][D] and of m, v [64][2D]")
-    E.raw("    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * LDS_LANE + SPEC_WAVES * (TRK_LDS_SPHERES * 4 + (BOX ? TRK_LDS_PRIMS * 8 : 0))];")
-    E.raw("    const int lane = __builtin_amdgcn_workitem_id_x() & (TRK_WAVE - 1);")
-    E.raw("    const int wave = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_workitem_id_x() / TRK_WAVE);")
-    E.raw("    float* lds = lds_all + wave * (TRK_WAVE * LDS_LANE);")
-    E.raw("    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * LDS_LANE) + wave * (TRK_LDS_SPHERES + (BOX ? 2 * TRK_LDS_PRIMS : 0));")
-    E.raw("    float4* lds_prm = BOX ? lds_sph + TRK_LDS_SPHERES : nullptr;")
-    E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);")
-    E.raw("    const SpheresInFlight prm = BOX ? spec_load_prims_issue(A.C, lane) : sph;")
-    E.raw("    const int64_t wblock = (int64_t)__builtin_amdgcn_workgroup_id_x() * SPEC_WAVES + wave;")
-    E.raw("    const int64_t base = wblock * TRK_WAVE;")
-    E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));      // lanes beyond: clamped loads, no stores")
-    E.raw("    const bool update = A.update != 0;")
-    E.raw("    float x[D], qd[D], am[2 * D], av[2 * D];")
-    E.raw("    spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, x);")
-    E.raw("    spec_load_q<D>(static_cast<const float*>(A.qd), base, rows, lane, lds, qd);")
-    E.raw("    if (update) {")
-    E.raw("        spec_load_q<2 * D>(static_cast<const float*>(A.adam_m), base, rows, lane, lds, am);")
-    E.raw("        spec_load_q<2 * D>(static_cast<const float*>(A.adam_v), base, rows, lane, lds, av);")
-    E.raw("    } else {")
-    E.raw("#pragma unroll")
-    E.raw("        for (int d = 0; d < 2 * D; ++d) { am[d] = 0.0f; av[d] = 0.0f; }")
-    E.raw("    }")
-    E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
-    E.raw("    if constexpr (BOX) spec_load_spheres_finish(lds_prm, lane, prm);")
-    E.raw("    const NoFlush flush{};                 // this kernel writes no positions")
-    E.raw("    // time step: 64 is a multiple of the horizon, so a wavefront starts at step 0 of a trajectory")
-    E.raw("    const int tl = lane & (A.gp_H - 1);")
-    E.raw("    const bool t_first = tl == 0, t_last = tl == A.gp_H - 1;")
-    E.raw("    const bool pin_q = ((A.pin & 1) && t_first) || ((A.pin & 2) && t_last);        // a pinned component's gradient is taken as zero")
-    E.raw("    const bool pin_qd = ((A.pin & 4) && t_first) || ((A.pin & 8) && t_last);")
+    _emit_traj_head(E, "k_traj_via_adam_bi" if base_identity else "k_traj_via_adam_bg", "TrajViaAdamArgs", "2 * D",
+                    "the transposes of q, qd [64][D] and of m, v [64][2D]", "TRAJ_VIA_ADAM_OCCUPANCY")
+    _emit_adam_state_load(E, "x")
+    _emit_traj_tables_finish(E)
+    _emit_traj_pins(E)
     E.raw("    const bool on = lane < rows && !t_last;                          // the segment t -> t + 1 exists: via points and the prior's factor")
     E.raw("    const float wm = on ? A.gp_w : 0.0f;")
-    E.raw("    const float dt = A.gp_dt, gaw = wm * A.gp_a, gbw = wm * A.gp_b, gcw = wm * A.gp_c;")
-    E.raw("    float cost0 = 0.0f;")
-    E.raw("#pragma nounroll")
-    E.raw("    for (int it = 0; it < A.n_steps; ++it) {")
+    _emit_adam_loop_open(E)
     E.raw("    // the next sample's position: the via points' other end and the prior's p_t+1.  A lane without a segment keeps its own value:")
     E.raw("    // neither the next trajectory's first way point nor lane 63's missing source is read anywhere")
     E.raw("    float xn[D], g_lo[D], g_hi[D], csum = 0.0f;")
@@ -2360,18 +2354,7 @@ def _traj_via_adam_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     E.raw("    float q[D];")
     E.raw("#pragma unroll")
     E.raw("    for (int d = 0; d < D; ++d) q[d] = way ? x[d] : __fadd_rn(__fmul_rn(x[d], fa), __fmul_rn(xn[d], fb));")
-    # ---------------- forward, objectives, reverse: k_rollout's ----------------
-    R, t, passv = _root_pose(base_identity)
-    _emit_angles(E, kin)
-    for p in range(1, L):
-        _emit_fk_link(E, kin, u.walk[p], R, t, passv, u.snap)
-    ticks = _Ticks()
-    _emit_collision_objectives(u, E, t, ticks, fast_arg=", decltype(ticks), false, BOX", prims_ptr="lds_prm")
-    _emit_ee_terms(E, u.tracked, R, t)
-    E.raw(ticks())
-    gq_expr = _emit_reverse_links(E, kin, R, t, {i: [f"tb{i}_{k}" for k in range(3)] for i in u.real_adj},
-                                  {l: rb for l, _, rb in u.tracked}, u.masked, tick=ticks, order=u.walk)
-    E.raw(f"    const float gc[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(D))}}};")
+    _emit_rollout_iteration(u, E, base_identity)
     E.raw("    // the fold of include/trk.h, every operation rounded once.  A lane without a segment leaves the via passes by SELECT, not by a")
     E.raw("    // zero weight: 0 * (a non-finite gradient) must not reach its neighbours' rows (as k_via_cost)")
     E.raw("    const float wa = __fmul_rn(A.w_via, fa), wb = __fmul_rn(A.w_via, fb);")
@@ -2400,23 +2383,8 @@ def _traj_via_adam_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     E.raw("        gvv[d] = fmaf(dt, rp, rv_) - trk_dpp_from_prev(0.0f, rv_);")
     E.raw("    }")
     E.raw("    if (it == 0) cost0 = fmaf(0.5f, accg, csum);      // the state as passed in; the segment t -> t + 1 attributed to sample t")
-    E.raw("    if (update) {")
-    E.raw("        const float step = spec_adam_step_size(A.lr, A.sched.bc1[it]), rs = A.sched.rsqrt_bc2[it];")
-    E.raw("#pragma unroll")
-    E.raw("        for (int d = 0; d < D; ++d) {")
-    E.raw("            spec_adam_component(pin_q ? 0.0f : gqv[d], step, rs, x[d], am[d], av[d]);")
-    E.raw("            spec_adam_component(pin_qd ? 0.0f : gvv[d], step, rs, qd[d], am[D + d], av[D + d]);")
-    E.raw("        }")
-    E.raw("    }")
-    E.raw("    }")
-    E.raw("    if (A.cost && lane < rows) store_wt_f1(A.cost + base + lane, cost0);")
-    E.raw("    if (update) {")
-    E.raw("        spec_store_gq<D>(A.q, base, rows, lane, lds, x);")
-    E.raw("        spec_store_gq<D>(A.qd, base, rows, lane, lds, qd);")
-    E.raw("        spec_store_gq<2 * D>(A.adam_m, base, rows, lane, lds, am);")
-    E.raw("        spec_store_gq<2 * D>(A.adam_v, base, rows, lane, lds, av);")
-    E.raw("    }")
-    E.raw("}")
+    _emit_adam_update(E, "x", "gqv[d]")
+    _emit_adam_state_store(E, "x")
     return E.lines
 
 
@@ -2426,37 +2394,13 @@ def via_adam_kernels(ident: str) -> List[str]:
 
 
 def generate_via_adam_source(kin: KinModel, tmpl: CollisionTemplate, ident: str, snap: float = SNAP) -> str:
-    """spec_<ident>_vadam.hip: the planning-loop kernels with the via-point term (_traj_via_adam_kernel), a translation unit of its
-    own like generate_via_cost_source's -- same namespace, same _LinkUnit plan, the same FP freedoms, nothing shared but the headers.
-    The unit announces its launcher under the main unit's ident, model hash and template identity (trk_spec_register_via_adam), and
-    trk_rollout_gp_via_adam_steps looks it up by those of the entry that serves the cost model.  Linked / dlopen-ed units only."""
+    """spec_<ident>_vadam.hip: the planning-loop kernels with the via-point term (_traj_via_adam_kernel), a satellite unit like
+    generate_via_cost_source's.  It announces its launcher by trk_spec_register_via_adam, and trk_rollout_gp_via_adam_steps looks it
+    up by the ident, model hash and template identity of the entry that serves the cost model."""
     u = _LinkUnit(kin, tmpl, ident, snap)
-    assert u.traj_adam_ok, "the planning-loop kernel exists for the whole-row four-wavefront units"
-    out: List[str] = [f"// GENERATED by torch_robotics_amd/codegen.py for model '{kin.name}' ({u.L} links, {u.D} DOF): planning-loop "
-                      f"kernels with the via-point term -- do not edit."]
-    out.append("#pragma clang fp reassociate(on) contract(fast) reciprocal(on)")
-    out.append('#include "trk_spec_common.h"')
-    out.append(f"namespace spec_{ident} {{")
-    out.append(f"constexpr int L = {u.L}, D = {u.D}, NL = {u.NL};")
-    out.append(f'static_assert(TRK_OBJ_TICK_SLOTS == {OBJ_TICK_SLOTS}, "chunk numbering of this unit assumes another TRK_OBJ_TICK_SLOTS");')
-    for base_identity in (True, False):
-        out.extend(_traj_via_adam_kernel(u, base_identity) + [""])
-    out.append("#ifndef __HIPCC_RTC__          // the unit's host half: its launcher, announced under the main unit's ident, hash and template")
-    out += ["static void launch_via_adam(const TrajViaAdamArgs& a, int base_identity, hipStream_t st) {",
-            "    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);",
-            f"    if ({u.scene_switch}) {{",
-            "        if (base_identity) hipLaunchKernelGGL((k_traj_via_adam_bi<true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
-            "        else hipLaunchKernelGGL((k_traj_via_adam_bg<true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
-            "    } else {",
-            "        if (base_identity) hipLaunchKernelGGL((k_traj_via_adam_bi<false>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
-            "        else hipLaunchKernelGGL((k_traj_via_adam_bg<false>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
-            "    }",
-            "}"]
-    out.append(f"static struct RegViaAdam {{ RegViaAdam() {{ trk_spec_register_via_adam(\"{ident}\", 0x{model_hash(kin):016x}ull, "
-               f"0x{template_identity(tmpl):016x}ull, (uint32_t)sizeof(TrajViaAdamArgs), launch_via_adam); }} }} reg_via_adam;")
-    out.append("#endif      // !__HIPCC_RTC__")
-    out.append(f"}}  // namespace spec_{ident}")
-    return "\n".join(out) + "\n"
+    return _via_unit_source(u, "planning-loop kernels with the via-point term", _traj_via_adam_kernel,
+                            _scene_switch_launcher_lines(u, "via_adam", "TrajViaAdamArgs", "traj_via_adam", _GRID_PER_SAMPLE, False),
+                            "adam", "TrajViaAdamArgs")
 
 
 def _jac_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
@@ -2697,19 +2641,9 @@ def _rjac_launcher_lines(u: _LinkUnit) -> List[str]:
     when this call is not served (the C ABI then runs the two launches).  Ring-staged units instantiate JAC with positions (POS = true)
     only; the others take the positions as a run-time option."""
     pos_t = "true, " if u.chunked else ""
-    out = ["static int launch_rjac(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {",
-           f"    if (a.io_f16 != TRK_IO_F32 || {'!a.link_pos || ' if u.chunked else ''}a.jac_link != {u.tmpl.ee_link}) return 1;",
-           "    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);",
-           f"    if ({u.scene_switch}) {{",
-           f"        if (base_identity) hipLaunchKernelGGL((k_rollout_bi<float, {pos_t}true, true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
-           f"        else hipLaunchKernelGGL((k_rollout_bg<float, {pos_t}true, true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
-           "    } else {",
-           f"        if (base_identity) hipLaunchKernelGGL((k_rollout_bi<float, {pos_t}false, true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
-           f"        else hipLaunchKernelGGL((k_rollout_bg<float, {pos_t}false, true>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
-           "    }",
-           "    return 0;",
-           "}"]
-    return out
+    return ["static int launch_rjac(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {",
+            f"    if (a.io_f16 != TRK_IO_F32 || {'!a.link_pos || ' if u.chunked else ''}a.jac_link != {u.tmpl.ee_link}) return 1;",
+            *_GRID_PER_SAMPLE, *_scene_switch_lines(u, lambda b, box: f"k_rollout_{b}<float, {pos_t}{box}, true>"), "    return 0;", "}"]
 
 
 def _gp_launcher_lines(u: _LinkUnit) -> List[str]:
@@ -2802,7 +2736,7 @@ def _link_host_lines(u: _LinkUnit) -> List[str]:
                f"{slot(bool(u.fx_terms) and bool(u.fx_const), 'launch_fx_points')}, {len(u.fx_const) if u.fx_terms else 0}}};")
     out.append("static struct Reg { Reg() { trk_spec_register(&kEntry); } } reg;")
     if u.traj_adam_ok:
-        out += _traj_adam_launcher_lines(u)
+        out += _scene_switch_launcher_lines(u, "traj_adam", "TrajAdamArgs", "traj_adam", _GRID_PER_SAMPLE, True)
         out.append("static struct RegTrajAdam { RegTrajAdam() { trk_spec_register_traj_adam(&kEntry, (uint32_t)sizeof(TrajAdamArgs), launch_traj_adam); } } reg_traj_adam;")
     out.append("#endif      // !__HIPCC_RTC__")
     return out
@@ -3451,20 +3385,12 @@ def generate_points_collision_source(kin: KinModel, pt: PointsTemplate, ident: s
     (trk_spec_register_points_coll), and trk_rollout_points_collision looks it up by those of the entry that serves the cost model.
     Linked / dlopen-ed units only: a code-object (hipRTC) build of the model carries no boolean kernel."""
     u = _PointsUnit(kin, pt, ident, snap)
-    out: List[str] = [f"// GENERATED by torch_robotics_amd/codegen.py for model '{kin.name}' ({u.L} links, {u.D} DOF) with {u.P} attached points: "
-                      f"boolean collision kernels -- do not edit."]
-    out.append('#include "trk_spec_common.h"')
-    out.append(f"namespace spec_{ident} {{")
-    out.append(f"constexpr int L = {u.L}, D = {u.D}, P = {u.P};")
-    for base_identity in (True, False):
-        out.extend(_points_coll_kernel(u, base_identity) + [""])
-    out.append("#ifndef __HIPCC_RTC__          // the unit's host half: its launcher, announced under the main unit's ident and hashes")
-    out += _launcher_lines("pcoll")
-    out.append(f"static struct RegPointsColl {{ RegPointsColl() {{ trk_spec_register_points_coll(\"{ident}\", 0x{model_hash(kin):016x}ull, "
-               f"0x{u.points_hash:016x}ull, (uint32_t)sizeof(SpecArgs), launch_pcoll); }} }} reg_points_coll;")
-    out.append("#endif      // !__HIPCC_RTC__")
-    out.append(f"}}  // namespace spec_{ident}")
-    return "\n".join(out) + "\n"
+    return _satellite_unit_source(
+        f"'{kin.name}' ({u.L} links, {u.D} DOF) with {u.P} attached points: boolean collision kernels", ident,
+        [f"constexpr int L = {u.L}, D = {u.D}, P = {u.P};"], False, [_points_coll_kernel(u, b) for b in (True, False)], "ident and hashes",
+        _launcher_lines("pcoll"),
+        f"static struct RegPointsColl {{ RegPointsColl() {{ trk_spec_register_points_coll(\"{ident}\", 0x{model_hash(kin):016x}ull, "
+        f"0x{u.points_hash:016x}ull, (uint32_t)sizeof(SpecArgs), launch_pcoll); }} }} reg_points_coll;")
 
 
 def link_points_template(kin: KinModel, tmpl: CollisionTemplate) -> PointsTemplate:
@@ -3641,50 +3567,26 @@ def aot_units():
 
 
 def generate_all(out_dir) -> List[str]:
+    """every ahead-of-time unit into out_dir (a file is rewritten only when its text changed: make sees no new timestamp); returns the
+    file names: the main units, then the satellite units of the link units (planning loop with the via-point term, via-point cost) and
+    of the attached-point units (their boolean kernels), which register after the main ones"""
     from pathlib import Path
     from .kinematics import URDF_DIR
     out_dir = Path(out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
-    written = []
-    for ident, (urdf, tmpl_fn) in SPEC_ROBOTS.items():
-        kin = KinModel.from_urdf(str(URDF_DIR / urdf))
-        src = generate_link_kernel_source(kin, tmpl_fn(kin), ident)
-        path = out_dir / f"spec_{ident}.hip"
+
+    def load(robots):
+        kins = {ident: KinModel.from_urdf(str(URDF_DIR / urdf)) for ident, (urdf, _) in robots.items()}
+        return [(ident, kins[ident], robots[ident][1](kins[ident])) for ident in robots]
+    links, points = load(SPEC_ROBOTS), load(SPEC_POINT_ROBOTS)
+    small = [(ident, kin, tmpl) for ident, kin, tmpl in links if via_cost_ok(kin, tmpl, ident)]
+    units = ([(f"spec_{i}.hip", generate_link_kernel_source(k, t, i)) for i, k, t in links] +
+             [(f"spec_{i}.hip", generate_points_rollout_source(k, t, i)) for i, k, t in points] +
+             [(f"spec_{i}_vadam.hip", generate_via_adam_source(k, t, i)) for i, k, t in small] +
+             [(f"spec_{i}_via.hip", generate_via_cost_source(k, t, i)) for i, k, t in small] +
+             [(f"spec_{i}_coll.hip", generate_points_collision_source(k, t, i)) for i, k, t in points])
+    for name, src in units:
+        path = out_dir / name
         if not path.exists() or path.read_text() != src:
             path.write_text(src)
-        written.append(path.name)
-    for ident, (urdf, tmpl_fn) in SPEC_POINT_ROBOTS.items():
-        kin = KinModel.from_urdf(str(URDF_DIR / urdf))
-        src = generate_points_rollout_source(kin, tmpl_fn(kin), ident)
-        path = out_dir / f"spec_{ident}.hip"
-        if not path.exists() or path.read_text() != src:
-            path.write_text(src)
-        written.append(path.name)
-    for ident, (urdf, tmpl_fn) in SPEC_ROBOTS.items():                 # the planning loop with the via-point term: units of their own
-        kin = KinModel.from_urdf(str(URDF_DIR / urdf))
-        tmpl = tmpl_fn(kin)
-        if not via_adam_ok(kin, tmpl, ident):
-            continue
-        src = generate_via_adam_source(kin, tmpl, ident)
-        path = out_dir / f"spec_{ident}_vadam.hip"
-        if not path.exists() or path.read_text() != src:
-            path.write_text(src)
-        written.append(path.name)
-    for ident, (urdf, tmpl_fn) in SPEC_ROBOTS.items():                 # the via-point cost kernels of the small arms: units of their own
-        kin = KinModel.from_urdf(str(URDF_DIR / urdf))
-        tmpl = tmpl_fn(kin)
-        if not via_cost_ok(kin, tmpl, ident):
-            continue
-        src = generate_via_cost_source(kin, tmpl, ident)
-        path = out_dir / f"spec_{ident}_via.hip"
-        if not path.exists() or path.read_text() != src:
-            path.write_text(src)
-        written.append(path.name)
-    for ident, (urdf, tmpl_fn) in SPEC_POINT_ROBOTS.items():           # their boolean kernels: units of their own, after the main ones
-        kin = KinModel.from_urdf(str(URDF_DIR / urdf))
-        src = generate_points_collision_source(kin, tmpl_fn(kin), ident)
-        path = out_dir / f"spec_{ident}_coll.hip"
-        if not path.exists() or path.read_text() != src:
-            path.write_text(src)
-        written.append(path.name)
-    return written
+    return [name for name, _ in units]

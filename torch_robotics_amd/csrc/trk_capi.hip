@@ -122,39 +122,40 @@ int trk_spec_register_traj_adam(const SpecEntry* e, uint32_t sizeof_args, SpecTr
     traj_adam_registry().emplace_back(e, fn);
     return 0;
 }
-// the boolean kernels of the attached-point units (k_pcoll): translation units of their own, which name the main unit they belong to
-// by its ident and hashes.  Nothing here depends on which of the two registered first.
+// Satellite units: the kernels of a generated unit that live in translation units of their own -- the boolean kernels of the
+// attached-point units (k_pcoll, spec_<ident>_coll), the via-point cost kernels (k_via_cost, spec_<ident>_via) and the planning-loop
+// kernels with the via-point term (k_traj_via_adam, spec_<ident>_vadam) of the small link-column units.  Each names the main unit it
+// belongs to by its ident, its model hash and one more key (the points hash / the template identity).  Nothing here depends on which
+// of the two registered first; a unit that announces itself again (a rebuilt run-time unit) replaces its launcher.
 namespace {
-struct PointsCollUnit { std::string ident; uint64_t model_hash, points_hash; SpecLaunchFn fn; };
-std::vector<PointsCollUnit>& points_coll_registry() { static std::vector<PointsCollUnit> r; return r; }
-// a run-time unit registers from the thread that loads it (jit.specialize_points) while other threads may be dispatching
-std::mutex& points_coll_mutex() { static std::mutex m; return m; }
+template <class Fn>
+struct SatelliteRegistry {
+    struct Unit { std::string ident; uint64_t model_hash, key; Fn fn; };
+    std::vector<Unit> units;
+    std::mutex mutex;       // a run-time unit registers from the thread that loads it (jit.py) while other threads may be dispatching
+    Unit* locate(const char* ident, uint64_t model_hash, uint64_t key) {
+        for (auto& r : units) if (r.model_hash == model_hash && r.key == key && r.ident == ident) return &r;
+        return nullptr;
+    }
+    int announce(const char* ident, uint64_t model_hash, uint64_t key, Fn fn) {
+        std::lock_guard<std::mutex> lock(mutex);
+        if (Unit* r = locate(ident, model_hash, key)) r->fn = fn;
+        else units.push_back(Unit{ident, model_hash, key, fn});
+        return 0;
+    }
+    Fn find(const char* ident, uint64_t model_hash, uint64_t key) {
+        std::lock_guard<std::mutex> lock(mutex);
+        const Unit* r = locate(ident, model_hash, key);
+        return r ? r->fn : nullptr;
+    }
+};
+SatelliteRegistry<SpecLaunchFn>& points_coll_registry() { static SatelliteRegistry<SpecLaunchFn> r; return r; }
+SatelliteRegistry<SpecViaCostLaunchFn>& via_cost_registry() { static SatelliteRegistry<SpecViaCostLaunchFn> r; return r; }
+SatelliteRegistry<SpecViaAdamLaunchFn>& via_adam_registry() { static SatelliteRegistry<SpecViaAdamLaunchFn> r; return r; }
 SpecLaunchFn points_coll_launcher(const SpecEntry* e) {
     if (!e->name || e->module_ctx) return nullptr;          // (a code-object unit has no boolean kernel)
-    std::lock_guard<std::mutex> lock(points_coll_mutex());
-    for (const auto& r : points_coll_registry())
-        if (r.model_hash == e->model_hash && r.points_hash == e->points_hash && r.ident == e->name) return r.fn;
-    return nullptr;
+    return points_coll_registry().find(e->name, e->model_hash, e->points_hash);
 }
-}  // namespace
-int trk_spec_register_points_coll(const char* ident, uint64_t model_hash, uint64_t points_hash, uint32_t sizeof_args, SpecLaunchFn fn) {
-    if (!ident || !fn || sizeof_args != sizeof(SpecArgs)) {
-        fprintf(stderr, "libtrk: refusing a generated unit's boolean point kernels (compiled against another SpecArgs layout) -- they "
-                        "will not be dispatched\n");
-        return TRK_ERR_INVALID_ARG;
-    }
-    std::lock_guard<std::mutex> lock(points_coll_mutex());
-    for (auto& r : points_coll_registry())
-        if (r.model_hash == model_hash && r.points_hash == points_hash && r.ident == ident) { r.fn = fn; return 0; }
-    points_coll_registry().push_back(PointsCollUnit{ident, model_hash, points_hash, fn});
-    return 0;
-}
-// the via-point cost kernels of the small link-column units (k_via_cost): translation units of their own, like the boolean point
-// kernels above, which name the main unit they belong to by its ident, model hash and template identity
-namespace {
-struct ViaCostUnit { std::string ident; uint64_t model_hash, template_identity; SpecViaCostLaunchFn fn; };
-std::vector<ViaCostUnit>& via_cost_registry() { static std::vector<ViaCostUnit> r; return r; }
-std::mutex& via_cost_mutex() { static std::mutex m; return m; }       // (a run-time unit registers from the thread that loads it)
 // must hash the same bytes, in the same order, as torch_robotics_amd/codegen.py: template_identity
 uint64_t via_template_identity(const SpecEntry* e) {
     uint64_t h = 0xcbf29ce484222325ull;
@@ -163,53 +164,37 @@ uint64_t via_template_identity(const SpecEntry* e) {
     h = fnv1a(h, &e->ee_link, 4); h = fnv1a(h, &e->ee2_link, 4);
     return h;
 }
-SpecViaCostLaunchFn via_cost_launcher(const SpecEntry* e) {
+template <class Fn>
+Fn via_launcher(SatelliteRegistry<Fn>& reg, const SpecEntry* e) {
     if (!e->name || e->module_ctx || e->n_points != 0 || e->n_virtual != 0) return nullptr;      // (a code-object unit has none)
-    const uint64_t id = via_template_identity(e);
-    std::lock_guard<std::mutex> lock(via_cost_mutex());
-    for (const auto& r : via_cost_registry())
-        if (r.model_hash == e->model_hash && r.template_identity == id && r.ident == e->name) return r.fn;
-    return nullptr;
+    return reg.find(e->name, e->model_hash, via_template_identity(e));
 }
+SpecViaCostLaunchFn via_cost_launcher(const SpecEntry* e) { return via_launcher(via_cost_registry(), e); }
+SpecViaAdamLaunchFn via_adam_launcher(const SpecEntry* e) { return via_launcher(via_adam_registry(), e); }
 }  // namespace
+int trk_spec_register_points_coll(const char* ident, uint64_t model_hash, uint64_t points_hash, uint32_t sizeof_args, SpecLaunchFn fn) {
+    if (!ident || !fn || sizeof_args != sizeof(SpecArgs)) {
+        fprintf(stderr, "libtrk: refusing a generated unit's boolean point kernels (compiled against another SpecArgs layout) -- they "
+                        "will not be dispatched\n");
+        return TRK_ERR_INVALID_ARG;
+    }
+    return points_coll_registry().announce(ident, model_hash, points_hash, fn);
+}
 int trk_spec_register_via_cost(const char* ident, uint64_t model_hash, uint64_t template_identity, uint32_t sizeof_args, SpecViaCostLaunchFn fn) {
     if (!ident || !fn || sizeof_args != sizeof(ViaCostArgs)) {
         fprintf(stderr, "libtrk: refusing a generated unit's via-point cost kernels (compiled against another ViaCostArgs layout) -- they "
                         "will not be dispatched\n");
         return TRK_ERR_INVALID_ARG;
     }
-    std::lock_guard<std::mutex> lock(via_cost_mutex());
-    for (auto& r : via_cost_registry())
-        if (r.model_hash == model_hash && r.template_identity == template_identity && r.ident == ident) { r.fn = fn; return 0; }
-    via_cost_registry().push_back(ViaCostUnit{ident, model_hash, template_identity, fn});
-    return 0;
+    return via_cost_registry().announce(ident, model_hash, template_identity, fn);
 }
-// the planning-loop kernels with the via-point term (k_traj_via_adam): translation units of their own, spec_<ident>_vadam, announced
-// like the via-point cost kernels above
-namespace {
-struct ViaAdamUnit { std::string ident; uint64_t model_hash, template_identity; SpecViaAdamLaunchFn fn; };
-std::vector<ViaAdamUnit>& via_adam_registry() { static std::vector<ViaAdamUnit> r; return r; }
-std::mutex& via_adam_mutex() { static std::mutex m; return m; }       // (a run-time unit registers from the thread that loads it)
-SpecViaAdamLaunchFn via_adam_launcher(const SpecEntry* e) {
-    if (!e->name || e->module_ctx || e->n_points != 0 || e->n_virtual != 0) return nullptr;      // (a code-object unit has none)
-    const uint64_t id = via_template_identity(e);
-    std::lock_guard<std::mutex> lock(via_adam_mutex());
-    for (const auto& r : via_adam_registry())
-        if (r.model_hash == e->model_hash && r.template_identity == id && r.ident == e->name) return r.fn;
-    return nullptr;
-}
-}  // namespace
 int trk_spec_register_via_adam(const char* ident, uint64_t model_hash, uint64_t template_identity, uint32_t sizeof_args, SpecViaAdamLaunchFn fn) {
     if (!ident || !fn || sizeof_args != sizeof(TrajViaAdamArgs)) {
         fprintf(stderr, "libtrk: refusing a generated unit's planning-loop kernels with the via-point term (compiled against another "
                         "TrajViaAdamArgs layout) -- they will not be dispatched\n");
         return TRK_ERR_INVALID_ARG;
     }
-    std::lock_guard<std::mutex> lock(via_adam_mutex());
-    for (auto& r : via_adam_registry())
-        if (r.model_hash == model_hash && r.template_identity == template_identity && r.ident == ident) { r.fn = fn; return 0; }
-    via_adam_registry().push_back(ViaAdamUnit{ident, model_hash, template_identity, fn});
-    return 0;
+    return via_adam_registry().announce(ident, model_hash, template_identity, fn);
 }
 int trk_spec_layout_stamp(int64_t* out) {
     if (!out) return TRK_ERR_INVALID_ARG;
@@ -630,6 +615,11 @@ static int spec_launch(Fn fn, const SpecEntry* e, const Args& a, const TrkModel*
     TRK_HIP(last_launch_error());
     return TRK_OK;
 }
+// a satellite unit's launcher takes no SpecEntry: spec_launch calls it through this
+template <class Args>
+static auto without_self(void (*fn)(const Args&, int, hipStream_t)) {
+    return [fn](const SpecEntry*, const Args& a, int base_identity, hipStream_t st) { fn(a, base_identity, st); };
+}
 // The plan-specialised rollout family (k_rollout_fx).  The unit's fx_select says which of its instantiations serves the
 // bound arguments (-1: none); the answer travels to the unit's launcher in fx_pick.  A unit with collision points at constant
 // positions reads their signed distance and gradient from a record evaluated ONCE per (cost model, unit): one wavefront of the unit's
@@ -672,8 +662,8 @@ static int bind_plan_specialized(SpecArgs& a, const SpecEntry* e, const TrkModel
 }
 
 // the rollout family records which kernel family served the call (trk_last_dispatch); the other entry points do not
-static int served_generated(int rc) {
-    if (rc == TRK_OK) g_last_dispatch = TRK_DISPATCH_GENERATED;
+static int served_generated(int rc, int dispatch = TRK_DISPATCH_GENERATED) {
+    if (rc == TRK_OK) g_last_dispatch = dispatch;
     return rc;
 }
 
@@ -698,6 +688,98 @@ static int check_rollout_call(const char* who, const TrkModel* m, const TrkCostM
     if (!cm) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null cost model");
     if (batch < 0 || horizon < 1) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": bad batch/horizon");
     if (link_columns && cm->hdr.n_links_in != m->hdr.n_links) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": cost model n_links_in != model n_links");
+    return TRK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// The trajectory-layout entries (trk_rollout_gp_adam_steps, trk_rollout_gp_via_adam_steps, trk_rollout_via_cost_grad): only a
+// generated kernel serves them (no table-driven twin, like trk_ik_gn_steps), and the kernel is not a slot of SpecEntry -- the unit,
+// or a satellite unit of it, announced a launcher of its own.  Same vocabulary as above: validate (check_traj_adam_call), choose the
+// unit (find_traj_unit), fill the arguments (fill_traj_adam_args), spec_launch (traj_adam_launches: the loop over the launches).
+// ------------------------------------------------------------------------------------------------------------------------------
+// the words of an entry's refusals: the kernel's name, what a unit "carries", what "bakes this cost model", what has no table-driven form
+struct TrajKernelKind { const char *kernel, *carries, *bakes, *form; };
+static const TrajKernelKind kTrajAdam{"k_traj_adam", "planning-loop kernel", "planning-loop kernel", "planning loop"};
+static const TrajKernelKind kTrajViaAdam{"k_traj_via_adam", "planning-loop kernel with the via-point term", "planning-loop kernel", "planning loop"};
+static const TrajKernelKind kViaCost{"k_via_cost", "via-point cost kernel", "via-point cost kernel", "via-point cost"};
+
+// The unit that serves (m, cm, effective weights) among the model's link-column units for which lookup(unit) has a launcher.
+template <class Fn, class Lookup>
+static int find_traj_unit(const char* who, const TrajKernelKind& k, const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights& we,
+                          Lookup lookup, const SpecEntry** e, Fn* fn) {
+    if (!m->spec_enabled)
+        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": generated kernels are switched off for this model (trk_model_enable_specialized) "
+                                         "and the " + k.form + " has no table-driven form");
+    bool any = false;
+    for (const SpecEntry* c : spec_registry()) {
+        if (c->n_points != 0 || c->model_hash != m->hash || c->n_links != m->hdr.n_links || c->n_dofs != m->hdr.n_dofs) continue;
+        Fn f = lookup(c);
+        if (!f) continue;
+        any = true;
+        if (spec_matches(c, cm, &we)) { *e = c; *fn = f; return TRK_OK; }
+    }
+    if (!any)
+        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": no generated unit of this model carries the " + k.carries + " (" + k.kernel +
+                                         ": link-column units of robots up to 8 DOF, built ahead of time or by hipcc at run time; a unit "
+                                         "loaded as a code object through the hipRTC fall-back has none)");
+    return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": no generated unit with the " + k.bakes + " bakes this cost model's link "
+                                     "sets for the non-zero weights");
+}
+
+static bool traj_adam_updates(const TrkTrajAdam* ad) { return ad->lr != 0.0f && ad->n_steps > 0; }
+// What the two planning-loop entries check alike, in this order.  via: the entry's TrkTrajVia (with_via), checked right after the
+// structs are known to be there; other_horizons: what the horizon rule's refusal points to.
+static int check_traj_adam_call(const char* who, const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w, const TrkGpPrior* gp,
+                                const TrkTrajVia* via, bool with_via, const TrkTrajAdam* ad, const float* q, const float* qd,
+                                const float* adam_m, const float* adam_v, int64_t batch, int32_t horizon, const char* other_horizons) {
+    if (int rc = check_rollout_call(who, m, cm, batch, horizon)) return rc;
+    if (!w || !gp || !ad) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null weights / prior / TrkTrajAdam");
+    if (with_via) {
+        if (!via || !via->alpha || !via->beta) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null TrkTrajVia / alpha / beta");
+        if (via->n_interp < 1 || !std::isfinite(via->w_via))
+            return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": n_interp must be >= 1 and w_via finite");
+    }
+    if (!std::isfinite(w->w_self) || !std::isfinite(w->w_obj) || !std::isfinite(w->w_ws) || !std::isfinite(w->w_ee) ||
+        !std::isfinite(gp->weight) || !std::isfinite(gp->dt) || !std::isfinite(gp->sigma) || !(gp->dt > 0.0f) || !(gp->sigma > 0.0f))
+        return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": the weights must be finite, the prior needs finite dt > 0 and sigma > 0");
+    if (ad->n_steps < 0 || ad->first_step < 1 || !std::isfinite(ad->lr) || ad->pin < 0 || ad->pin > 15)
+        return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": n_steps >= 0, first_step >= 1, lr finite and pin in 0 .. 15");
+    if (batch > 0 && (!q || !qd || (traj_adam_updates(ad) && (!adam_m || !adam_v))))
+        return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null q / qd / adam_m / adam_v");
+    if (horizon > TRK_TRAJ_ADAM_MAX_HORIZON || (horizon & (horizon - 1)) != 0)
+        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": the horizon must be a power of two <= TRK_TRAJ_ADAM_MAX_HORIZON (64): a wavefront "
+                                         "owns whole trajectories and their neighbours in time are neighbouring lanes; " + other_horizons);
+    return TRK_OK;
+}
+// TrajAdamArgs / TrajViaAdamArgs of a call, everything else zero: the header, weights and base pose, the buffers, the prior's
+// coefficients and the optimiser's constants
+template <class Args>
+static void fill_traj_adam_args(Args& a, const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights& we, const TrkGpPrior* gp,
+                                const TrkTrajAdam* ad, float* q, float* qd, float* adam_m, float* adam_v, int64_t batch, int32_t horizon) {
+    std::memset(&a, 0, sizeof(a));
+    a.C = cm->hdr; a.w = we;
+    set_base_pose(a, m);
+    a.q = q; a.qd = qd; a.adam_m = adam_m; a.adam_v = adam_v; a.n = batch * horizon;
+    const float s2 = 1.0f / (gp->sigma * gp->sigma);
+    a.gp_dt = gp->dt; a.gp_w = gp->weight; a.gp_H = horizon;
+    a.gp_a = 12.0f * s2 / (gp->dt * gp->dt * gp->dt); a.gp_b = -6.0f * s2 / (gp->dt * gp->dt); a.gp_c = 4.0f * s2 / gp->dt;
+    a.lr = ad->lr; a.pin = ad->pin; a.update = traj_adam_updates(ad) ? 1 : 0;
+}
+// The launches of a call: at most TRK_IK_MAX_STEPS iterations each, with their slice of the bias-correction schedule (formed in
+// double); the cost comes from the first launch (the state as the caller passed it).  launch(): one spec_launch of `a`.
+template <class Args, class Launch>
+static int traj_adam_launches(Args& a, const TrkTrajAdam* ad, float* cost, Launch launch) {
+    const int32_t total = a.update ? ad->n_steps : 1;
+    for (int32_t done = 0; done < total; done += TRK_IK_MAX_STEPS) {
+        a.n_steps = std::min<int32_t>(TRK_IK_MAX_STEPS, total - done);
+        a.cost = done == 0 ? cost : nullptr;
+        for (int32_t i = 0; i < a.n_steps; ++i) {
+            const double k = (double)ad->first_step + (double)done + (double)i;
+            a.sched.bc1[i] = (float)(1.0 - std::pow(0.9, k));
+            a.sched.rsqrt_bc2[i] = (float)(1.0 / std::sqrt(1.0 - std::pow(0.999, k)));
+        }
+        if (int rc = launch()) return rc;
+    }
     return TRK_OK;
 }
 
@@ -1806,139 +1888,38 @@ int trk_rollout_gp_adam_steps(const TrkModel* m, const TrkCostModel* cm, const T
                               const TrkTrajAdam* ad, float* q, float* qd, float* adam_m, float* adam_v, int64_t batch, int32_t horizon,
                               float* cost, trk_stream_t stream) {
     const char* who = "trk_rollout_gp_adam_steps";
-    int rc = check_rollout_call(who, m, cm, batch, horizon);
+    int rc = check_traj_adam_call(who, m, cm, w, gp, nullptr, false, ad, q, qd, adam_m, adam_v, batch, horizon,
+                                  "trk_rollout_gp_cost_grad serves any horizon");
     if (rc) return rc;
-    if (!w || !gp || !ad) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null weights / prior / TrkTrajAdam");
-    if (!std::isfinite(w->w_self) || !std::isfinite(w->w_obj) || !std::isfinite(w->w_ws) || !std::isfinite(w->w_ee) ||
-        !std::isfinite(gp->weight) || !std::isfinite(gp->dt) || !std::isfinite(gp->sigma) || !(gp->dt > 0.0f) || !(gp->sigma > 0.0f))
-        return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": the weights must be finite, the prior needs finite dt > 0 and sigma > 0");
-    if (ad->n_steps < 0 || ad->first_step < 1 || !std::isfinite(ad->lr) || ad->pin < 0 || ad->pin > 15)
-        return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": n_steps >= 0, first_step >= 1, lr finite and pin in 0 .. 15");
-    const bool update = ad->lr != 0.0f && ad->n_steps > 0;
-    if (batch > 0 && (!q || !qd || (update && (!adam_m || !adam_v))))
-        return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null q / qd / adam_m / adam_v");
-    if (horizon > TRK_TRAJ_ADAM_MAX_HORIZON || (horizon & (horizon - 1)) != 0)
-        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": the horizon must be a power of two <= TRK_TRAJ_ADAM_MAX_HORIZON (64): a wavefront "
-                                         "owns whole trajectories and their neighbours in time are neighbouring lanes; "
-                                         "trk_rollout_gp_cost_grad serves any horizon");
     if (batch == 0 || m->hdr.n_dofs == 0) return TRK_OK;
-    // only the generated kernel serves this call (no table-driven twin, like trk_ik_gn_steps)
-    if (!m->spec_enabled)
-        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": generated kernels are switched off for this model (trk_model_enable_specialized) "
-                                         "and the planning loop has no table-driven form");
     const TrkRolloutWeights we = effective_weights(cm, *w);
     SpecTrajAdamLaunchFn fn = nullptr;
     const SpecEntry* e = nullptr;
-    bool any = false;
-    for (const SpecEntry* c : spec_registry()) {
-        if (c->n_points != 0 || c->model_hash != m->hash || c->n_links != m->hdr.n_links || c->n_dofs != m->hdr.n_dofs) continue;
-        SpecTrajAdamLaunchFn f = traj_adam_launcher(c);
-        if (!f) continue;
-        any = true;
-        if (spec_matches(c, cm, &we)) { e = c; fn = f; break; }
-    }
-    if (!any)
-        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": no generated unit of this model carries the planning-loop kernel (k_traj_adam: "
-                                         "link-column units of robots up to 8 DOF, built ahead of time or by hipcc at run time; a unit "
-                                         "loaded as a code object through the hipRTC fall-back has none)");
-    if (!e)
-        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": no generated unit with the planning-loop kernel bakes this cost model's link "
-                                         "sets for the non-zero weights");
-    if (!update && !cost) return TRK_OK;
+    if ((rc = find_traj_unit(who, kTrajAdam, m, cm, we, traj_adam_launcher, &e, &fn)) != TRK_OK) return rc;
+    if (!traj_adam_updates(ad) && !cost) return TRK_OK;
     TrajAdamArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.C = cm->hdr; a.w = we;
-    set_base_pose(a, m);
-    a.q = q; a.qd = qd; a.adam_m = adam_m; a.adam_v = adam_v; a.n = batch * horizon;
-    const float s2 = 1.0f / (gp->sigma * gp->sigma);
-    a.gp_dt = gp->dt; a.gp_w = gp->weight; a.gp_H = horizon;
-    a.gp_a = 12.0f * s2 / (gp->dt * gp->dt * gp->dt); a.gp_b = -6.0f * s2 / (gp->dt * gp->dt); a.gp_c = 4.0f * s2 / gp->dt;
-    a.lr = ad->lr; a.pin = ad->pin; a.update = update ? 1 : 0;
-    // at most TRK_IK_MAX_STEPS iterations per launch; the cost comes from the first launch (the state as the caller passed it)
-    const int32_t total = update ? ad->n_steps : 1;
-    for (int32_t done = 0; done < total; done += TRK_IK_MAX_STEPS) {
-        a.n_steps = std::min<int32_t>(TRK_IK_MAX_STEPS, total - done);
-        a.cost = done == 0 ? cost : nullptr;
-        for (int32_t i = 0; i < a.n_steps; ++i) {
-            const double k = (double)ad->first_step + (double)done + (double)i;
-            a.sched.bc1[i] = (float)(1.0 - std::pow(0.9, k));
-            a.sched.rsqrt_bc2[i] = (float)(1.0 / std::sqrt(1.0 - std::pow(0.999, k)));
-        }
-        if ((rc = spec_launch(fn, e, a, m, stream)) != TRK_OK) return rc;
-    }
-    return served_generated(TRK_OK);
+    fill_traj_adam_args(a, m, cm, we, gp, ad, q, qd, adam_m, adam_v, batch, horizon);
+    return served_generated(traj_adam_launches(a, ad, cost, [&] { return spec_launch(fn, e, a, m, stream); }));
 }
 
 int trk_rollout_gp_via_adam_steps(const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w, const TrkGpPrior* gp,
                                   const TrkTrajVia* via, const TrkTrajAdam* ad, float* q, float* qd, float* adam_m, float* adam_v,
                                   int64_t batch, int32_t horizon, float* cost, trk_stream_t stream) {
     const char* who = "trk_rollout_gp_via_adam_steps";
-    int rc = check_rollout_call(who, m, cm, batch, horizon);
+    int rc = check_traj_adam_call(who, m, cm, w, gp, via, true, ad, q, qd, adam_m, adam_v, batch, horizon,
+                                  "trk_rollout_gp_cost_grad + trk_rollout_via_cost_grad serve the other horizons");
     if (rc) return rc;
-    if (!w || !gp || !ad) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null weights / prior / TrkTrajAdam");
-    if (!via || !via->alpha || !via->beta) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null TrkTrajVia / alpha / beta");
-    if (via->n_interp < 1 || !std::isfinite(via->w_via))
-        return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": n_interp must be >= 1 and w_via finite");
-    if (!std::isfinite(w->w_self) || !std::isfinite(w->w_obj) || !std::isfinite(w->w_ws) || !std::isfinite(w->w_ee) ||
-        !std::isfinite(gp->weight) || !std::isfinite(gp->dt) || !std::isfinite(gp->sigma) || !(gp->dt > 0.0f) || !(gp->sigma > 0.0f))
-        return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": the weights must be finite, the prior needs finite dt > 0 and sigma > 0");
-    if (ad->n_steps < 0 || ad->first_step < 1 || !std::isfinite(ad->lr) || ad->pin < 0 || ad->pin > 15)
-        return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": n_steps >= 0, first_step >= 1, lr finite and pin in 0 .. 15");
-    const bool update = ad->lr != 0.0f && ad->n_steps > 0;
-    if (batch > 0 && (!q || !qd || (update && (!adam_m || !adam_v))))
-        return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null q / qd / adam_m / adam_v");
-    if (horizon > TRK_TRAJ_ADAM_MAX_HORIZON || (horizon & (horizon - 1)) != 0)
-        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": the horizon must be a power of two <= TRK_TRAJ_ADAM_MAX_HORIZON (64): a wavefront "
-                                         "owns whole trajectories and their neighbours in time are neighbouring lanes; "
-                                         "trk_rollout_gp_cost_grad + trk_rollout_via_cost_grad serve the other horizons");
     if (batch == 0 || m->hdr.n_dofs == 0) return TRK_OK;
-    // only the generated kernel serves this call (no table-driven twin, like trk_rollout_gp_adam_steps)
-    if (!m->spec_enabled)
-        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": generated kernels are switched off for this model (trk_model_enable_specialized) "
-                                         "and the planning loop has no table-driven form");
     const TrkRolloutWeights we = effective_weights(cm, *w);
     SpecViaAdamLaunchFn fn = nullptr;
-    bool any = false;
-    for (const SpecEntry* c : spec_registry()) {
-        if (c->n_points != 0 || c->model_hash != m->hash || c->n_links != m->hdr.n_links || c->n_dofs != m->hdr.n_dofs) continue;
-        SpecViaAdamLaunchFn f = via_adam_launcher(c);
-        if (!f) continue;
-        any = true;
-        if (spec_matches(c, cm, &we)) { fn = f; break; }
-    }
-    if (!any)
-        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": no generated unit of this model carries the planning-loop kernel with the via-point "
-                                         "term (k_traj_via_adam: link-column units of robots up to 8 DOF, built ahead of time or by hipcc at "
-                                         "run time; a unit loaded as a code object through the hipRTC fall-back has none)");
-    if (!fn)
-        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": no generated unit with the planning-loop kernel bakes this cost model's link "
-                                         "sets for the non-zero weights");
-    if (!update && !cost) return TRK_OK;
+    const SpecEntry* e = nullptr;
+    if ((rc = find_traj_unit(who, kTrajViaAdam, m, cm, we, via_adam_launcher, &e, &fn)) != TRK_OK) return rc;
+    if (!traj_adam_updates(ad) && !cost) return TRK_OK;
     TrajViaAdamArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.C = cm->hdr; a.w = we;
-    set_base_pose(a, m);
-    a.q = q; a.qd = qd; a.adam_m = adam_m; a.adam_v = adam_v; a.n = batch * horizon;
-    const float s2 = 1.0f / (gp->sigma * gp->sigma);
-    a.gp_dt = gp->dt; a.gp_w = gp->weight; a.gp_H = horizon;
-    a.gp_a = 12.0f * s2 / (gp->dt * gp->dt * gp->dt); a.gp_b = -6.0f * s2 / (gp->dt * gp->dt); a.gp_c = 4.0f * s2 / gp->dt;
-    a.lr = ad->lr; a.pin = ad->pin; a.update = update ? 1 : 0;
+    fill_traj_adam_args(a, m, cm, we, gp, ad, q, qd, adam_m, adam_v, batch, horizon);
     a.alpha = via->alpha; a.beta = via->beta; a.n_via = via->n_interp; a.w_via = via->w_via;
-    // at most TRK_IK_MAX_STEPS iterations per launch; the cost comes from the first launch (the state as the caller passed it)
-    const int32_t total = update ? ad->n_steps : 1;
-    for (int32_t done = 0; done < total; done += TRK_IK_MAX_STEPS) {
-        a.n_steps = std::min<int32_t>(TRK_IK_MAX_STEPS, total - done);
-        a.cost = done == 0 ? cost : nullptr;
-        for (int32_t i = 0; i < a.n_steps; ++i) {
-            const double k = (double)ad->first_step + (double)done + (double)i;
-            a.sched.bc1[i] = (float)(1.0 - std::pow(0.9, k));
-            a.sched.rsqrt_bc2[i] = (float)(1.0 / std::sqrt(1.0 - std::pow(0.999, k)));
-        }
-        fn(a, base_is_identity(m), (hipStream_t)stream);
-        TRK_HIP(last_launch_error());
-    }
-    g_last_dispatch = TRK_DISPATCH_GENERATED_VIA_ADAM;
-    return TRK_OK;
+    return served_generated(traj_adam_launches(a, ad, cost, [&] { return spec_launch(without_self(fn), e, a, m, stream); }),
+                            TRK_DISPATCH_GENERATED_VIA_ADAM);
 }
 
 int trk_rollout_via_cost_grad(const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w, const float* x, int64_t n_traj,
@@ -1961,36 +1942,16 @@ int trk_rollout_via_cost_grad(const TrkModel* m, const TrkCostModel* cm, const T
                                          "trajectories and a way point's successor is the next lane; trk_interpolate_via_points + "
                                          "trk_rollout_cost_grad serve any horizon");
     if (n_traj == 0 || m->hdr.n_dofs == 0) return TRK_OK;
-    // only the generated kernel serves this call (no table-driven twin, like trk_rollout_gp_adam_steps)
-    if (!m->spec_enabled)
-        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": generated kernels are switched off for this model (trk_model_enable_specialized) "
-                                         "and the via-point cost has no table-driven form");
     const TrkRolloutWeights we = effective_weights(cm, *w);
     SpecViaCostLaunchFn fn = nullptr;
-    bool any = false;
-    for (const SpecEntry* c : spec_registry()) {
-        if (c->n_points != 0 || c->model_hash != m->hash || c->n_links != m->hdr.n_links || c->n_dofs != m->hdr.n_dofs) continue;
-        SpecViaCostLaunchFn f = via_cost_launcher(c);
-        if (!f) continue;
-        any = true;
-        if (spec_matches(c, cm, &we)) { fn = f; break; }
-    }
-    if (!any)
-        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": no generated unit of this model carries the via-point cost kernel (k_via_cost: "
-                                         "link-column units of robots up to 8 DOF, built ahead of time or by hipcc at run time; a unit "
-                                         "loaded as a code object through the hipRTC fall-back has none)");
-    if (!fn)
-        return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": no generated unit with the via-point cost kernel bakes this cost model's link "
-                                         "sets for the non-zero weights");
+    const SpecEntry* e = nullptr;
+    if ((rc = find_traj_unit(who, kViaCost, m, cm, we, via_cost_launcher, &e, &fn)) != TRK_OK) return rc;
     ViaCostArgs a;
     std::memset(&a, 0, sizeof(a));
     a.C = cm->hdr; a.w = we;
     set_base_pose(a, m);
     a.x = x; a.seed = seed; a.cost = cost; a.gq = gq; a.T = n_traj; a.H = horizon; a.n = n_interp; a.alpha = alpha; a.beta = beta;
-    fn(a, base_is_identity(m), (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    g_last_dispatch = TRK_DISPATCH_GENERATED_VIA_COST;
-    return TRK_OK;
+    return served_generated(spec_launch(without_self(fn), e, a, m, stream), TRK_DISPATCH_GENERATED_VIA_COST);
 }
 
 int trk_rollout_points_cost_grad(const TrkModel* m, const TrkPointSet* ps, const TrkCostModel* cm, const TrkRolloutWeights* w,
