@@ -1155,7 +1155,14 @@ int trk_ik_steps(const TrkModel* m, int32_t link, const float* H_target, int32_t
     if (n == 0 || m->hdr.n_dofs == 0) return TRK_OK;
     // generated kernel (configurations and Adam state in registers) when the target is the link the unit tracks
     const SpecEntry* gen = enabled_spec(m);
-    if (gen && !(gen->launch_ik && gen->ee_link == link)) gen = nullptr;
+    if (gen && !(gen->launch_ik && gen->ee_link == link)) {
+        // the model's first unit tracks another link: a unit loaded for this link (jit.specialize(kin, obj_links, ee_link=link))
+        // serves it, found as trk_ik_gn_steps finds its unit
+        gen = nullptr;
+        for (const SpecEntry* e : spec_registry())
+            if (e->n_points == 0 && e->model_hash == m->hash && e->n_links == m->hdr.n_links && e->n_dofs == m->hdr.n_dofs &&
+                e->launch_ik && e->ee_link == link) { gen = e; break; }
+    }
     // at most TRK_IK_MAX_STEPS iterations per launch; loss / valid come from the first launch (q as the caller passed it)
     for (int32_t done = 0; done < n_steps; done += TRK_IK_MAX_STEPS) {
         const int32_t k = std::min<int32_t>(TRK_IK_MAX_STEPS, n_steps - done);
