@@ -1,7 +1,7 @@
 """CPU-only checks of the 2-D point mass's via-point entry points (trk_scene2d_traj_via_cost_grad, trk_scene2d_traj_via_adam_steps):
 header, EXPORTS, library and INTEGRATION.md agree, the ctypes struct has the header's layout, bad arguments are refused before any
 device work (the scene pointer of these calls is a block of zeros that is never read), only a planar task hands out the optimiser, and
-every instantiation of the new kernel compiles for gfx950 without scratch at the occupancy DESIGN.md 6b records."""
+every instantiation of the two loop kernels compiles for gfx950 without scratch at the occupancy DESIGN.md 6b records."""
 import ctypes as C
 import re
 import subprocess
@@ -109,6 +109,9 @@ def test_only_a_planar_task_takes_the_via_keywords():
 # DESIGN.md 6b, "via-point term": wavefronts per SIMD of k_planar_traj_via by variant -- 7 where the analytic objects are walked
 # (66 - 68 VGPRs), 8 everywhere else (41 - 55 VGPRs); 32 instantiations = grid x analytic x workspace x clamp x WAVE
 MIN_WAVES = {True: 7, False: 8}
+# k_planar_traj_adam, the same loop body without the via term: 8 in all 32 (30 - 55 VGPRs) -- what a compile of the commit before the
+# two kernels shared their body gives for every variant, and what DESIGN.md 6b's paragraph on the kernel records
+MIN_WAVES_PLAIN = 8
 
 
 def test_every_instantiation_compiles_without_scratch_at_the_recorded_occupancy():
@@ -120,18 +123,20 @@ def test_every_instantiation_compiles_without_scratch_at_the_recorded_occupancy(
         res = subprocess.run([hipcc, *flags, "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
                               "trk_planar.hip", "-o", str(Path(d) / "planar_device.o")], cwd=csrc, capture_output=True, text=True)
     assert res.returncode == 0, res.stderr[-3000:]
-    seen = {}
+    seen = {"adam": {}, "via": {}}
     for block in re.split(r"remark: [^\n]*Function Name: ", res.stderr)[1:]:
         name = block.split()[0]
-        m = re.match(r"_ZN\d+_GLOBAL__N_1\d+k_planar_traj_viaILb([01])ELb([01])ELb([01])ELb([01])ELb([01])EEE", name)
+        m = re.match(r"_ZN\d+_GLOBAL__N_1\d+k_planar_traj_(adam|via)ILb([01])ELb([01])ELb([01])ELb([01])ELb([01])EEE", name)
         if not m:
             continue
         num = lambda key: int(re.search(re.escape(key) + r": (\d+)", block).group(1))
-        seen[tuple(int(v) for v in m.groups())] = (num("ScratchSize [bytes/lane]"), num("Occupancy [waves/SIMD]"), num("VGPRs"),
-                                                   num("LDS Size [bytes/block]"))
-    assert len(seen) == 32, sorted(seen)
-    for variant, (scratch, waves, vgprs, lds) in sorted(seen.items()):
-        print(f"k_planar_traj_via<grid, analytic, workspace, clamp, wave> = {variant}: {vgprs} VGPRs, {waves} waves / SIMD, {lds} B of LDS")
-        assert scratch == 0, variant
-        assert waves >= MIN_WAVES[bool(variant[1])], (variant, waves, vgprs)
-        assert lds == (0 if variant[4] else 10240), (variant, lds)
+        seen[m.group(1)][tuple(int(v) for v in m.groups()[1:])] = (num("ScratchSize [bytes/lane]"), num("Occupancy [waves/SIMD]"),
+                                                                    num("VGPRs"), num("LDS Size [bytes/block]"))
+    for kernel, lds_form in (("adam", 8192), ("via", 10240)):
+        assert len(seen[kernel]) == 32, (kernel, sorted(seen[kernel]))
+        for variant, (scratch, waves, vgprs, lds) in sorted(seen[kernel].items()):
+            print(f"k_planar_traj_{kernel}<grid, analytic, workspace, clamp, wave> = {variant}: {vgprs} VGPRs, {waves} waves / SIMD, "
+                  f"{lds} B of LDS")
+            assert scratch == 0, (kernel, variant)
+            assert waves >= (MIN_WAVES_PLAIN if kernel == "adam" else MIN_WAVES[bool(variant[1])]), (kernel, variant, waves, vgprs)
+            assert lds == (0 if variant[4] else lds_form), (kernel, variant, lds)

@@ -773,11 +773,7 @@ static int traj_adam_launches(Args& a, const TrkTrajAdam* ad, float* cost, Launc
     for (int32_t done = 0; done < total; done += TRK_IK_MAX_STEPS) {
         a.n_steps = std::min<int32_t>(TRK_IK_MAX_STEPS, total - done);
         a.cost = done == 0 ? cost : nullptr;
-        for (int32_t i = 0; i < a.n_steps; ++i) {
-            const double k = (double)ad->first_step + (double)done + (double)i;
-            a.sched.bc1[i] = (float)(1.0 - std::pow(0.9, k));
-            a.sched.rsqrt_bc2[i] = (float)(1.0 / std::sqrt(1.0 - std::pow(0.999, k)));
-        }
+        trk_adam_bias_schedule(a.sched.bc1, a.sched.rsqrt_bc2, (int64_t)ad->first_step + done, a.n_steps);
         if (int rc = launch()) return rc;
     }
     return TRK_OK;

@@ -1,5 +1,6 @@
 // trk_launch.h -- host-callable launchers defined next to the kernels they start.
 #pragma once
+#include <cmath>
 #include "trk_device.h"
 
 void trk_launch_fk_forward(int mode, const DevModelHdr& hdr, const DevLink* links, const SelMap& sel, int n_sel,
@@ -77,6 +78,16 @@ void trk_launch_reduce_sum(const float* x, int64_t n, float* out, hipStream_t st
 void trk_launch_sdf_points(const DevCostHdr& C, const float* pts, int64_t n, float* sdf, float* grad, hipStream_t st);
 // trajectories that 64 consecutive samples can touch when a trajectory has `hi` samples: floor((hi - 1 + 63) / hi) + 1 (SpecArgs::via_slots)
 inline int trk_via_slots(int64_t hi) { return (int)((hi + 62) / hi) + 1; }
+// Adam's bias corrections of the n iterations from the 1-based iteration `first`, as the trajectory loops take them (trk_planar.hip,
+// trk_capi.hip: traj_adam_launches): bc1 = 1 - 0.9^k and 1 / sqrt(1 - 0.999^k), formed in double and rounded once to fp32.
+// trk_ik_steps forms its schedule in fp32 by another formula, which its tests pin: it does not use this.
+inline void trk_adam_bias_schedule(float* bc1, float* rsqrt_bc2, int64_t first, int32_t n) {
+    for (int32_t i = 0; i < n; ++i) {
+        const double k = (double)(first + i);
+        bc1[i] = (float)(1.0 - std::pow(0.9, k));
+        rsqrt_bc2[i] = (float)(1.0 / std::sqrt(1.0 - std::pow(0.999, k)));
+    }
+}
 // raises the dynamic-LDS ceiling of every kernel once (gfx950: 160 KiB per workgroup)
 int trk_kernels_init(void);
 // trk_capi.hip's error string / initialisation, for the other translation units of the library

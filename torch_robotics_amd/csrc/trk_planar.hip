@@ -272,16 +272,58 @@ __device__ __forceinline__ void adam_component(float g, float step, float rsqrt_
     x = x - step * (m1 / denom);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The via-point term (include/trk.h, trk_scene2d_traj_via_cost_grad): the hinge at the n interpolated points of the segment t -> t+1,
+// attributed to sample t like the prior's factor.
+// ---------------------------------------------------------------------------------------------------------------------------
+struct ViaPar { float w_via; int32_t n; const float* alpha; const float* beta; };      // alpha, beta: device [n], the same for every lane
+
+// The segment from x to xn: v[a] = x * alpha[a] + xn * beta[a], each product and the sum rounded once (k_planar_collision_via's
+// arithmetic) -> c = sum_a h(v[a]), l = sum_a alpha[a] g(v[a]) (the segment's gradient on its own sample), u = sum_a beta[a] g(v[a])
+// (on the next one); ascending a from 0.0f, c by plain adds, l and u by fmaf.  A run-time loop: the hinge's code is there once.
+template <bool GRID, bool ANALYTIC, bool WS, bool CLAMP>
+__device__ __forceinline__ void via_segment(const P2Hdr& S, const ViaPar& V, const float4& x, const float4& xn, float& c, float2& l,
+                                            float2& u) {
+    c = 0.0f; l = make_float2(0.0f, 0.0f); u = l;
+    const TRK_CAS float* al = cptr(V.alpha);
+    const TRK_CAS float* be = cptr(V.beta);
+#pragma nounroll
+    for (int a = 0; a < V.n; ++a) {
+        const float wa = al[a], wb = be[a];
+        const float px = __fadd_rn(__fmul_rn(x.x, wa), __fmul_rn(xn.x, wb));
+        const float py = __fadd_rn(__fmul_rn(x.y, wa), __fmul_rn(xn.y, wb));
+        float gx, gy;
+        c = c + hinge_term<GRID, ANALYTIC, WS, CLAMP>(S, make_float2(px, py), gx, gy);
+        l.x = fmaf(wa, gx, l.x); l.y = fmaf(wa, gy, l.y);
+        u.x = fmaf(wb, gx, u.x); u.y = fmaf(wb, gy, u.y);
+    }
+}
+
+// The persistent loop of the three entries (trk_scene2d_traj_adam_steps, trk_scene2d_traj_via_adam_steps and the one evaluation of
+// trk_scene2d_traj_via_cost_grad: update == 0, which also stores the gradient), behind the two __global__ shells below.
 // One lane per sample, a workgroup of 256 lanes owns floor(256 / H) whole trajectories (lanes beyond them idle); (q, qd, m, v) of a
 // sample stay in its lane's registers for the n_steps iterations of the launch.  Each iteration a lane needs (q, qd) of t - 1 and t + 1:
 //   WAVE (H == 64, a wavefront is a trajectory): two DPP wavefront shifts per value, no LDS and no barrier;
 //   otherwise: through LDS, two buffers used in turn and ONE barrier per iteration -- a lane that writes buffer k & 1 for iteration
 //   k + 2 has passed the barrier of iteration k + 1, which every lane reaches only after its reads of iteration k.
-template <bool GRID, bool ANALYTIC, bool WS, bool CLAMP, bool WAVE>
-__global__ void __launch_bounds__(256)
-k_planar_traj_adam(P2Hdr S, TrajPar P, AdamPar A, float2* __restrict__ q, float2* __restrict__ qd, float4* __restrict__ mom,
-                   float4* __restrict__ vel, int64_t B, int H, float* __restrict__ cost) {
+// VIA: the via term in the objective.  After the first exchange a lane with a segment (t < H - 1) walks the segment's n via points with
+// (c, l, u) in registers, and u goes to lane t + 1:
+//   WAVE: two more DPP shifts;
+//   otherwise: one float2 per lane through LDS, ONE buffer and a second barrier per iteration.  A lane that writes uch for iteration
+//   k + 1 has passed the first barrier of iteration k + 1, which every lane reaches only after its read of uch in iteration k; a
+//   lane that reads uch in iteration k has passed the second barrier of iteration k, which every lane reaches only after its write.
+//   With two barriers per iteration xch's two buffers are more than the first exchange needs; they stay as without the via term.
+// Idle lanes (beyond the workgroup's whole trajectories, or beyond the batch) reach every barrier.  The lane without a segment and
+// the lane without a predecessor have their shares removed by a select: what lane tid - 1 of another trajectory wrote never enters.
+// The structs come by value, as the kernels take them: nothing is copied at run time, the fields stay scalar loads from the kernarg
+// segment.  (By const& the compiler moved the grid cell's first use ahead of the workspace term in the grid + workspace + clamp
+// variants, which exposes the gather's latency to a lone wavefront: 0.92 -> 1.02 us per iteration at 512 x 64 on EnvDense2D.)
+template <bool GRID, bool ANALYTIC, bool WS, bool CLAMP, bool WAVE, bool VIA>
+__device__ __forceinline__ void traj_loop(const P2Hdr S, const TrajPar P, const ViaPar V, const AdamPar A, float2* __restrict__ q,
+                                          float2* __restrict__ qd, float4* __restrict__ mom, float4* __restrict__ vel, int64_t B, int H,
+                                          float* __restrict__ cost, float2* __restrict__ gq, float2* __restrict__ gqd) {
     __shared__ float4 xch[WAVE ? 1 : 2][WAVE ? 1 : 256];
+    __shared__ float2 uch[WAVE || !VIA ? 1 : 256];
     const int tid = threadIdx.x;
     const int per_wg = WAVE ? 4 : 256 / H;
     const int tl = WAVE ? tid >> 6 : tid / H;                      // the lane's trajectory within the workgroup
@@ -314,10 +356,28 @@ k_planar_traj_adam(P2Hdr S, TrajPar P, AdamPar A, float2* __restrict__ q, float2
             if (active && has_prev) xm = xch[it & 1][tid - 1];
             if (active && has_next) xn = xch[it & 1][tid + 1];
         }
+        float vc = 0.0f;
+        float2 vl = make_float2(0.0f, 0.0f), vu = vl, up = vl;
+        if (VIA) {
+            if (active && has_next) via_segment<GRID, ANALYTIC, WS, CLAMP>(S, V, x, xn, vc, vl, vu);
+            if (WAVE) {
+                up.x = trk_dpp_from_prev(0.0f, vu.x); up.y = trk_dpp_from_prev(0.0f, vu.y);
+            } else {
+                uch[tid] = vu;
+                __syncthreads();
+                if (active && has_prev) up = uch[tid - 1];
+            }
+            if (!has_prev) up = make_float2(0.0f, 0.0f);
+        }
         if (active) {
             float g[4];
-            const float c = traj_objective<GRID, ANALYTIC, WS, CLAMP>(S, P, has_prev, has_next, x, xm, xn, g);
+            float c = traj_objective<GRID, ANALYTIC, WS, CLAMP>(S, P, has_prev, has_next, x, xm, xn, g);
+            if (VIA) {
+                c = fmaf(V.w_via, vc, c);
+                g[0] = fmaf(V.w_via, vl.x + up.x, g[0]); g[1] = fmaf(V.w_via, vl.y + up.y, g[1]);
+            }
             if (it == 0 && cost) cost[s] = c;
+            if (VIA && it == 0 && gq) { gq[s] = make_float2(g[0], g[1]); gqd[s] = make_float2(g[2], g[3]); }
             if (update) {
                 const float step = A.lr / A.bc1[it], rs = A.rsqrt_bc2[it];
                 adam_component(pin_q ? 0.0f : g[0], step, rs, x.x, m.x, v.x);
@@ -333,112 +393,20 @@ k_planar_traj_adam(P2Hdr S, TrajPar P, AdamPar A, float2* __restrict__ q, float2
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// The via-point term (include/trk.h, trk_scene2d_traj_via_cost_grad): the hinge at the n interpolated points of the segment t -> t+1,
-// attributed to sample t like the prior's factor.
-// ---------------------------------------------------------------------------------------------------------------------------
-struct ViaPar { float w_via; int32_t n; const float* alpha; const float* beta; };      // alpha, beta: device [n], the same for every lane
-
-// The segment from x to xn: v[a] = x * alpha[a] + xn * beta[a], each product and the sum rounded once (k_planar_collision_via's
-// arithmetic) -> c = sum_a h(v[a]), l = sum_a alpha[a] g(v[a]) (the segment's gradient on its own sample), u = sum_a beta[a] g(v[a])
-// (on the next one); ascending a from 0.0f, c by plain adds, l and u by fmaf.  A run-time loop: the hinge's code is there once.
-template <bool GRID, bool ANALYTIC, bool WS, bool CLAMP>
-__device__ __forceinline__ void via_segment(const P2Hdr& S, const ViaPar& V, const float4& x, const float4& xn, float& c, float2& l,
-                                            float2& u) {
-    c = 0.0f; l = make_float2(0.0f, 0.0f); u = l;
-    const TRK_CAS float* al = cptr(V.alpha);
-    const TRK_CAS float* be = cptr(V.beta);
-#pragma nounroll
-    for (int a = 0; a < V.n; ++a) {
-        const float wa = al[a], wb = be[a];
-        const float px = __fadd_rn(__fmul_rn(x.x, wa), __fmul_rn(xn.x, wb));
-        const float py = __fadd_rn(__fmul_rn(x.y, wa), __fmul_rn(xn.y, wb));
-        float gx, gy;
-        c = c + hinge_term<GRID, ANALYTIC, WS, CLAMP>(S, make_float2(px, py), gx, gy);
-        l.x = fmaf(wa, gx, l.x); l.y = fmaf(wa, gy, l.y);
-        u.x = fmaf(wb, gx, u.x); u.y = fmaf(wb, gy, u.y);
-    }
+// the two shells keep their names and their kernel-argument segments: tools, tests and profiles find the kernels by them
+template <bool GRID, bool ANALYTIC, bool WS, bool CLAMP, bool WAVE>
+__global__ void __launch_bounds__(256)
+k_planar_traj_adam(P2Hdr S, TrajPar P, AdamPar A, float2* __restrict__ q, float2* __restrict__ qd, float4* __restrict__ mom,
+                   float4* __restrict__ vel, int64_t B, int H, float* __restrict__ cost) {
+    traj_loop<GRID, ANALYTIC, WS, CLAMP, WAVE, false>(S, P, ViaPar{}, A, q, qd, mom, vel, B, H, cost, nullptr, nullptr);
 }
 
-// k_planar_traj_adam with the via term in the objective; it serves both entry points (trk_scene2d_traj_via_cost_grad is one
-// evaluation, update == 0, that also stores the gradient).  The layout and the first exchange are k_planar_traj_adam's.  After it a
-// lane with a segment (t < H - 1) walks the segment's n via points with (c, l, u) in registers, and u goes to lane t + 1:
-//   WAVE: two more DPP shifts;
-//   otherwise: one float2 per lane through LDS, ONE buffer and a second barrier per iteration.  A lane that writes uch for iteration
-//   k + 1 has passed the first barrier of iteration k + 1, which every lane reaches only after its read of uch in iteration k; a
-//   lane that reads uch in iteration k has passed the second barrier of iteration k, which every lane reaches only after its write.
-//   With two barriers per iteration xch's two buffers are more than the first exchange needs; they stay as in k_planar_traj_adam.
-// Idle lanes (beyond the workgroup's whole trajectories, or beyond the batch) reach every barrier.  The lane without a segment and
-// the lane without a predecessor have their shares removed by a select: what lane tid - 1 of another trajectory wrote never enters.
 template <bool GRID, bool ANALYTIC, bool WS, bool CLAMP, bool WAVE>
 __global__ void __launch_bounds__(256)
 k_planar_traj_via(P2Hdr S, TrajPar P, ViaPar V, AdamPar A, float2* __restrict__ q, float2* __restrict__ qd, float4* __restrict__ mom,
                   float4* __restrict__ vel, int64_t B, int H, float* __restrict__ cost, float2* __restrict__ gq,
                   float2* __restrict__ gqd) {
-    __shared__ float4 xch[WAVE ? 1 : 2][WAVE ? 1 : 256];
-    __shared__ float2 uch[WAVE ? 1 : 256];
-    const int tid = threadIdx.x;
-    const int per_wg = WAVE ? 4 : 256 / H;
-    const int tl = WAVE ? tid >> 6 : tid / H;                      // the lane's trajectory within the workgroup
-    const int t = WAVE ? tid & 63 : tid - tl * H;
-    const int64_t traj = (int64_t)blockIdx.x * per_wg + tl;
-    const bool active = tl < per_wg && traj < B;
-    if (WAVE && !active) return;                                   // a whole wavefront: the DPP shifts below see all 64 lanes
-    const int64_t s = traj * H + t;
-    const bool has_prev = t > 0, has_next = t + 1 < H;
-    const bool update = A.update != 0;
-    float4 x = make_float4(0.0f, 0.0f, 0.0f, 0.0f), m = x, v = x;
-    if (active) {
-        const float2 a = q[s], b = qd[s];
-        x = make_float4(a.x, a.y, b.x, b.y);
-        if (update) { m = mom[s]; v = vel[s]; }
-    }
-    const bool pin_q = ((A.pin & 1) && t == 0) || ((A.pin & 2) && t == H - 1);
-    const bool pin_qd = ((A.pin & 4) && t == 0) || ((A.pin & 8) && t == H - 1);
-    for (int it = 0; it < A.n_steps; ++it) {
-        float4 xm = x, xn = x;
-        if (WAVE) {
-            xm.x = trk_dpp_from_prev(x.x, x.x); xm.y = trk_dpp_from_prev(x.y, x.y);
-            xm.z = trk_dpp_from_prev(x.z, x.z); xm.w = trk_dpp_from_prev(x.w, x.w);
-            xn.x = trk_dpp_from_next(x.x, x.x); xn.y = trk_dpp_from_next(x.y, x.y);
-            xn.z = trk_dpp_from_next(x.z, x.z); xn.w = trk_dpp_from_next(x.w, x.w);
-        } else {
-            xch[it & 1][tid] = x;
-            __syncthreads();
-            if (active && has_prev) xm = xch[it & 1][tid - 1];
-            if (active && has_next) xn = xch[it & 1][tid + 1];
-        }
-        float vc = 0.0f;
-        float2 vl = make_float2(0.0f, 0.0f), vu = vl, up = vl;
-        if (active && has_next) via_segment<GRID, ANALYTIC, WS, CLAMP>(S, V, x, xn, vc, vl, vu);
-        if (WAVE) {
-            up.x = trk_dpp_from_prev(0.0f, vu.x); up.y = trk_dpp_from_prev(0.0f, vu.y);
-        } else {
-            uch[tid] = vu;
-            __syncthreads();
-            if (active && has_prev) up = uch[tid - 1];
-        }
-        if (!has_prev) up = make_float2(0.0f, 0.0f);
-        if (active) {
-            float g[4];
-            float c = traj_objective<GRID, ANALYTIC, WS, CLAMP>(S, P, has_prev, has_next, x, xm, xn, g);
-            c = fmaf(V.w_via, vc, c);
-            g[0] = fmaf(V.w_via, vl.x + up.x, g[0]); g[1] = fmaf(V.w_via, vl.y + up.y, g[1]);
-            if (it == 0 && cost) cost[s] = c;
-            if (it == 0 && gq) { gq[s] = make_float2(g[0], g[1]); gqd[s] = make_float2(g[2], g[3]); }
-            if (update) {
-                const float step = A.lr / A.bc1[it], rs = A.rsqrt_bc2[it];
-                adam_component(pin_q ? 0.0f : g[0], step, rs, x.x, m.x, v.x);
-                adam_component(pin_q ? 0.0f : g[1], step, rs, x.y, m.y, v.y);
-                adam_component(pin_qd ? 0.0f : g[2], step, rs, x.z, m.z, v.z);
-                adam_component(pin_qd ? 0.0f : g[3], step, rs, x.w, m.w, v.w);
-            }
-        }
-    }
-    if (active && update) {
-        q[s] = make_float2(x.x, x.y); qd[s] = make_float2(x.z, x.w);
-        mom[s] = m; vel[s] = v;
-    }
+    traj_loop<GRID, ANALYTIC, WS, CLAMP, WAVE, true>(S, P, V, A, q, qd, mom, vel, B, H, cost, gq, gqd);
 }
 
 template <bool GRID, bool ANALYTIC, bool WS>
@@ -509,18 +477,6 @@ k_planar_sdf_points(P2Hdr S, const float2* __restrict__ pts, int64_t n, int n_df
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 
-template <bool G, bool A, bool W>
-void launch_cost3(const P2Hdr& S, const float2* q, int64_t n, bool clamp, float* cost, float2* grad, hipStream_t st) {
-    const dim3 g(blocks_for(n)), b(256);
-    if (clamp) {
-        if (grad) hipLaunchKernelGGL((k_planar_cost<G, A, W, true, true>), g, b, 0, st, S, q, n, cost, grad);
-        else hipLaunchKernelGGL((k_planar_cost<G, A, W, true, false>), g, b, 0, st, S, q, n, cost, grad);
-    } else {
-        if (grad) hipLaunchKernelGGL((k_planar_cost<G, A, W, false, true>), g, b, 0, st, S, q, n, cost, grad);
-        else hipLaunchKernelGGL((k_planar_cost<G, A, W, false, false>), g, b, 0, st, S, q, n, cost, grad);
-    }
-}
-
 // (grid, analytic, workspace) -> the compiled variant: f.go<G, A, W>()
 template <class F>
 void dispatch3(bool g, bool a, bool w, F&& f) {
@@ -533,10 +489,20 @@ void dispatch3(bool g, bool a, bool w, F&& f) {
     }
 }
 
-// the three launchers behind dispatch3: one struct per entry point, go<G, A, W>() starts that variant
+// two more run-time switches under a variant: f.launch<G, A, W, X, Y>()
+template <bool G, bool A, bool W, class F>
+void dispatch2(bool x, bool y, F& f) {
+    if (x) { if (y) f.template launch<G, A, W, true, true>(); else f.template launch<G, A, W, true, false>(); }
+    else { if (y) f.template launch<G, A, W, false, true>(); else f.template launch<G, A, W, false, false>(); }
+}
+
+// the launchers behind dispatch3: go<G, A, W>() starts that variant
 struct CostGo {
     const P2Hdr& S; const float2* q; int64_t n; bool clamp; float* cost; float2* grad; hipStream_t st;
-    template <bool G, bool A, bool W> void go() { launch_cost3<G, A, W>(S, q, n, clamp, cost, grad, st); }
+    template <bool G, bool A, bool W, bool C, bool GR> void launch() {
+        hipLaunchKernelGGL((k_planar_cost<G, A, W, C, GR>), dim3(blocks_for(n)), dim3(256), 0, st, S, q, n, cost, grad);
+    }
+    template <bool G, bool A, bool W> void go() { dispatch2<G, A, W>(clamp, grad != nullptr, *this); }
 };
 struct CollGo {
     const P2Hdr& S; const float2* q; int64_t n; float m; uint8_t* out; hipStream_t st;
@@ -550,44 +516,25 @@ struct ViaGo {
         hipLaunchKernelGGL((k_planar_collision_via<G, A, W>), dim3(blocks_for(total)), dim3(256), 0, st, S, x, total, H, SD, ni, al, be, m, out);
     }
 };
-
 struct TrajCostGo {
     const P2Hdr& S; const TrajPar& P; const float2* q; const float2* qd; int64_t n; int H; bool clamp; float* cost; float2* gq; float2* gqd;
     hipStream_t st;
     template <bool G, bool A, bool W, bool C, bool GR> void launch() {
         hipLaunchKernelGGL((k_planar_traj_cost<G, A, W, C, GR>), dim3(blocks_for(n)), dim3(256), 0, st, S, P, q, qd, n, H, cost, gq, gqd);
     }
-    template <bool G, bool A, bool W> void go() {
-        if (clamp) { if (gq) launch<G, A, W, true, true>(); else launch<G, A, W, true, false>(); }
-        else { if (gq) launch<G, A, W, false, true>(); else launch<G, A, W, false, false>(); }
-    }
+    template <bool G, bool A, bool W> void go() { dispatch2<G, A, W>(clamp, gq != nullptr, *this); }
 };
-struct TrajAdamGo {
-    const P2Hdr& S; const TrajPar& P; const AdamPar& Ad; float2* q; float2* qd; float4* m; float4* v; int64_t B; int H; bool clamp, wave;
-    float* cost; hipStream_t st;
-    template <bool G, bool A, bool W, bool C, bool WV> void launch() {
-        const int per_wg = WV ? 4 : 256 / H;
-        hipLaunchKernelGGL((k_planar_traj_adam<G, A, W, C, WV>), dim3((unsigned)((B + per_wg - 1) / per_wg)), dim3(256), 0, st, S, P, Ad,
-                           q, qd, m, v, B, H, cost);
-    }
-    template <bool G, bool A, bool W> void go() {
-        if (clamp) { if (wave) launch<G, A, W, true, true>(); else launch<G, A, W, true, false>(); }
-        else { if (wave) launch<G, A, W, false, true>(); else launch<G, A, W, false, false>(); }
-    }
-};
-
-struct TrajViaGo {
-    const P2Hdr& S; const TrajPar& P; const ViaPar& V; const AdamPar& Ad; float2* q; float2* qd; float4* m; float4* v; int64_t B; int H;
+// the two loop kernels: k_planar_traj_via where there is a via term (V), k_planar_traj_adam otherwise; a workgroup owns per_wg trajectories
+struct TrajLoopGo {
+    const P2Hdr& S; const TrajPar& P; const ViaPar* V; const AdamPar& Ad; float2* q; float2* qd; float4* m; float4* v; int64_t B; int H;
     bool clamp, wave; float* cost; float2* gq; float2* gqd; hipStream_t st;
     template <bool G, bool A, bool W, bool C, bool WV> void launch() {
         const int per_wg = WV ? 4 : 256 / H;
-        hipLaunchKernelGGL((k_planar_traj_via<G, A, W, C, WV>), dim3((unsigned)((B + per_wg - 1) / per_wg)), dim3(256), 0, st, S, P, V, Ad,
-                           q, qd, m, v, B, H, cost, gq, gqd);
+        const dim3 g((unsigned)((B + per_wg - 1) / per_wg)), b(256);
+        if (V) hipLaunchKernelGGL((k_planar_traj_via<G, A, W, C, WV>), g, b, 0, st, S, P, *V, Ad, q, qd, m, v, B, H, cost, gq, gqd);
+        else hipLaunchKernelGGL((k_planar_traj_adam<G, A, W, C, WV>), g, b, 0, st, S, P, Ad, q, qd, m, v, B, H, cost);
     }
-    template <bool G, bool A, bool W> void go() {
-        if (clamp) { if (wave) launch<G, A, W, true, true>(); else launch<G, A, W, true, false>(); }
-        else { if (wave) launch<G, A, W, false, true>(); else launch<G, A, W, false, false>(); }
-    }
+    template <bool G, bool A, bool W> void go() { dispatch2<G, A, W>(clamp, wave, *this); }
 };
 
 }  // namespace
@@ -698,6 +645,17 @@ void trk_scene2d_destroy(TrkScene2D* s) {
 }
 
 static bool aligned_to(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+// the tail of every entry: what the launch of `kernel` left behind
+static int launched(const char* kernel) {
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? TRK_OK : trk_hip_fail((int)e, kernel);
+}
+// "<entry>: <what>" as the error text
+static int fail_for(int code, const char* who, const char* what) {
+    static thread_local char msg[256];
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return trk_fail(code, msg);
+}
 
 int trk_scene2d_cost_grad(const TrkScene2D* s, const float* q, int64_t n, int32_t clamp, float* cost, float* grad, trk_stream_t stream) {
     if (!s || n < 0 || (n > 0 && (!q || !cost))) return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_cost_grad: bad argument");
@@ -706,8 +664,7 @@ int trk_scene2d_cost_grad(const TrkScene2D* s, const float* q, int64_t n, int32_
     if (n == 0) return TRK_OK;
     CostGo f{s->hdr, (const float2*)q, n, clamp != 0, cost, (float2*)grad, (hipStream_t)stream};
     dispatch3(s->hdr.has_grid != 0, s->hdr.n_objects > 0, s->has_ws != 0, f);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? TRK_OK : trk_hip_fail((int)e, "k_planar_cost");
+    return launched("k_planar_cost");
 }
 
 int trk_scene2d_collision(const TrkScene2D* s, const float* q, int64_t n, float margin_override, uint8_t* out, trk_stream_t stream) {
@@ -717,8 +674,7 @@ int trk_scene2d_collision(const TrkScene2D* s, const float* q, int64_t n, float 
     const float m = std::isnan(margin_override) ? s->hdr.margin : margin_override;
     CollGo f{s->hdr, (const float2*)q, n, m, out, (hipStream_t)stream};
     dispatch3(s->hdr.has_grid != 0, s->hdr.n_objects > 0, s->has_ws != 0, f);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? TRK_OK : trk_hip_fail((int)e, "k_planar_collision");
+    return launched("k_planar_collision");
 }
 
 int trk_scene2d_collision_via(const TrkScene2D* s, const float* x, int64_t n_traj, int32_t horizon, int32_t state_dim, int32_t n_interp,
@@ -732,8 +688,7 @@ int trk_scene2d_collision_via(const TrkScene2D* s, const float* x, int64_t n_tra
     const int64_t total = n_traj * (int64_t)(horizon - 1) * n_interp;
     ViaGo f{s->hdr, x, total, horizon, state_dim, n_interp, alpha, beta, m, out, (hipStream_t)stream};
     dispatch3(s->hdr.has_grid != 0, s->hdr.n_objects > 0, s->has_ws != 0, f);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? TRK_OK : trk_hip_fail((int)e, "k_planar_collision_via");
+    return launched("k_planar_collision_via");
 }
 
 int trk_grid2d_precompute(const TrkScene2D* s, const int32_t dims[2], const float lim_min[2], const float lim_max[2], float* cells,
@@ -746,8 +701,7 @@ int trk_grid2d_precompute(const TrkScene2D* s, const int32_t dims[2], const floa
     const int64_t total = (int64_t)dims[0] * dims[1];
     hipLaunchKernelGGL(k_grid2d_precompute, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, s->hdr, dims[0], dims[1],
                        lim_min[0], lim_min[1], lim_max[0], lim_max[1], (float4*)cells);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? TRK_OK : trk_hip_fail((int)e, "k_grid2d_precompute");
+    return launched("k_grid2d_precompute");
 }
 
 int trk_scene2d_sdf_points(const TrkScene2D* s, const float* points, int64_t n, float* sdf, float* grad, trk_stream_t stream) {
@@ -757,26 +711,84 @@ int trk_scene2d_sdf_points(const TrkScene2D* s, const float* points, int64_t n, 
     if (n == 0 || s->n_df == 0) return TRK_OK;
     hipLaunchKernelGGL(k_planar_sdf_points, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, s->hdr, (const float2*)points, n,
                        s->n_df, sdf, (float2*)grad);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? TRK_OK : trk_hip_fail((int)e, "k_planar_sdf_points");
+    return launched("k_planar_sdf_points");
 }
 
-// What both trajectory entry points ask of their common arguments, before anything is dereferenced or launched; fills P.
+// What the trajectory entry points ask of their common arguments, before anything is dereferenced or launched; fills P.
 static int check_traj_call(const char* who, const TrkScene2D* s, const TrkPlanarObjective* o, int64_t batch, int32_t horizon, TrajPar& P) {
-    static thread_local char msg[160];
     const char* bad = nullptr;
     if (!s || !o) bad = "null scene / objective";
     else if (batch < 0 || horizon < 1) bad = "batch must be >= 0 and horizon >= 1";
     else if (!(o->gp.dt > 0.0f) || !std::isfinite(o->gp.dt) || !(o->gp.sigma > 0.0f) || !std::isfinite(o->gp.sigma))
         bad = "the prior needs finite dt > 0 and sigma > 0";
     else if (!std::isfinite(o->w_obj) || !std::isfinite(o->gp.weight)) bad = "w_obj and gp.weight must be finite";
-    if (bad) { snprintf(msg, sizeof(msg), "%s: %s", who, bad); return trk_fail(TRK_ERR_INVALID_ARG, msg); }
-    if (batch > 0x7fffffff || (batch * (int64_t)horizon + 255) / 256 > 0x7fffffff) {
-        snprintf(msg, sizeof(msg), "%s: batch x horizon too large", who);
-        return trk_fail(TRK_ERR_UNSUPPORTED, msg);
-    }
+    if (bad) return fail_for(TRK_ERR_INVALID_ARG, who, bad);
+    if (batch > 0x7fffffff || (batch * (int64_t)horizon + 255) / 256 > 0x7fffffff)
+        return fail_for(TRK_ERR_UNSUPPORTED, who, "batch x horizon too large");
     const float dt = o->gp.dt, s2 = 1.0f / (o->gp.sigma * o->gp.sigma);               // as trk_launch_gp_prior forms them
     P = TrajPar{o->w_obj, dt, 12.0f * s2 / (dt * dt * dt), -6.0f * s2 / (dt * dt), 4.0f * s2 / dt, o->gp.weight};
+    return TRK_OK;
+}
+
+// What both via entry points ask on top of check_traj_call, before anything is dereferenced or launched; fills P and V.
+static int check_via_call(const char* who, const TrkScene2D* s, const TrkPlanarViaObjective* o, int64_t batch, int32_t horizon, TrajPar& P,
+                          ViaPar& V) {
+    if (!o) return fail_for(TRK_ERR_INVALID_ARG, who, "null TrkPlanarViaObjective");
+    int rc = check_traj_call(who, s, &o->base, batch, horizon, P);
+    if (rc) return rc;
+    if (!std::isfinite(o->w_via) || o->n_interp < 1 || !o->alpha || !o->beta)
+        return fail_for(TRK_ERR_INVALID_ARG, who, "w_via must be finite, n_interp >= 1 and alpha, beta device arrays of n_interp weights");
+    if (horizon > TRK_PLANAR_MAX_HORIZON)
+        return fail_for(TRK_ERR_UNSUPPORTED, who, "horizon above TRK_PLANAR_MAX_HORIZON (256): a workgroup owns whole trajectories");
+    V = ViaPar{o->w_via, o->n_interp, o->alpha, o->beta};
+    return TRK_OK;
+}
+
+// The two checks of the loop entries.  Each entry places them among its other checks itself: the via entry looks at the TrkPlanarAdam
+// before check_via_call, the plain one after check_traj_call (and at its horizon limit last) -- the order a caller sees.
+static int check_planar_adam(const char* who, const TrkPlanarAdam* ad) {
+    if (!ad) return fail_for(TRK_ERR_INVALID_ARG, who, "null TrkPlanarAdam");
+    if (ad->n_steps < 0 || ad->first_step < 1 || !std::isfinite(ad->lr) || ad->pin < 0 || ad->pin > 15)
+        return fail_for(TRK_ERR_INVALID_ARG, who, "n_steps >= 0, first_step >= 1, lr finite and pin in 0 .. 15");
+    return TRK_OK;
+}
+static bool planar_adam_updates(const TrkPlanarAdam* ad) { return ad->lr != 0.0f && ad->n_steps > 0; }
+// the state buffers: adam_m, adam_v may be null where nothing is updated
+static int check_state_buffers(const char* who, const TrkPlanarAdam* ad, const float* q, const float* qd, const float* adam_m,
+                               const float* adam_v, int64_t batch) {
+    if (batch > 0 && (!q || !qd || (planar_adam_updates(ad) && (!adam_m || !adam_v))))
+        return fail_for(TRK_ERR_INVALID_ARG, who, "null q / qd / adam_m / adam_v");
+    if (!aligned_to(q, 8) || !aligned_to(qd, 8) || !aligned_to(adam_m, 16) || !aligned_to(adam_v, 16))
+        return fail_for(TRK_ERR_INVALID_ARG, who, "q, qd must be 8-byte and adam_m, adam_v 16-byte aligned");
+    return TRK_OK;
+}
+
+// H == 64: a wavefront is a trajectory and the neighbours come by DPP; TRK_PLANAR_ADAM_LDS64=1 runs the LDS form there too
+// (the same arithmetic, for measuring one exchange against the other)
+static bool wave_form(int32_t horizon) {
+    static const bool lds64 = [] { const char* v = getenv("TRK_PLANAR_ADAM_LDS64"); return v && v[0] == '1'; }();
+    return horizon == 64 && !lds64;
+}
+
+// The launches of a call to one of the three loop entries (V: the via term, or null for the plain loop): at most PLANAR_ADAM_MAX_STEPS
+// iterations each, with their slice of the bias-correction schedule; cost (and gq, gqd) come from the first launch, the state as the
+// caller passed it.  Without an update it is one evaluation.
+static int run_traj_loop(const TrkScene2D* s, const TrajPar& P, const ViaPar* V, bool clamp, const TrkPlanarAdam& ad, float* q, float* qd,
+                         float* adam_m, float* adam_v, int64_t batch, int32_t horizon, float* cost, float* gq, float* gqd,
+                         trk_stream_t stream) {
+    const bool update = planar_adam_updates(&ad);
+    const int32_t total = update ? ad.n_steps : 1;
+    for (int32_t done = 0; done < total; done += PLANAR_ADAM_MAX_STEPS) {
+        AdamPar A{};
+        A.lr = ad.lr; A.pin = ad.pin; A.update = update ? 1 : 0;
+        A.n_steps = std::min<int32_t>(PLANAR_ADAM_MAX_STEPS, total - done);
+        trk_adam_bias_schedule(A.bc1, A.rsqrt_bc2, (int64_t)ad.first_step + done, A.n_steps);
+        const bool first = done == 0;
+        TrajLoopGo f{s->hdr, P, V, A, (float2*)q, (float2*)qd, (float4*)adam_m, (float4*)adam_v, batch, horizon, clamp, wave_form(horizon),
+                     first ? cost : nullptr, (float2*)(first ? gq : nullptr), (float2*)(first ? gqd : nullptr), (hipStream_t)stream};
+        dispatch3(s->hdr.has_grid != 0, s->hdr.n_objects > 0, s->has_ws != 0, f);
+        if (int rc = launched(V ? "k_planar_traj_via" : "k_planar_traj_adam")) return rc;
+    }
     return TRK_OK;
 }
 
@@ -794,8 +806,7 @@ int trk_scene2d_traj_cost_grad(const TrkScene2D* s, const TrkPlanarObjective* o,
     TrajCostGo f{s->hdr, P, (const float2*)q, (const float2*)qd, batch * horizon, horizon, o->clamp != 0, cost, (float2*)gq, (float2*)gqd,
                  (hipStream_t)stream};
     dispatch3(s->hdr.has_grid != 0, s->hdr.n_objects > 0, s->has_ws != 0, f);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? TRK_OK : trk_hip_fail((int)e, "k_planar_traj_cost");
+    return launched("k_planar_traj_cost");
 }
 
 int trk_scene2d_traj_adam_steps(const TrkScene2D* s, const TrkPlanarObjective* o, const TrkPlanarAdam* ad, float* q, float* qd,
@@ -803,65 +814,14 @@ int trk_scene2d_traj_adam_steps(const TrkScene2D* s, const TrkPlanarObjective* o
     const char* who = "trk_scene2d_traj_adam_steps";
     TrajPar P;
     int rc = check_traj_call(who, s, o, batch, horizon, P);
+    if (!rc) rc = check_planar_adam(who, ad);
+    if (!rc) rc = check_state_buffers(who, ad, q, qd, adam_m, adam_v, batch);
     if (rc) return rc;
-    if (!ad) return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_adam_steps: null TrkPlanarAdam");
-    if (ad->n_steps < 0 || ad->first_step < 1 || !std::isfinite(ad->lr) || ad->pin < 0 || ad->pin > 15)
-        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_adam_steps: n_steps >= 0, first_step >= 1, lr finite and pin in 0 .. 15");
-    const bool update = ad->lr != 0.0f && ad->n_steps > 0;
-    if (batch > 0 && (!q || !qd || (update && (!adam_m || !adam_v))))
-        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_adam_steps: null q / qd / adam_m / adam_v");
-    if (!aligned_to(q, 8) || !aligned_to(qd, 8) || !aligned_to(adam_m, 16) || !aligned_to(adam_v, 16))
-        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_adam_steps: q, qd must be 8-byte and adam_m, adam_v 16-byte aligned");
     if (horizon > TRK_PLANAR_MAX_HORIZON)
         return trk_fail(TRK_ERR_UNSUPPORTED, "trk_scene2d_traj_adam_steps: horizon above TRK_PLANAR_MAX_HORIZON (256): a workgroup owns "
                                              "whole trajectories; trk_scene2d_traj_cost_grad serves any horizon");
-    if (batch == 0 || (!update && !cost)) return TRK_OK;
-    // H == 64: a wavefront is a trajectory and the neighbours come by DPP; TRK_PLANAR_ADAM_LDS64=1 runs the LDS form there too
-    // (the same arithmetic, for measuring one exchange against the other)
-    static const bool lds64 = [] { const char* v = getenv("TRK_PLANAR_ADAM_LDS64"); return v && v[0] == '1'; }();
-    // at most PLANAR_ADAM_MAX_STEPS iterations per launch; the cost comes from the first launch (the state as the caller passed it)
-    const int32_t total = update ? ad->n_steps : 1;
-    for (int32_t done = 0; done < total; done += PLANAR_ADAM_MAX_STEPS) {
-        AdamPar A{};
-        A.lr = ad->lr; A.pin = ad->pin; A.update = update ? 1 : 0;
-        A.n_steps = std::min<int32_t>(PLANAR_ADAM_MAX_STEPS, total - done);
-        for (int32_t i = 0; i < A.n_steps; ++i) {
-            const double k = (double)ad->first_step + (double)done + (double)i;
-            A.bc1[i] = (float)(1.0 - std::pow(0.9, k));
-            A.rsqrt_bc2[i] = (float)(1.0 / std::sqrt(1.0 - std::pow(0.999, k)));
-        }
-        TrajAdamGo f{s->hdr, P, A, (float2*)q, (float2*)qd, (float4*)adam_m, (float4*)adam_v, batch, horizon, o->clamp != 0,
-                     horizon == 64 && !lds64, done == 0 ? cost : nullptr, (hipStream_t)stream};
-        dispatch3(s->hdr.has_grid != 0, s->hdr.n_objects > 0, s->has_ws != 0, f);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return trk_hip_fail((int)e, "k_planar_traj_adam");
-    }
-    return TRK_OK;
-}
-
-// What both via entry points ask on top of check_traj_call, before anything is dereferenced or launched; fills P and V.
-static int check_via_call(const char* who, const TrkScene2D* s, const TrkPlanarViaObjective* o, int64_t batch, int32_t horizon, TrajPar& P,
-                          ViaPar& V) {
-    static thread_local char msg[200];
-    if (!o) { snprintf(msg, sizeof(msg), "%s: null TrkPlanarViaObjective", who); return trk_fail(TRK_ERR_INVALID_ARG, msg); }
-    int rc = check_traj_call(who, s, &o->base, batch, horizon, P);
-    if (rc) return rc;
-    if (!std::isfinite(o->w_via) || o->n_interp < 1 || !o->alpha || !o->beta) {
-        snprintf(msg, sizeof(msg), "%s: w_via must be finite, n_interp >= 1 and alpha, beta device arrays of n_interp weights", who);
-        return trk_fail(TRK_ERR_INVALID_ARG, msg);
-    }
-    if (horizon > TRK_PLANAR_MAX_HORIZON) {
-        snprintf(msg, sizeof(msg), "%s: horizon above TRK_PLANAR_MAX_HORIZON (256): a workgroup owns whole trajectories", who);
-        return trk_fail(TRK_ERR_UNSUPPORTED, msg);
-    }
-    V = ViaPar{o->w_via, o->n_interp, o->alpha, o->beta};
-    return TRK_OK;
-}
-
-// H == 64 runs the WAVE form; TRK_PLANAR_ADAM_LDS64=1 runs the LDS form there too, as in trk_scene2d_traj_adam_steps
-static bool via_wave_form(int32_t horizon) {
-    static const bool lds64 = [] { const char* v = getenv("TRK_PLANAR_ADAM_LDS64"); return v && v[0] == '1'; }();
-    return horizon == 64 && !lds64;
+    if (batch == 0 || (!planar_adam_updates(ad) && !cost)) return TRK_OK;
+    return run_traj_loop(s, P, nullptr, o->clamp != 0, *ad, q, qd, adam_m, adam_v, batch, horizon, cost, nullptr, nullptr, stream);
 }
 
 int trk_scene2d_traj_via_cost_grad(const TrkScene2D* s, const TrkPlanarViaObjective* o, const float* q, const float* qd, int64_t batch,
@@ -876,13 +836,10 @@ int trk_scene2d_traj_via_cost_grad(const TrkScene2D* s, const TrkPlanarViaObject
     if (!aligned_to(q, 8) || !aligned_to(qd, 8) || !aligned_to(gq, 8) || !aligned_to(gqd, 8))
         return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_via_cost_grad: q, qd, gq and gqd must be 8-byte aligned (one float2 per sample)");
     if (batch == 0) return TRK_OK;
-    AdamPar A{};                                        // one evaluation: update == 0, nothing but cost, gq and gqd is written
-    A.n_steps = 1;
-    TrajViaGo f{s->hdr, P, V, A, (float2*)q, (float2*)qd, nullptr, nullptr, batch, horizon, o->base.clamp != 0, via_wave_form(horizon),
-                cost, (float2*)gq, (float2*)gqd, (hipStream_t)stream};
-    dispatch3(s->hdr.has_grid != 0, s->hdr.n_objects > 0, s->has_ws != 0, f);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? TRK_OK : trk_hip_fail((int)e, "k_planar_traj_via");
+    // one evaluation: no update, nothing but cost, gq and gqd is written (q, qd are read only)
+    const TrkPlanarAdam once{0.0f, 0, 1, 1};
+    return run_traj_loop(s, P, &V, o->base.clamp != 0, once, const_cast<float*>(q), const_cast<float*>(qd), nullptr, nullptr, batch, horizon,
+                         cost, gq, gqd, stream);
 }
 
 int trk_scene2d_traj_via_adam_steps(const TrkScene2D* s, const TrkPlanarViaObjective* o, const TrkPlanarAdam* ad, float* q, float* qd,
@@ -890,35 +847,12 @@ int trk_scene2d_traj_via_adam_steps(const TrkScene2D* s, const TrkPlanarViaObjec
     const char* who = "trk_scene2d_traj_via_adam_steps";
     TrajPar P;
     ViaPar V;
-    if (!ad) return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_via_adam_steps: null TrkPlanarAdam");
-    if (ad->n_steps < 0 || ad->first_step < 1 || !std::isfinite(ad->lr) || ad->pin < 0 || ad->pin > 15)
-        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_via_adam_steps: n_steps >= 0, first_step >= 1, lr finite and pin in 0 .. 15");
-    int rc = check_via_call(who, s, o, batch, horizon, P, V);
+    int rc = check_planar_adam(who, ad);
+    if (!rc) rc = check_via_call(who, s, o, batch, horizon, P, V);
+    if (!rc) rc = check_state_buffers(who, ad, q, qd, adam_m, adam_v, batch);
     if (rc) return rc;
-    const bool update = ad->lr != 0.0f && ad->n_steps > 0;
-    if (batch > 0 && (!q || !qd || (update && (!adam_m || !adam_v))))
-        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_via_adam_steps: null q / qd / adam_m / adam_v");
-    if (!aligned_to(q, 8) || !aligned_to(qd, 8) || !aligned_to(adam_m, 16) || !aligned_to(adam_v, 16))
-        return trk_fail(TRK_ERR_INVALID_ARG, "trk_scene2d_traj_via_adam_steps: q, qd must be 8-byte and adam_m, adam_v 16-byte aligned");
-    if (batch == 0 || (!update && !cost)) return TRK_OK;
-    // at most PLANAR_ADAM_MAX_STEPS iterations per launch; the cost comes from the first launch (the state as the caller passed it)
-    const int32_t total = update ? ad->n_steps : 1;
-    for (int32_t done = 0; done < total; done += PLANAR_ADAM_MAX_STEPS) {
-        AdamPar A{};
-        A.lr = ad->lr; A.pin = ad->pin; A.update = update ? 1 : 0;
-        A.n_steps = std::min<int32_t>(PLANAR_ADAM_MAX_STEPS, total - done);
-        for (int32_t i = 0; i < A.n_steps; ++i) {
-            const double k = (double)ad->first_step + (double)done + (double)i;
-            A.bc1[i] = (float)(1.0 - std::pow(0.9, k));
-            A.rsqrt_bc2[i] = (float)(1.0 / std::sqrt(1.0 - std::pow(0.999, k)));
-        }
-        TrajViaGo f{s->hdr, P, V, A, (float2*)q, (float2*)qd, (float4*)adam_m, (float4*)adam_v, batch, horizon, o->base.clamp != 0,
-                    via_wave_form(horizon), done == 0 ? cost : nullptr, nullptr, nullptr, (hipStream_t)stream};
-        dispatch3(s->hdr.has_grid != 0, s->hdr.n_objects > 0, s->has_ws != 0, f);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return trk_hip_fail((int)e, "k_planar_traj_via");
-    }
-    return TRK_OK;
+    if (batch == 0 || (!planar_adam_updates(ad) && !cost)) return TRK_OK;
+    return run_traj_loop(s, P, &V, o->base.clamp != 0, *ad, q, qd, adam_m, adam_v, batch, horizon, cost, nullptr, nullptr, stream);
 }
 
 }  // extern "C"

@@ -1643,19 +1643,23 @@ def _planar_objective(dt, sigma, gp_weight, w_obj, clamp) -> "_abi.PlanarObjecti
     return _abi.PlanarObjective(float(w_obj), int(bool(clamp)), _abi.GpPrior(float(dt), float(sigma), float(gp_weight)))
 
 
+def _planar_traj_eval(fn, scene, obj, q, qd, B, H, want_grad):
+    """one evaluation by trk_scene2d_traj_cost_grad or its via sibling `fn`: allocates the outputs, launches -> (cost, gq, gqd)"""
+    cost = torch.empty((B, H), device=q.device, dtype=torch.float32)
+    gq, gqd = (torch.empty_like(q), torch.empty_like(q)) if want_grad else (None, None)
+    with _on(q.device):
+        check(fn(scene._h, C.byref(obj), q.data_ptr(), qd.data_ptr(), B, H, cost.data_ptr(), _ptr(gq), _ptr(gqd), _stream(q)), fn.__name__)
+    return cost, gq, gqd
+
+
 def planar_traj_cost_grad(scene: Scene2DHandle, q: torch.Tensor, qd: torch.Tensor, dt: float, sigma: float, gp_weight: float = 1.0,
                           w_obj: float = 1.0, clamp: bool = False, want_grad: bool = True):
     """The 2-D point mass's trajectory objective in one launch (include/trk.h: trk_scene2d_traj_cost_grad): w_obj x planar_cost_grad's
     hinge + the constant-velocity GP prior on q, qd (B,H,2) -> (cost (B,H) with the prior's factor t -> t+1 at sample t, gq, gqd),
     the gradients None without want_grad."""
     B, H = _planar_traj_args(q, qd, "planar_traj_cost_grad")
-    obj = _planar_objective(dt, sigma, gp_weight, w_obj, clamp)
-    cost = torch.empty((B, H), device=q.device, dtype=torch.float32)
-    gq, gqd = (torch.empty_like(q), torch.empty_like(q)) if want_grad else (None, None)
-    with _on(q.device):
-        check(lib().trk_scene2d_traj_cost_grad(scene._h, C.byref(obj), q.data_ptr(), qd.data_ptr(), B, H, cost.data_ptr(), _ptr(gq), _ptr(gqd),
-                                               _stream(q)), "trk_scene2d_traj_cost_grad")
-    return cost, gq, gqd
+    return _planar_traj_eval(lib().trk_scene2d_traj_cost_grad, scene, _planar_objective(dt, sigma, gp_weight, w_obj, clamp), q, qd,
+                             B, H, want_grad)
 
 
 def _planar_via_objective(dt, sigma, gp_weight, w_obj, clamp, w_via, num_interpolation, device):
@@ -1675,12 +1679,7 @@ def planar_traj_via_cost_grad(scene: Scene2DHandle, q: torch.Tensor, qd: torch.T
     (cost (B,H) with the segment t -> t+1 at sample t, gq, gqd), the gradients None without want_grad."""
     B, H = _planar_traj_args(q, qd, "planar_traj_via_cost_grad")
     obj, _keep = _planar_via_objective(dt, sigma, gp_weight, w_obj, clamp, w_via, num_interpolation, q.device)
-    cost = torch.empty((B, H), device=q.device, dtype=torch.float32)
-    gq, gqd = (torch.empty_like(q), torch.empty_like(q)) if want_grad else (None, None)
-    with _on(q.device):
-        check(lib().trk_scene2d_traj_via_cost_grad(scene._h, C.byref(obj), q.data_ptr(), qd.data_ptr(), B, H, cost.data_ptr(), _ptr(gq),
-                                                   _ptr(gqd), _stream(q)), "trk_scene2d_traj_via_cost_grad")
-    return cost, gq, gqd
+    return _planar_traj_eval(lib().trk_scene2d_traj_via_cost_grad, scene, obj, q, qd, B, H, want_grad)
 
 
 def planar_adam_bias_terms(step: int):
@@ -1689,7 +1688,35 @@ def planar_adam_bias_terms(step: int):
     return float(np.float32(1.0 - 0.9 ** float(step))), float(np.float32(1.0 / np.sqrt(1.0 - 0.999 ** float(step))))
 
 
-class PlanarAdamPlan(_Plan):
+class _AdamLoopPlan(_Plan):
+    """What PlanarAdamPlan and ArmAdamPlan share: the state the plan owns, the pin mask, the rule that binds the via loop, and step().
+    A subclass checks its own arguments, calls _own_state with its state width and TrkPlanarAdam / TrkTrajAdam, and binds in _bind."""
+
+    def _own_state(self, q, qd, B, H, width, adam_struct, lr, pins, w_via, num_interpolation) -> None:
+        self.q, self.qd, self.device, self.B, self.H = q, qd, q.device, B, H
+        self.m = torch.zeros((B, H, width), device=q.device, dtype=torch.float32)
+        self.v = torch.zeros((B, H, width), device=q.device, dtype=torch.float32)
+        self.cost = torch.empty((B, H), device=q.device, dtype=torch.float32)
+        self.t = 0                              # iterations done
+        self.pin = sum(bit * bool(on) for bit, on in zip((1, 2, 4, 8), pins))       # start, goal, start velocity, goal velocity
+        self._adam = adam_struct(float(lr), self.pin, 1, 0)
+        self.w_via, self.num_interpolation = float(w_via), int(num_interpolation)
+
+    def _via_on(self) -> bool:
+        return self.num_interpolation > 0 and self.w_via != 0.0
+
+    def step(self, n: int = 1, stream: Optional[int] = None) -> torch.Tensor:
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"{type(self).__name__}.step: n must be >= 0")
+        self._adam.first_step, self._adam.n_steps = self.t + 1, n
+        self._launch(stream)
+        if self._adam.lr != 0.0:
+            self.t += n
+        return self.cost
+
+
+class PlanarAdamPlan(_AdamLoopPlan):
     """Adam on planar_traj_cost_grad's objective with the trajectories and the optimiser's state on the chip (include/trk.h:
     trk_scene2d_traj_adam_steps).  Pre-bound: `step(n)` runs the next n iterations on the caller's q, qd (B,H,2) IN PLACE -- one
     launch per 32 iterations -- and returns the (B,H) cost of the state it started from.  The plan owns `m`, `v` (B,H,4) and the
@@ -1704,16 +1731,9 @@ class PlanarAdamPlan(_Plan):
         if H > _abi.TRK_PLANAR_MAX_HORIZON:
             raise NotImplementedError(f"PlanarAdamPlan: horizon {H} is above the {_abi.TRK_PLANAR_MAX_HORIZON} samples a workgroup of the "
                                       f"persistent kernel holds (planar_traj_cost_grad serves any horizon)")
-        self.scene, self.q, self.qd, self.device, self.B, self.H = scene, q, qd, q.device, B, H
-        self.m = torch.zeros((B, H, 4), device=q.device, dtype=torch.float32)
-        self.v = torch.zeros((B, H, 4), device=q.device, dtype=torch.float32)
-        self.cost = torch.empty((B, H), device=q.device, dtype=torch.float32)
-        self.t = 0                              # iterations done
-        self.pin = 1 * bool(pin_start) | 2 * bool(pin_goal) | 4 * bool(pin_start_vel) | 8 * bool(pin_goal_vel)
-        self._objective = (dt, sigma, gp_weight, w_obj, clamp)
-        self.w_via, self.num_interpolation = float(w_via), int(num_interpolation)
-        self._adam = _abi.PlanarAdam(float(lr), self.pin, 1, 0)
-        self._bind(via=self.num_interpolation > 0 and self.w_via != 0.0)
+        self._own_state(q, qd, B, H, 4, _abi.PlanarAdam, lr, (pin_start, pin_goal, pin_start_vel, pin_goal_vel), w_via, num_interpolation)
+        self.scene, self._objective = scene, (dt, sigma, gp_weight, w_obj, clamp)
+        self._bind(via=self._via_on())
 
     def _bind(self, via: bool) -> None:
         """the entry point and its arguments: the via loop only where the via term is on, otherwise exactly the plain loop"""
@@ -1726,18 +1746,8 @@ class PlanarAdamPlan(_Plan):
         self._args = (self.scene._h, C.byref(self._obj), C.byref(self._adam), self.q.data_ptr(), self.qd.data_ptr(), self.m.data_ptr(),
                       self.v.data_ptr(), self.B, self.H, self.cost.data_ptr())
 
-    def step(self, n: int = 1, stream: Optional[int] = None) -> torch.Tensor:
-        n = int(n)
-        if n < 0:
-            raise ValueError("PlanarAdamPlan.step: n must be >= 0")
-        self._adam.first_step, self._adam.n_steps = self.t + 1, n
-        self._launch(stream)
-        if self._adam.lr != 0.0:
-            self.t += n
-        return self.cost
 
-
-class ArmAdamPlan(_Plan):
+class ArmAdamPlan(_AdamLoopPlan):
     """Adam on RolloutGpPlan's objective with the trajectories and the optimiser's state on the chip (include/trk.h:
     trk_rollout_gp_adam_steps; generated kernel k_traj_adam, robots up to 8 DOF).  Pre-bound: `step(n)` runs the next n iterations on
     the caller's q, qd (B,H,D) fp32 IN PLACE -- one launch per 32 iterations -- and returns the (B,H) cost of the state it started
@@ -1756,17 +1766,11 @@ class ArmAdamPlan(_Plan):
         if H > _abi.TRK_TRAJ_ADAM_MAX_HORIZON or H & (H - 1):
             raise NotImplementedError(f"ArmAdamPlan: horizon {H} is not a power of two <= {_abi.TRK_TRAJ_ADAM_MAX_HORIZON} (a wavefront of the "
                                       f"planning-loop kernel owns whole trajectories; RolloutGpPlan serves any horizon)")
-        self.model, self.cm, self.q, self.qd, self.device, self.B, self.H = model, cm, q, qd, q.device, B, H
-        self.m = torch.zeros((B, H, 2 * D), device=q.device, dtype=torch.float32)
-        self.v = torch.zeros((B, H, 2 * D), device=q.device, dtype=torch.float32)
-        self.cost = torch.empty((B, H), device=q.device, dtype=torch.float32)
-        self.t = 0                              # iterations done
-        self.pin = 1 * bool(pin_start) | 2 * bool(pin_goal) | 4 * bool(pin_start_vel) | 8 * bool(pin_goal_vel)
+        self._own_state(q, qd, B, H, 2 * D, _abi.TrajAdam, lr, (pin_start, pin_goal, pin_start_vel, pin_goal_vel), w_via, num_interpolation)
+        self.model, self.cm = model, cm
         self._w = _weights_struct(weights)
         self._gp = _abi.GpPrior(float(dt), float(sigma), float(gp_weight))
-        self._adam = _abi.TrajAdam(float(lr), self.pin, 1, 0)
-        self.w_via, self.num_interpolation = float(w_via), int(num_interpolation)
-        self._bind(via=self.num_interpolation > 0 and self.w_via != 0.0)
+        self._bind(via=self._via_on())
 
     def _bind(self, via: bool) -> None:
         """the entry point and its arguments: the via loop only where the via term is on, otherwise exactly the plain loop"""
@@ -1783,16 +1787,6 @@ class ArmAdamPlan(_Plan):
         else:
             self._fn = lib().trk_rollout_gp_adam_steps
             self._args = head + tail
-
-    def step(self, n: int = 1, stream: Optional[int] = None) -> torch.Tensor:
-        n = int(n)
-        if n < 0:
-            raise ValueError("ArmAdamPlan.step: n must be >= 0")
-        self._adam.first_step, self._adam.n_steps = self.t + 1, n
-        self._launch(stream)
-        if self._adam.lr != 0.0:
-            self.t += n
-        return self.cost
 
 
 def reduce_sum(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
