@@ -1698,13 +1698,10 @@ def _posbwd_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     return E.lines
 
 
-def _coll_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
-    """k_coll_bi / _bg: boolean mode (trk_rollout_collision): FK + the OR of the selected fields' "signed distance < margin" tests, one
-    byte per sample out.  Its own kernel: inside k_rollout the extra SpecArgs fields and the cold path cost the hot path ~100 SGPR spill
-    moves (v_writelane / v_readlane) per wavefront."""
-    kin, L, D = u.kin, u.L, u.D
+def _boolean_kernel_head(name: str, occupancy: int) -> "Emitter":
+    """what _coll_kernel and _points_coll_kernel open with: the kernel's head, q (in via mode: interpolated here), the sphere table"""
     E = Emitter()
-    _kernel_head(E, "k_coll_bi" if base_identity else "k_coll_bg", 4 if D <= 8 else 2, "D", spheres=True)
+    _kernel_head(E, name, occupancy, "D", spheres=True)
     E.raw("    float q[D];")
     E.raw("    unsigned via_slot = 0u;")
     E.raw("    int64_t via_traj0 = 0;")
@@ -1712,15 +1709,29 @@ def _coll_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     E.raw("    if (A.via_n > 0) spec_load_q_via<D>(A, base, rows, lane, q, via_slot, via_traj0, via_outside);     // trajectory validation: interpolate the via points here")
     E.raw("    else spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
     E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
+    return E
+
+
+def _boolean_kernel_tail(E: "Emitter") -> List[str]:
+    """... and close with: `hit` as one byte per sample, plus the per-trajectory partial flags in via mode -> the kernel's lines"""
+    E.raw("    if (lane < rows) A.coll_out[base + lane] = hit ? 1 : 0;")
+    E.raw("    if (A.via_n > 0 && A.via_partial) spec_via_partial_flags(A, wblock, via_traj0, via_slot, hit, via_outside, lane < rows, lane);     // wave-uniform")
+    E.raw("}")
+    return E.lines
+
+
+def _coll_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
+    """k_coll_bi / _bg: boolean mode (trk_rollout_collision): FK + the OR of the selected fields' "signed distance < margin" tests, one
+    byte per sample out.  Its own kernel: inside k_rollout the extra SpecArgs fields and the cold path cost the hot path ~100 SGPR spill
+    moves (v_writelane / v_readlane) per wavefront."""
+    kin, L, D = u.kin, u.L, u.D
+    E = _boolean_kernel_head("k_coll_bi" if base_identity else "k_coll_bg", 4 if D <= 8 else 2)
     R, t, passv = _root_pose(base_identity)
     _emit_angles(E, kin)
     for p in range(1, L):
         _emit_fk_link(E, kin, int(kin.order[p]), R, t, passv, u.snap)
     _emit_boolean_fields(u, E, t)
-    E.raw("    if (lane < rows) A.coll_out[base + lane] = hit ? 1 : 0;")
-    E.raw("    if (A.via_n > 0 && A.via_partial) spec_via_partial_flags(A, wblock, via_traj0, via_slot, hit, via_outside, lane < rows, lane);     // wave-uniform")
-    E.raw("}")
-    return E.lines
+    return _boolean_kernel_tail(E)
 
 
 def _fkh_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
@@ -3320,21 +3331,12 @@ POINTS_COLL_OCCUPANCY = 4
 
 def _points_coll_kernel(u: _PointsUnit, base_identity: bool) -> List[str]:
     """k_pcoll_bi / k_pcoll_bg: boolean mode of an attached-point model (trk_rollout_points_collision, ..._via) -- the twin of
-    _points_rollout_kernel that k_coll is of k_rollout.  k_coll's head (q through the LDS transpose, or interpolated from the way
-    points in via mode), then the walk: a link's collision columns are scored against objects / workspace box in groups of at most
-    OBJ_GROUP as soon as the link's pose exists, a self pair at the link that owns its later column (the earlier column's position
-    is still a named value).  `hit` ORs every test; one byte per sample leaves, plus the per-trajectory partial flags in via mode.
-    No wrench, no staged positions, no position stores: a column that no test reads is never computed."""
+    _points_rollout_kernel that k_coll is of k_rollout.  k_coll's head and tail (_boolean_kernel_head, _boolean_kernel_tail) around
+    the walk: a link's collision columns are scored against objects / workspace box in groups of at most OBJ_GROUP as soon as the
+    link's pose exists, a self pair at the link that owns its later column (the earlier column's position is still a named value);
+    `hit` ORs every test.  No wrench, no staged positions, no position stores: a column that no test reads is never computed."""
     kin, L = u.kin, u.L
-    E = Emitter()
-    _kernel_head(E, "k_pcoll_bi" if base_identity else "k_pcoll_bg", POINTS_COLL_OCCUPANCY, "D", spheres=True)
-    E.raw("    float q[D];")
-    E.raw("    unsigned via_slot = 0u;")
-    E.raw("    int64_t via_traj0 = 0;")
-    E.raw("    bool via_outside = false;")
-    E.raw("    if (A.via_n > 0) spec_load_q_via<D>(A, base, rows, lane, q, via_slot, via_traj0, via_outside);     // trajectory validation: interpolate the via points here")
-    E.raw("    else spec_load_q<D>(static_cast<const float*>(A.q), base, rows, lane, lds, q);")
-    E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
+    E = _boolean_kernel_head("k_pcoll_bi" if base_identity else "k_pcoll_bg", POINTS_COLL_OCCUPANCY)
     w = _WrenchWalk(u, E, base_identity)          # for the pose tables and colpos (the column arithmetic of the cost rollout); no wrench is declared
     _emit_angles(E, kin)
     E.raw("    bool hit = false;")
@@ -3367,10 +3369,7 @@ def _points_coll_kernel(u: _PointsUnit, base_identity: bool) -> List[str]:
                 pb = ", ".join(E.expr(w.pos[b][k]) for k in range(3))
                 E.raw(f"        hit |= spec_self_hit(A.coll_use_default ? cptr(A.C.self_margin)[{pi}] : A.coll_margin, {pa}, {pb});")
             E.raw("    }")
-    E.raw("    if (lane < rows) A.coll_out[base + lane] = hit ? 1 : 0;")
-    E.raw("    if (A.via_n > 0 && A.via_partial) spec_via_partial_flags(A, wblock, via_traj0, via_slot, hit, via_outside, lane < rows, lane);     // wave-uniform")
-    E.raw("}")
-    return E.lines
+    return _boolean_kernel_tail(E)
 
 
 def points_collision_kernels(ident: str) -> List[str]:

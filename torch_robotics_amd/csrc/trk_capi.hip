@@ -691,6 +691,46 @@ static int check_rollout_call(const char* who, const TrkModel* m, const TrkCostM
     return TRK_OK;
 }
 
+// Boolean mode (trk_rollout_collision, ..._via, ..._via_flags, trk_rollout_points_collision, ..._via): what the five entries do alike
+// once their own checks have passed.  The cost model's columns are the model's links (ps == nullptr) or the points of ps.
+// Unit lookup: the unit whose baked column sets equal the cost model's for every field of the EFFECTIVE mask, its boolean launcher
+// (a slot of a link unit, a satellite of a point unit) and the weights that chose it; fn == nullptr: none serves the call.
+struct CollUnit { const SpecEntry* e; SpecLaunchFn fn; TrkRolloutWeights w; };
+static CollUnit coll_unit_for(const TrkModel* m, const TrkPointSet* ps, const TrkCostModel* cm, int32_t eff_fields) {
+    CollUnit u{nullptr, nullptr, field_weights(eff_fields, true)};
+    u.e = ps ? (m->spec_enabled ? points_spec_for(ps, cm, &u.w) : nullptr) : enabled_spec_for(m, cm, &u.w);
+    if (u.e) u.fn = ps ? points_coll_launcher(u.e) : u.e->launch_coll;
+    return u;
+}
+// nothing to test: nobody collides
+static int nothing_to_test(uint8_t* in_collision, int64_t n, trk_stream_t stream) {
+    TRK_HIP(hipMemsetAsync(in_collision, 0, (size_t)n, (hipStream_t)stream));
+    g_last_dispatch = TRK_DISPATCH_NONE;
+    return TRK_OK;
+}
+// The via forms: the way points' layout, the interpolation weights and, with traj_flags, the fused per-trajectory flags' outputs.
+// via_samples fills in hi = the via points of one trajectory (refused under the caller's name beyond the limit) and n = all of them.
+struct CollVia { int32_t horizon, state_dim, n_interp; const float *alpha, *beta; uint8_t* traj_flags; const float *q_min, *q_max; int64_t hi; };
+static int via_samples(const char* who, int64_t n_traj, CollVia& v, int64_t* n) {
+    v.hi = (int64_t)(v.horizon - 1) * v.n_interp;
+    if (v.hi > 0x7fffffff - 64) return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": (horizon - 1) * n_interp too large");
+    *n = n_traj * v.hi;
+    return TRK_OK;
+}
+// the one launch: q = the n configurations, or with `via` the way points they are interpolated from
+static int launch_coll(const CollUnit& u, const TrkModel* m, const TrkCostModel* cm, const float* q, int64_t n, int32_t eff_fields,
+                       float margin_override, uint8_t* in_collision, const CollVia* via, trk_stream_t stream) {
+    SpecArgs a;
+    spec_args(a, m, cm, &u.w);
+    a.q = q; a.n = n;
+    bind_collision(a, in_collision, eff_fields, margin_override);
+    if (via) {
+        a.via_alpha = via->alpha; a.via_beta = via->beta; a.via_n = via->n_interp; a.via_H = via->horizon; a.via_S = via->state_dim;
+        if (via->traj_flags) { a.via_partial = via->traj_flags; a.via_slots = trk_via_slots(via->hi); a.via_qmin = via->q_min; a.via_qmax = via->q_max; }
+    }
+    return served_generated(spec_launch(u.fn, u.e, a, m, stream));
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------
 // The trajectory-layout entries (trk_rollout_gp_adam_steps, trk_rollout_gp_via_adam_steps, trk_rollout_via_cost_grad): only a
 // generated kernel serves them (no table-driven twin, like trk_ik_gn_steps), and the kernel is not a slot of SpecEntry -- the unit,
@@ -1691,21 +1731,9 @@ int trk_rollout_collision(const TrkModel* m, const TrkCostModel* cm, int32_t fie
     if (n == 0) return TRK_OK;
     const int use_default = std::isnan(margin_override) ? 1 : 0;
     fields = effective_fields(cm, fields);
-    if (!fields) {                              // nothing to test: nobody collides
-        TRK_HIP(hipMemsetAsync(in_collision, 0, (size_t)n, (hipStream_t)stream));
-        g_last_dispatch = TRK_DISPATCH_NONE;
-        return TRK_OK;
-    }
-    // the unit's baked link sets must equal the cost model's for every field that is asked for (the mask is already effective)
-    const TrkRolloutWeights w = field_weights(fields, true);
-    const SpecEntry* e = enabled_spec_for(m, cm, &w);
-    if (e && e->launch_coll) {
-        SpecArgs a;
-        spec_args(a, m, cm, &w);
-        a.q = q; a.n = n;
-        bind_collision(a, in_collision, fields, margin_override);
-        return served_generated(spec_launch(e->launch_coll, e, a, m, stream));
-    }
+    if (!fields) return nothing_to_test(in_collision, n, stream);
+    const CollUnit u = coll_unit_for(m, nullptr, cm, fields);
+    if (u.fn) return launch_coll(u, m, cm, q, n, fields, margin_override, in_collision, nullptr, stream);
     if ((rc = strict_refusal("trk_rollout_collision", m)) != TRK_OK) return rc;
     g_last_dispatch = TRK_DISPATCH_TABLE;
     // no generated unit serves this model / cost model: table-driven FK into the caller's scratch, then the field kernel
@@ -1726,31 +1754,20 @@ static int rollout_collision_via_impl(const TrkModel* m, const TrkCostModel* cm,
     if (rc) return rc;
     if (horizon < 2 || n_interp < 1 || state_dim < m->hdr.n_dofs || (fields & ~7) || !fields || !alpha || !beta)
         return fail(TRK_ERR_INVALID_ARG, "trk_rollout_collision_via: bad argument");
-    const int64_t hi = (int64_t)(horizon - 1) * n_interp;
-    if (hi > 0x7fffffff - 64) return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_collision_via: (horizon - 1) * n_interp too large");
-    const int64_t n = n_traj * hi;
+    CollVia via{horizon, state_dim, n_interp, alpha, beta, traj_flags, q_min, q_max};
+    int64_t n;
+    if ((rc = via_samples(who, n_traj, via, &n)) != TRK_OK) return rc;
     if (n > 0 && (!x || !in_collision)) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_collision_via: null x / in_collision");
     if (n == 0) return TRK_OK;
     if (!m->spec_enabled) return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_collision_via: generated kernels are disabled for this model");
     fields = effective_fields(cm, fields);
     // (the fused flags need the generated kernel even when no field has anything to test: the joint limits are looked at there)
-    if (!fields && !traj_flags) {
-        TRK_HIP(hipMemsetAsync(in_collision, 0, (size_t)n, (hipStream_t)stream));
-        g_last_dispatch = TRK_DISPATCH_NONE;
-        return TRK_OK;
-    }
-    const TrkRolloutWeights w = field_weights(fields, true);
-    const SpecEntry* e = enabled_spec_for(m, cm, &w);
-    if (!e || !e->launch_coll)
+    if (!fields && !traj_flags) return nothing_to_test(in_collision, n, stream);
+    const CollUnit u = coll_unit_for(m, nullptr, cm, fields);
+    if (!u.fn)
         return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_collision_via: no generated kernel serves this model / cost model "
                                          "(use trk_interpolate_via_points + trk_rollout_collision)");
-    SpecArgs a;
-    spec_args(a, m, cm, &w);
-    a.q = x; a.n = n;
-    bind_collision(a, in_collision, fields, margin_override);
-    a.via_alpha = alpha; a.via_beta = beta; a.via_n = n_interp; a.via_H = horizon; a.via_S = state_dim;
-    if (traj_flags) { a.via_partial = traj_flags; a.via_slots = trk_via_slots(hi); a.via_qmin = q_min; a.via_qmax = q_max; }
-    return served_generated(spec_launch(e->launch_coll, e, a, m, stream));
+    return launch_coll(u, m, cm, x, n, fields, margin_override, in_collision, &via, stream);
 }
 
 int trk_rollout_collision_via(const TrkModel* m, const TrkCostModel* cm, int32_t fields, const float* x, int64_t n_traj,
@@ -2008,11 +2025,6 @@ static int check_points_collision_handles(const char* who, const TrkPointSet* ps
     if (cm->hdr.n_links_in != ps->dev.n_points) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": cost model n_links_in != number of points");
     return TRK_OK;
 }
-// the unit that serves (ps, cm, effective mask) and its boolean launcher; both null when there is none
-static SpecLaunchFn points_coll_for(const TrkPointSet* ps, const TrkCostModel* cm, const TrkRolloutWeights* w, const SpecEntry** e) {
-    *e = ps->model->spec_enabled ? points_spec_for(ps, cm, w) : nullptr;      // also: the unit bakes the cost model's column sets for these fields
-    return *e ? points_coll_launcher(*e) : nullptr;
-}
 
 int trk_rollout_points_collision(const TrkPointSet* ps, const TrkCostModel* cm, int32_t fields, const float* q, int64_t batch,
                                  int32_t horizon, float margin_override, uint8_t* in_collision, float* point_pos_ws, trk_stream_t stream) {
@@ -2025,20 +2037,9 @@ int trk_rollout_points_collision(const TrkPointSet* ps, const TrkCostModel* cm, 
     if (n == 0) return TRK_OK;
     const TrkModel* m = ps->model;
     const int32_t eff = effective_fields(cm, fields);
-    if (!eff) {                                 // nothing to test: nobody collides
-        TRK_HIP(hipMemsetAsync(in_collision, 0, (size_t)n, (hipStream_t)stream));
-        g_last_dispatch = TRK_DISPATCH_NONE;
-        return TRK_OK;
-    }
-    const TrkRolloutWeights w = field_weights(eff, true);
-    const SpecEntry* e = nullptr;
-    if (SpecLaunchFn fn = points_coll_for(ps, cm, &w, &e)) {
-        SpecArgs a;
-        spec_args(a, m, cm, &w);
-        a.q = q; a.n = n;
-        bind_collision(a, in_collision, eff, margin_override);
-        return served_generated(spec_launch(fn, e, a, m, stream));
-    }
+    if (!eff) return nothing_to_test(in_collision, n, stream);
+    const CollUnit u = coll_unit_for(m, ps, cm, eff);
+    if (u.fn) return launch_coll(u, m, cm, q, n, eff, margin_override, in_collision, nullptr, stream);
     if (strict_specialized() && m->spec_enabled && points_spec(ps))
         return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_points_collision: strict mode: the point set has generated kernels but no boolean kernel that bakes this "
                                          "cost model's columns for the fields asked for -- the call would take the two-launch path");
@@ -2060,9 +2061,9 @@ int trk_rollout_points_collision_via(const TrkPointSet* ps, const TrkCostModel* 
     if (n_interp < 1 || state_dim < 1 || !alpha || !beta) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_points_collision_via: bad n_interp / state_dim / alpha / beta");
     if ((traj_flags != nullptr) != (q_min != nullptr) || (traj_flags != nullptr) != (q_max != nullptr))
         return fail(TRK_ERR_INVALID_ARG, "trk_rollout_points_collision_via: traj_flags (trk_via_partial_flags_bytes), q_min and q_max are given together or not at all");
-    const int64_t hi = (int64_t)(horizon - 1) * n_interp;
-    if (hi > 0x7fffffff - 64) return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_points_collision_via: (horizon - 1) * n_interp too large");
-    const int64_t n = n_traj * hi;
+    CollVia via{horizon, state_dim, n_interp, alpha, beta, traj_flags, q_min, q_max};
+    int64_t n;
+    if ((rc = via_samples(who, n_traj, via, &n)) != TRK_OK) return rc;
     if (n > 0 && (!x || !in_collision)) return fail(TRK_ERR_INVALID_ARG, "trk_rollout_points_collision_via: null x / in_collision");
     if ((rc = check_points_collision_handles(who, ps, cm)) != TRK_OK) return rc;
     const TrkModel* m = ps->model;
@@ -2070,24 +2071,12 @@ int trk_rollout_points_collision_via(const TrkPointSet* ps, const TrkCostModel* 
     if (n == 0) return TRK_OK;
     const int32_t eff = effective_fields(cm, fields);
     // (the fused flags need the generated kernel even when no field has anything to test: the joint limits are looked at there)
-    if (!eff && !traj_flags) {
-        TRK_HIP(hipMemsetAsync(in_collision, 0, (size_t)n, (hipStream_t)stream));
-        g_last_dispatch = TRK_DISPATCH_NONE;
-        return TRK_OK;
-    }
-    const TrkRolloutWeights w = field_weights(eff, true);
-    const SpecEntry* e = nullptr;
-    SpecLaunchFn fn = points_coll_for(ps, cm, &w, &e);
-    if (!fn)
+    if (!eff && !traj_flags) return nothing_to_test(in_collision, n, stream);
+    const CollUnit u = coll_unit_for(m, ps, cm, eff);
+    if (!u.fn)
         return fail(TRK_ERR_UNSUPPORTED, "trk_rollout_points_collision_via: no generated boolean kernel serves this point set / cost model "
                                          "(use trk_interpolate_via_points + trk_rollout_points_collision)");
-    SpecArgs a;
-    spec_args(a, m, cm, &w);
-    a.q = x; a.n = n;
-    bind_collision(a, in_collision, eff, margin_override);
-    a.via_alpha = alpha; a.via_beta = beta; a.via_n = n_interp; a.via_H = horizon; a.via_S = state_dim;
-    if (traj_flags) { a.via_partial = traj_flags; a.via_slots = trk_via_slots(hi); a.via_qmin = q_min; a.via_qmax = q_max; }
-    return served_generated(spec_launch(fn, e, a, m, stream));
+    return launch_coll(u, m, cm, x, n, eff, margin_override, in_collision, &via, stream);
 }
 
 int trk_interpolate_via_points(const float* x, int64_t n_traj, int32_t horizon, int32_t dim, int32_t n_interp,

@@ -179,6 +179,26 @@ class _Plan:
         if rc:
             check(rc, self._fn.__name__)
 
+    def _bind_outputs(self, who: str, model, q: torch.Tensor, n_cols: int, want_pos: bool, gio, gq_out) -> None:
+        """What RolloutPlan and PointsRolloutPlan bind alike for q (B, H, D): `q`, `device`, `B`, `H`, `link_pos` (B, H, n_cols, 3) in q's
+        dtype (want_pos), `cost` (B, H) fp32 and `gq` (B, H, D) in `gio`."""
+        if q.dim() != 3:
+            raise ValueError(f"{who}: q must be (batch, horizon, dof)")
+        _check_q_dofs(q, model.n_dofs, f"{who}(q)")
+        self.q, self.device = q, q.device
+        self.B, self.H = B, H = int(q.shape[0]), int(q.shape[1])
+        self.link_pos = torch.empty((B, H, n_cols, 3), device=q.device, dtype=q.dtype) if want_pos else None
+        self.cost = torch.empty((B, H), device=q.device, dtype=torch.float32)
+        self.gq = _gq_buffer(f"{who}(gq_out)", gq_out, (B, H, model.n_dofs), gio, q.device)
+
+
+def _gq_buffer(what: str, gq_out: Optional[torch.Tensor], shape, dtype, device) -> torch.Tensor:
+    """A plan's gradient buffer: the caller's `gq_out`, checked and viewed in `shape`, or a buffer of the plan's own."""
+    if gq_out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    _check_buffer(gq_out, math.prod(shape), dtype, device, what)
+    return gq_out.view(shape)
+
 
 # Integer ids of the live handles, for the dispatcher ops (torch.ops.trk.*, custom_ops.py): an op schema carries tensors and
 # scalars only, so a model / cost model / point set travels as the value of its C pointer.
@@ -965,24 +985,33 @@ class strict_specialized:
         return False
 
 
-def rollout_collision(model: ModelHandle, cm: CostHandle, fields: int, q: torch.Tensor, margin: Optional[float] = None) -> torch.Tensor:
-    """Fused FK + boolean collision fields: q (B,H,D) or (N,D) -> bool (B,H) / (N,).  One launch, one byte per sample out
-    (`PlanningTask.compute_collision`, tasks.py:131-133); `margin=None` uses the fields' own margins."""
-    q = _dev_f32(q, "rollout_collision(q)")
-    _check_q_dofs(q, model.n_dofs, "rollout_collision(q)")
+def _rollout_collision(who: str, fn, heads, model: ModelHandle, n_cols: int, scratch_first: bool, retry_empty: bool, cm: CostHandle,
+                       fields: int, q: torch.Tensor, margin: Optional[float]) -> torch.Tensor:
+    """The body of rollout_collision / rollout_points_collision: the C function `fn` after its leading handles `heads`.  The scratch
+    (n, n_cols, 3) serves the table-driven fall-back only (a model / cost model that no generated kernel serves): allocated before the
+    call (scratch_first), or when the library asks for it with TRK_ERR_INVALID_ARG (retry_empty: for an empty batch too) -- a unit
+    exists for the model, but none serves this cost model."""
+    q = _dev_f32(q, f"{who}(q)")
+    _check_q_dofs(q, model.n_dofs, f"{who}(q)")
     q, lead, B, Hh = _lead_batch_horizon(q, model.n_dofs)
     n = B * Hh
     out = torch.empty((n,), device=q.device, dtype=torch.bool)      # the kernel writes 0 / 1 bytes
-    # scratch for the table-driven fallback only (a model / cost model that no generated kernel serves)
-    ws = None if model.specialized else torch.empty((n, model.n_links, 3), device=q.device, dtype=torch.float32)
+    ws = torch.empty((n, n_cols, 3), device=q.device, dtype=torch.float32) if scratch_first else None
     m = float("nan") if margin is None else float(margin)
     with _on(q.device):
-        rc = lib().trk_rollout_collision(model._h, cm._h, int(fields), q.data_ptr(), B, Hh, m, out.data_ptr(), _ptr(ws), _stream(q))
-        if rc == _abi.TRK_ERR_INVALID_ARG and ws is None:       # a unit exists for the model, but not for this cost model
-            ws = torch.empty((n, model.n_links, 3), device=q.device, dtype=torch.float32)
-            rc = lib().trk_rollout_collision(model._h, cm._h, int(fields), q.data_ptr(), B, Hh, m, out.data_ptr(), ws.data_ptr(), _stream(q))
-        check(rc, "trk_rollout_collision")
+        rc = fn(*heads, cm._h, int(fields), q.data_ptr(), B, Hh, m, out.data_ptr(), _ptr(ws), _stream(q))
+        if rc == _abi.TRK_ERR_INVALID_ARG and ws is None and (retry_empty or n > 0):
+            ws = torch.empty((n, n_cols, 3), device=q.device, dtype=torch.float32)
+            rc = fn(*heads, cm._h, int(fields), q.data_ptr(), B, Hh, m, out.data_ptr(), ws.data_ptr(), _stream(q))
+        check(rc, fn.__name__)
     return out.reshape(lead)
+
+
+def rollout_collision(model: ModelHandle, cm: CostHandle, fields: int, q: torch.Tensor, margin: Optional[float] = None) -> torch.Tensor:
+    """Fused FK + boolean collision fields: q (B,H,D) or (N,D) -> bool (B,H) / (N,).  One launch, one byte per sample out
+    (`PlanningTask.compute_collision`, tasks.py:131-133); `margin=None` uses the fields' own margins."""
+    return _rollout_collision("rollout_collision", lib().trk_rollout_collision, (model._h,), model, model.n_links, not model.specialized,
+                              True, cm, fields, q, margin)
 
 
 def rollout_points_cost_grad(ps: PointSetHandle, cm: CostHandle, weights, q: torch.Tensor, want_pos: bool = True,
@@ -1012,20 +1041,8 @@ def rollout_points_collision(ps: PointSetHandle, cm: CostHandle, fields: int, q:
     position stored; `margin=None` uses the fields' own margins.  Where no generated boolean kernel serves the call (no unit for the
     point set, or one loaded as a code object by the hipRTC fall-back) the library runs `fk_points` + `collision_fields` through a
     scratch tensor allocated here; `last_dispatch()` tells which."""
-    model = ps.model
-    q = _dev_f32(q, "rollout_points_collision(q)")
-    _check_q_dofs(q, model.n_dofs, "rollout_points_collision(q)")
-    q, lead, B, Hh = _lead_batch_horizon(q, model.n_dofs)
-    n = B * Hh
-    out = torch.empty((n,), device=q.device, dtype=torch.bool)      # the kernel writes 0 / 1 bytes
-    m = float("nan") if margin is None else float(margin)
-    with _on(q.device):
-        rc = lib().trk_rollout_points_collision(ps._h, cm._h, int(fields), q.data_ptr(), B, Hh, m, out.data_ptr(), None, _stream(q))
-        if rc == _abi.TRK_ERR_INVALID_ARG and n > 0:       # no boolean kernel serves the call: the two launches need scratch (as rollout_collision)
-            ws = torch.empty((n, ps.n_points, 3), device=q.device, dtype=torch.float32)
-            rc = lib().trk_rollout_points_collision(ps._h, cm._h, int(fields), q.data_ptr(), B, Hh, m, out.data_ptr(), ws.data_ptr(), _stream(q))
-        check(rc, "trk_rollout_points_collision")
-    return out.reshape(lead)
+    return _rollout_collision("rollout_points_collision", lib().trk_rollout_points_collision, (ps._h,), ps.model, ps.n_points, False, False,
+                              cm, fields, q, margin)
 
 
 def rollout_points_collision_via(ps: PointSetHandle, cm: CostHandle, fields: int, trajs: torch.Tensor, num_interpolation: int,
@@ -1034,31 +1051,8 @@ def rollout_points_collision_via(ps: PointSetHandle, cm: CostHandle, fields: int
     (T, (H-1) * num_interpolation) -- with limits=(q_min, q_max): (bool tensor, flags buffer for `traj_validate(..., flags=...)`) --
     or None when no generated boolean kernel serves the point set / cost model (a unit loaded by the hipRTC fall-back has none): the
     caller then interpolates first."""
-    model = ps.model
-    x = _dev_f32(trajs, "rollout_points_collision_via(trajs)")
-    T, H, S = (int(v) for v in x.shape)
-    if S < model.n_dofs:
-        raise ValueError(f"rollout_points_collision_via: way points have {S} columns, the model has {model.n_dofs} DOF")
-    n = int(num_interpolation)
-    alpha, beta = via_point_weights(n, x.device)
-    out = torch.empty((T, (H - 1) * n), device=x.device, dtype=torch.bool)
-    m = float("nan") if margin is None else float(margin)
-    small, qmin_p, qmax_p, flags_p = None, None, None, None
-    if limits is not None:
-        q_min, q_max = limits
-        _check_buffer(q_min, model.n_dofs, torch.float32, x.device, "rollout_points_collision_via(q_min)")
-        _check_buffer(q_max, model.n_dofs, torch.float32, x.device, "rollout_points_collision_via(q_max)")
-        # [counts 16 B | pad 16 B | flags T, padded to 16 | per-wavefront partial flags]: the layout traj_validate carries on with
-        nb = int(lib().trk_via_partial_flags_bytes(T, H, n))
-        small = torch.empty(32 + (T + 15) // 16 * 16 + nb, device=x.device, dtype=torch.uint8)
-        qmin_p, qmax_p, flags_p = q_min.data_ptr(), q_max.data_ptr(), small.data_ptr() + 32 + (T + 15) // 16 * 16
-    with _on(x.device):
-        rc = lib().trk_rollout_points_collision_via(ps._h, cm._h, int(fields), x.data_ptr(), T, H, S, n, alpha.data_ptr(), beta.data_ptr(),
-                                                    m, qmin_p, qmax_p, out.data_ptr(), flags_p, _stream(x))
-    if rc == _abi.TRK_ERR_UNSUPPORTED:
-        return None
-    check(rc, "trk_rollout_points_collision_via")
-    return out if limits is None else (out, (small, (H - 1) * n))
+    return _rollout_collision_via("rollout_points_collision_via", None, lib().trk_rollout_points_collision_via, (ps._h,), ps.model, cm,
+                                  fields, trajs, num_interpolation, margin, limits)
 
 
 def gp_prior_cost_grad(q: torch.Tensor, qd: torch.Tensor, dt: float, sigma: float, weight: float = 1.0,
@@ -1296,6 +1290,42 @@ def interpolate_traj_via_points_ad(trajs: torch.Tensor, num_interpolation: int) 
     return interpolate_traj_via_points(x, num_interpolation)
 
 
+def _via_flags_offset(T: int) -> int:
+    """The flags buffer of T trajectories that the via forms fill with limits= and `traj_validate` carries on with:
+    [counts 16 B | pad 16 B | flags T, padded to 16 | per-wavefront partial flags] -> where the partial flags start (the flags: 32)."""
+    return 32 + (T + 15) // 16 * 16
+
+
+def _rollout_collision_via(who: str, fn_plain, fn_flags, heads, model: ModelHandle, cm: CostHandle, fields: int, trajs: torch.Tensor,
+                           num_interpolation: int, margin: Optional[float], limits):
+    """The body of rollout_collision_via / rollout_points_collision_via.  fn_flags takes (q_min, q_max, out, partial flags) behind the
+    margin and serves limits=; without limits fn_plain (out alone) is called -- or, where there is none, fn_flags with null pointers."""
+    x = _dev_f32(trajs, f"{who}(trajs)")
+    T, H, S = (int(v) for v in x.shape)
+    if S < model.n_dofs:
+        raise ValueError(f"{who}: way points have {S} columns, the model has {model.n_dofs} DOF")
+    n = int(num_interpolation)
+    alpha, beta = via_point_weights(n, x.device)
+    out = torch.empty((T, (H - 1) * n), device=x.device, dtype=torch.bool)
+    m = float("nan") if margin is None else float(margin)
+    small, qmin_p, qmax_p, flags_p = None, None, None, None
+    if limits is not None:
+        q_min, q_max = limits
+        _check_buffer(q_min, model.n_dofs, torch.float32, x.device, f"{who}(q_min)")
+        _check_buffer(q_max, model.n_dofs, torch.float32, x.device, f"{who}(q_max)")
+        off = _via_flags_offset(T)
+        small = torch.empty(off + int(lib().trk_via_partial_flags_bytes(T, H, n)), device=x.device, dtype=torch.uint8)
+        qmin_p, qmax_p, flags_p = q_min.data_ptr(), q_max.data_ptr(), small.data_ptr() + off
+    fn = fn_plain if limits is None and fn_plain is not None else fn_flags
+    tail = (out.data_ptr(),) if fn is fn_plain else (qmin_p, qmax_p, out.data_ptr(), flags_p)
+    with _on(x.device):
+        rc = fn(*heads, cm._h, int(fields), x.data_ptr(), T, H, S, n, alpha.data_ptr(), beta.data_ptr(), m, *tail, _stream(x))
+    if rc == _abi.TRK_ERR_UNSUPPORTED:
+        return None
+    check(rc, fn.__name__)
+    return out if limits is None else (out, (small, (H - 1) * n))
+
+
 def rollout_collision_via(model: ModelHandle, cm: CostHandle, fields: int, trajs: torch.Tensor, num_interpolation: int,
                           margin: Optional[float] = None, limits=None):
     """Boolean collision fields on the interpolated via points of trajs (T, H, S >= D) without materialising them:
@@ -1304,32 +1334,8 @@ def rollout_collision_via(model: ModelHandle, cm: CostHandle, fields: int, trajs
     limits=(q_min, q_max) (float32 device vectors of n_dofs): the launch also folds the per-trajectory flags of `traj_validate` --
     bit 0 some via point collides, bit 1 some way point lies outside the limits -- and the result is (bool tensor, flags buffer): hand
     the buffer to `traj_validate(..., flags=...)`, which then skips its own flags launch."""
-    x = _dev_f32(trajs, "rollout_collision_via(trajs)")
-    T, H, S = (int(v) for v in x.shape)
-    if S < model.n_dofs:
-        raise ValueError(f"rollout_collision_via: way points have {S} columns, the model has {model.n_dofs} DOF")
-    n = int(num_interpolation)
-    alpha, beta = via_point_weights(n, x.device)
-    out = torch.empty((T, (H - 1) * n), device=x.device, dtype=torch.bool)
-    m = float("nan") if margin is None else float(margin)
-    with _on(x.device):
-        if limits is None:
-            rc = lib().trk_rollout_collision_via(model._h, cm._h, int(fields), x.data_ptr(), T, H, S, n, alpha.data_ptr(), beta.data_ptr(),
-                                                 m, out.data_ptr(), _stream(x))
-        else:
-            q_min, q_max = limits
-            _check_buffer(q_min, model.n_dofs, torch.float32, x.device, "rollout_collision_via(q_min)")
-            _check_buffer(q_max, model.n_dofs, torch.float32, x.device, "rollout_collision_via(q_max)")
-            # [counts 16 B | pad 16 B | flags T, padded to 16 | per-wavefront partial flags]: the layout traj_validate carries on with
-            nb = int(lib().trk_via_partial_flags_bytes(T, H, n))
-            small = torch.empty(32 + (T + 15) // 16 * 16 + nb, device=x.device, dtype=torch.uint8)
-            rc = lib().trk_rollout_collision_via_flags(model._h, cm._h, int(fields), x.data_ptr(), T, H, S, n, alpha.data_ptr(), beta.data_ptr(),
-                                                       m, q_min.data_ptr(), q_max.data_ptr(), out.data_ptr(),
-                                                       small.data_ptr() + 32 + (T + 15) // 16 * 16, _stream(x))
-    if rc == _abi.TRK_ERR_UNSUPPORTED:
-        return None
-    check(rc, "trk_rollout_collision_via" + ("" if limits is None else "_flags"))
-    return out if limits is None else (out, (small, (H - 1) * n))
+    return _rollout_collision_via("rollout_collision_via", lib().trk_rollout_collision_via, lib().trk_rollout_collision_via_flags,
+                                  (model._h,), model, cm, fields, trajs, num_interpolation, margin, limits)
 
 
 class _PinnedCounters:
@@ -1396,10 +1402,10 @@ def traj_validate(waypoint_collisions: Optional[torch.Tensor], trajs: torch.Tens
     r = TrajPartition()
     if flags is not None:
         buf, hi = flags
-        if buf.device != x.device or buf.dtype != torch.uint8 or buf.numel() < 32 + (T + 15) // 16 * 16 or hi < 1:
+        if buf.device != x.device or buf.dtype != torch.uint8 or buf.numel() < _via_flags_offset(T) or hi < 1:
             raise ValueError("traj_validate(flags): expected what rollout_collision_via(..., limits=...) returned for these trajectories")
         # the per-wavefront partial flags ride in as `waypoint_collisions`, n_waypoints = -(samples per trajectory)
-        wp_ptr, W, r._small = buf.data_ptr() + 32 + (T + 15) // 16 * 16, -int(hi), buf
+        wp_ptr, W, r._small = buf.data_ptr() + _via_flags_offset(T), -int(hi), buf
     else:
         wp = waypoint_collisions
         if wp.device != x.device or wp.element_size() != 1 or not wp.is_contiguous() or wp.numel() % max(T, 1):
@@ -2081,11 +2087,7 @@ class RolloutViaPlan(_Plan):
         _check_buffer(seed, T * (H - 1) * n, torch.float32, x.device, "RolloutViaPlan(seed)")
         self.seed = seed
         self.cost = torch.empty((T, (H - 1) * n), device=x.device, dtype=torch.float32)
-        if gq_out is not None:
-            _check_buffer(gq_out, T * H * model.n_dofs, torch.float32, x.device, "RolloutViaPlan(gq_out)")
-            self.gq = gq_out.view(T, H, model.n_dofs)
-        else:
-            self.gq = torch.empty((T, H, model.n_dofs), device=x.device, dtype=torch.float32)
+        self.gq = _gq_buffer("RolloutViaPlan(gq_out)", gq_out, (T, H, model.n_dofs), torch.float32, x.device)
         self._alpha, self._beta = via_point_weights(n, x.device)
         self._w = _weights_struct(weights)        # the plan's own reference: the cache may be cleared
         self._fn = lib().trk_rollout_via_cost_grad
@@ -2162,25 +2164,12 @@ class RolloutPlan(_Plan):
         gio, gcode, gs = _grad_mode(f16, grad_dtype, grad_scale, "RolloutPlan")
         self.grad_scale = gs
         q = q.contiguous() if (f16 and q.device.type == "cuda") else _dev_f32(q, "RolloutPlan(q)")
-        if q.dim() != 3:
-            raise ValueError("RolloutPlan: q must be (batch, horizon, dof)")
-        _check_q_dofs(q, model.n_dofs, "RolloutPlan(q)")
-        self.model, self.cm, self.q = model, cm, q
-        self.B, self.H = int(q.shape[0]), int(q.shape[1])
-        n, L, D = self.B * self.H, model.n_links, model.n_dofs
-        kw = dict(device=q.device, dtype=q.dtype)
-        self.link_pos = torch.empty((self.B, self.H, L, 3), **kw) if want_pos else None
-        self.cost = torch.empty((self.B, self.H), device=q.device, dtype=torch.float32)
-        if gq_out is not None:
-            _check_buffer(gq_out, n * D, gio, q.device, "RolloutPlan(gq_out)")
-            self.gq = gq_out.view(self.B, self.H, D)
-        else:
-            self.gq = torch.empty((self.B, self.H, D), device=q.device, dtype=gio)
+        self._bind_outputs("RolloutPlan", model, q, model.n_links, want_pos, gio, gq_out)
+        self.model, self.cm = model, cm
         self._w = _weights_struct(weights)        # the plan's own reference: the cache may be cleared
         self._fn = lib().trk_rollout_cost_grad_f16 if f16 else lib().trk_rollout_cost_grad
         self._args = (model._h, cm._h, C.byref(self._w), q.data_ptr(), self.B, self.H, _ptr(self.link_pos),
                       self.cost.data_ptr(), self.gq.data_ptr()) + ((gcode, gs) if f16 else ())
-        self.device = q.device
 
     def launch(self, cost_sum_ptr: Optional[int] = None, stream: Optional[int] = None) -> None:
         self._launch(stream, cost_sum_ptr)
@@ -2222,25 +2211,13 @@ class PointsRolloutPlan(_Plan):
         if strict and ps.specialized and not self.generated:
             _require_generated("PointsRolloutPlan", model, False)
         q = _dev_f32(q, "PointsRolloutPlan(q)")
-        if q.dim() != 3:
-            raise ValueError("PointsRolloutPlan: q must be (batch, horizon, dof)")
-        _check_q_dofs(q, model.n_dofs, "PointsRolloutPlan(q)")
-        self.model, self.ps, self.cm, self.q = model, ps, cm, q
-        self.B, self.H = int(q.shape[0]), int(q.shape[1])
-        n, P, D = self.B * self.H, ps.n_points, model.n_dofs
-        self.link_pos = torch.empty((self.B, self.H, P, 3), device=q.device, dtype=torch.float32) if want_pos else None
-        self.cost = torch.empty((self.B, self.H), device=q.device, dtype=torch.float32)
-        if gq_out is not None:
-            _check_buffer(gq_out, n * D, torch.float32, q.device, "PointsRolloutPlan(gq_out)")
-            self.gq = gq_out.view(self.B, self.H, D)
-        else:
-            self.gq = torch.empty((self.B, self.H, D), device=q.device, dtype=torch.float32)
+        self._bind_outputs("PointsRolloutPlan", model, q, ps.n_points, want_pos, torch.float32, gq_out)
+        self.model, self.ps, self.cm = model, ps, cm
         self.grad_scale = 1.0
         self._w = _weights_struct(weights)        # the plan's own reference: the cache may be cleared
         self._fn = lib().trk_rollout_points_cost_grad
         self._args = (model._h, ps._h, cm._h, C.byref(self._w), q.data_ptr(), self.B, self.H, _ptr(self.link_pos),
                       self.cost.data_ptr(), self.gq.data_ptr())
-        self.device = q.device
 
     def launch(self, cost_sum_ptr: Optional[int] = None, stream: Optional[int] = None) -> None:
         self._launch(stream, cost_sum_ptr)
