@@ -7,6 +7,7 @@ import torch
 
 import torch_robotics_amd as tra
 from helpers import gold, grad_close, rel_err
+from traj_utils_helpers import partition_ref as _expected_partition
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -1018,24 +1019,6 @@ def test_fields_with_interpolated_link_points_like_the_reference():
     assert grad_close(q2.grad.cpu().numpy(), g["gq_total"])
     coll = g["coll_self"] | g["coll_objects"] | g["coll_ws"]
     assert np.array_equal(task.compute_collision(q2.detach()).cpu().numpy(), coll)
-
-
-def _expected_partition(coll_any, outside, inner=0):
-    """What get_trajs_collision_and_free's bookkeeping (tasks.py:253-284) yields for given per-trajectory facts, stated directly:
-    free = collision free and inside the limits; the other list = colliding ones, then the collision-free limit violators --
-    except that it is ONLY the violators when nothing is free but something was collision free."""
-    t = np.arange(len(coll_any))
-    free = t[~coll_any & ~outside]
-    viol = t[~coll_any & outside]
-    coll = t[coll_any]
-    if len(free) + len(viol) == 0:
-        other = coll
-    elif len(free) == 0:
-        other = viol
-    else:
-        other = np.concatenate([coll, viol])
-    rows = (lambda a: np.stack([a // inner, a % inner], 1)) if inner else (lambda a: a.reshape(-1, 1))
-    return rows(free), rows(other)
 
 
 @pytest.mark.parametrize("case", ["mixed", "all_free", "none_free", "one_free", "only_violators", "ragged_big", "batched"])

@@ -1990,13 +1990,13 @@ k_gp_prior(const T* __restrict__ q, const T* __restrict__ qd, int H, int D, floa
     }
     __syncthreads();
     float acc = 0.0f;
-    auto element = [&](int i, float& gp, float& gv) {
+    auto element = [&](int i, float& gp, float& gv, float& csum) {
         const float p0 = ps[i], v0 = vs[i];
         gp = 0.0f; gv = 0.0f;
         if (i + D < total) {                       // t + 1 < H for t = i / D, without the division
             const float ep = fmaf(dt, v0, p0) - ps[i + D], ev = v0 - vs[i + D];
             const float rp = fmaf(a, ep, b * ev), rv = fmaf(b, ep, c * ev);
-            acc = fmaf(0.5f, fmaf(ep, rp, ev * rv), acc);
+            csum = fmaf(0.5f, fmaf(ep, rp, ev * rv), csum);
             gp = rp; gv = fmaf(dt, rp, rv);
         }
         if (i >= D) {                              // t > 0
@@ -2010,7 +2010,7 @@ k_gp_prior(const T* __restrict__ q, const T* __restrict__ qd, int H, int D, floa
         for (int i = 4 * threadIdx.x; i < total; i += 4 * 256) {
             float gp[4], gv[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) element(i + k, gp[k], gv[k]);
+            for (int k = 0; k < 4; ++k) element(i + k, gp[k], gv[k], acc);
             float4 o0 = make_float4(gp[0], gp[1], gp[2], gp[3]), o1 = make_float4(gv[0], gv[1], gv[2], gv[3]);
             if (accumulate) {
                 const float4 c0 = GpVec<G>::load(gq + base + i), c1 = GpVec<G>::load(gqd + base + i);
@@ -2021,11 +2021,34 @@ k_gp_prior(const T* __restrict__ q, const T* __restrict__ qd, int H, int D, floa
             GpVec<G>::store(gqd + base + i, o1);
         }
     } else {
-        for (int i = threadIdx.x; i < total; i += 256) {
-            float gp, gv;
-            element(i, gp, gv);
-            if (accumulate) { gp += (float)gq[base + i]; gv += (float)gqd[base + i]; }
-            put_scaled(gq + base + i, gp); put_scaled(gqd + base + i, gv);
+        // H D a multiple of 4: only the alignment of the buffers kept this launch off the 16-byte path.  The cost is then summed apart,
+        // the way that path sums it (a thread takes the factors of 4 consecutive elements per trip, in order), so that a trajectory's
+        // cost has the same bits wherever its buffers start; summed one element per thread as below, it differed from the aligned
+        // launch in the last bit.  The second loop reads LDS only; the gradient stores stay coalesced.
+        auto elements = [&](float& csum) {
+            for (int i = threadIdx.x; i < total; i += 256) {
+                float gp, gv;
+                element(i, gp, gv, csum);
+                if (accumulate) { gp += (float)gq[base + i]; gv += (float)gqd[base + i]; }
+                put_scaled(gq + base + i, gp); put_scaled(gqd + base + i, gv);
+            }
+        };
+        if ((total & 3) != 0) elements(acc);
+        else {
+            float unused = 0.0f;
+            elements(unused);
+            for (int i0 = 4 * threadIdx.x; i0 < total; i0 += 4 * 256) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int i = i0 + k;
+                    if (i + D < total) {
+                        const float v0 = vs[i];
+                        const float ep = fmaf(dt, v0, ps[i]) - ps[i + D], ev = v0 - vs[i + D];
+                        const float rp = fmaf(a, ep, b * ev), rv = fmaf(b, ep, c * ev);
+                        acc = fmaf(0.5f, fmaf(ep, rp, ev * rv), acc);
+                    }
+                }
+            }
         }
     }
     acc = wave_sum(acc);
