@@ -1895,7 +1895,11 @@ __global__ void __launch_bounds__(256)
 k_scale_rows(const IO* __restrict__ g, const float* __restrict__ sc, int sc_stride, int64_t n, int D, IO* __restrict__ out) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n * D) return;
-    out[idx] = (IO)((float)g[idx] * (sc_stride ? sc[idx / D] : sc[0]));
+    // The product is rounded to fp32 and THEN to IO.  Left to the compiler, the fp16 instantiation folds the two into v_fma_mixlo_f16 with
+    // a +0 addend, and (-0) + (+0) = +0 loses the sign of a zero product: the empty asm keeps v_mul_f32 and v_cvt_f16_f32 apart.
+    float p = (float)g[idx] * (sc_stride ? sc[idx / D] : sc[0]);
+    asm volatile("" : "+v"(p));
+    out[idx] = (IO)p;
 }
 
 // interpolate_points_v1 distance_fields.py:66-69 (F.interpolate linear, align_corners=True, along the link axis) with the index /

@@ -1817,7 +1817,7 @@ class PackedSums:
         _check_buffer(block_sums, n_blocks(self.B * self.H), torch.float32, plan.device, "PackedSums(block_sums)", at_least=True)
         _check_buffer(traj_cost, self.B, torch.float32, plan.device, "PackedSums(traj_cost)")
         nbytes = int(lib().trk_pack_sums_scratch_bytes(self.H, self.D))
-        self._scratch = torch.zeros(nbytes // 4, device=plan.device, dtype=torch.float32)     # zeroed once: holds the ticket
+        self._scratch = torch.zeros(nbytes // 4, device=plan.device, dtype=torch.float32)     # the partial rows: every word read is written first
         self._args = (plan.cost.data_ptr(), plan.gq.data_ptr(), int(plan.gq.dtype == torch.float16), float(plan.grad_scale),
                       block_sums.data_ptr(), _ptr(traj_cost), self.B, self.H, self.D, self._scratch.data_ptr())
         self._keep = (plan, block_sums, traj_cost)
