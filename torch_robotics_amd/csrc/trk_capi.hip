@@ -620,6 +620,49 @@ template <class Args>
 static auto without_self(void (*fn)(const Args&, int, hipStream_t)) {
     return [fn](const SpecEntry*, const Args& a, int base_identity, hipStream_t st) { fn(a, base_identity, st); };
 }
+// The tail of every entry that started a kernel itself: a failed launch is reported, else TRK_OK.
+static int launched() {
+    TRK_HIP(last_launch_error());
+    return TRK_OK;
+}
+// A stateless utility entry once its own argument ladder and empty-batch return have passed: initialise, launch(), the tail.  A
+// launcher that answers (trk_launch_jtj, trk_launch_gp_prior) declines with a non-zero value: nothing was started and the entry's
+// own text goes out as TRK_ERR_UNSUPPORTED.
+template <class Launch>
+static int run_utility(Launch launch, const char* declined = nullptr) {
+    if (int rc = ensure_init()) return rc;
+    if constexpr (std::is_void_v<decltype(launch())>) launch();
+    else if (launch()) return fail(TRK_ERR_UNSUPPORTED, declined);
+    return launched();
+}
+// Generated unit or table-driven kernel (the FK, point-FK, Jacobian and field entries): with a launcher fn of unit e, spec_args of
+// (m, cm, w), bind(a) for the entry's own fields, spec_launch; with none, table() starts the table-driven kernel, then the tail.
+template <class Bind, class Table>
+static int unit_or_table(SpecLaunchFn fn, const SpecEntry* e, const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w,
+                         trk_stream_t stream, Bind bind, Table table) {
+    if (!fn) { table(); return launched(); }
+    SpecArgs a;
+    if (int rc = spec_args(a, m, cm, w)) return rc;
+    bind(a);
+    return spec_launch(fn, e, a, m, stream);
+}
+// The IK entries' unit: the first link-column unit of this model that tracks `link` and has the launcher `member` (several units can
+// exist for one model: jit.specialize(kin, obj_links, ee_link=link) loads one per tracked link).  The caller honours spec_enabled.
+template <class Fn>
+static const SpecEntry* unit_tracking(const TrkModel* m, int32_t link, Fn SpecEntry::*member) {
+    for (const SpecEntry* e : spec_registry())
+        if (e->n_points == 0 && e->model_hash == m->hash && e->n_links == m->hdr.n_links && e->n_dofs == m->hdr.n_dofs &&
+            e->*member && e->ee_link == link) return e;
+    return nullptr;
+}
+// what IkArgs and IkGnArgs have in common: the base pose, the target, the limits, the SE3 threshold, the iterations and the batch
+template <class Args>
+static void fill_ik_args(Args& a, const TrkModel* m, const float* H_target, int32_t per_sample, const float* lower, const float* upper,
+                         float se3_eps, int32_t n_steps, int64_t n, float* q, uint8_t* valid) {
+    set_base_pose(a, m);
+    a.H_target = H_target; a.per_sample = per_sample; a.lower = lower; a.upper = upper; a.se3_eps = se3_eps;
+    a.n_steps = n_steps; a.n = n; a.q = q; a.valid = valid;
+}
 // The plan-specialised rollout family (k_rollout_fx).  The unit's fx_select says which of its instantiations serves the
 // bound arguments (-1: none); the answer travels to the unit's launcher in fx_pick.  A unit with collision points at constant
 // positions reads their signed distance and gradient from a record evaluated ONCE per (cost model, unit): one wavefront of the unit's
@@ -973,20 +1016,11 @@ static int fk_fwd(int mode, const TrkModel* m, const float* q, int64_t n, const 
     if (e && mode == 0 && ns == 1 && e->launch_fk1)
         for (int l = 0; l < m->hdr.n_links; ++l) if (sel.col[l] == 0) fk1_link = l;
     const SpecLaunchFn fn = mode == 1 ? (all ? e->launch : nullptr) : fk1_link >= 0 ? e->launch_fk1 : (all ? e->launch_fkh : nullptr);
-    if (fn) {
-        SpecArgs a;
-        if ((rc = spec_args(a, m)) != TRK_OK) return rc;
+    return unit_or_table(fn, e, m, nullptr, nullptr, stream, [&](SpecArgs& a) {
         a.q = q; a.n = n;
         if (mode == 1) a.link_pos = out; else a.fk_H = out;
-        if (fk1_link >= 0) {
-            a.jac_link = fk1_link; a.jac_p_end = 1;
-            for (int p = 0; p < m->hdr.n_links; ++p) if (m->links[p].link == fk1_link) a.jac_p_end = p + 1;
-        }
-        return spec_launch(fn, e, a, m, stream);
-    }
-    trk_launch_fk_forward(mode, m->hdr, m->d_links, sel, ns, q, n, out, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+        if (fk1_link >= 0) { a.jac_link = fk1_link; a.jac_p_end = trk_walk_end(m->links.data(), m->hdr.n_links, fk1_link); }
+    }, [&] { trk_launch_fk_forward(mode, m->hdr, m->d_links, sel, ns, q, n, out, (hipStream_t)stream); });
 }
 
 int trk_fk_forward(const TrkModel* m, const float* q, int64_t n, const int32_t* link_sel, int32_t n_sel, float* H_out, trk_stream_t stream) {
@@ -1008,19 +1042,15 @@ static int fk_bwd(int mode, const TrkModel* m, const float* q, const float* gin,
     // generated reverse mode (every link selected): the adjoint travels in the slot of the forward output it belongs to
     const SpecEntry* e = enabled_spec(m);
     const SpecLaunchFn fn = e && all_links_selected(m, sel, ns) ? (mode == 0 ? e->launch_fkhbwd : e->launch_posbwd) : nullptr;
-    if (fn) {
-        SpecArgs a;
-        if ((rc = spec_args(a, m)) != TRK_OK) return rc;
+    return unit_or_table(fn, e, m, nullptr, nullptr, stream, [&](SpecArgs& a) {
         a.q = q; a.n = n; a.gq = gq;
         if (mode == 0) a.fk_H = const_cast<float*>(gin); else a.link_pos = const_cast<float*>(gin);
-        return spec_launch(fn, e, a, m, stream);
-    }
-    SelMap selp;
-    for (int k = 0; k < TRK_MAX_LINKS; ++k) selp.col[k] = -1;
-    for (int p = 0; p < m->hdr.n_links; ++p) selp.col[p] = sel.col[m->links[p].link];
-    trk_launch_fk_backward(mode, m->hdr, m->d_links, m->d_fin, sel, selp, ns, q, gin, n, gq, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    }, [&] {
+        SelMap selp;
+        for (int k = 0; k < TRK_MAX_LINKS; ++k) selp.col[k] = -1;
+        for (int p = 0; p < m->hdr.n_links; ++p) selp.col[p] = sel.col[m->links[p].link];
+        trk_launch_fk_backward(mode, m->hdr, m->d_links, m->d_fin, sel, selp, ns, q, gin, n, gq, (hipStream_t)stream);
+    });
 }
 
 int trk_fk_backward(const TrkModel* m, const float* q, const float* gH, int64_t n, const int32_t* link_sel, int32_t n_sel, float* gq, trk_stream_t stream) {
@@ -1096,17 +1126,11 @@ int trk_fk_points(const TrkModel* m, const TrkPointSet* ps, const float* q, int6
     if (n < 0 || (n > 0 && (!pos_out || (!q && m->hdr.n_dofs > 0)))) return fail(TRK_ERR_INVALID_ARG, "trk_fk_points: bad q/out/n");
     if (trk_lds_fk_points(m->hdr, ps->dev.n_points, false) > kMaxLds) return fail(TRK_ERR_UNSUPPORTED, "trk_fk_points: point tile exceeds the 160 KiB LDS");
     if (n == 0) return TRK_OK;
+    // generated kernel with this point set baked in, all weights zero and no gradient output: FK + positions only
     const SpecEntry* e = enabled_points_spec(ps);
-    if (e && (reinterpret_cast<uintptr_t>(pos_out) & 15) == 0) {
-        // generated kernel with this point set baked in, all weights zero and no gradient output: FK + positions only
-        SpecArgs a;
-        if ((rc = spec_args(a, m)) != TRK_OK) return rc;
-        a.q = q; a.n = n; a.link_pos = pos_out;
-        return spec_launch(e->launch, e, a, m, stream);
-    }
-    trk_launch_fk_points(m->hdr, m->d_links, ps->dev, q, n, pos_out, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    const SpecLaunchFn fn = e && (reinterpret_cast<uintptr_t>(pos_out) & 15) == 0 ? e->launch : nullptr;
+    return unit_or_table(fn, e, m, nullptr, nullptr, stream, [&](SpecArgs& a) { a.q = q; a.n = n; a.link_pos = pos_out; },
+                         [&] { trk_launch_fk_points(m->hdr, m->d_links, ps->dev, q, n, pos_out, (hipStream_t)stream); });
 }
 
 int trk_fk_points_backward(const TrkModel* m, const TrkPointSet* ps, const float* q, const float* gpos, int64_t n, float* gq,
@@ -1118,15 +1142,10 @@ int trk_fk_points_backward(const TrkModel* m, const TrkPointSet* ps, const float
     if (trk_lds_fk_points(m->hdr, ps->dev.n_points, true) > kMaxLds) return fail(TRK_ERR_UNSUPPORTED, "trk_fk_points_backward: point tile exceeds the 160 KiB LDS");
     if (n == 0 || m->hdr.n_dofs == 0) return TRK_OK;
     const SpecEntry* e = enabled_points_spec(ps);
-    if (e && e->launch_posbwd && (reinterpret_cast<uintptr_t>(gpos) & 15) == 0) {
-        SpecArgs a;
-        if ((rc = spec_args(a, m)) != TRK_OK) return rc;
-        a.q = q; a.n = n; a.link_pos = const_cast<float*>(gpos); a.gq = gq;
-        return spec_launch(e->launch_posbwd, e, a, m, stream);
-    }
-    trk_launch_fk_points_backward(m->hdr, m->d_links, m->d_fin, ps->dev, q, gpos, n, gq, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    const SpecLaunchFn fn = e && (reinterpret_cast<uintptr_t>(gpos) & 15) == 0 ? e->launch_posbwd : nullptr;
+    return unit_or_table(fn, e, m, nullptr, nullptr, stream,
+                         [&](SpecArgs& a) { a.q = q; a.n = n; a.link_pos = const_cast<float*>(gpos); a.gq = gq; },
+                         [&] { trk_launch_fk_points_backward(m->hdr, m->d_links, m->d_fin, ps->dev, q, gpos, n, gq, (hipStream_t)stream); });
 }
 
 int trk_fk_jacobian(const TrkModel* m, const float* q, const float* qd, int64_t n, int32_t link, float* pos, float* quat,
@@ -1137,29 +1156,16 @@ int trk_fk_jacobian(const TrkModel* m, const float* q, const float* qd, int64_t 
     if (n < 0 || (n > 0 && (!q || !pos || !quat || !lin_jac || !ang_jac))) return fail(TRK_ERR_INVALID_ARG, "trk_fk_jacobian: null argument");
     if (n == 0) return TRK_OK;
     const SpecEntry* e = enabled_spec(m);
-    if (e && e->launch_jac && !vel_lin && !vel_ang) {
-        // generated kernel: the stateful walk unrolled with the URDF constants folded; the link velocities stay table-driven
-        SpecArgs a;
-        if ((rc = spec_args(a, m)) != TRK_OK) return rc;
+    // generated kernel: the stateful walk unrolled with the URDF constants folded; the link velocities stay table-driven
+    const SpecLaunchFn fn = e && !vel_lin && !vel_ang ? e->launch_jac : nullptr;
+    return unit_or_table(fn, e, m, nullptr, nullptr, stream, [&](SpecArgs& a) {
         a.q = q; a.n = n;
         bind_jacobian(a, m, link, pos, quat, lin_jac, ang_jac);
-        // which DOFs get a column and where the walk may stop (same rule as trk_launch_fk_jacobian: robot_tree.py:239-244)
-        a.jac_p_end = 1; a.jac_n_cols = 0;
-        for (int d = 0; d < TRK_MAX_DOFS; ++d) a.jac_slot[d] = -1;
-        for (int p = 0; p < m->hdr.n_links; ++p) {
-            const DevLink& Lk = m->links[p];
-            if (Lk.link == link) a.jac_p_end = std::max(a.jac_p_end, p + 1);
-            if (Lk.dof >= 0 && (Lk.link - 1) <= a.jac_joint_idx && Lk.jac_axis >= 0) {
-                a.jac_slot[Lk.dof] = (int8_t)a.jac_n_cols++;
-                a.jac_p_end = std::max(a.jac_p_end, p + 1);
-            }
-        }
-        return spec_launch(e->launch_jac, e, a, m, stream);
-    }
-    trk_launch_fk_jacobian(m->hdr, m->d_links, m->links.data(), q, qd, n, link, m->joint_list_idx[link], pos, quat, lin_jac, ang_jac,
-                           vel_lin, vel_ang, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+        trk_jacobian_columns(m->links.data(), m->hdr.n_links, link, a.jac_joint_idx, a.jac_slot, &a.jac_n_cols, &a.jac_p_end);
+    }, [&] {
+        trk_launch_fk_jacobian(m->hdr, m->d_links, m->links.data(), q, qd, n, link, m->joint_list_idx[link], pos, quat, lin_jac, ang_jac,
+                               vel_lin, vel_ang, (hipStream_t)stream);
+    });
 }
 
 int trk_fk_analytic_jacobian(const TrkModel* m, const float* q, int64_t n, float* J, trk_stream_t stream) {
@@ -1168,15 +1174,8 @@ int trk_fk_analytic_jacobian(const TrkModel* m, const float* q, int64_t n, float
     if (n < 0 || (n > 0 && (!J || (!q && m->hdr.n_dofs > 0)))) return fail(TRK_ERR_INVALID_ARG, "trk_fk_analytic_jacobian: bad q/J/n");
     if (n == 0 || m->hdr.n_dofs == 0) return TRK_OK;
     const SpecEntry* e = enabled_spec(m);
-    if (e && e->launch_ajac) {
-        SpecArgs a;
-        if ((rc = spec_args(a, m)) != TRK_OK) return rc;
-        a.q = q; a.n = n; a.jac_lin = J;
-        return spec_launch(e->launch_ajac, e, a, m, stream);
-    }
-    trk_launch_fk_analytic_jacobian(m->hdr, m->d_links, m->d_dofs, q, n, J, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return unit_or_table(e ? e->launch_ajac : nullptr, e, m, nullptr, nullptr, stream, [&](SpecArgs& a) { a.q = q; a.n = n; a.jac_lin = J; },
+                         [&] { trk_launch_fk_analytic_jacobian(m->hdr, m->d_links, m->d_dofs, q, n, J, (hipStream_t)stream); });
 }
 
 int trk_ik_steps(const TrkModel* m, int32_t link, const float* H_target, int32_t per_sample_target, const float* lower,
@@ -1191,14 +1190,9 @@ int trk_ik_steps(const TrkModel* m, int32_t link, const float* H_target, int32_t
     if (n == 0 || m->hdr.n_dofs == 0) return TRK_OK;
     // generated kernel (configurations and Adam state in registers) when the target is the link the unit tracks
     const SpecEntry* gen = enabled_spec(m);
-    if (gen && !(gen->launch_ik && gen->ee_link == link)) {
-        // the model's first unit tracks another link: a unit loaded for this link (jit.specialize(kin, obj_links, ee_link=link))
-        // serves it, found as trk_ik_gn_steps finds its unit
-        gen = nullptr;
-        for (const SpecEntry* e : spec_registry())
-            if (e->n_points == 0 && e->model_hash == m->hash && e->n_links == m->hdr.n_links && e->n_dofs == m->hdr.n_dofs &&
-                e->launch_ik && e->ee_link == link) { gen = e; break; }
-    }
+    // the model's first unit tracks another link: a unit loaded for this link (jit.specialize(kin, obj_links, ee_link=link))
+    // serves it, found as trk_ik_gn_steps finds its unit
+    if (gen && !(gen->launch_ik && gen->ee_link == link)) gen = unit_tracking(m, link, &SpecEntry::launch_ik);
     // at most TRK_IK_MAX_STEPS iterations per launch; loss / valid come from the first launch (q as the caller passed it)
     for (int32_t done = 0; done < n_steps; done += TRK_IK_MAX_STEPS) {
         const int32_t k = std::min<int32_t>(TRK_IK_MAX_STEPS, n_steps - done);
@@ -1210,18 +1204,17 @@ int trk_ik_steps(const TrkModel* m, int32_t link, const float* H_target, int32_t
         }
         if (gen) {
             IkArgs a{};
-            set_base_pose(a, m);
-            a.H_target = H_target; a.per_sample = per_sample_target; a.n_steps = k; a.lower = lower; a.upper = upper;
-            a.w_jl = w_joint_limits; a.se3_eps = se3_eps; a.lr = lr; a.sched = sched; a.n = n;
-            a.q = q; a.adam_m = adam_m; a.adam_v = adam_v;
-            a.loss = done == 0 ? loss : nullptr; a.valid = done == 0 ? valid : nullptr;
-            if ((rc = spec_launch(gen->launch_ik, gen, a, m, stream)) != TRK_OK) return rc;
-            continue;
+            fill_ik_args(a, m, H_target, per_sample_target, lower, upper, se3_eps, k, n, q, done == 0 ? valid : nullptr);
+            a.w_jl = w_joint_limits; a.lr = lr; a.sched = sched; a.adam_m = adam_m; a.adam_v = adam_v;
+            a.loss = done == 0 ? loss : nullptr;
+            rc = spec_launch(gen->launch_ik, gen, a, m, stream);
+        } else {
+            trk_launch_ik_step(m->hdr, m->d_links, m->d_fin, link, H_target, per_sample_target, lower, upper, w_joint_limits,
+                               se3_eps, lr, sched, k, n, q, adam_m, adam_v, done == 0 ? loss : nullptr, done == 0 ? valid : nullptr,
+                               (hipStream_t)stream);
+            rc = launched();
         }
-        trk_launch_ik_step(m->hdr, m->d_links, m->d_fin, link, H_target, per_sample_target, lower, upper, w_joint_limits,
-                           se3_eps, lr, sched, k, n, q, adam_m, adam_v, done == 0 ? loss : nullptr, done == 0 ? valid : nullptr,
-                           (hipStream_t)stream);
-        TRK_HIP(last_launch_error());
+        if (rc) return rc;
     }
     return TRK_OK;
 }
@@ -1238,20 +1231,14 @@ int trk_ik_gn_steps(const TrkModel* m, int32_t link, const float* H_target, int3
     if (n == 0 || m->hdr.n_dofs == 0) return TRK_OK;
     // the Jacobian, the normal equations and their factor live in one lane's registers: a generated kernel only, for the link a
     // unit tracks (any link of any robot up to 9 DOF is one jit.specialize away)
-    const SpecEntry* gen = nullptr;
-    if (m->spec_enabled)
-        for (const SpecEntry* e : spec_registry())
-            if (e->n_points == 0 && e->model_hash == m->hash && e->n_links == m->hdr.n_links && e->n_dofs == m->hdr.n_dofs &&
-                e->launch_ikgn && e->ee_link == link) { gen = e; break; }
+    const SpecEntry* gen = m->spec_enabled ? unit_tracking(m, link, &SpecEntry::launch_ikgn) : nullptr;
     if (!gen)
         return fail(TRK_ERR_UNSUPPORTED, "trk_ik_gn_steps: no generated unit of this model tracks this link (robots up to 9 DOF: "
                                          "torch_robotics_amd.jit.specialize(kin, obj_links, ee_link=link)); the two-launch form is "
                                          "trk_fk_jacobian + trk_jtj");
     IkGnArgs a{};
-    set_base_pose(a, m);
-    a.H_target = H_target; a.per_sample = per_sample_target; a.n_steps = n_steps; a.lower = lower; a.upper = upper;
-    a.damping = damping; a.lm_gain = lm_gain; a.step_scale = step_scale; a.se3_eps = se3_eps; a.n = n;
-    a.q = q; a.err = err; a.valid = valid;
+    fill_ik_args(a, m, H_target, per_sample_target, lower, upper, se3_eps, n_steps, n, q, valid);
+    a.damping = damping; a.lm_gain = lm_gain; a.step_scale = step_scale; a.err = err;
     return spec_launch(gen->launch_ikgn, gen, a, m, stream);
 }
 
@@ -1265,31 +1252,19 @@ int trk_ik_step(const TrkModel* m, int32_t link, const float* H_target, int32_t 
 int trk_rotmat_to_quat(const float* R, int64_t n, int32_t stride, int32_t row_pitch, float* quat, trk_stream_t stream) {
     if (n < 0 || stride < 9 || row_pitch < 3 || (n > 0 && (!R || !quat))) return fail(TRK_ERR_INVALID_ARG, "trk_rotmat_to_quat: bad argument");
     if (n == 0) return TRK_OK;
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_rotmat_to_quat(R, n, stride, row_pitch, quat, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { trk_launch_rotmat_to_quat(R, n, stride, row_pitch, quat, (hipStream_t)stream); });
 }
 
 int trk_rotation_from(int32_t kind, const float* in, int64_t n, float* R_out, trk_stream_t stream) {
     if (kind < TRK_ROT_X || kind > TRK_ROT_QUAT_WXYZ || n < 0 || (n > 0 && (!in || !R_out))) return fail(TRK_ERR_INVALID_ARG, "trk_rotation_from: bad argument");
     if (n == 0) return TRK_OK;
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_rotation_from(kind, in, n, R_out, nullptr, nullptr, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { trk_launch_rotation_from(kind, in, n, R_out, nullptr, nullptr, (hipStream_t)stream); });
 }
 
 int trk_rotation_from_backward(int32_t kind, const float* angle, const float* gR, int64_t n, float* gangle, trk_stream_t stream) {
     if (kind < TRK_ROT_X || kind > TRK_ROT_QUAT_WXYZ || n < 0 || (n > 0 && (!angle || !gR || !gangle))) return fail(TRK_ERR_INVALID_ARG, "trk_rotation_from_backward: bad argument");
     if (n == 0) return TRK_OK;
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_rotation_from(kind, angle, n, nullptr, gR, gangle, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { trk_launch_rotation_from(kind, angle, n, nullptr, gR, gangle, (hipStream_t)stream); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1305,12 +1280,9 @@ int trk_frame_compose(int32_t op, const float* Ra, const float* ta, int64_t na, 
     if (two && (na == 0 || nb == 0)) return TRK_OK;
     if (n == 0) return TRK_OK;
     if (!Ra || !ta || (two && (!Rb || !tb)) || !R_out || !t_out) return fail(TRK_ERR_INVALID_ARG, "trk_frame_compose: null pointer");
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_frame_compose(op, Ra, ta, two && na == 1 && n > 1, Rb, tb, two && nb == 1 && n > 1, n, R_out, t_out,
-                             (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] {
+        trk_launch_frame_compose(op, Ra, ta, two && na == 1 && n > 1, Rb, tb, two && nb == 1 && n > 1, n, R_out, t_out, (hipStream_t)stream);
+    });
 }
 
 int trk_frame_compose_backward(int32_t op, const float* Ra, const float* ta, const float* Rb, const float* tb, const float* gR,
@@ -1321,11 +1293,7 @@ int trk_frame_compose_backward(int32_t op, const float* Ra, const float* ta, con
     const bool two = op != TRK_FRAME_INVERSE;
     if (!Ra || !ta || !gR || !gt || !gRa || !gta || (two && (!Rb || !tb || !gRb || !gtb)))
         return fail(TRK_ERR_INVALID_ARG, "trk_frame_compose_backward: null pointer");
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_frame_compose_bwd(op, Ra, ta, Rb, tb, gR, gt, n, gRa, gta, gRb, gtb, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { trk_launch_frame_compose_bwd(op, Ra, ta, Rb, tb, gR, gt, n, gRa, gta, gRb, gtb, (hipStream_t)stream); });
 }
 
 int trk_frame_transform_points(const float* R, const float* t, int64_t n, const float* points, int32_t P, float* out,
@@ -1333,11 +1301,7 @@ int trk_frame_transform_points(const float* R, const float* t, int64_t n, const 
     if (n < 0 || P < 0) return fail(TRK_ERR_INVALID_ARG, "trk_frame_transform_points: negative size");
     if (n == 0 || P == 0) return TRK_OK;
     if (!R || !t || !points || !out) return fail(TRK_ERR_INVALID_ARG, "trk_frame_transform_points: null pointer");
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_frame_transform_points(R, t, n, points, P, out, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { trk_launch_frame_transform_points(R, t, n, points, P, out, (hipStream_t)stream); });
 }
 
 int trk_frame_transform_points_backward(const float* gout, int64_t n, const float* points, int32_t P, float* gR, float* gt,
@@ -1345,33 +1309,21 @@ int trk_frame_transform_points_backward(const float* gout, int64_t n, const floa
     if (n < 0 || P < 0) return fail(TRK_ERR_INVALID_ARG, "trk_frame_transform_points_backward: negative size");
     if (n == 0) return TRK_OK;
     if ((P > 0 && (!gout || !points)) || !gR || !gt) return fail(TRK_ERR_INVALID_ARG, "trk_frame_transform_points_backward: null pointer");
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_frame_transform_points_bwd(gout, n, points, P, gR, gt, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { trk_launch_frame_transform_points_bwd(gout, n, points, P, gR, gt, (hipStream_t)stream); });
 }
 
 int trk_frame_quat_euler(const float* R, int64_t n, int32_t stride, int32_t row_pitch, float* quat_xyzw, float* euler,
                          trk_stream_t stream) {
     if (n < 0 || stride < 9 || row_pitch < 3 || (n > 0 && !R)) return fail(TRK_ERR_INVALID_ARG, "trk_frame_quat_euler: bad argument");
     if (n == 0 || (!quat_xyzw && !euler)) return TRK_OK;
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_frame_quat_euler(R, n, stride, row_pitch, quat_xyzw, euler, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { trk_launch_frame_quat_euler(R, n, stride, row_pitch, quat_xyzw, euler, (hipStream_t)stream); });
 }
 
 int trk_frame_quat_euler_backward(const float* R, int64_t n, int32_t stride, int32_t row_pitch, const float* gquat_xyzw,
                                   const float* geuler, float* gR, trk_stream_t stream) {
     if (n < 0 || stride < 9 || row_pitch < 3 || (n > 0 && (!R || !gR))) return fail(TRK_ERR_INVALID_ARG, "trk_frame_quat_euler_backward: bad argument");
     if (n == 0) return TRK_OK;
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_frame_quat_euler_bwd(R, n, stride, row_pitch, gquat_xyzw, geuler, gR, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { trk_launch_frame_quat_euler_bwd(R, n, stride, row_pitch, gquat_xyzw, geuler, gR, (hipStream_t)stream); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1630,15 +1582,10 @@ int trk_cost_fields(const TrkCostModel* cm, int32_t fields, const float* link_po
     if (n < 0 || (n > 0 && (!link_pos || !cost)) || (fields & ~7) || !fields) return fail(TRK_ERR_INVALID_ARG, "trk_cost_fields: bad argument");
     if (n == 0) return TRK_OK;
     const TrkRolloutWeights w = effective_weights(cm, field_weights(fields, false));      // vacuous terms dropped, like the rollouts
-    if (const SpecEntry* e = fields_spec_for(cm, &w)) {      // the fused kernel's objective code on the caller's positions
-        SpecArgs a;
-        spec_args(a, nullptr, cm, &w);
-        a.n = n; a.fld_pos = link_pos; a.fld_gcost = gcost; a.fld_g = g_link_pos; a.cost = cost;
-        return spec_launch(e->launch_fields, e, a, nullptr, stream);
-    }
-    trk_launch_cost_fields(cm->hdr, fields, link_pos, n, gcost, cost, g_link_pos, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    const SpecEntry* e = fields_spec_for(cm, &w);             // the fused kernel's objective code on the caller's positions
+    return unit_or_table(e ? e->launch_fields : nullptr, e, nullptr, cm, &w, stream,
+                         [&](SpecArgs& a) { a.n = n; a.fld_pos = link_pos; a.fld_gcost = gcost; a.fld_g = g_link_pos; a.cost = cost; },
+                         [&] { trk_launch_cost_fields(cm->hdr, fields, link_pos, n, gcost, cost, g_link_pos, (hipStream_t)stream); });
 }
 
 int trk_collision_fields(const TrkCostModel* cm, int32_t fields, const float* link_pos, int64_t n, float margin_override,
@@ -1650,16 +1597,11 @@ int trk_collision_fields(const TrkCostModel* cm, int32_t fields, const float* li
     // the mask as given: neither effective_fields nor effective_weights is applied here (a vacuous field still asks for a unit
     // that bakes the cost model's empty set; its test finds nothing either way)
     const TrkRolloutWeights w = field_weights(fields, false);
-    if (const SpecEntry* e = fields_spec_for(cm, &w)) {      // the fused boolean kernel's tests on the caller's positions
-        SpecArgs a;
-        spec_args(a, nullptr, cm, &w);
-        a.n = n; a.fld_pos = link_pos;
-        bind_collision(a, in_collision, fields, margin_override);
-        return spec_launch(e->launch_fields, e, a, nullptr, stream);
-    }
-    trk_launch_collision_fields(cm->hdr, fields, link_pos, n, use_default ? 0.0f : margin_override, use_default, in_collision, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    const SpecEntry* e = fields_spec_for(cm, &w);             // the fused boolean kernel's tests on the caller's positions
+    return unit_or_table(e ? e->launch_fields : nullptr, e, nullptr, cm, &w, stream,
+                         [&](SpecArgs& a) { a.n = n; a.fld_pos = link_pos; bind_collision(a, in_collision, fields, margin_override); },
+                         [&] { trk_launch_collision_fields(cm->hdr, fields, link_pos, n, use_default ? 0.0f : margin_override, use_default,
+                                                           in_collision, (hipStream_t)stream); });
 }
 
 int trk_ee_cost(const TrkCostModel* cm, const float* H_ee, int64_t n, int64_t stride, const float* target, int32_t per_sample,
@@ -1669,8 +1611,7 @@ int trk_ee_cost(const TrkCostModel* cm, const float* H_ee, int64_t n, int64_t st
         return fail(TRK_ERR_INVALID_ARG, "trk_ee_cost: bad argument (strides must be multiples of 4 floats, >= 16)");
     if (n == 0) return TRK_OK;
     trk_launch_ee_cost(cm->hdr, H_ee, n, stride, target, per_sample, gcost, cost, gH, g_stride, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return launched();
 }
 
 static int rollout_impl(const char* who, const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w, int io_f16, float grad_scale,
@@ -1696,8 +1637,7 @@ static int rollout_impl(const char* who, const TrkModel* m, const TrkCostModel* 
     g_last_dispatch = TRK_DISPATCH_TABLE;
     if (trk_lds_rollout(m->hdr, m->hdr.n_links + cm->hdr.n_virtual) > kMaxLds) return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": position tiles (links + interpolated points) exceed the 160 KiB LDS");
     trk_launch_rollout_generic(m->hdr, m->d_links, m->d_fin, nullptr, cm->hdr, *w, io_f16, grad_scale, q, n, link_pos_out, cost, gq, cost_sum, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return launched();
 }
 
 int trk_last_dispatch(void) { return g_last_dispatch; }
@@ -1741,8 +1681,7 @@ int trk_rollout_collision(const TrkModel* m, const TrkCostModel* cm, int32_t fie
     rc = trk_fk_positions(m, q, n, nullptr, 0, link_pos_ws, stream);
     if (rc) return rc;
     trk_launch_collision_fields(cm->hdr, fields, link_pos_ws, n, use_default ? 0.0f : margin_override, use_default, in_collision, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return launched();
 }
 
 static int rollout_collision_via_impl(const TrkModel* m, const TrkCostModel* cm, int32_t fields, const float* x, int64_t n_traj,
@@ -1803,12 +1742,10 @@ int trk_traj_validate(const uint8_t* waypoint_collisions, const float* x, int64_
         (n_traj > 0 && (!x || !flags || !idx || (n_waypoints != 0 && !waypoint_collisions))))
         return fail(TRK_ERR_INVALID_ARG, "trk_traj_validate: bad argument");      // n_traj == 0: only the (zero) counters are written
     if (inner > 0 && n_traj % inner) return fail(TRK_ERR_INVALID_ARG, "trk_traj_validate: n_traj is not a multiple of the inner batch");
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_traj_validate(waypoint_collisions, x, n_traj, horizon, state_dim, n_waypoints, n_dofs, q_min, q_max, inner, flags,
-                             idx, counts, counts_host, ticket, gathered, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] {
+        trk_launch_traj_validate(waypoint_collisions, x, n_traj, horizon, state_dim, n_waypoints, n_dofs, q_min, q_max, inner, flags,
+                                 idx, counts, counts_host, ticket, gathered, (hipStream_t)stream);
+    });
 }
 
 int trk_rollout_jacobian_cost_grad(const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w, const float* q, int64_t batch,
@@ -1900,8 +1837,7 @@ int trk_rollout_gp_cost_grad(const TrkModel* m, const TrkCostModel* cm, const Tr
         return fail(TRK_ERR_UNSUPPORTED, std::string(who) + ": one trajectory (horizon x dof x 2 floats) must fit the 160 KiB LDS");
     trk_launch_gp_sample_cost(io_dtype == TRK_F16, q, qd, n, horizon, m->hdr.n_dofs, gp->dt, gp->sigma, gp->weight, cost, cost_sum,
                               (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return launched();
 }
 
 int trk_rollout_gp_adam_steps(const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w, const TrkGpPrior* gp,
@@ -2004,8 +1940,7 @@ int trk_rollout_points_cost_grad(const TrkModel* m, const TrkPointSet* ps, const
                                          "for the non-zero weights (or point_pos_out is not 16-byte aligned) -- the call would take the table-driven kernel");
     g_last_dispatch = TRK_DISPATCH_TABLE;
     trk_launch_rollout_generic(m->hdr, m->d_links, m->d_fin, &ps->dev, cm->hdr, *w, 0, 1.0f, q, n, point_pos_out, cost, gq, cost_sum, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return launched();
 }
 
 // Boolean mode of the attached-point models.  What both entry points check alike, in this order (nothing of a handle beyond its own
@@ -2084,11 +2019,7 @@ int trk_interpolate_via_points(const float* x, int64_t n_traj, int32_t horizon, 
     if (n_traj < 0 || horizon < 2 || dim < 1 || n_interp < 1 || !alpha || !beta || (n_traj > 0 && (!x || !out)))
         return fail(TRK_ERR_INVALID_ARG, "trk_interpolate_via_points: bad argument");
     if (n_traj == 0) return TRK_OK;
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_interpolate(x, n_traj, horizon, dim, n_interp, alpha, beta, out, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { trk_launch_interpolate(x, n_traj, horizon, dim, n_interp, alpha, beta, out, (hipStream_t)stream); });
 }
 
 int trk_jtj(const float* lin_jac, const float* ang_jac, const float* residual, int64_t n, int32_t dof, int32_t use_mfma,
@@ -2098,12 +2029,8 @@ int trk_jtj(const float* lin_jac, const float* ang_jac, const float* residual, i
         return fail(TRK_ERR_INVALID_ARG, "trk_jtj: bad argument");
     if (use_mfma && dof > 8) return fail(TRK_ERR_UNSUPPORTED, "trk_jtj: the MFMA kernel tiles an 8 x 8 matrix per sample (dof <= 8)");
     if (n == 0) return TRK_OK;
-    int rc = ensure_init();
-    if (rc) return rc;
-    if (trk_launch_jtj(use_mfma != 0, lin_jac, ang_jac, residual, n, dof, JtJ, Jtr, damping, damping_stride, dq, (hipStream_t)stream))
-        return fail(TRK_ERR_UNSUPPORTED, "trk_jtj: tiles exceed the 160 KiB LDS");
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { return trk_launch_jtj(use_mfma != 0, lin_jac, ang_jac, residual, n, dof, JtJ, Jtr, damping, damping_stride, dq,
+                                                   (hipStream_t)stream); }, "trk_jtj: tiles exceed the 160 KiB LDS");
 }
 
 int trk_scale_rows(const void* g, const float* scale, int32_t scale_stride, int64_t n, int32_t dim, int32_t io_dtype, void* out,
@@ -2112,11 +2039,7 @@ int trk_scale_rows(const void* g, const float* scale, int32_t scale_stride, int6
         (n > 0 && (!g || !scale || !out)))
         return fail(TRK_ERR_INVALID_ARG, "trk_scale_rows: bad argument");
     if (n == 0) return TRK_OK;
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_scale_rows(io_dtype == TRK_F16, g, scale, scale_stride, n, dim, out, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { trk_launch_scale_rows(io_dtype == TRK_F16, g, scale, scale_stride, n, dim, out, (hipStream_t)stream); });
 }
 
 int trk_interpolate_columns(const float* x, int64_t n, int32_t n_in, int32_t channels, int32_t n_out, const int32_t* src,
@@ -2124,11 +2047,7 @@ int trk_interpolate_columns(const float* x, int64_t n, int32_t n_in, int32_t cha
     if (n < 0 || n_in < 1 || channels < 1 || n_out < 1 || !src || !w || (n > 0 && (!x || !out)))
         return fail(TRK_ERR_INVALID_ARG, "trk_interpolate_columns: bad argument");
     if (n == 0) return TRK_OK;
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_interpolate_columns(x, n, n_in, channels, n_out, src, w, out, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { trk_launch_interpolate_columns(x, n, n_in, channels, n_out, src, w, out, (hipStream_t)stream); });
 }
 
 int trk_interpolate_columns_backward(const float* gout, int64_t n, int32_t n_in, int32_t channels, int32_t n_out, const int32_t* src,
@@ -2136,11 +2055,7 @@ int trk_interpolate_columns_backward(const float* gout, int64_t n, int32_t n_in,
     if (n < 0 || n_in < 1 || channels < 1 || n_out < 1 || !src || !w || (n > 0 && (!gout || !gx)))
         return fail(TRK_ERR_INVALID_ARG, "trk_interpolate_columns_backward: bad argument");
     if (n == 0) return TRK_OK;
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_interpolate_columns_bwd(gout, n, n_in, channels, n_out, src, w, gx, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { trk_launch_interpolate_columns_bwd(gout, n, n_in, channels, n_out, src, w, gx, (hipStream_t)stream); });
 }
 
 int trk_gp_prior_cost_grad(const void* q, const void* qd, int64_t batch, int32_t horizon, int32_t dof, int32_t io_dtype,
@@ -2153,13 +2068,9 @@ int trk_gp_prior_cost_grad(const void* q, const void* qd, int64_t batch, int32_t
         !std::isfinite(grad_scale))
         return fail(TRK_ERR_INVALID_ARG, "trk_gp_prior_cost_grad: grad_dtype must be TRK_F32 or (with fp16 trajectories) TRK_F16, grad_scale finite and > 0");
     if (batch == 0) return TRK_OK;
-    int rc = ensure_init();
-    if (rc) return rc;
-    if (trk_launch_gp_prior(io_dtype == TRK_F16, grad_dtype == TRK_F16, grad_scale, q, qd, batch, horizon, dof, dt, sigma, weight, cost, gq, gqd,
-                            accumulate, (hipStream_t)stream))
-        return fail(TRK_ERR_UNSUPPORTED, "trk_gp_prior_cost_grad: one trajectory (horizon x dof x 2 floats) must fit the 160 KiB LDS");
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { return trk_launch_gp_prior(io_dtype == TRK_F16, grad_dtype == TRK_F16, grad_scale, q, qd, batch, horizon, dof, dt,
+                                                        sigma, weight, cost, gq, gqd, accumulate, (hipStream_t)stream); },
+                       "trk_gp_prior_cost_grad: one trajectory (horizon x dof x 2 floats) must fit the 160 KiB LDS");
 }
 
 int trk_finite_difference(const float* x, int64_t batch, int32_t horizon, int32_t dim, float dt, int32_t method, float* out,
@@ -2167,11 +2078,7 @@ int trk_finite_difference(const float* x, int64_t batch, int32_t horizon, int32_
     if (batch < 0 || horizon < 1 || dim < 1 || method < 0 || method > 2 || !(dt != 0.0f) || (batch > 0 && (!x || !out)))
         return fail(TRK_ERR_INVALID_ARG, "trk_finite_difference: bad argument");
     if (batch == 0) return TRK_OK;
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_finite_difference(x, batch, horizon, dim, dt, method, out, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { trk_launch_finite_difference(x, batch, horizon, dim, dt, method, out, (hipStream_t)stream); });
 }
 
 int trk_traj_diff_norm_sum(const float* x, int64_t batch, int32_t horizon, int32_t state_dim, int32_t c0, int32_t dim, float* out,
@@ -2179,11 +2086,7 @@ int trk_traj_diff_norm_sum(const float* x, int64_t batch, int32_t horizon, int32
     if (batch < 0 || batch > 0x7fffffff || horizon < 1 || dim < 1 || c0 < 0 || c0 + dim > state_dim || (batch > 0 && (!x || !out)))
         return fail(TRK_ERR_INVALID_ARG, "trk_traj_diff_norm_sum: bad argument");
     if (batch == 0) return TRK_OK;
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_traj_diff_norm_sum(x, batch, horizon, state_dim, c0, dim, out, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { trk_launch_traj_diff_norm_sum(x, batch, horizon, state_dim, c0, dim, out, (hipStream_t)stream); });
 }
 
 int trk_debug_set_stamp_buffer(void* device_u64) {
@@ -2201,21 +2104,15 @@ int trk_pack_sums(const float* cost, const void* gq, int32_t grad_dtype, float g
     if (batch < 1 || batch > 0x7fffffff || horizon < 1 || dof < 1 || !cost || !gq || !cost_block_sums || !scratch || !packed ||
         (grad_dtype != TRK_F32 && grad_dtype != TRK_F16) || !(grad_scale > 0.0f) || !std::isfinite(grad_scale))
         return fail(TRK_ERR_INVALID_ARG, "trk_pack_sums: bad argument");
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_pack_sums(cost, gq, grad_dtype == TRK_F16, 1.0f / grad_scale, cost_block_sums, traj_cost, (int)batch, horizon, dof,
-                         (batch * horizon + 63) / 64, scratch, packed, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] {
+        trk_launch_pack_sums(cost, gq, grad_dtype == TRK_F16, 1.0f / grad_scale, cost_block_sums, traj_cost, (int)batch, horizon, dof,
+                             (batch * horizon + 63) / 64, scratch, packed, (hipStream_t)stream);
+    });
 }
 
 int trk_reduce_sum(const float* x, int64_t n, float* out, trk_stream_t stream) {
     if (n < 0 || !out || (n > 0 && !x)) return fail(TRK_ERR_INVALID_ARG, "trk_reduce_sum: bad argument");
-    int rc = ensure_init();
-    if (rc) return rc;
-    trk_launch_reduce_sum(x, n, out, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return run_utility([&] { trk_launch_reduce_sum(x, n, out, (hipStream_t)stream); });
 }
 
 int trk_grid_precompute(const TrkCostModel* cm, const int32_t dims[3], const float lim_min[3], const float lim_max[3],
@@ -2223,8 +2120,7 @@ int trk_grid_precompute(const TrkCostModel* cm, const int32_t dims[3], const flo
     if (!cm || !dims || !lim_min || !lim_max || !sdf || !grad) return fail(TRK_ERR_INVALID_ARG, "trk_grid_precompute: null argument");
     for (int k = 0; k < 3; ++k) if (dims[k] < 1) return fail(TRK_ERR_INVALID_ARG, "trk_grid_precompute: bad dims");
     trk_launch_grid_precompute(cm->hdr, dims, lim_min, lim_max, sdf, grad, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return launched();
 }
 
 int trk_sdf_points(const TrkCostModel* cm, const float* points, int64_t n, float* sdf, float* grad, trk_stream_t stream) {
@@ -2232,8 +2128,7 @@ int trk_sdf_points(const TrkCostModel* cm, const float* points, int64_t n, float
     if (n < 0 || (n > 0 && (!points || !sdf))) return fail(TRK_ERR_INVALID_ARG, "trk_sdf_points: bad argument");
     if (n == 0 || cm->hdr.n_objects == 0) return TRK_OK;
     trk_launch_sdf_points(cm->hdr, points, n, sdf, grad, (hipStream_t)stream);
-    TRK_HIP(last_launch_error());
-    return TRK_OK;
+    return launched();
 }
 
 }  // extern "C"

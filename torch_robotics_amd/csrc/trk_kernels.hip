@@ -2389,18 +2389,8 @@ void trk_launch_fk_points_backward(const DevModelHdr& hdr, const DevLink* links,
 void trk_launch_fk_jacobian(const DevModelHdr& hdr, const DevLink* links_dev, const DevLink* links_host, const float* q,
                             const float* qd, int64_t n, int link, int link_joint_idx, float* pos, float* quat,
                             float* lin_jac, float* ang_jac, float* vel_lin, float* vel_ang, hipStream_t st) {
-    // which DOFs get a column (robot_tree.py:239-244, the reference's serial-chain rule applied to every visited link)
     JacCols cols;
-    for (int d = 0; d < TRK_MAX_DOFS; ++d) cols.slot[d] = -1;
-    cols.n_cols = 0; cols.p_end = 1;
-    for (int p = 0; p < hdr.n_links; ++p) {
-        const DevLink& Lk = links_host[p];
-        if (Lk.link == link) cols.p_end = std::max(cols.p_end, p + 1);
-        if (Lk.dof >= 0 && (Lk.link - 1) <= link_joint_idx && Lk.jac_axis >= 0) {
-            cols.slot[Lk.dof] = (int8_t)cols.n_cols++;
-            cols.p_end = std::max(cols.p_end, p + 1);
-        }
-    }
+    trk_jacobian_columns(links_host, hdr.n_links, link, link_joint_idx, cols.slot, &cols.n_cols, &cols.p_end);
     const int rstride = (6 * cols.n_cols + 3) | 1;
     size_t lds = sizeof(float) * ((size_t)TRK_WAVE * hdr.n_dofs * (qd ? 2 : 1) + (size_t)hdr.n_slots * (qd ? 18 : 12) * TRK_WAVE +
                                   (size_t)TRK_WAVE * rstride + TRK_MAX_DOFS);

@@ -30,6 +30,29 @@ void trk_launch_fk_points_backward(const DevModelHdr& hdr, const DevLink* links,
                                    const float* q, const float* gin, int64_t n, float* gq, hipStream_t st);
 size_t trk_lds_rollout(const DevModelHdr& hdr, int n_cols);                 // dynamic LDS bytes a launch needs
 size_t trk_lds_fk_points(const DevModelHdr& hdr, int n_points, bool backward);
+// The pre-order position after `link` in the host link table (by position): where a walk that needs this link alone may stop.
+inline int trk_walk_end(const DevLink* links_host, int n_links, int link) {
+    int p_end = 1;
+    for (int p = 0; p < n_links; ++p) if (links_host[p].link == link) p_end = p + 1;
+    return p_end;
+}
+// The Jacobian column rule (robot_tree.py:239-244, the reference's serial-chain rule applied to every visited link), stated once for
+// the table-driven kernel (JacCols) and the generated ones (SpecArgs::jac_*): slot[d] = the record slot of DOF d's column in walk
+// order (-1: the column stays zero), their number, and the position after which the walk may stop -- past `link` and past every
+// joint that gets a column.
+inline void trk_jacobian_columns(const DevLink* links_host, int n_links, int link, int link_joint_idx, int8_t* slot, int32_t* n_cols,
+                                 int32_t* p_end) {
+    for (int d = 0; d < TRK_MAX_DOFS; ++d) slot[d] = -1;
+    *n_cols = 0;
+    *p_end = trk_walk_end(links_host, n_links, link);
+    for (int p = 0; p < n_links; ++p) {
+        const DevLink& Lk = links_host[p];
+        if (Lk.dof >= 0 && (Lk.link - 1) <= link_joint_idx && Lk.jac_axis >= 0) {
+            slot[Lk.dof] = (int8_t)(*n_cols)++;
+            if (*p_end < p + 1) *p_end = p + 1;
+        }
+    }
+}
 void trk_launch_fk_jacobian(const DevModelHdr& hdr, const DevLink* links_dev, const DevLink* links_host, const float* q,
                             const float* qd, int64_t n, int link, int link_joint_idx, float* pos, float* quat,
                             float* lin_jac, float* ang_jac, float* vel_lin, float* vel_ang, hipStream_t st);

@@ -157,6 +157,15 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _call(name: str, device: torch.device, *args) -> None:
+    """One C call of a plain wrapper: `lib().<name>(*args, stream)` on `device` and torch's current stream there; a failure is
+    reported under `name`.  (The rollouts, the plans and `PackedSums.pack` keep a call of their own: see HISTORY.md, round 21.)"""
+    with _on(device):
+        rc = getattr(lib(), name)(*args, _stream_of(device))
+    if rc:
+        check(rc, name)
+
+
 def _lead_batch_horizon(q: torch.Tensor, n_dofs: int):
     """q (B,H,D) or (N,D) -> (q as the C ABI reads it, leading shape of the results, B, H): an (N,D) batch is N trajectories of one step."""
     lead = tuple(q.shape[:-1])
@@ -372,28 +381,23 @@ def fk_positions(model: ModelHandle, q: torch.Tensor, sel=None) -> torch.Tensor:
     return pos
 
 
-def fk_backward(model: ModelHandle, q: torch.Tensor, gH: torch.Tensor, sel=None) -> torch.Tensor:
-    q = _dev_f32(q, "fk_backward(q)").reshape(-1, model.n_dofs)
-    gH = _dev_f32(gH, "fk_backward(gH)")
-    n = q.shape[0]
-    p, ns, keep = _sel(sel)
+def _fk_reverse(name: str, gname: str, model: ModelHandle, heads, q: torch.Tensor, g: torch.Tensor, *sel) -> torch.Tensor:
+    """What the three FK reverse modes do alike (trk_<name>): q (N, D) and the adjoint `gname` as fp32 device tensors, the link
+    selection of an entry that takes one (`sel`: none or one argument), gq like q, the call behind the leading handles `heads`."""
+    q = _dev_f32(q, f"{name}(q)").reshape(-1, model.n_dofs)
+    g = _dev_f32(g, f"{name}({gname})")
+    p, ns, keep = _sel(*sel) if sel else (None, 0, None)
     gq = torch.empty_like(q)            # the kernel writes every element (zeros where the reference clamps)
-    with _on(q.device):
-        check(lib().trk_fk_backward(model._h, q.data_ptr(), gH.data_ptr(), n, p, ns, gq.data_ptr(), _stream(q)),
-              "trk_fk_backward")
+    _call("trk_" + name, q.device, *heads, q.data_ptr(), g.data_ptr(), q.shape[0], *((p, ns) if sel else ()), gq.data_ptr())
     return gq
+
+
+def fk_backward(model: ModelHandle, q: torch.Tensor, gH: torch.Tensor, sel=None) -> torch.Tensor:
+    return _fk_reverse("fk_backward", "gH", model, (model._h,), q, gH, sel)
 
 
 def fk_positions_backward(model: ModelHandle, q: torch.Tensor, gpos: torch.Tensor, sel=None) -> torch.Tensor:
-    q = _dev_f32(q, "fk_positions_backward(q)").reshape(-1, model.n_dofs)
-    gpos = _dev_f32(gpos, "fk_positions_backward(gpos)")
-    n = q.shape[0]
-    p, ns, keep = _sel(sel)
-    gq = torch.empty_like(q)            # the kernel writes every element (zeros where the reference clamps)
-    with _on(q.device):
-        check(lib().trk_fk_positions_backward(model._h, q.data_ptr(), gpos.data_ptr(), n, p, ns, gq.data_ptr(),
-                                              _stream(q)), "trk_fk_positions_backward")
-    return gq
+    return _fk_reverse("fk_positions_backward", "gpos", model, (model._h,), q, gpos, sel)
 
 
 def fk_points(ps: PointSetHandle, q: torch.Tensor) -> torch.Tensor:
@@ -408,14 +412,7 @@ def fk_points(ps: PointSetHandle, q: torch.Tensor) -> torch.Tensor:
 
 
 def fk_points_backward(ps: PointSetHandle, q: torch.Tensor, gpos: torch.Tensor) -> torch.Tensor:
-    model = ps.model
-    q = _dev_f32(q, "fk_points_backward(q)").reshape(-1, model.n_dofs)
-    gpos = _dev_f32(gpos, "fk_points_backward(gpos)")
-    gq = torch.empty_like(q)            # the kernel writes every element (zeros where the reference clamps)
-    with _on(q.device):
-        check(lib().trk_fk_points_backward(model._h, ps._h, q.data_ptr(), gpos.data_ptr(), q.shape[0], gq.data_ptr(),
-                                           _stream(q)), "trk_fk_points_backward")
-    return gq
+    return _fk_reverse("fk_points_backward", "gpos", ps.model, (ps.model._h, ps._h), q, gpos)
 
 
 def fk_jacobian(model: ModelHandle, q: torch.Tensor, qd: Optional[torch.Tensor], link: int, want_vel=False):
@@ -427,9 +424,8 @@ def fk_jacobian(model: ModelHandle, q: torch.Tensor, qd: Optional[torch.Tensor],
     lin, ang = torch.empty((n, 3, D), **kw), torch.empty((n, 3, D), **kw)
     vl = torch.empty((n, 3), **kw) if want_vel else None
     va = torch.empty((n, 3), **kw) if want_vel else None
-    with _on(q.device):
-        check(lib().trk_fk_jacobian(model._h, q.data_ptr(), _ptr(qd_t), n, int(link), pos.data_ptr(), quat.data_ptr(),
-                                    lin.data_ptr(), ang.data_ptr(), _ptr(vl), _ptr(va), _stream(q)), "trk_fk_jacobian")
+    _call("trk_fk_jacobian", q.device, model._h, q.data_ptr(), _ptr(qd_t), n, int(link), pos.data_ptr(), quat.data_ptr(),
+          lin.data_ptr(), ang.data_ptr(), _ptr(vl), _ptr(va))
     return (pos, quat, lin, ang, vl, va) if want_vel else (pos, quat, lin, ang)
 
 
@@ -460,8 +456,7 @@ def fk_analytic_jacobian(model: ModelHandle, q: torch.Tensor) -> torch.Tensor:
     q = _dev_f32(q, "fk_analytic_jacobian(q)").reshape(-1, model.n_dofs)
     n = q.shape[0]
     J = torch.empty((n, model.n_links, 7, model.n_dofs), device=q.device, dtype=torch.float32)
-    with _on(q.device):
-        check(lib().trk_fk_analytic_jacobian(model._h, q.data_ptr(), n, J.data_ptr(), _stream(q)), "trk_fk_analytic_jacobian")
+    _call("trk_fk_analytic_jacobian", q.device, model._h, q.data_ptr(), n, J.data_ptr())
     return J
 
 
@@ -487,20 +482,24 @@ def _check_ik_buffers(who, model, q, lower, upper, adam_m, adam_v, loss, valid):
     return n, D
 
 
+def _ik_target(who: str, H_target: torch.Tensor, n: int):
+    """(target as an fp32 device tensor, per_sample): one (4, 4) target for the batch, or (n, 4, 4) with one per sample"""
+    Ht = _dev_f32(H_target, f"{who}(H_target)")
+    per_sample = int(Ht.dim() == 3)
+    if per_sample and Ht.shape[0] != n:
+        raise ValueError(f"{who}: per-sample target batch mismatch")
+    return Ht, per_sample
+
+
 def ik_step(model: ModelHandle, link: int, H_target: torch.Tensor, lower: torch.Tensor, upper: torch.Tensor,
             q: torch.Tensor, adam_m: Optional[torch.Tensor], adam_v: Optional[torch.Tensor], step: int, lr: float = 1e-2,
             w_joint_limits: float = 300.0, se3_eps: float = 1e-1, loss: Optional[torch.Tensor] = None,
             valid: Optional[torch.Tensor] = None) -> None:
     """One fused IK iteration IN PLACE on q / adam_m / adam_v (all (N, D) float32 contiguous CUDA tensors)."""
     n, D = _check_ik_buffers("ik_step", model, q, lower, upper, adam_m, adam_v, loss, valid)
-    Ht = _dev_f32(H_target, "ik_step(H_target)")
-    per_sample = int(Ht.dim() == 3)
-    if per_sample and Ht.shape[0] != n:
-        raise ValueError("ik_step: per-sample target batch mismatch")
-    with _on(q.device):
-        check(lib().trk_ik_step(model._h, int(link), Ht.data_ptr(), per_sample, lower.data_ptr(), upper.data_ptr(),
-                                float(w_joint_limits), float(se3_eps), float(lr), int(step), n, q.data_ptr(),
-                                _ptr(adam_m), _ptr(adam_v), _ptr(loss), _ptr(valid), _stream(q)), "trk_ik_step")
+    Ht, per_sample = _ik_target("ik_step", H_target, n)
+    _call("trk_ik_step", q.device, model._h, int(link), Ht.data_ptr(), per_sample, lower.data_ptr(), upper.data_ptr(),
+          float(w_joint_limits), float(se3_eps), float(lr), int(step), n, q.data_ptr(), _ptr(adam_m), _ptr(adam_v), _ptr(loss), _ptr(valid))
 
 
 def ik_steps(model: ModelHandle, link: int, H_target: torch.Tensor, lower: torch.Tensor, upper: torch.Tensor,
@@ -512,14 +511,10 @@ def ik_steps(model: ModelHandle, link: int, H_target: torch.Tensor, lower: torch
     n, D = _check_ik_buffers("ik_steps", model, q, lower, upper, adam_m, adam_v, loss, valid)
     if adam_m is None or adam_v is None:
         raise ValueError("ik_steps: adam_m and adam_v are required")
-    Ht = _dev_f32(H_target, "ik_steps(H_target)")
-    per_sample = int(Ht.dim() == 3)
-    if per_sample and Ht.shape[0] != n:
-        raise ValueError("ik_steps: per-sample target batch mismatch")
-    with _on(q.device):
-        check(lib().trk_ik_steps(model._h, int(link), Ht.data_ptr(), per_sample, lower.data_ptr(), upper.data_ptr(),
-                                 float(w_joint_limits), float(se3_eps), float(lr), int(first_step), int(n_steps), n, q.data_ptr(),
-                                 adam_m.data_ptr(), adam_v.data_ptr(), _ptr(loss), _ptr(valid), _stream(q)), "trk_ik_steps")
+    Ht, per_sample = _ik_target("ik_steps", H_target, n)
+    _call("trk_ik_steps", q.device, model._h, int(link), Ht.data_ptr(), per_sample, lower.data_ptr(), upper.data_ptr(),
+          float(w_joint_limits), float(se3_eps), float(lr), int(first_step), int(n_steps), n, q.data_ptr(), adam_m.data_ptr(),
+          adam_v.data_ptr(), _ptr(loss), _ptr(valid))
 
 
 def ik_gn_steps(model: ModelHandle, link: int, H_target: torch.Tensor, lower: torch.Tensor, upper: torch.Tensor, q: torch.Tensor,
@@ -529,85 +524,55 @@ def ik_gn_steps(model: ModelHandle, link: int, H_target: torch.Tensor, lower: to
     q (N,D) <- clamp(q + step_scale (J^T J + (damping + lm_gain |r|^2) I)^-1 J^T r, lower, upper) per iteration, the Jacobian in
     registers.  err (N,) / valid (N, bool or uint8): SE3 distance / validity of q as passed in."""
     n, D = _check_ik_buffers("ik_gn_steps", model, q, lower, upper, None, None, err, valid)
-    Ht = _dev_f32(H_target, "ik_gn_steps(H_target)")
-    per_sample = int(Ht.dim() == 3)
-    if per_sample and Ht.shape[0] != n:
-        raise ValueError("ik_gn_steps: per-sample target batch mismatch")
-    with _on(q.device):
-        check(lib().trk_ik_gn_steps(model._h, int(link), Ht.data_ptr(), per_sample, lower.data_ptr(), upper.data_ptr(), float(damping),
-                                    float(lm_gain), float(step_scale), float(se3_eps), int(n_steps), n, q.data_ptr(), _ptr(err),
-                                    _ptr(valid), _stream(q)), "trk_ik_gn_steps")
+    Ht, per_sample = _ik_target("ik_gn_steps", H_target, n)
+    _call("trk_ik_gn_steps", q.device, model._h, int(link), Ht.data_ptr(), per_sample, lower.data_ptr(), upper.data_ptr(), float(damping),
+          float(lm_gain), float(step_scale), float(se3_eps), int(n_steps), n, q.data_ptr(), _ptr(err), _ptr(valid))
 
 
 @host_round_trip
 def rotmat_to_quat(R: torch.Tensor) -> torch.Tensor:
     """rotation_matrix_to_q on (..., 3, 3) rotations or (..., 4, 4) transforms -> (..., 4) wxyz."""
     R = _dev_f32(R, "rotmat_to_quat(R)")
-    if R.shape[-2:] == (3, 3):
-        stride, pitch = 9, 3
-    elif R.shape[-2:] == (4, 4):
-        stride, pitch = 16, 4
-    else:
-        raise ValueError("rotmat_to_quat: expected (...,3,3) or (...,4,4)")
-    batch = R.shape[:-2]
-    n = int(np.prod(batch)) if len(batch) else 1
-    out = torch.empty(tuple(batch) + (4,), device=R.device, dtype=torch.float32)
-    with _on(R.device):
-        check(lib().trk_rotmat_to_quat(R.data_ptr(), n, stride, pitch, out.data_ptr(), _stream(R)), "trk_rotmat_to_quat")
+    stride, pitch, batch, n = _rot_layout(R, "rotmat_to_quat")
+    out = torch.empty(batch + (4,), device=R.device, dtype=torch.float32)
+    _call("trk_rotmat_to_quat", R.device, R.data_ptr(), n, stride, pitch, out.data_ptr())
     return out
 
 
-class _AxisRotation(torch.autograd.Function):
+_ROT_QUAT = 3          # TRK_ROT_QUAT_WXYZ; 0 / 1 / 2: an angle about x / y / z
+
+
+def _rotation_raw(kind: int, x: torch.Tensor) -> torch.Tensor:
+    """trk_rotation_from: x (n,) angles or (n, 4) wxyz quaternions -> (n, 3, 3)"""
+    n = int(x.shape[0])
+    R = torch.empty((n, 3, 3), device=x.device, dtype=torch.float32)
+    _call("trk_rotation_from", x.device, kind, x.data_ptr(), n, R.data_ptr())
+    return R
+
+
+class _Rotation(torch.autograd.Function):
+    """The axis rotations and the quaternion's rotation, keyed by `kind`, with trk_rotation_from_backward as reverse mode."""
+
     @staticmethod
-    def forward(ctx, kind, angle):
-        n = int(angle.shape[0])
-        R = torch.empty((n, 3, 3), device=angle.device, dtype=torch.float32)
-        with _on(angle.device):
-            check(lib().trk_rotation_from(kind, angle.data_ptr(), n, R.data_ptr(), _stream(angle)), "trk_rotation_from")
+    def forward(ctx, kind, x):
         ctx.kind = kind
-        ctx.save_for_backward(angle)
-        return R
+        ctx.save_for_backward(x)
+        return _rotation_raw(kind, x)
 
     @staticmethod
     def backward(ctx, gR):
-        (angle,) = ctx.saved_tensors
-        gR = _dev_f32(gR, "axis rotation backward")
-        ga = torch.empty_like(angle)
-        with _on(angle.device):
-            check(lib().trk_rotation_from_backward(ctx.kind, angle.data_ptr(), gR.data_ptr(), int(angle.shape[0]), ga.data_ptr(),
-                                                   _stream(angle)), "trk_rotation_from_backward")
-        return None, ga
+        (x,) = ctx.saved_tensors
+        gR = _dev_f32(gR, "quat_to_rotmat backward" if ctx.kind == _ROT_QUAT else "axis rotation backward")
+        gx = torch.empty_like(x)
+        _call("trk_rotation_from_backward", x.device, ctx.kind, x.data_ptr(), gR.data_ptr(), int(x.shape[0]), gx.data_ptr())
+        return None, gx
 
 
 @host_round_trip
 def axis_rotation(kind: int, angle: torch.Tensor) -> torch.Tensor:
     """x_rot / y_rot / z_rot (kind 0 / 1 / 2; spatial_vector.py:8-47): angles (n,) | (n,1) | () -> (n,3,3); differentiable."""
     a = _dev_f32(angle, "axis_rotation(angle)").reshape(-1)
-    return _AxisRotation.apply(int(kind), a)
-
-
-def _quat_to_rotmat_raw(flat: torch.Tensor) -> torch.Tensor:
-    R = torch.empty((flat.shape[0], 3, 3), device=flat.device, dtype=torch.float32)
-    with _on(flat.device):
-        check(lib().trk_rotation_from(3, flat.data_ptr(), int(flat.shape[0]), R.data_ptr(), _stream(flat)), "trk_rotation_from")
-    return R
-
-
-class _QuatRotation(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, flat):
-        ctx.save_for_backward(flat)
-        return _quat_to_rotmat_raw(flat)
-
-    @staticmethod
-    def backward(ctx, gR):
-        (flat,) = ctx.saved_tensors
-        gR = _dev_f32(gR, "quat_to_rotmat backward")
-        gq = torch.empty_like(flat)
-        with _on(flat.device):
-            check(lib().trk_rotation_from_backward(3, flat.data_ptr(), gR.data_ptr(), int(flat.shape[0]), gq.data_ptr(),
-                                                   _stream(flat)), "trk_rotation_from_backward")
-        return gq
+    return _Rotation.apply(int(kind), a)
 
 
 @host_round_trip
@@ -620,9 +585,9 @@ def quat_to_rotmat(q: torch.Tensor) -> torch.Tensor:
     lead = q.shape[:-1]
     flat = q.reshape(-1, 4).contiguous()
     if torch.is_grad_enabled() and flat.requires_grad:
-        R = _QuatRotation.apply(flat)
+        R = _Rotation.apply(_ROT_QUAT, flat)
     else:
-        R = _quat_to_rotmat_raw(flat)
+        R = _rotation_raw(_ROT_QUAT, flat)
     return R.reshape(tuple(lead) + (3, 3))
 
 
@@ -647,9 +612,7 @@ def _frame_compose_raw(op, Ra, ta, Rb, tb):
     n = na if op == FRAME_INVERSE else max(na, nb)
     Ro = torch.empty((n, 3, 3), device=Ra.device, dtype=torch.float32)
     to = torch.empty((n, 3), device=Ra.device, dtype=torch.float32)
-    with _on(Ra.device):
-        check(lib().trk_frame_compose(op, Ra.data_ptr(), ta.data_ptr(), na, _ptr(Rb), _ptr(tb), nb, Ro.data_ptr(),
-                                      to.data_ptr(), _stream(Ra)), "trk_frame_compose")
+    _call("trk_frame_compose", Ra.device, op, Ra.data_ptr(), ta.data_ptr(), na, _ptr(Rb), _ptr(tb), nb, Ro.data_ptr(), to.data_ptr())
     return Ro, to
 
 
@@ -669,11 +632,8 @@ class _FrameCompose(torch.autograd.Function):
         gRa, gta = torch.empty_like(Ra), torch.empty_like(ta)
         two = ctx.op != FRAME_INVERSE
         gRb, gtb = (torch.empty_like(Rb), torch.empty_like(tb)) if two else (None, None)
-        with _on(Ra.device):
-            check(lib().trk_frame_compose_backward(ctx.op, Ra.data_ptr(), ta.data_ptr(), _ptr(Rb) if two else None,
-                                                   _ptr(tb) if two else None, gR.data_ptr(), gt.data_ptr(), n, gRa.data_ptr(),
-                                                   gta.data_ptr(), _ptr(gRb), _ptr(gtb), _stream(Ra)),
-                  "trk_frame_compose_backward")
+        _call("trk_frame_compose_backward", Ra.device, ctx.op, Ra.data_ptr(), ta.data_ptr(), _ptr(Rb) if two else None,
+              _ptr(tb) if two else None, gR.data_ptr(), gt.data_ptr(), n, gRa.data_ptr(), gta.data_ptr(), _ptr(gRb), _ptr(gtb))
         return None, gRa, gta, gRb, gtb
 
 
@@ -702,9 +662,7 @@ class _FrameTransformPoints(torch.autograd.Function):
     def forward(ctx, R, t, pts):
         n, P = int(R.shape[0]), int(pts.shape[0])
         out = torch.empty((n, P, 3), device=R.device, dtype=torch.float32)
-        with _on(R.device):
-            check(lib().trk_frame_transform_points(R.data_ptr(), t.data_ptr(), n, pts.data_ptr(), P, out.data_ptr(), _stream(R)),
-                  "trk_frame_transform_points")
+        _call("trk_frame_transform_points", R.device, R.data_ptr(), t.data_ptr(), n, pts.data_ptr(), P, out.data_ptr())
         ctx.save_for_backward(pts)
         ctx.n = n
         return out
@@ -715,10 +673,8 @@ class _FrameTransformPoints(torch.autograd.Function):
         g = _dev_f32(g, "transform_point backward")
         gR = torch.empty((ctx.n, 3, 3), device=g.device, dtype=torch.float32)
         gt = torch.empty((ctx.n, 3), device=g.device, dtype=torch.float32)
-        with _on(g.device):
-            check(lib().trk_frame_transform_points_backward(g.data_ptr(), ctx.n, pts.data_ptr(), int(pts.shape[0]),
-                                                            gR.data_ptr(), gt.data_ptr(), _stream(g)),
-                  "trk_frame_transform_points_backward")
+        _call("trk_frame_transform_points_backward", g.device, g.data_ptr(), ctx.n, pts.data_ptr(), int(pts.shape[0]), gR.data_ptr(),
+              gt.data_ptr())
         return gR, gt, None
 
 
@@ -748,8 +704,7 @@ def _frame_quat_euler_raw(R, want_quat, want_euler):
     stride, pitch, batch, n = _rot_layout(R, "frame_quat_euler")
     quat = torch.empty(batch + (4,), device=R.device, dtype=torch.float32) if want_quat else None
     eul = torch.empty(batch + (3,), device=R.device, dtype=torch.float32) if want_euler else None
-    with _on(R.device):
-        check(lib().trk_frame_quat_euler(R.data_ptr(), n, stride, pitch, _ptr(quat), _ptr(eul), _stream(R)), "trk_frame_quat_euler")
+    _call("trk_frame_quat_euler", R.device, R.data_ptr(), n, stride, pitch, _ptr(quat), _ptr(eul))
     return quat, eul
 
 
@@ -771,9 +726,7 @@ class _FrameQuatEuler(torch.autograd.Function):
         ge = None if ge is None else _dev_f32(ge, "frame_quat_euler backward")
         stride, pitch, batch, n = _rot_layout(R, "frame_quat_euler")
         g9 = torch.empty((n, 3, 3), device=R.device, dtype=torch.float32)
-        with _on(R.device):
-            check(lib().trk_frame_quat_euler_backward(R.data_ptr(), n, stride, pitch, _ptr(gq), _ptr(ge), g9.data_ptr(),
-                                                      _stream(R)), "trk_frame_quat_euler_backward")
+        _call("trk_frame_quat_euler_backward", R.device, R.data_ptr(), n, stride, pitch, _ptr(gq), _ptr(ge), g9.data_ptr())
         if pitch == 3:
             return g9.reshape(R.shape), None, None
         gR = torch.zeros_like(R)                      # 4x4 transforms: only the rotation block receives a gradient
@@ -800,9 +753,7 @@ def cost_fields(cm: CostHandle, fields: int, link_pos: torch.Tensor, gcost: Opti
     cost = torch.empty((n,), device=link_pos.device, dtype=torch.float32)
     g = torch.empty_like(link_pos) if want_grad else None
     gc = None if gcost is None else _dev_f32(gcost, "cost_fields(gcost)").reshape(n)
-    with _on(link_pos.device):
-        check(lib().trk_cost_fields(cm._h, int(fields), link_pos.data_ptr(), n, _ptr(gc), cost.data_ptr(), _ptr(g),
-                                    _stream(link_pos)), "trk_cost_fields")
+    _call("trk_cost_fields", link_pos.device, cm._h, int(fields), link_pos.data_ptr(), n, _ptr(gc), cost.data_ptr(), _ptr(g))
     return (cost, g) if want_grad else cost
 
 
@@ -810,10 +761,8 @@ def collision_fields(cm: CostHandle, fields: int, link_pos: torch.Tensor, margin
     link_pos = _dev_f32(link_pos, "collision_fields(link_pos)").reshape(-1, cm.n_links_in, 3)
     n = link_pos.shape[0]
     out = torch.empty((n,), device=link_pos.device, dtype=torch.bool)       # the kernel writes 0 / 1 bytes
-    with _on(link_pos.device):
-        check(lib().trk_collision_fields(cm._h, int(fields), link_pos.data_ptr(), n,
-                                         float("nan") if margin is None else float(margin), out.data_ptr(),
-                                         _stream(link_pos)), "trk_collision_fields")
+    _call("trk_collision_fields", link_pos.device, cm._h, int(fields), link_pos.data_ptr(), n,
+          float("nan") if margin is None else float(margin), out.data_ptr())
     return out
 
 
@@ -831,9 +780,7 @@ def ee_cost(cm: CostHandle, H: torch.Tensor, target: Optional[torch.Tensor] = No
     cost = torch.empty((n,), device=H.device, dtype=torch.float32)
     gH = torch.empty_like(H) if want_grad else None      # all 16 entries are written (bottom row: zeros)
     gc = None if gcost is None else _dev_f32(gcost, "ee_cost(gcost)").reshape(n)
-    with _on(H.device):
-        check(lib().trk_ee_cost(cm._h, H.data_ptr(), n, 16, _ptr(tgt), per_sample, _ptr(gc), cost.data_ptr(),
-                                _ptr(gH), 16, _stream(H)), "trk_ee_cost")
+    _call("trk_ee_cost", H.device, cm._h, H.data_ptr(), n, 16, _ptr(tgt), per_sample, _ptr(gc), cost.data_ptr(), _ptr(gH), 16)
     return (cost, gH) if want_grad else cost
 
 
@@ -1178,9 +1125,7 @@ def finite_difference(x: torch.Tensor, dt: float = 1.0, method: str = "forward")
     H, D = int(x.shape[-2]), int(x.shape[-1])
     B = int(x.numel() // max(1, H * D))
     out = torch.empty_like(x)
-    with _on(x.device):
-        check(lib().trk_finite_difference(x.data_ptr(), B, H, D, float(dt), _FD_METHODS[method], out.data_ptr(), _stream(x)),
-              "trk_finite_difference")
+    _call("trk_finite_difference", x.device, x.data_ptr(), B, H, D, float(dt), _FD_METHODS[method], out.data_ptr())
     return out
 
 
@@ -1192,9 +1137,7 @@ def traj_diff_norm_sum(x: torch.Tensor, c0: int, dim: int) -> torch.Tensor:
         raise ValueError("traj_diff_norm_sum: x must be (batch, horizon, state_dim)")
     B, H, S = (int(v) for v in x.shape)
     out = torch.empty((B,), device=x.device, dtype=torch.float32)
-    with _on(x.device):
-        check(lib().trk_traj_diff_norm_sum(x.data_ptr(), B, H, S, int(c0), int(dim), out.data_ptr(), _stream(x)),
-              "trk_traj_diff_norm_sum")
+    _call("trk_traj_diff_norm_sum", x.device, x.data_ptr(), B, H, S, int(c0), int(dim), out.data_ptr())
     return out
 
 
@@ -1210,9 +1153,8 @@ def interpolate_traj_via_points(trajs: torch.Tensor, num_interpolation: int = 10
     T = int(np.prod(lead)) if len(lead) else 1
     alpha, beta = via_point_weights(num_interpolation, x.device)
     out = torch.empty(tuple(lead) + ((H - 1) * num_interpolation, D), device=x.device, dtype=torch.float32)
-    with _on(x.device):
-        check(lib().trk_interpolate_via_points(x.data_ptr(), T, H, D, int(num_interpolation), alpha.data_ptr(),
-                                               beta.data_ptr(), out.data_ptr(), _stream(x)), "trk_interpolate_via_points")
+    _call("trk_interpolate_via_points", x.device, x.data_ptr(), T, H, D, int(num_interpolation), alpha.data_ptr(), beta.data_ptr(),
+          out.data_ptr())
     return out
 
 
@@ -1228,9 +1170,7 @@ def interpolate_columns(x: torch.Tensor, src: torch.Tensor, w: torch.Tensor, n_o
     _check_buffer(src, 2 * int(n_out), torch.int32, x.device, "interpolate_columns(src)")
     _check_buffer(w, 2 * int(n_out), torch.float32, x.device, "interpolate_columns(w)")
     out = torch.empty(lead + (int(n_out), Cc), device=x.device, dtype=torch.float32)
-    with _on(x.device):
-        check(lib().trk_interpolate_columns(x.data_ptr(), n, L, Cc, int(n_out), src.data_ptr(), w.data_ptr(), out.data_ptr(),
-                                            _stream(x)), "trk_interpolate_columns")
+    _call("trk_interpolate_columns", x.device, x.data_ptr(), n, L, Cc, int(n_out), src.data_ptr(), w.data_ptr(), out.data_ptr())
     return out
 
 
@@ -1240,9 +1180,7 @@ def interpolate_columns_backward(g: torch.Tensor, src: torch.Tensor, w: torch.Te
     lead = tuple(g.shape[:-2])
     n = int(np.prod(lead)) if lead else 1
     gx = torch.empty(lead + (int(n_in), Cc), device=g.device, dtype=torch.float32)
-    with _on(g.device):
-        check(lib().trk_interpolate_columns_backward(g.data_ptr(), n, int(n_in), Cc, K, src.data_ptr(), w.data_ptr(),
-                                                     gx.data_ptr(), _stream(g)), "trk_interpolate_columns_backward")
+    _call("trk_interpolate_columns_backward", g.device, g.data_ptr(), n, int(n_in), Cc, K, src.data_ptr(), w.data_ptr(), gx.data_ptr())
     return gx
 
 
@@ -1452,9 +1390,8 @@ def jtj(lin_jac: torch.Tensor, ang_jac: torch.Tensor, residual: Optional[torch.T
     JtJ = torch.empty((n, D, D), device=lin.device, dtype=torch.float32)
     Jtr = torch.empty((n, D), device=lin.device, dtype=torch.float32) if res is not None else None
     dq = torch.empty((n, D), device=lin.device, dtype=torch.float32) if solve else None
-    with _on(lin.device):
-        check(lib().trk_jtj(lin.data_ptr(), ang.data_ptr(), _ptr(res), n, D, int(bool(mfma)), JtJ.data_ptr(), _ptr(Jtr), _ptr(dmp), stride,
-                            _ptr(dq), _stream(lin)), "trk_jtj")
+    _call("trk_jtj", lin.device, lin.data_ptr(), ang.data_ptr(), _ptr(res), n, D, int(bool(mfma)), JtJ.data_ptr(), _ptr(Jtr), _ptr(dmp),
+          stride, _ptr(dq))
     if solve:
         return JtJ, Jtr, dq
     return (JtJ, Jtr) if res is not None else JtJ
@@ -1476,9 +1413,7 @@ def scale_rows(g: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     else:
         sc, stride = _dev_f32(scale, "scale_rows(scale)"), 1
     out = torch.empty_like(g)
-    with _on(g.device):
-        check(lib().trk_scale_rows(g.data_ptr(), sc.data_ptr(), stride, rows, D, int(g.dtype == torch.float16), out.data_ptr(),
-                                   _stream(g)), "trk_scale_rows")
+    _call("trk_scale_rows", g.device, g.data_ptr(), sc.data_ptr(), stride, rows, D, int(g.dtype == torch.float16), out.data_ptr())
     return out
 
 
@@ -1800,8 +1735,7 @@ def reduce_sum(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Ten
     x = _dev_f32(x, "reduce_sum(x)").reshape(-1)
     if out is None:
         out = torch.empty(1, device=x.device, dtype=torch.float32)
-    with _on(x.device):
-        check(lib().trk_reduce_sum(x.data_ptr(), x.numel(), out.data_ptr(), _stream(x)), "trk_reduce_sum")
+    _call("trk_reduce_sum", x.device, x.data_ptr(), x.numel(), out.data_ptr())
     return out
 
 
@@ -1840,10 +1774,7 @@ def grid_precompute(cm: CostHandle, dims, lim_min, lim_max):
     shape = tuple(int(d) for d in dims_a)
     sdf = torch.empty(shape, device=cm.device, dtype=torch.float32)
     grad = torch.empty(shape + (3,), device=cm.device, dtype=torch.float32)
-    with _on(cm.device):
-        check(lib().trk_grid_precompute(cm._h, dims_a.ctypes.data, lo.ctypes.data, hi.ctypes.data, sdf.data_ptr(),
-                                        grad.data_ptr(), _stream_of(cm.device)),
-              "trk_grid_precompute")
+    _call("trk_grid_precompute", cm.device, cm._h, dims_a.ctypes.data, lo.ctypes.data, hi.ctypes.data, sdf.data_ptr(), grad.data_ptr())
     return sdf, grad
 
 
@@ -1852,8 +1783,7 @@ def sdf_points(cm: CostHandle, pts: torch.Tensor, want_grad=False):
     n = pts.shape[0]
     sdf = torch.empty((n, cm.n_objects), device=pts.device, dtype=torch.float32)
     grad = torch.empty((n, cm.n_objects, 3), device=pts.device, dtype=torch.float32) if want_grad else None
-    with _on(pts.device):
-        check(lib().trk_sdf_points(cm._h, pts.data_ptr(), n, sdf.data_ptr(), _ptr(grad), _stream(pts)), "trk_sdf_points")
+    _call("trk_sdf_points", pts.device, cm._h, pts.data_ptr(), n, sdf.data_ptr(), _ptr(grad))
     return (sdf, grad) if want_grad else sdf
 
 
