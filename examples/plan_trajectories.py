@@ -9,6 +9,7 @@ with the GP prior fused in: `task.rollout_gp_plan`); the result is validated the
 (`get_trajs_collision_and_free`: 5 via points per segment, fused FK + boolean fields).  Needs the MI355X: there is no CPU path.
 
     python examples/plan_trajectories.py [--batch 256] [--horizon 64] [--iters 200] [--fused] [--via-cost N]
+                                         [--model links|spheres|grasp|both]
 
 --fused runs the same problem with the whole loop on the chip (`task.rollout_adam_plan(...).step(32)`, `trk_rollout_gp_adam_steps`):
 trajectories and Adam's state stay in registers, one launch per 32 iterations (horizons that are a power of two up to 64).
@@ -18,6 +19,10 @@ In the eager loop it is one more launch per iteration (`task.rollout_via_plan`, 
 at the way points, same weight as the way points' own cost).  With --fused the term is part of the planning-loop kernel
 (`task.rollout_adam_plan(..., w_via=1 / N, num_interpolation=N)`, `trk_rollout_gp_via_adam_steps`): the N via points of a segment
 together weigh as much as one way point.
+--model chooses the Panda's collision geometry: `links` (default: the link origins), `spheres` (the 45 link spheres), `grasp` (a
+grasped box) or `both`.  For the three attached-point models an evaluation is `task.rollout_plan` (`trk_rollout_points_cost_grad`)
+plus `ops.gp_prior_cost_grad`, and --fused is `task.points_adam_plan(...).step(32)` (`trk_rollout_points_gp_adam_steps`); the
+via-point cost is not available for them (--via-cost is refused).
 """
 import argparse
 import sys
@@ -32,12 +37,30 @@ import torch_robotics_amd as tra
 from torch_robotics_amd import ops
 
 
-def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0, fused=False, stats=None, via_cost=0):
+MODELS = ("links", "spheres", "grasp", "both")
+
+
+def make_robot(model, ta):
+    """the Panda with the collision geometry --model names"""
+    if model not in MODELS:
+        raise ValueError(f"--model must be one of {', '.join(MODELS)}")
+    kw = {}
+    if model in ("spheres", "both"):
+        kw["link_sphere_model"] = "panda"
+    if model in ("grasp", "both"):
+        kw["grasped_object"] = tra.GraspedObjectPandaBox(tensor_args=ta)
+    return tra.RobotPanda(tensor_args=ta, **kw)
+
+
+def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0, fused=False, stats=None, via_cost=0, model="links"):
+    points = model != "links"
+    if points and via_cost > 0:
+        raise NotImplementedError("--via-cost is for --model links: the via-point cost kernels serve link-column cost models only")
     if via_cost > 0:                       # the same problem (same seed) without the via-point term first, for the comparison
         n_free_plain = main(batch, horizon, iters, device, False, seed, fused=fused)[1]
     torch.manual_seed(seed)
     ta = dict(device=torch.device(device), dtype=torch.float32)
-    robot = tra.RobotPanda(tensor_args=ta)
+    robot = make_robot(model, ta)
     # clamp_sdf=True: the fields are hinges relu(margin - sdf) (distance_fields.py:114-117) -- what an optimiser needs; the plain
     # margin - sdf that the reference's PlanningTask sums decreases without bound away from the obstacles
     task = tra.PlanningTask(env=tra.EnvSpheres3D(tensor_args=ta), robot=robot, obstacle_cutoff_margin=0.05, clamp_sdf=True,
@@ -51,7 +74,7 @@ def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0
 
     w_obj, sigma_gp, lr = 50.0, 2.0, 1e-2
     if fused:
-        res = _main_fused(task, q, qd, q_start + s * (q_goal - q_start), dt, sigma_gp, w_obj, lr, iters, verbose, stats, via_cost)
+        res = _main_fused(task, q, qd, q_start + s * (q_goal - q_start), dt, sigma_gp, w_obj, lr, iters, verbose, stats, via_cost, points)
         if via_cost > 0:
             if stats is not None:
                 stats.update(n_free_plain=n_free_plain, n_free_via=res[1])
@@ -60,7 +83,10 @@ def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0
                       f"w_via = 1/{via_cost}): {res[1]}/{batch}")
         return res
     # pre-bound launch: reads q, qd in place; cost = w_obj * (self + object + workspace hinges) + the prior's factor costs
-    plan = task.rollout_gp_plan(q, qd, dt, sigma_gp, gp_weight=1.0, w_self=w_obj, w_obj=w_obj, w_ws=w_obj)
+    if points:                             # attached points: the collision rollout pre-bound, the prior a call of its own per iteration
+        plan = task.rollout_plan(q, w_self=w_obj, w_obj=w_obj, w_ws=w_obj, want_pos=False)
+    else:
+        plan = task.rollout_gp_plan(q, qd, dt, sigma_gp, gp_weight=1.0, w_self=w_obj, w_obj=w_obj, w_ws=w_obj)
     # the collision hinges at via_cost via points per segment, same weights: one more launch, its gradient lands on the way points
     via = task.rollout_via_plan(q, via_cost, w_self=w_obj, w_obj=w_obj, w_ws=w_obj) if via_cost > 0 else None
     free_mask = torch.ones(1, horizon, 1, **ta)
@@ -72,6 +98,14 @@ def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0
     t0 = time.perf_counter()
     for it in range(iters):
         plan.launch()                                                    # plan.cost (B,H), plan.gq, plan.gqd (B,H,D)
+        if points:                                                       # the prior from the SAME q / qd the launch read
+            c_gp, gp_gq, gp_gqd = ops.gp_prior_cost_grad(q, qd, dt, sigma_gp)
+            if verbose and (it % 50 == 0 or it == iters - 1):
+                hist.append((it, float(plan.cost.sum(1).mean()) / w_obj, float(c_gp.mean())))
+            q.grad = free_mask * (plan.gq + gp_gq)
+            qd.grad = gp_gqd
+            opt.step()
+            continue
         if verbose and (it % 50 == 0 or it == iters - 1):
             # the prior's share of plan.cost, from the SAME q / qd the launch read (before the step moves them in place)
             c_gp = ops.gp_prior_cost_grad(q, qd, dt, sigma_gp)[0]
@@ -99,12 +133,13 @@ def main(batch=256, horizon=64, iters=200, device="cuda:0", verbose=True, seed=0
     return q, n_free, coll0
 
 
-def _main_fused(task, q, qd, q_lines, dt, sigma_gp, w_obj, lr, iters, verbose, stats, via_cost=0):
+def _main_fused(task, q, qd, q_lines, dt, sigma_gp, w_obj, lr, iters, verbose, stats, via_cost=0, points=False):
     """the same objective, pins and Adam, `iters` iterations in launches of 32: plan.step(n) returns the cost of the state it started from"""
     batch, horizon = q.shape[:2]
     via = dict(w_via=1.0 / via_cost, num_interpolation=via_cost) if via_cost > 0 else {}
-    plan = task.rollout_adam_plan(q, qd, dt, sigma_gp, gp_weight=1.0, w_self=w_obj, w_obj=w_obj, w_ws=w_obj, lr=lr, **via)   # start and goal pinned
-    probe = task.rollout_adam_plan(q, qd, dt, sigma_gp, gp_weight=0.0, w_self=w_obj, w_obj=w_obj, w_ws=w_obj, lr=0.0)   # collision cost only
+    make_plan = task.points_adam_plan if points else task.rollout_adam_plan      # attached points: their own planning-loop kernel
+    plan = make_plan(q, qd, dt, sigma_gp, gp_weight=1.0, w_self=w_obj, w_obj=w_obj, w_ws=w_obj, lr=lr, **via)   # start and goal pinned
+    probe = make_plan(q, qd, dt, sigma_gp, gp_weight=0.0, w_self=w_obj, w_obj=w_obj, w_ws=w_obj, lr=0.0)   # collision cost only
     cost0 = float(probe.step(1).sum(1).mean()) / w_obj
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -137,5 +172,8 @@ if __name__ == "__main__":
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--fused", action="store_true", help="the whole loop in one kernel (rollout_adam_plan)")
     ap.add_argument("--via-cost", type=int, default=0, help="N > 0: add the collision cost at N via points per segment")
+    ap.add_argument("--model", choices=MODELS, default="links", help="the Panda's collision geometry (default: link origins)")
     a = ap.parse_args()
-    main(a.batch, a.horizon, a.iters, a.device, fused=a.fused, via_cost=a.via_cost)
+    if a.model != "links" and a.via_cost > 0:
+        ap.error("--via-cost is for --model links: the via-point cost kernels serve link-column cost models only")
+    main(a.batch, a.horizon, a.iters, a.device, fused=a.fused, via_cost=a.via_cost, model=a.model)

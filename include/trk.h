@@ -980,6 +980,20 @@ int trk_rollout_gp_via_adam_steps(const TrkModel* model, const TrkCostModel* cm,
                                   const TrkTrajVia* via, const TrkTrajAdam* adam, float* q, float* qd, float* adam_m, float* adam_v,
                                   int64_t batch, int32_t horizon, float* cost, trk_stream_t stream);
 
+/* trk_rollout_gp_adam_steps for the attached-point models (link spheres, grasped-object points): the planning loop on the objective
+ * of trk_rollout_points_cost_grad -- the collision fields on the points of `ps`, the EE term -- plus the constant-velocity GP prior.
+ * Buffers, pin, first_step, cost, lr = 0, the 32 iterations per launch and the grouping rule are trk_rollout_gp_adam_steps'.
+ * Validation (before any device work), in this order: everything trk_rollout_gp_adam_steps checks except the column count, horizon
+ * rule included (TRK_ERR_UNSUPPORTED unless a power of two <= TRK_TRAJ_ADAM_MAX_HORIZON); then the point set as
+ * trk_rollout_points_cost_grad checks it (null, of no model or of another model, cost model n_links_in != its points, ee_link):
+ * TRK_ERR_INVALID_ARG.  Served by a generated kernel only (k_padam: attached-point units of robots up to 8 DOF, a satellite unit
+ * spec_<ident>_padam); TRK_ERR_UNSUPPORTED with the reason when no unit of the point set carries the kernel (a unit loaded as a code
+ * object through hipRTC has none), when none bakes the cost model's column sets, or when trk_model_enable_specialized is off.
+ * batch = 0: TRK_OK without a launch.  trk_last_dispatch: TRK_DISPATCH_GENERATED.  No host synchronisation: capturable. */
+int trk_rollout_points_gp_adam_steps(const TrkModel* model, const TrkPointSet* ps, const TrkCostModel* cm,
+                                     const TrkRolloutWeights* weights, const TrkGpPrior* gp, const TrkTrajAdam* adam, float* q, float* qd,
+                                     float* adam_m, float* adam_v, int64_t batch, int32_t horizon, float* cost, trk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,7 +139,7 @@ TRK_TRAJ_ADAM_MAX_HORIZON = 64
 TRK_VIA_COST_MAX_HORIZON = 64
 
 
-class TrajAdam(C.Structure):            # TrkTrajAdam
+class TrajAdam(C.Structure):            # TrkTrajAdam (trk_rollout_gp_adam_steps, trk_rollout_gp_via_adam_steps, trk_rollout_points_gp_adam_steps)
     _fields_ = [("lr", C.c_float), ("pin", C.c_int32), ("first_step", C.c_int32), ("n_steps", C.c_int32)]
 
 

@@ -42,6 +42,7 @@ EXPORTS = [
     "trk_rollout_via_cost_grad",
     "trk_scene2d_traj_via_cost_grad", "trk_scene2d_traj_via_adam_steps",
     "trk_rollout_gp_via_adam_steps",
+    "trk_rollout_points_gp_adam_steps",
 ]
 
 
@@ -53,7 +54,7 @@ def build(verbose: bool = False) -> Path:
     """Compile libtrk.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     jobs = str(min(8, os.cpu_count() or 1))
     from . import codegen
-    codegen.generate_all(_CSRC / "generated")          # model-specialised kernels (source is a build product)
+    codegen.generate_sources(_CSRC / "generated")      # model-specialised kernels (source is a build product)
     res = subprocess.run(["make", "-C", str(_CSRC), "-j", jobs], capture_output=True, text=True)
     if res.returncode != 0:
         raise TrkError(f"building libtrk.so failed:\n{res.stdout}\n{res.stderr}")
@@ -208,6 +209,8 @@ def lib():
     L.trk_rollout_via_cost_grad.argtypes = [vp, vp, C.POINTER(_abi.RolloutWeights), vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]
     L.trk_rollout_gp_via_adam_steps.argtypes = [vp, vp, C.POINTER(_abi.RolloutWeights), C.POINTER(_abi.GpPrior), C.POINTER(_abi.TrajVia),
                                                 C.POINTER(_abi.TrajAdam), vp, vp, vp, vp, i64, i32, vp, vp]
+    L.trk_rollout_points_gp_adam_steps.argtypes = [vp, vp, vp, C.POINTER(_abi.RolloutWeights), C.POINTER(_abi.GpPrior),
+                                                   C.POINTER(_abi.TrajAdam), vp, vp, vp, vp, i64, i32, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)        # AttributeError here = the library does not export the ABI
         if name not in ("trk_last_error", "trk_model_destroy", "trk_cost_model_destroy", "trk_point_set_destroy",

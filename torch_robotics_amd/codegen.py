@@ -826,8 +826,9 @@ def _root_pose(base_identity: bool):
     return R, t, {}
 
 
-def _kernel_head(E: Emitter, kname: str, occupancy, lds_lane, args: str = "SpecArgs", spheres: bool = False) -> None:
-    """signature, the static LDS (lds_lane floats per lane; spheres: plus the wavefronts' sphere tables) and the wavefront's rows"""
+def _kernel_head(E: Emitter, kname: str, occupancy, lds_lane, args: str = "SpecArgs", spheres: bool = False, rows: bool = True) -> None:
+    """signature, the static LDS (lds_lane floats per lane; spheres: plus the wavefronts' sphere tables) and the wavefront's rows
+    (rows=False: the kernel states its own, as the Adam kernels do in _emit_adam_state_load)"""
     E.raw(f"__global__ void __launch_bounds__(SPEC_BLOCK, {occupancy}) {kname}({args} A) {{")
     E.raw(f"    __shared__ __attribute__((aligned(16))) float lds_all[SPEC_BLOCK * {lds_lane}{' + SPEC_WAVES * TRK_LDS_SPHERES * 4' if spheres else ''}];")
     E.raw("    const int lane = __builtin_amdgcn_workitem_id_x() & (TRK_WAVE - 1);")
@@ -836,6 +837,8 @@ def _kernel_head(E: Emitter, kname: str, occupancy, lds_lane, args: str = "SpecA
     if spheres:
         E.raw(f"    float4* lds_sph = reinterpret_cast<float4*>(lds_all + SPEC_BLOCK * {lds_lane}) + wave * TRK_LDS_SPHERES;")
         E.raw("    const SpheresInFlight sph = spec_load_spheres_issue(A.C, lane);   // waited for together with the rows below")
+    if not rows:
+        return
     E.raw("    const int64_t wblock = (int64_t)__builtin_amdgcn_workgroup_id_x() * SPEC_WAVES + wave;")
     E.raw("    const int64_t base = wblock * TRK_WAVE;")
     E.raw("    const int rows = (int)max((int64_t)0, min((int64_t)TRK_WAVE, A.n - base));")
@@ -2106,6 +2109,26 @@ def _emit_adam_loop_open(E: Emitter) -> None:
     E.raw("    for (int it = 0; it < A.n_steps; ++it) {")
 
 
+def _emit_adam_prior(E: Emitter) -> None:
+    """the constant-velocity GP prior on the register copies q, qd (_emit_gpt_prior's expressions): its gradients gpv[D], gvv[D], and
+    the cost of the state as passed in (rollout's `cost` + the prior's factors) into cost0 on the first iteration"""
+    E.raw("    // the prior: e_t = (p_t + dt v_t - p_t+1, v_t - v_t+1), r = w Q^-1 e; the next sample's (p, v) come by wave_shl:1, the finished")
+    E.raw("    // factor goes to the next lane by wave_shr:1.  A lane at the last step has weight 0, so a lane at step 0 receives 0; lanes 63 / 0")
+    E.raw("    // have no source and keep the shift's `old` operand: their own value (weight 0) / 0.")
+    E.raw("    float gpv[D], gvv[D], accg = 0.0f;")
+    E.raw("#pragma unroll")
+    E.raw("    for (int d = 0; d < D; ++d) {")
+    E.raw("        const float p0 = q[d], v0 = qd[d];")
+    E.raw("        const float pn = trk_dpp_from_next(p0, p0), vn = trk_dpp_from_next(v0, v0);")
+    E.raw("        const float ep = fmaf(dt, v0, p0) - pn, ev = v0 - vn;")
+    E.raw("        const float rp = fmaf(gaw, ep, gbw * ev), rv_ = fmaf(gbw, ep, gcw * ev);")
+    E.raw("        accg = fmaf(ep, rp, fmaf(ev, rv_, accg));")
+    E.raw("        gpv[d] = rp - trk_dpp_from_prev(0.0f, rp);")
+    E.raw("        gvv[d] = fmaf(dt, rp, rv_) - trk_dpp_from_prev(0.0f, rv_);")
+    E.raw("    }")
+    E.raw("    if (it == 0) cost0 = fmaf(0.5f, accg, cost);      // the state as passed in; the factor t -> t + 1 attributed to sample t")
+
+
 def _emit_adam_update(E: Emitter, pos: str, grad_q: str) -> None:
     """trk_ik_step's Adam update of (pos, qd) with the gradients (grad_q, gvv[d]), and the end of the iteration"""
     E.raw("    if (update) {")
@@ -2153,22 +2176,7 @@ def _traj_adam_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     E.raw("    const float wm = (lane < rows && !t_last) ? A.gp_w : 0.0f;       // the factor t -> t + 1 exists")
     _emit_adam_loop_open(E)
     _emit_rollout_iteration(u, E, base_identity)
-    # ---------------- the prior on the register copies (_emit_gpt_prior's expressions) ----------------
-    E.raw("    // the prior: e_t = (p_t + dt v_t - p_t+1, v_t - v_t+1), r = w Q^-1 e; the next sample's (p, v) come by wave_shl:1, the finished")
-    E.raw("    // factor goes to the next lane by wave_shr:1.  A lane at the last step has weight 0, so a lane at step 0 receives 0; lanes 63 / 0")
-    E.raw("    // have no source and keep the shift's `old` operand: their own value (weight 0) / 0.")
-    E.raw("    float gpv[D], gvv[D], accg = 0.0f;")
-    E.raw("#pragma unroll")
-    E.raw("    for (int d = 0; d < D; ++d) {")
-    E.raw("        const float p0 = q[d], v0 = qd[d];")
-    E.raw("        const float pn = trk_dpp_from_next(p0, p0), vn = trk_dpp_from_next(v0, v0);")
-    E.raw("        const float ep = fmaf(dt, v0, p0) - pn, ev = v0 - vn;")
-    E.raw("        const float rp = fmaf(gaw, ep, gbw * ev), rv_ = fmaf(gbw, ep, gcw * ev);")
-    E.raw("        accg = fmaf(ep, rp, fmaf(ev, rv_, accg));")
-    E.raw("        gpv[d] = rp - trk_dpp_from_prev(0.0f, rp);")
-    E.raw("        gvv[d] = fmaf(dt, rp, rv_) - trk_dpp_from_prev(0.0f, rv_);")
-    E.raw("    }")
-    E.raw("    if (it == 0) cost0 = fmaf(0.5f, accg, cost);      // the state as passed in; the factor t -> t + 1 attributed to sample t")
+    _emit_adam_prior(E)
     _emit_adam_update(E, "q", "gc[d] + gpv[d]")
     _emit_adam_state_store(E, "q")
     return E.lines
@@ -2954,6 +2962,12 @@ class _PointsUnit:
         return 0 if self.link_mode else points_hash(self.pt.point_link, self.pt.point_offset)
 
     @property
+    def traj_adam_ok(self) -> bool:
+        """does the unit get a spec_<ident>_padam unit (k_padam: the planning loop on its points)?  Up to 8 DOF: the walk's registers
+        plus 5 D of state (qd, m, v) per lane must fit without scratch.  A link-mode unit is a link unit to the dispatcher and has none."""
+        return self.D <= 8 and not self.link_mode
+
+    @property
     def kernels(self) -> List[str]:
         """what a code-object (hipRTC) build of this unit must contain: the name expressions of its kernels (jit.py,
         trk_spec_register_module)"""
@@ -3201,6 +3215,43 @@ def _points_finish_joints(u: _PointsUnit, E: Emitter, w: _WrenchWalk, p: int, gf
         gfin[j] = S(1.0, E.tmp(E.expr(E.named(w.difference(j)))))
 
 
+def _emit_points_walk(u: _PointsUnit, E: Emitter, w: _WrenchWalk, stage_positions: bool) -> Dict[int, S]:
+    """The walk of the attached-point cost kernels after the angles: `cost`, the running wrench and the `late` accumulators are
+    declared HERE (a kernel that walks inside a loop gets them fresh every pass), then link by link the pose, the link's columns,
+    objects / workspace, self pairs, the EE term and the joints whose subtree ends.  stage_positions: the columns also leave through
+    the chunk buffer `row` (k_rollout); otherwise only the columns a test reads are formed and nothing is stored.  Returns the
+    gradient's expressions by DOF."""
+    kin = u.kin
+    E.raw("    float cost = 0.0f;")
+    w.declare()
+    for i in u.joint_links:
+        E.raw(f"    float late{int(kin.dof_idx[i])} = 0.0f;")
+    gfin: Dict[int, S] = {}
+    chunk_start = 0                       # first float of the chunk being filled
+    in_pair = {c for pr in u.pt.self_pairs for c in pr}
+    for p in range(u.L):
+        i = int(kin.order[p])
+        if p > 0:
+            w.enter(i)
+        if stage_positions:
+            chunk_start = _points_stage_positions(u, E, w, i, chunk_start)
+        else:
+            for c in u.cols_of_link[i]:
+                if c in u.obj_rank or c in in_pair:
+                    w.colpos(i, c)
+        _points_obj_groups(u, E, w, i)
+        _points_self_pairs(u, E, w, i)
+        _points_ee_term(u, E, w, i)
+        _points_finish_joints(u, E, w, p, gfin)
+    assert chunk_start == (u.W if stage_positions else 0)
+    gq_expr: Dict[int, S] = {}
+    for i in [i for i in u.joint_links if i in gfin]:
+        d = int(kin.dof_idx[i])
+        g = E.lincomb([(gfin[i], ONE), (S(1.0, f"late{d}"), ONE)])
+        gq_expr[d] = u.masked(E, i, d, S(g.c * u.sign[i], g.n))
+    return gq_expr
+
+
 def _points_rollout_kernel(u: _PointsUnit, base_identity: bool) -> List[str]:
     """k_rollout_bi / k_rollout_bg: fused FK + objectives + gradient with the collision fields on attached points.  Differences to the
     link kernel:
@@ -3228,27 +3279,7 @@ def _points_rollout_kernel(u: _PointsUnit, base_identity: bool) -> List[str]:
     E.raw("    NoTick notick;")
     w = _WrenchWalk(u, E, base_identity)
     _emit_angles(E, kin)
-    E.raw("    float cost = 0.0f;")
-    w.declare()
-    for i in u.joint_links:
-        E.raw(f"    float late{int(kin.dof_idx[i])} = 0.0f;")
-    gfin: Dict[int, S] = {}
-    chunk_start = 0                       # first float of the chunk being filled
-    for p in range(u.L):
-        i = int(kin.order[p])
-        if p > 0:
-            w.enter(i)
-        chunk_start = _points_stage_positions(u, E, w, i, chunk_start)
-        _points_obj_groups(u, E, w, i)
-        _points_self_pairs(u, E, w, i)
-        _points_ee_term(u, E, w, i)
-        _points_finish_joints(u, E, w, p, gfin)
-    assert chunk_start == u.W
-    gq_expr: Dict[int, S] = {}
-    for i in [i for i in u.joint_links if i in gfin]:
-        d = int(kin.dof_idx[i])
-        g = E.lincomb([(gfin[i], ONE), (S(1.0, f"late{d}"), ONE)])
-        gq_expr[d] = u.masked(E, i, d, S(g.c * u.sign[i], g.n))
+    gq_expr = _emit_points_walk(u, E, w, stage_positions=True)
     E.raw("    if (!A.gq) return;                       // positions only (trk_fk_points): weights are zero, nothing else to write")
     E.raw("    if (lane < rows) store_wt_f1(A.cost + base + lane, cost);")
     E.raw("    if (A.cost_sum) {")
@@ -3285,6 +3316,16 @@ def generate_points_rollout_source(kin: KinModel, pt: PointsTemplate, ident: str
     return "\n".join(out) + "\n"
 
 
+def _points_fast_switch_lines(kernel) -> List[str]:
+    """the body of an attached-point launcher: the grid (a lane per sample) and the four launches by scene path (FAST) and base pose;
+    kernel(base, fast) names the instantiation"""
+    def pair(fast: str) -> List[str]:
+        return [f"        if (base_identity) hipLaunchKernelGGL(({kernel('bi', fast)}), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);",
+                f"        else hipLaunchKernelGGL(({kernel('bg', fast)}), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);"]
+    return [*_GRID_PER_SAMPLE, "    const bool fast = scene_is_fast(a.C) || a.w.w_obj == 0.0f;", "    if (fast) {", *pair("true"),
+            "    } else {", *pair("false"), "    }", "}"]
+
+
 def _points_entry_lines(u: _PointsUnit) -> List[str]:
     """the unit's host half: launchers and its registry entry"""
     kin, pt = u.kin, u.pt
@@ -3296,16 +3337,7 @@ def _points_entry_lines(u: _PointsUnit) -> List[str]:
     out.append(f"static const int32_t kSelfPairs[] = {{{pairs}}};")
     out.append("template <class IO>")
     out.append("static void launch_io(const SpecArgs& a, int base_identity, hipStream_t st) {")
-    out.append("    const unsigned grid = (unsigned)((a.n + SPEC_BLOCK - 1) / SPEC_BLOCK);")
-    out.append("    const bool fast = scene_is_fast(a.C) || a.w.w_obj == 0.0f;")
-    out.append("    if (fast) {")
-    out.append("        if (base_identity) hipLaunchKernelGGL((k_rollout_bi<true, IO>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-    out.append("        else hipLaunchKernelGGL((k_rollout_bg<true, IO>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-    out.append("    } else {")
-    out.append("        if (base_identity) hipLaunchKernelGGL((k_rollout_bi<false, IO>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-    out.append("        else hipLaunchKernelGGL((k_rollout_bg<false, IO>), dim3(grid), dim3(SPEC_BLOCK), 0, st, a);")
-    out.append("    }")
-    out.append("}")
+    out += _points_fast_switch_lines(lambda b, fast: f"k_rollout_{b}<{fast}, IO>")
     out.append("static void launch(const SpecEntry*, const SpecArgs& a, int base_identity, hipStream_t st) {")
     if u.link_mode:
         out.append("    if (a.io_f16) launch_io<_Float16>(a, base_identity, st); else launch_io<float>(a, base_identity, st);")
@@ -3390,6 +3422,66 @@ def generate_points_collision_source(kin: KinModel, pt: PointsTemplate, ident: s
         _launcher_lines("pcoll"),
         f"static struct RegPointsColl {{ RegPointsColl() {{ trk_spec_register_points_coll(\"{ident}\", 0x{model_hash(kin):016x}ull, "
         f"0x{u.points_hash:016x}ull, (uint32_t)sizeof(SpecArgs), launch_pcoll); }} }} reg_points_coll;")
+
+
+# Wavefronts per SIMD k_padam runs at: what every instantiation of the three bundled units reaches without scratch.  The
+# points rollout already states two wavefronts (217 VGPRs for the 45 spheres); the loop adds qd, m, v (5 D) and the loop-invariant
+# scalars the compiler parks in VGPR lanes.
+POINTS_ADAM_OCCUPANCY = 1
+
+
+def _points_adam_kernel(u: _PointsUnit, base_identity: bool) -> List[str]:
+    """k_padam_bi / k_padam_bg<FAST>: the planning loop of an attached-point model (trk_rollout_points_gp_adam_steps) -- k_traj_adam's
+    loop around the walk of _points_rollout_kernel.  One lane per sample, fp32, the horizon a power of two <= 64, (q, qd, m, v) in
+    the lane's registers across the launch's iterations, the prior's neighbours in time by DPP wavefront shifts.  An iteration is
+    the walk (_emit_points_walk: cost, wrench and late forces start from zero every pass) without staged positions, chunk buffer or
+    any position / cost-sum / gradient store, then the prior on the register copies and trk_ik_step's Adam update.  Nothing crosses
+    a wavefront: no barrier, no LDS exchange, no atomics; lanes beyond the rows run every iteration on clamped loads and store
+    nothing (the shifts need all 64 lanes)."""
+    E = Emitter()
+    E.raw("template <bool FAST>     // FAST: scene_is_fast(A.C) -- only the few-equal-spheres scene path is compiled in (as k_rollout)")
+    _kernel_head(E, "k_padam_bi" if base_identity else "k_padam_bg", POINTS_ADAM_OCCUPANCY, "(2 * D)", args="TrajAdamArgs", spheres=True,
+                 rows=False)
+    _emit_adam_state_load(E, "q")
+    E.raw("    spec_load_spheres_finish(lds_sph, lane, sph);")
+    E.raw("    NoTick notick;")
+    _emit_traj_pins(E)
+    E.raw("    const float wm = (lane < rows && !t_last) ? A.gp_w : 0.0f;       // the factor t -> t + 1 exists")
+    _emit_adam_loop_open(E)
+    w = _WrenchWalk(u, E, base_identity)
+    _emit_angles(E, u.kin)
+    gq_expr = _emit_points_walk(u, E, w, stage_positions=False)
+    E.raw(f"    const float gc[D] = {{{', '.join(E.expr(gq_expr.get(d, ZERO)) for d in range(u.D))}}};")
+    _emit_adam_prior(E)
+    _emit_adam_update(E, "q", "gc[d] + gpv[d]")
+    _emit_adam_state_store(E, "q")
+    return E.lines
+
+
+def points_adam_kernels(ident: str) -> List[str]:
+    """the kernels a spec_<ident>_padam unit defines"""
+    return [f"spec_{ident}::k_padam_{b}<{f}>" for b in ("bi", "bg") for f in ("true", "false")]
+
+
+def points_adam_ok(kin: KinModel, pt: PointsTemplate) -> bool:
+    """does the attached-point unit of (kin, pt) get a spec_<ident>_padam unit?  (_PointsUnit.traj_adam_ok, the one statement of the rule)"""
+    return _PointsUnit(kin, pt, "").traj_adam_ok
+
+
+def generate_points_adam_source(kin: KinModel, pt: PointsTemplate, ident: str, snap: float = SNAP) -> str:
+    """spec_<ident>_padam.hip: the planning-loop kernels of an attached-point model (_points_adam_kernel), a satellite unit
+    (_satellite_unit_source) like generate_points_collision_source's -- same namespace, same _PointsUnit plan.  It announces its
+    launcher under the main unit's ident and hashes (trk_spec_register_points_adam), and trk_rollout_points_gp_adam_steps looks it up
+    by those of the entry that serves the cost model.  Linked / dlopen-ed units only."""
+    u = _PointsUnit(kin, pt, ident, snap)
+    assert u.traj_adam_ok, "the planning-loop kernels exist for attached-point units of robots up to 8 DOF"
+    return _satellite_unit_source(
+        f"'{kin.name}' ({u.L} links, {u.D} DOF) with {u.P} attached points: planning-loop kernels", ident,
+        [f"constexpr int L = {u.L}, D = {u.D}, P = {u.P};"], False, [_points_adam_kernel(u, b) for b in (True, False)], "ident and hashes",
+        ["static void launch_padam(const TrajAdamArgs& a, int base_identity, hipStream_t st) {",
+         *_points_fast_switch_lines(lambda b, fast: f"k_padam_{b}<{fast}>")],
+        f"static struct RegPointsAdam {{ RegPointsAdam() {{ trk_spec_register_points_adam(\"{ident}\", 0x{model_hash(kin):016x}ull, "
+        f"0x{u.points_hash:016x}ull, (uint32_t)sizeof(TrajAdamArgs), launch_padam); }} }} reg_points_adam;")
 
 
 def link_points_template(kin: KinModel, tmpl: CollisionTemplate) -> PointsTemplate:
@@ -3565,27 +3657,56 @@ def aot_units():
     return [(k, v[0], v[1]) for k, v in _template_cache.items()]
 
 
-def generate_all(out_dir) -> List[str]:
-    """every ahead-of-time unit into out_dir (a file is rewritten only when its text changed: make sees no new timestamp); returns the
-    file names: the main units, then the satellite units of the link units (planning loop with the via-point term, via-point cost) and
-    of the attached-point units (their boolean kernels), which register after the main ones"""
-    from pathlib import Path
+def _load_units(robots):
+    """[(ident, KinModel, template)] of a table of bundled robots (SPEC_ROBOTS, SPEC_POINT_ROBOTS)"""
     from .kinematics import URDF_DIR
+    kins = {ident: KinModel.from_urdf(str(URDF_DIR / urdf)) for ident, (urdf, _) in robots.items()}
+    return [(ident, kins[ident], robots[ident][1](kins[ident])) for ident in robots]
+
+
+def _write_units(out_dir, units) -> List[str]:
+    """(file name, source) pairs into out_dir (a file is rewritten only when its text changed: make sees no new timestamp); the names"""
+    from pathlib import Path
     out_dir = Path(out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
-
-    def load(robots):
-        kins = {ident: KinModel.from_urdf(str(URDF_DIR / urdf)) for ident, (urdf, _) in robots.items()}
-        return [(ident, kins[ident], robots[ident][1](kins[ident])) for ident in robots]
-    links, points = load(SPEC_ROBOTS), load(SPEC_POINT_ROBOTS)
-    small = [(ident, kin, tmpl) for ident, kin, tmpl in links if via_cost_ok(kin, tmpl, ident)]
-    units = ([(f"spec_{i}.hip", generate_link_kernel_source(k, t, i)) for i, k, t in links] +
-             [(f"spec_{i}.hip", generate_points_rollout_source(k, t, i)) for i, k, t in points] +
-             [(f"spec_{i}_vadam.hip", generate_via_adam_source(k, t, i)) for i, k, t in small] +
-             [(f"spec_{i}_via.hip", generate_via_cost_source(k, t, i)) for i, k, t in small] +
-             [(f"spec_{i}_coll.hip", generate_points_collision_source(k, t, i)) for i, k, t in points])
     for name, src in units:
         path = out_dir / name
         if not path.exists() or path.read_text() != src:
             path.write_text(src)
     return [name for name, _ in units]
+
+
+def generate_all(out_dir) -> List[str]:
+    """every ahead-of-time unit of csrc/generated/ itself into out_dir; returns the file names: the main units, then the satellite
+    units of the link units (planning loop with the via-point term, via-point cost) and of the attached-point units (their boolean
+    kernels), which register after the main ones.  (The attached-point units' planning loop: generate_points_adam_units.)"""
+    links, points = _load_units(SPEC_ROBOTS), _load_units(SPEC_POINT_ROBOTS)
+    small = [(ident, kin, tmpl) for ident, kin, tmpl in links if via_cost_ok(kin, tmpl, ident)]
+    return _write_units(out_dir, [(f"spec_{i}.hip", generate_link_kernel_source(k, t, i)) for i, k, t in links] +
+                        [(f"spec_{i}.hip", generate_points_rollout_source(k, t, i)) for i, k, t in points] +
+                        [(f"spec_{i}_vadam.hip", generate_via_adam_source(k, t, i)) for i, k, t in small] +
+                        [(f"spec_{i}_via.hip", generate_via_cost_source(k, t, i)) for i, k, t in small] +
+                        [(f"spec_{i}_coll.hip", generate_points_collision_source(k, t, i)) for i, k, t in points])
+
+
+# The planning-loop units of the attached-point models are generated into a directory of their own below csrc/generated/: what
+# generate_all returns, and which spec_*.hip files csrc/generated/ itself may hold, is pinned unit for unit by the tests of the earlier
+# kernel families (tests/test_arm_traj_via_cpu.py, tests/test_codegen_cpu.py).
+POINTS_ADAM_DIR = "padam"
+
+
+def generate_points_adam_units(out_dir) -> List[str]:
+    """spec_<ident>_padam.hip of every bundled attached-point unit that qualifies (points_adam_ok) into out_dir; the file names"""
+    return _write_units(out_dir, [(f"spec_{i}_padam.hip", generate_points_adam_source(k, t, i))
+                                  for i, k, t in _load_units(SPEC_POINT_ROBOTS) if points_adam_ok(k, t)])
+
+
+def generate_sources(out_dir) -> List[str]:
+    """Everything libtrk.so is built from, generated into out_dir (csrc/generated), as paths relative to it and in link order:
+    generate_all's units, with the attached-point units' planning-loop units (POINTS_ADAM_DIR/) after the via units and in front of
+    the boolean units.  What csrc/Makefile and _lib.build() call."""
+    from pathlib import Path
+    names = generate_all(out_dir)
+    padam = [f"{POINTS_ADAM_DIR}/{n}" for n in generate_points_adam_units(Path(out_dir) / POINTS_ADAM_DIR)]
+    first_coll = next(i for i, n in enumerate(names) if n.endswith("_coll.hip"))
+    return names[:first_coll] + padam + names[first_coll:]

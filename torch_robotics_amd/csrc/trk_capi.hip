@@ -122,9 +122,10 @@ int trk_spec_register_traj_adam(const SpecEntry* e, uint32_t sizeof_args, SpecTr
     traj_adam_registry().emplace_back(e, fn);
     return 0;
 }
-// Satellite units: the kernels of a generated unit that live in translation units of their own -- the boolean kernels of the
-// attached-point units (k_pcoll, spec_<ident>_coll), the via-point cost kernels (k_via_cost, spec_<ident>_via) and the planning-loop
-// kernels with the via-point term (k_traj_via_adam, spec_<ident>_vadam) of the small link-column units.  Each names the main unit it
+// Satellite units: the kernels of a generated unit that live in translation units of their own -- the boolean kernels and the
+// planning-loop kernels of the attached-point units (k_pcoll, spec_<ident>_coll; k_padam, spec_<ident>_padam), the via-point cost
+// kernels (k_via_cost, spec_<ident>_via) and the planning-loop kernels with the via-point term (k_traj_via_adam, spec_<ident>_vadam)
+// of the small link-column units.  Each names the main unit it
 // belongs to by its ident, its model hash and one more key (the points hash / the template identity).  Nothing here depends on which
 // of the two registered first; a unit that announces itself again (a rebuilt run-time unit) replaces its launcher.
 namespace {
@@ -156,6 +157,11 @@ SpecLaunchFn points_coll_launcher(const SpecEntry* e) {
     if (!e->name || e->module_ctx) return nullptr;          // (a code-object unit has no boolean kernel)
     return points_coll_registry().find(e->name, e->model_hash, e->points_hash);
 }
+SatelliteRegistry<SpecPointsAdamLaunchFn>& points_adam_registry() { static SatelliteRegistry<SpecPointsAdamLaunchFn> r; return r; }
+SpecPointsAdamLaunchFn points_adam_launcher(const SpecEntry* e) {
+    if (!e->name || e->module_ctx) return nullptr;          // (a code-object unit has no planning-loop kernel)
+    return points_adam_registry().find(e->name, e->model_hash, e->points_hash);
+}
 // must hash the same bytes, in the same order, as torch_robotics_amd/codegen.py: template_identity
 uint64_t via_template_identity(const SpecEntry* e) {
     uint64_t h = 0xcbf29ce484222325ull;
@@ -179,6 +185,14 @@ int trk_spec_register_points_coll(const char* ident, uint64_t model_hash, uint64
         return TRK_ERR_INVALID_ARG;
     }
     return points_coll_registry().announce(ident, model_hash, points_hash, fn);
+}
+int trk_spec_register_points_adam(const char* ident, uint64_t model_hash, uint64_t points_hash, uint32_t sizeof_args, SpecPointsAdamLaunchFn fn) {
+    if (!ident || !fn || sizeof_args != sizeof(TrajAdamArgs)) {
+        fprintf(stderr, "libtrk: refusing a generated unit's planning-loop point kernels (compiled against another TrajAdamArgs layout) -- "
+                        "they will not be dispatched\n");
+        return TRK_ERR_INVALID_ARG;
+    }
+    return points_adam_registry().announce(ident, model_hash, points_hash, fn);
 }
 int trk_spec_register_via_cost(const char* ident, uint64_t model_hash, uint64_t template_identity, uint32_t sizeof_args, SpecViaCostLaunchFn fn) {
     if (!ident || !fn || sizeof_args != sizeof(ViaCostArgs)) {
@@ -810,12 +824,14 @@ static int find_traj_unit(const char* who, const TrajKernelKind& k, const TrkMod
 }
 
 static bool traj_adam_updates(const TrkTrajAdam* ad) { return ad->lr != 0.0f && ad->n_steps > 0; }
-// What the two planning-loop entries check alike, in this order.  via: the entry's TrkTrajVia (with_via), checked right after the
-// structs are known to be there; other_horizons: what the horizon rule's refusal points to.
+// What the three planning-loop entries check alike, in this order.  via: the entry's TrkTrajVia (with_via), checked right after the
+// structs are known to be there; other_horizons: what the horizon rule's refusal points to; link_columns: the cost model's columns are
+// the model's links (the attached-point entry checks its columns against its point set afterwards).
 static int check_traj_adam_call(const char* who, const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w, const TrkGpPrior* gp,
                                 const TrkTrajVia* via, bool with_via, const TrkTrajAdam* ad, const float* q, const float* qd,
-                                const float* adam_m, const float* adam_v, int64_t batch, int32_t horizon, const char* other_horizons) {
-    if (int rc = check_rollout_call(who, m, cm, batch, horizon)) return rc;
+                                const float* adam_m, const float* adam_v, int64_t batch, int32_t horizon, const char* other_horizons,
+                                bool link_columns = true) {
+    if (int rc = check_rollout_call(who, m, cm, batch, horizon, link_columns)) return rc;
     if (!w || !gp || !ad) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null weights / prior / TrkTrajAdam");
     if (with_via) {
         if (!via || !via->alpha || !via->beta) return fail(TRK_ERR_INVALID_ARG, std::string(who) + ": null TrkTrajVia / alpha / beta");
@@ -1876,6 +1892,44 @@ int trk_rollout_gp_via_adam_steps(const TrkModel* m, const TrkCostModel* cm, con
     a.alpha = via->alpha; a.beta = via->beta; a.n_via = via->n_interp; a.w_via = via->w_via;
     return served_generated(traj_adam_launches(a, ad, cost, [&] { return spec_launch(without_self(fn), e, a, m, stream); }),
                             TRK_DISPATCH_GENERATED_VIA_ADAM);
+}
+
+int trk_rollout_points_gp_adam_steps(const TrkModel* m, const TrkPointSet* ps, const TrkCostModel* cm, const TrkRolloutWeights* w,
+                                     const TrkGpPrior* gp, const TrkTrajAdam* ad, float* q, float* qd, float* adam_m, float* adam_v,
+                                     int64_t batch, int32_t horizon, float* cost, trk_stream_t stream) {
+    const std::string who = "trk_rollout_points_gp_adam_steps";
+    int rc = check_traj_adam_call(who.c_str(), m, cm, w, gp, nullptr, false, ad, q, qd, adam_m, adam_v, batch, horizon,
+                                  "trk_rollout_points_cost_grad + trk_gp_prior_cost_grad serve any horizon", /*link_columns=*/false);
+    if (rc) return rc;
+    // the point set, as trk_rollout_points_cost_grad checks it
+    if (!ps) return fail(TRK_ERR_INVALID_ARG, who + ": null point set");
+    if (!ps->model) return fail(TRK_ERR_INVALID_ARG, who + ": the point set belongs to no model");
+    if (ps->model != m) return fail(TRK_ERR_INVALID_ARG, who + ": point set does not belong to this model");
+    if (cm->hdr.n_links_in != ps->dev.n_points) return fail(TRK_ERR_INVALID_ARG, who + ": cost model n_links_in != number of points");
+    if (cm->hdr.ee_link >= m->hdr.n_links || cm->hdr.ee2_link >= m->hdr.n_links)
+        return fail(TRK_ERR_INVALID_ARG, who + ": ee_link is not a link of the model");
+    if (batch == 0 || m->hdr.n_dofs == 0) return TRK_OK;
+    const TrkRolloutWeights we = effective_weights(cm, *w);
+    if (!m->spec_enabled)
+        return fail(TRK_ERR_UNSUPPORTED, who + ": generated kernels are switched off for this model (trk_model_enable_specialized) and the "
+                                               "planning loop has no table-driven form");
+    // the unit that bakes this cost model's columns, and the planning-loop launcher announced under its ident and hashes
+    const SpecEntry* e = points_spec_for(ps, cm, &we);
+    if (!e) {
+        if (points_spec(ps))
+            return fail(TRK_ERR_UNSUPPORTED, who + ": no generated unit of this point set bakes this cost model's column sets for the non-zero weights");
+        return fail(TRK_ERR_UNSUPPORTED, who + ": no generated unit serves this point set (k_padam: attached-point units of robots up to 8 "
+                                               "DOF, built ahead of time or by hipcc at run time)");
+    }
+    const SpecPointsAdamLaunchFn fn = points_adam_launcher(e);
+    if (!fn)
+        return fail(TRK_ERR_UNSUPPORTED, who + ": the unit of this point set carries no planning-loop kernel (k_padam: attached-point units of "
+                                               "robots up to 8 DOF, built ahead of time or by hipcc at run time; a unit loaded as a code "
+                                               "object through the hipRTC fall-back has none)");
+    if (!traj_adam_updates(ad) && !cost) return TRK_OK;
+    TrajAdamArgs a;
+    fill_traj_adam_args(a, m, cm, we, gp, ad, q, qd, adam_m, adam_v, batch, horizon);
+    return served_generated(traj_adam_launches(a, ad, cost, [&] { return spec_launch(without_self(fn), e, a, m, stream); }));
 }
 
 int trk_rollout_via_cost_grad(const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w, const float* x, int64_t n_traj,

@@ -163,6 +163,10 @@ int trk_spec_register_traj_adam(const SpecEntry* e, uint32_t sizeof_args, SpecTr
 // spec_<ident>_coll, which cannot see the main unit's entry: it announces its launcher under the main unit's ident and hashes, and
 // the dispatcher looks it up by those of the entry points_spec_for chose.  Refused when compiled against another SpecArgs.
 int trk_spec_register_points_coll(const char* ident, uint64_t model_hash, uint64_t points_hash, uint32_t sizeof_args, SpecLaunchFn fn);
+// the planning-loop kernels of an attached-point unit (k_padam; trk_rollout_points_gp_adam_steps) live in spec_<ident>_padam and are
+// announced the same way, under the main unit's ident and hashes.  Refused when compiled against another TrajAdamArgs.
+typedef void (*SpecPointsAdamLaunchFn)(const TrajAdamArgs& args, int base_identity, hipStream_t stream);
+int trk_spec_register_points_adam(const char* ident, uint64_t model_hash, uint64_t points_hash, uint32_t sizeof_args, SpecPointsAdamLaunchFn fn);
 #endif
 
 // Arguments of the generated via-point cost kernel (k_via_cost; trk_rollout_via_cost_grad): the cost header, weights and base pose

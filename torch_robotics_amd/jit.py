@@ -455,11 +455,34 @@ def has_matching_points_unit(kin: KinModel, point_link, point_offset, spec) -> b
     return False
 
 
+_pending_points_adam: Dict[str, tuple] = {}    # run-time point units whose spec_<ident>_padam unit has not been asked for yet: ident -> (kin, pt)
+
+
+def load_points_adam_units(kin: KinModel, verbose: bool = False) -> List[str]:
+    """Compile (cached under the generator's stamp, like every unit) and load the planning-loop kernels of every run-time
+    attached-point unit of this robot that qualifies for them; each unit's initialiser announces its launcher under the main unit's
+    ident and hashes (trk_spec_register_points_adam).  Called when a plan binds trk_rollout_points_gp_adam_steps; idempotent, and a
+    no-op for the bundled units, whose kernels are linked into libtrk.so.  Returns the idents loaded by this call."""
+    h, done = codegen.model_hash(kin), []
+    for ident, (k2, pt) in list(_pending_points_adam.items()):
+        if codegen.model_hash(k2) != h:
+            continue
+        aso, astamp = JIT_DIR / f"spec_{ident}_padam.so", JIT_DIR / f"spec_{ident}_padam.stamp"
+        if not (aso.exists() and astamp.exists() and astamp.read_text() == _generator_stamp()):
+            aso = _compile_unit(codegen.generate_points_adam_source(k2, pt, ident), f"{ident}_padam", verbose)
+        _loaded[f"{ident}_padam"] = C.CDLL(str(aso))
+        del _pending_points_adam[ident]
+        done.append(ident)
+    return done
+
+
 def specialize_points(kin: KinModel, point_link, point_offset, spec, verbose: bool = False) -> Optional[str]:
     """Generated fused kernel for a robot whose collision columns are attached points (RobotPanda with another sphere
     table, another grasped object ...).  Returns None when the column layout is not one the generator handles.
     With hipcc the unit's boolean kernels (codegen.generate_points_collision_source) are compiled and loaded next to it; the hipRTC
-    fall-back carries none: such a robot keeps the two-step boolean path (fk_points + collision_fields)."""
+    fall-back carries none: such a robot keeps the two-step boolean path (fk_points + collision_fields).  The planning-loop kernels
+    (codegen.generate_points_adam_source) are a third unit under the same rule, compiled and loaded on the first request for them
+    (load_points_adam_units: ops.PointsAdamPlan), not here."""
     pt = _points_template_of(kin, point_link, point_offset, spec)
     if pt is None:
         return None
@@ -478,6 +501,10 @@ def specialize_points(kin: KinModel, point_link, point_offset, spec, verbose: bo
         if not (cso.exists() and cstamp.exists() and cstamp.read_text() == _generator_stamp()):
             cso = _compile_unit(codegen.generate_points_collision_source(kin, pt, ident), f"{ident}_coll", verbose)
         _loaded[f"{ident}_coll"] = C.CDLL(str(cso))
+        if codegen.points_adam_ok(kin, pt):
+            # its planning-loop kernels (k_padam: ops.PointsAdamPlan) are a third unit, compiled only when a plan first binds the entry:
+            # load_points_adam_units
+            _pending_points_adam[ident] = (kin, pt)
     else:           # no compiler driver on this box: the unit's device half through hipRTC (round 5: attached-point units too)
         _loaded[ident] = _load_points_unit_rtc(kin, pt, ident)
     _loaded_point_templates[ident] = (codegen.model_hash(kin), pt)

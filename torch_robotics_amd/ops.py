@@ -1630,7 +1630,7 @@ def planar_adam_bias_terms(step: int):
 
 
 class _AdamLoopPlan(_Plan):
-    """What PlanarAdamPlan and ArmAdamPlan share: the state the plan owns, the pin mask, the rule that binds the via loop, and step().
+    """What PlanarAdamPlan, ArmAdamPlan and PointsAdamPlan share: the state the plan owns, the pin mask, the rule that binds the via loop, and step().
     A subclass checks its own arguments, calls _own_state with its state width and TrkPlanarAdam / TrkTrajAdam, and binds in _bind."""
 
     def _own_state(self, q, qd, B, H, width, adam_struct, lr, pins, w_via, num_interpolation) -> None:
@@ -1728,6 +1728,44 @@ class ArmAdamPlan(_AdamLoopPlan):
         else:
             self._fn = lib().trk_rollout_gp_adam_steps
             self._args = head + tail
+
+
+class PointsAdamPlan(_AdamLoopPlan):
+    """ArmAdamPlan for the attached-point models (link spheres, grasped-object points; include/trk.h:
+    trk_rollout_points_gp_adam_steps, generated kernel k_padam, robots up to 8 DOF): Adam on PointsRolloutPlan's objective plus the
+    constant-velocity GP prior, with the trajectories and the optimiser's state on the chip.  Pre-bound: `step(n)` runs the next n
+    iterations on the caller's q, qd (B,H,D) fp32 IN PLACE -- one launch per 32 iterations -- and returns the (B,H) cost of the state
+    it started from.  The plan owns `m`, `v` (B,H,2D) = [q part | qd part], `cost` and the iteration counter `t`.  H must be a power
+    of two <= 64.  pin_*: the start / goal position (velocity) keeps its value.  lr = 0 only evaluates.  The via-point term is not
+    part of this kernel: w_via / num_interpolation raise NotImplementedError."""
+
+    def __init__(self, ps: "PointSetHandle", cm: CostHandle, weights, q: torch.Tensor, qd: torch.Tensor, dt: float, sigma: float,
+                 gp_weight: float = 1.0, lr: float = 1e-2, pin_start: bool = True, pin_goal: bool = True, pin_start_vel: bool = False,
+                 pin_goal_vel: bool = False, w_via: float = 0.0, num_interpolation: int = 0):
+        if w_via != 0.0 or num_interpolation != 0:
+            raise NotImplementedError("PointsAdamPlan: the via-point term is outside the attached-point planning-loop kernel "
+                                      "(ArmAdamPlan has it for link-column cost models)")
+        model = ps.model
+        B, H, D = _gp_args(model, q, qd, "PointsAdamPlan")
+        if q.dtype != torch.float32:
+            raise ValueError("PointsAdamPlan: q, qd must be float32 (the planning-loop kernel has no fp16 I/O)")
+        if H > _abi.TRK_TRAJ_ADAM_MAX_HORIZON or H & (H - 1):
+            raise NotImplementedError(f"PointsAdamPlan: horizon {H} is not a power of two <= {_abi.TRK_TRAJ_ADAM_MAX_HORIZON} (a wavefront of "
+                                      f"the planning-loop kernel owns whole trajectories; PointsRolloutPlan + gp_prior_cost_grad serve any "
+                                      f"horizon)")
+        self._own_state(q, qd, B, H, 2 * D, _abi.TrajAdam, lr, (pin_start, pin_goal, pin_start_vel, pin_goal_vel), 0.0, 0)
+        self.model, self.ps, self.cm = model, ps, cm
+        self._w = _weights_struct(weights)
+        self._gp = _abi.GpPrior(float(dt), float(sigma), float(gp_weight))
+        self._bind()
+
+    def _bind(self) -> None:
+        """the entry point and its arguments"""
+        from . import jit
+        jit.load_points_adam_units(self.model.kin)       # a run-time unit's k_padam is compiled on the first request for it
+        self._fn = lib().trk_rollout_points_gp_adam_steps
+        self._args = (self.model._h, self.ps._h, self.cm._h, C.byref(self._w), C.byref(self._gp), C.byref(self._adam), self.q.data_ptr(),
+                      self.qd.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.B, self.H, self.cost.data_ptr())
 
 
 def reduce_sum(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

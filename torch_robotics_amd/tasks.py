@@ -264,7 +264,8 @@ class PlanningTask(Task):
         collision / EE objective at the num_interpolation via points of every segment, the points `get_trajs_collision_and_free`
         tests (`trk_rollout_gp_via_adam_steps`); otherwise the plan is the plain loop."""
         if getattr(self.robot, "has_extra_points", False):
-            raise NotImplementedError("rollout_adam_plan is for link-column cost models (no grasped object / link spheres)")
+            raise NotImplementedError("rollout_adam_plan is for link-column cost models (no grasped object / link spheres): "
+                                      "points_adam_plan is the planning loop of the attached-point models")
         if not self._has_tree:
             raise NotImplementedError("rollout_adam_plan needs a robot with a kinematic tree (the 2-D point mass has trajectory_optimizer)")
         H = int(q.shape[1]) if q.dim() == 3 else 0
@@ -274,6 +275,24 @@ class PlanningTask(Task):
         model, cm = self._fused_handles(q.device)
         return ops.ArmAdamPlan(model, cm, (w_self, w_obj, w_ws, w_ee), q, qd, dt, sigma_gp, gp_weight, lr, w_via=w_via,
                                num_interpolation=num_interpolation, **pins)
+
+    def points_adam_plan(self, q, qd, dt, sigma_gp, gp_weight=1.0, w_self=1.0, w_obj=1.0, w_ws=1.0, w_ee=0.0, lr=1e-2,
+                         **pins) -> "ops.PointsAdamPlan":
+        """`rollout_adam_plan` for a robot whose collision columns are attached points (link spheres, a grasped object, both):
+        the planning loop on the chip (`trk_rollout_points_gp_adam_steps`, kernel k_padam), Adam on `rollout_plan`'s objective plus
+        the constant-velocity GP prior with q, qd (B,H,D) fp32 and the optimiser's state in registers.  `plan.step(n)` improves q, qd
+        in place and returns the (B,H) cost they started from; pins as in `rollout_adam_plan`.  Robots up to 8 DOF, horizons that are
+        a power of two <= 64; a point set without a bundled unit compiles its kernels on first use (hipcc only).  The via-point term
+        is not part of this loop."""
+        if not getattr(self.robot, "has_extra_points", False):
+            raise NotImplementedError("points_adam_plan is for attached-point cost models (link spheres / a grasped object); "
+                                      "rollout_adam_plan is the planning loop of the link-column models")
+        H = int(q.shape[1]) if q.dim() == 3 else 0
+        if q.dim() == 3 and (H < 1 or H > 64 or H & (H - 1)):          # before _fused_handles, which may compile a unit
+            raise NotImplementedError(f"points_adam_plan: horizon {H} is not a power of two <= 64 (a wavefront of the planning-loop "
+                                      f"kernel owns whole trajectories; rollout_plan + ops.gp_prior_cost_grad serve any horizon)")
+        _model, cm = self._fused_handles(q.device)
+        return ops.PointsAdamPlan(self._points(q.device), cm, (w_self, w_obj, w_ws, w_ee), q, qd, dt, sigma_gp, gp_weight, lr, **pins)
 
     def rollout_via_plan(self, q, num_interpolation=5, w_self=1.0, w_obj=1.0, w_ws=1.0, w_ee=0.0, seed=None, gq_out=None) -> "ops.RolloutViaPlan":
         """Pre-bound via-point cost (`trk_rollout_via_cost_grad`): `plan.launch()` fills `plan.cost` (B, (H-1) n), the objective at the n
