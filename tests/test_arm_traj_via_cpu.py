@@ -1,7 +1,7 @@
 """CPU-only checks of the arm's planning loop with the via-point term (trk_rollout_gp_via_adam_steps, generated kernels
 k_traj_via_adam_bi / k_traj_via_adam_bg<BOX>): header, EXPORTS, library and documents agree and the ctypes struct has the header's
 layout; bad arguments are refused before any device work (model and cost model are blocks of zeros that are never dereferenced beyond
-their headers); the generator writes a unit of its own for the small arms only, generate_all lists it in front of the via-point cost
+their headers); the generator writes a unit of its own for the small arms only, generate_sources lists it in front of the via-point cost
 units, and the Panda's main and via-point cost units keep their text; the kernel body has one run-time loop over the via points
 inside the iteration loop, no barrier, one load and one store of each state array and the interpolation rounded operation by
 operation; the four compiled Panda instantiations use no scratch, fit the occupancy the generator states, have no barrier and no
@@ -111,8 +111,8 @@ def _vadam_text(ident):
     return kin, tmpl, codegen.generate_via_adam_source(kin, tmpl, ident)
 
 
-def test_generate_all_lists_the_units_of_the_small_arms_in_front_of_the_via_units(tmp_path):
-    names = codegen.generate_all(tmp_path)
+def test_generate_sources_lists_the_units_of_the_small_arms_in_front_of_the_via_units(tmp_path):
+    names = codegen.generate_sources(tmp_path)
     vadam = [n for n in names if n.endswith("_vadam.hip")]
     assert vadam == [f"spec_{i}_vadam.hip" for i in SMALL_ARMS]
     for ident in ("dual_panda", "ur10_allegro"):
@@ -120,8 +120,10 @@ def test_generate_all_lists_the_units_of_the_small_arms_in_front_of_the_via_unit
     assert len(set(names)) == len(names)
     via = [n for n in names if n.endswith("_via.hip")]
     first_main = [f"spec_{i}.hip" for i in list(codegen.SPEC_ROBOTS) + list(codegen.SPEC_POINT_ROBOTS)]
-    # after the main units, contiguous, in front of the first via unit; the via units contiguous, the three _coll units last
-    assert names == first_main + vadam + via + [f"spec_{i}_coll.hip" for i in codegen.SPEC_POINT_ROBOTS]
+    # after the main units, contiguous, in front of the first via unit; the via units contiguous, then the attached-point units'
+    # planning loops, the three _coll units last
+    padam = [f"spec_{i}_padam.hip" for i in codegen.SPEC_POINT_ROBOTS]
+    assert names == first_main + vadam + via + padam + [f"spec_{i}_coll.hip" for i in codegen.SPEC_POINT_ROBOTS]
     for ident in codegen.SPEC_ROBOTS:
         kin, tmpl = codegen.template_for(ident)
         assert codegen.via_adam_ok(kin, tmpl, ident) == (f"spec_{ident}_vadam.hip" in vadam), ident
@@ -222,15 +224,18 @@ def test_the_task_hands_the_plan_out_only_where_it_holds():
         ops.ArmAdamPlan(None, None, (1, 1, 1, 0), q7, q7.clone(), 0.1, 1.0, w_via=0.2, num_interpolation=5)
 
 
-def test_run_time_units_get_their_kernels_on_the_first_request():
-    """jit.specialize only notes that a qualifying run-time unit may get a spec_<ident>_vadam unit; ArmAdamPlan asks for it when it
-    binds the term.  A robot served by the bundled units has nothing to compile."""
+from test_satellite_units_cpu import rec          # noqa: E402,F401  (the recorder in place of compiler and dlopen)
+
+
+def test_run_time_units_get_their_kernels_on_the_first_request(rec):          # noqa: F811
+    """jit.specialize only notes that a qualifying run-time unit may get a spec_<ident>_vadam unit (told by the requests it makes:
+    tests/test_satellite_units_cpu.py has every other case); ArmAdamPlan asks for it when it binds the term.  A robot served by the
+    bundled units has nothing to compile."""
     import inspect
+    from test_satellite_units_cpu import first_request_of_the_iiwa7_unit
     from torch_robotics_amd import jit, ops
-    src = inspect.getsource(jit.specialize)
-    assert "_pending_via_adam[ident]" in src and "generate_via_adam_source(kin" not in src and "TRK_JIT_VIA_UNITS" in src
-    assert "generate_via_adam_source" in inspect.getsource(jit.load_via_adam_units)
+    first_request_of_the_iiwa7_unit(rec)
     bind = inspect.getsource(ops.ArmAdamPlan._bind)
-    assert bind.index("if via:") < bind.index("jit.load_via_adam_units(self.model.kin)") < bind.index("else:")
+    assert bind.index("if via:") < bind.index('jit.load_satellite_units(self.model.kin, "vadam")') < bind.index("else:")
     kin, _ = codegen.template_for("panda")
-    assert jit.load_via_adam_units(kin) == []
+    assert jit.load_satellite_units(kin, "vadam") == [] and len(rec.requests) == 3

@@ -207,7 +207,7 @@ def test_evaluation_on_the_bundled_ur10_unit(oracle_lib):
 
 def test_evaluation_on_a_run_time_compiled_iiwa7_unit(oracle_lib):
     """the unit of test_gpu_arm_traj.test_a_run_time_compiled_iiwa7_unit (compiled once per checkout, loaded once per process):
-    its spec_<ident>_vadam unit is built and loaded when a plan first binds the term (jit.load_via_adam_units)"""
+    its spec_<ident>_vadam unit is built and loaded when a plan first binds the term (jit.load_satellite_units)"""
     from oracle.oracle import Oracle
     from torch_robotics_amd import codegen, jit
     from torch_robotics_amd.costmodel import CostModelSpec
@@ -224,13 +224,13 @@ def test_evaluation_on_a_run_time_compiled_iiwa7_unit(oracle_lib):
     ident = jit.specialize_for_cost_spec(kin, spec)
     assert ident is not None and ident.startswith("jit_")
     # compiled and loaded on the first request for the term, not with the main unit
-    assert (ident in jit._pending_via_adam) != (f"{ident}_vadam" in jit._loaded)
+    assert ((ident, "vadam") in jit._pending) != (f"{ident}_vadam" in jit._loaded)
     h, cm, o = ops.ModelHandle(kin), ops.CostHandle(spec, DEV), Oracle(kin, spec)
     q, qd = (dev(x) for x in at.inputs(kin, 5, 64))
     plan_of(h, cm, q, qd)                                        # the term off: nothing is compiled for it
-    assert (ident in jit._pending_via_adam) != (f"{ident}_vadam" in jit._loaded)
+    assert ((ident, "vadam") in jit._pending) != (f"{ident}_vadam" in jit._loaded)
     plan_of(h, cm, q, qd, 5, 0.2)
-    assert f"{ident}_vadam" in jit._loaded and ident not in jit._pending_via_adam and jit.load_via_adam_units(kin) == []
+    assert f"{ident}_vadam" in jit._loaded and (ident, "vadam") not in jit._pending and jit.load_satellite_units(kin, "vadam") == []
     for shape in [(5, 64, 5), (17, 4, 1)]:
         evaluate("iiwa7 (run-time unit)", ("iiwa7 jit",), kin, h, cm, o, oracle_lib, W, shape, GP_OFF)
 

@@ -453,8 +453,8 @@ def test_run_time_unit_gets_the_planning_loop(oracle_lib):
     RunTime.ps, RunTime.cm = ps, cm
     for shape in ((5, 64), (9, 32), (130, 1)):
         evaluation_gradient_and_update(RunTime, oracle_lib, W, shape, "run-time unit (stretched grasped box)")
-    assert (jit.JIT_DIR / f"spec_{ident}_padam.so").exists() and ident not in jit._pending_points_adam
-    assert jit.load_points_adam_units(m) == []                    # idempotent
+    assert (jit.JIT_DIR / f"spec_{ident}_padam.so").exists() and (ident, "padam") not in jit._pending
+    assert jit.load_satellite_units(m, "padam") == []                   # idempotent
 
 
 # 11 --------------------------------------------------------------------------------------------------------------------------

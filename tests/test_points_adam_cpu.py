@@ -126,7 +126,7 @@ def test_the_prior_is_the_arm_kernels_text():
 def test_earlier_units_keep_their_text(tmp_path):
     """The committed sha1 goldens, read here: the main attached-point units (spec_points_units_r10.json), the Panda link unit's
     earlier kernels (spec_panda_kernels_r08.json), the shared structs (spec_common_structs_r08.json) -- and spec_units_r14.json, the
-    sha1 of every other unit generate_all wrote before this kernel family existed (the other link units, the _via, _vadam and _coll
+    sha1 of every other unit the build list held before this kernel family existed (the other link units, the _via, _vadam and _coll
     satellites), recorded from the generator as it stood then: the emitters this change shares with them must not move a character."""
     want = json.loads((GOLDEN / "spec_points_units_r10.json").read_text())
     assert sorted(want) == sorted(IDENTS)
@@ -145,9 +145,9 @@ def test_earlier_units_keep_their_text(tmp_path):
     for name, sha in json.loads((GOLDEN / "spec_common_structs_r08.json").read_text()).items():
         m = re.search(r"^struct " + name + r" \{\n.*?^\};", hdr, flags=re.M | re.S)
         assert m and _sha(m.group(0)) == sha, name
-    names = codegen.generate_all(tmp_path)
+    names = codegen.generate_sources(tmp_path)
     earlier = json.loads((GOLDEN / "spec_units_r14.json").read_text())
-    assert sorted(earlier) == sorted(set(names) - {"spec_panda.hip"} - {f"spec_{i}.hip" for i in IDENTS})
+    assert sorted(earlier) == sorted(set(names) - {"spec_panda.hip"} - {f"spec_{i}{k}.hip" for i in IDENTS for k in ("", "_padam")})
     assert sum(n.endswith("_coll.hip") for n in earlier) == 3 and sum(n.endswith("_via.hip") for n in earlier) == 3
     assert sum(n.endswith("_vadam.hip") for n in earlier) == 3
     for name, sha in earlier.items():
@@ -155,38 +155,33 @@ def test_earlier_units_keep_their_text(tmp_path):
 
 
 def test_the_build_lists_the_units_where_stated(tmp_path):
-    """generate_all's return and the spec_*.hip files of csrc/generated/ itself are pinned unit for unit by the tests of the earlier
-    kernel families, so the new units are generated into csrc/generated/padam/; generate_sources, which the Makefile and _lib.build()
-    call, lists them in link order: after the _via units, in front of the _coll units."""
+    """generate_sources, which the Makefile and _lib.build() call, lists the units in link order -- after the _via units, in front of
+    the _coll units -- and writes them into the directory itself, like every other unit."""
     srcs = codegen.generate_sources(tmp_path)
-    names = codegen.generate_all(tmp_path)
-    padam = [f"{codegen.POINTS_ADAM_DIR}/spec_{i}_padam.hip" for i in IDENTS]
+    padam = [f"spec_{i}_padam.hip" for i in IDENTS]
     coll = [f"spec_{i}_coll.hip" for i in IDENTS]
     assert srcs[-3:] == coll and srcs[-6:-3] == padam and len(set(srcs)) == len(srcs)
-    assert [n for n in srcs if n not in padam] == names and names[-3:] == coll and not any("padam" in n for n in names)
+    assert [n for n in srcs if "padam" in n] == padam
     via = [n for n in srcs if n.endswith("_via.hip")]
     vadam = [n for n in srcs if n.endswith("_vadam.hip")]
     assert via and srcs.index(via[-1]) == len(srcs) - 7 and max(srcs.index(n) for n in vadam) < srcs.index(via[0])
-    assert codegen.generate_points_adam_units(tmp_path / "again") == [f"spec_{i}_padam.hip" for i in IDENTS]
     for ident in IDENTS:
         kin, pt = _unit(ident)
-        text = codegen.generate_points_adam_source(kin, pt, ident)
-        assert (tmp_path / codegen.POINTS_ADAM_DIR / f"spec_{ident}_padam.hip").read_text() == text
-        assert (tmp_path / "again" / f"spec_{ident}_padam.hip").read_text() == text
-        assert not (tmp_path / f"spec_{ident}_padam.hip").exists()
+        assert (tmp_path / f"spec_{ident}_padam.hip").read_text() == codegen.generate_points_adam_source(kin, pt, ident)
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(srcs) and not any(p.is_dir() for p in tmp_path.iterdir())
     # a file is rewritten only when its text changed
     f = tmp_path / srcs[-4]
     before = f.stat().st_mtime_ns
     codegen.generate_sources(tmp_path)
     assert f.stat().st_mtime_ns == before
-    # the Makefile builds what generate_sources lists (its pattern rule reaches the directory below), _lib.build() generates the same,
-    # and git keeps the generated units out of history
+    # the Makefile builds what generate_sources lists, _lib.build() generates the same, and git keeps the generated units out of history
     mk = (CSRC / "Makefile").read_text()
-    assert mk.count("codegen.generate_sources(") == 2 and "codegen.generate_all(" not in mk and "$(GEN)" in mk
+    assert mk.count("codegen.generate_sources(") == 2 and "$(GEN)" in mk
     assert re.search(r"^generated/%\.o: generated/%\.hip \$\(HDRS\)$", mk, re.M)
     import inspect
     assert "codegen.generate_sources(" in inspect.getsource(_lib.build)
-    assert f"torch_robotics_amd/csrc/generated/{codegen.POINTS_ADAM_DIR}/" in (ROOT / ".gitignore").read_text().split("\n")
+    ignored = (ROOT / ".gitignore").read_text().split("\n")
+    assert "torch_robotics_amd/csrc/generated/spec_*.hip" in ignored and "!torch_robotics_amd/csrc/generated/spec_panda.hip" in ignored
 
 
 def test_units_above_eight_dof_get_none():

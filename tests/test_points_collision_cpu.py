@@ -1,6 +1,6 @@
 """CPU-only checks of the boolean kernels of the attached-point models (k_pcoll_bi / k_pcoll_bg; trk_rollout_points_collision,
 trk_rollout_points_collision_via): the generator writes a unit of its own that defines exactly those two kernels, starts only them
-and announces its launcher under the main unit's ident and hashes, without touching the main unit's text; generate_all lists the
+and announces its launcher under the main unit's ident and hashes, without touching the main unit's text; generate_sources lists the
 three units; both entry points refuse bad arguments before any device work (point set and cost model are blocks of zeros, never read
 beyond their own headers); header, EXPORTS, library and INTEGRATION.md agree; the six compiled kernels use no scratch and fit the
 occupancy the generator states."""
@@ -83,8 +83,8 @@ def test_the_main_units_keep_their_text():
         assert not any("pcoll" in k for k in u.kernels)
 
 
-def test_generate_all_lists_the_three_units(tmp_path):
-    names = codegen.generate_all(tmp_path)
+def test_generate_sources_lists_the_three_units(tmp_path):
+    names = codegen.generate_sources(tmp_path)
     coll = [f"spec_{i}_coll.hip" for i in IDENTS]
     assert names[-3:] == coll and len(set(names)) == len(names)
     for ident in IDENTS:

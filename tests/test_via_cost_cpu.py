@@ -1,7 +1,7 @@
 """CPU-only checks of the fused via-point cost (trk_rollout_via_cost_grad, generated kernels k_via_cost_bi / k_via_cost_bg<BOX>): header,
 EXPORTS, library and INTEGRATION.md agree; bad arguments of every kind are refused before any device work (model and cost model are
 blocks of zeros that are never dereferenced beyond their headers); the generator writes a unit of its own for the small arms only,
-generate_all lists it in front of the attached-point units' boolean kernels, and the main Panda unit keeps its text; the kernel body
+generate_sources lists it in front of the attached-point units' satellite units, and the main Panda unit keeps its text; the kernel body
 has no barrier, a run-time loop and one DPP exchange per joint in each direction; the compiled Panda unit uses no scratch, fits the
 occupancy the generator states and has no s_barrier; the task method takes its two-step route where the kernel does not serve."""
 import ctypes as C
@@ -83,18 +83,19 @@ def _via_text(ident):
     return kin, tmpl, codegen.generate_via_cost_source(kin, tmpl, ident)
 
 
-def test_generate_all_lists_the_via_units_of_the_small_arms(tmp_path):
-    names = codegen.generate_all(tmp_path)
+def test_generate_sources_lists_the_via_units_of_the_small_arms(tmp_path):
+    names = codegen.generate_sources(tmp_path)
     via = [n for n in names if n.endswith("_via.hip")]
     for ident in SMALL_ARMS:
         assert f"spec_{ident}_via.hip" in via, ident
     for ident in ("dual_panda", "ur10_allegro"):
         assert f"spec_{ident}_via.hip" not in names and not (tmp_path / f"spec_{ident}_via.hip").exists(), ident
     assert len(set(names)) == len(names)
-    # after every main unit, in front of the attached-point units' boolean kernels (which stay the last three names)
+    # after every main unit, in front of the attached-point units' planning loops and boolean kernels (which stay the last three names)
     first, last = names.index(via[0]), names.index(via[-1])
-    assert last - first == len(via) - 1 and names[last + 1:] == [f"spec_{i}_coll.hip" for i in codegen.SPEC_POINT_ROBOTS]
-    assert all(not n.endswith(("_via.hip", "_coll.hip")) for n in names[:first])
+    assert last - first == len(via) - 1 and names[-3:] == [f"spec_{i}_coll.hip" for i in codegen.SPEC_POINT_ROBOTS]
+    assert names[last + 1:-3] and all(n.endswith("_padam.hip") for n in names[last + 1:-3])
+    assert all(not n.endswith(("_via.hip", "_padam.hip", "_coll.hip")) for n in names[:first])
     for n in via:
         ident = n[len("spec_"):-len("_via.hip")]
         kin, tmpl, text = _via_text(ident)

@@ -20,7 +20,7 @@ from __future__ import annotations
 import os
 
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -2219,15 +2219,6 @@ def template_identity(tmpl: CollisionTemplate) -> int:
     return h
 
 
-def via_cost_ok(kin: KinModel, tmpl: CollisionTemplate, ident: str = "", snap: float = SNAP) -> bool:
-    """does the robot's link unit get a spec_<ident>_via unit?  The units that carry k_traj_adam: whole-row staging, no virtual
-    columns, up to 8 DOF (_LinkUnit.traj_adam_ok, the one statement of the rule)"""
-    return _LinkUnit(kin, tmpl, ident, snap).traj_adam_ok
-
-
-via_adam_ok = via_cost_ok         # spec_<ident>_vadam: the same units
-
-
 def _via_cost_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     """k_via_cost_bi / _bg<BOX>: the collision / EE objective of trk_rollout_cost_grad at the n via points of every segment of a batch
     of trajectories (trk_rollout_via_cost_grad), and its gradient with respect to the WAY points.  One lane per way point, fp32; a
@@ -2283,11 +2274,6 @@ def _via_cost_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     E.raw("    spec_store_gq<D>(A.gq, base, rows, lane, lds, gv);")
     E.raw("}")
     return E.lines
-
-
-def via_cost_kernels(ident: str) -> List[str]:
-    """the kernels a spec_<ident>_via unit defines"""
-    return [f"spec_{ident}::k_via_cost_{b}<{v}>" for b in ("bi", "bg") for v in ("false", "true")]
 
 
 def _satellite_unit_source(header_comment: str, ident: str, constants: Sequence[str], fp_pragma: bool, kernels: Sequence[List[str]],
@@ -2405,11 +2391,6 @@ def _traj_via_adam_kernel(u: _LinkUnit, base_identity: bool) -> List[str]:
     _emit_adam_update(E, "x", "gqv[d]")
     _emit_adam_state_store(E, "x")
     return E.lines
-
-
-def via_adam_kernels(ident: str) -> List[str]:
-    """the kernels a spec_<ident>_vadam unit defines"""
-    return [f"spec_{ident}::k_traj_via_adam_{b}<{v}>" for b in ("bi", "bg") for v in ("false", "true")]
 
 
 def generate_via_adam_source(kin: KinModel, tmpl: CollisionTemplate, ident: str, snap: float = SNAP) -> str:
@@ -3404,11 +3385,6 @@ def _points_coll_kernel(u: _PointsUnit, base_identity: bool) -> List[str]:
     return _boolean_kernel_tail(E)
 
 
-def points_collision_kernels(ident: str) -> List[str]:
-    """the kernels a spec_<ident>_coll unit defines"""
-    return [f"spec_{ident}::k_pcoll_{b}" for b in ("bi", "bg")]
-
-
 def generate_points_collision_source(kin: KinModel, pt: PointsTemplate, ident: str, snap: float = SNAP) -> str:
     """spec_<ident>_coll.hip: the boolean kernels of an attached-point model (_points_coll_kernel), a translation unit of its own next
     to generate_points_rollout_source's -- same namespace, same _PointsUnit plan, nothing shared but the headers.  The main unit's
@@ -3456,16 +3432,6 @@ def _points_adam_kernel(u: _PointsUnit, base_identity: bool) -> List[str]:
     _emit_adam_update(E, "q", "gc[d] + gpv[d]")
     _emit_adam_state_store(E, "q")
     return E.lines
-
-
-def points_adam_kernels(ident: str) -> List[str]:
-    """the kernels a spec_<ident>_padam unit defines"""
-    return [f"spec_{ident}::k_padam_{b}<{f}>" for b in ("bi", "bg") for f in ("true", "false")]
-
-
-def points_adam_ok(kin: KinModel, pt: PointsTemplate) -> bool:
-    """does the attached-point unit of (kin, pt) get a spec_<ident>_padam unit?  (_PointsUnit.traj_adam_ok, the one statement of the rule)"""
-    return _PointsUnit(kin, pt, "").traj_adam_ok
 
 
 def generate_points_adam_source(kin: KinModel, pt: PointsTemplate, ident: str, snap: float = SNAP) -> str:
@@ -3637,24 +3603,12 @@ TREE_PIPELINE = False     # measured on MI355X: dual Panda 23.5 -> 37.8 us, UR10
                           # (NL = 1) loses the ILP of the batched NL = 10 evaluation; kept switchable for robots with many links per DOF
 
 
-_template_cache: Dict[str, tuple] = {}
-
-
 def template_for(ident: str):
     """(KinModel, CollisionTemplate) of a robot in SPEC_ROBOTS (a fresh KinModel per call: callers may move its base)."""
     from .kinematics import URDF_DIR
     urdf, fn = SPEC_ROBOTS[ident]
     kin = KinModel.from_urdf(str(URDF_DIR / urdf))
     return kin, fn(kin)
-
-
-def aot_units():
-    """[(ident, model hash, CollisionTemplate)] of the ahead-of-time link units, computed once per process."""
-    if not _template_cache:
-        for ident in SPEC_ROBOTS:
-            kin, tmpl = template_for(ident)
-            _template_cache[ident] = (model_hash(kin), tmpl)
-    return [(k, v[0], v[1]) for k, v in _template_cache.items()]
 
 
 def _load_units(robots):
@@ -3664,9 +3618,72 @@ def _load_units(robots):
     return [(ident, kins[ident], robots[ident][1](kins[ident])) for ident in robots]
 
 
-def _write_units(out_dir, units) -> List[str]:
-    """(file name, source) pairs into out_dir (a file is rewritten only when its text changed: make sees no new timestamp); the names"""
+_template_cache: Dict[int, list] = {}
+
+
+def aot_units(robots=SPEC_ROBOTS):
+    """[(ident, model hash, template)] of the ahead-of-time units of a table of bundled robots (SPEC_ROBOTS, SPEC_POINT_ROBOTS),
+    computed once per process."""
+    if id(robots) not in _template_cache:
+        _template_cache[id(robots)] = [(ident, model_hash(kin), t) for ident, kin, t in _load_units(robots)]
+    return list(_template_cache[id(robots)])
+
+
+class SatelliteKind(NamedTuple):
+    """One kind of satellite unit (_satellite_unit_source): spec_<ident>_<suffix>.hip next to the main unit of its owner."""
+    suffix: str
+    points: bool            # the owner: an attached-point unit (SPEC_POINT_ROBOTS, a PointsTemplate), else a link unit (SPEC_ROBOTS)
+    eligible: Callable      # (kin, template) -> does the owner's unit get one?
+    source: Callable        # (kin, template, ident) -> the unit's text
+    kernels: Sequence[str]  # the kernels the unit defines, as name expressions within namespace spec_<ident>
+    deferred: bool          # a run-time unit gets it on the first request (jit.load_satellite_units), else with its main unit
+
+
+def _traj_adam_ok(kin: KinModel, t) -> bool:
+    """the units that carry the planning loop: whole-row staging, no virtual columns, up to 8 DOF (_LinkUnit.traj_adam_ok and
+    _PointsUnit.traj_adam_ok, the only statements of the rule)"""
+    return (_PointsUnit(kin, t, "") if isinstance(t, PointsTemplate) else _LinkUnit(kin, t, "", SNAP)).traj_adam_ok
+
+
+def _kernel_names(stem: str, *instances: str) -> List[str]:
+    return [f"{stem}_{b}{f'<{i}>' if i else ''}" for b in ("bi", "bg") for i in instances or ("",)]
+
+
+# Every kind of satellite unit, in link order (a satellite registers after the main units): what generate_sources lists behind the
+# main units and what jit.py gives a run-time unit.  A new kind is one row.
+SATELLITES: Dict[str, SatelliteKind] = {k.suffix: k for k in (
+    SatelliteKind("vadam", False, _traj_adam_ok, generate_via_adam_source, _kernel_names("k_traj_via_adam", "false", "true"), True),
+    SatelliteKind("via", False, _traj_adam_ok, generate_via_cost_source, _kernel_names("k_via_cost", "false", "true"), False),
+    SatelliteKind("padam", True, _traj_adam_ok, generate_points_adam_source, _kernel_names("k_padam", "true", "false"), True),
+    SatelliteKind("coll", True, lambda kin, pt: True, generate_points_collision_source, _kernel_names("k_pcoll"), False),
+)}
+
+
+def _row_ok(suffix: str) -> Callable:
+    """does (kin, template[, ident]) get a spec_<ident>_<suffix> unit?  The row's answer."""
+    return lambda kin, t, ident="": SATELLITES[suffix].eligible(kin, t)
+
+
+def _row_kernels(suffix: str) -> Callable:
+    """the kernels a spec_<ident>_<suffix> unit defines, as name expressions: the row's, within the unit's namespace"""
+    return lambda ident: [f"spec_{ident}::{k}" for k in SATELLITES[suffix].kernels]
+
+
+# the earlier names of the rows' answers, each through the table
+via_adam_ok, via_cost_ok, points_adam_ok = _row_ok("vadam"), _row_ok("via"), _row_ok("padam")
+via_adam_kernels, via_cost_kernels, points_adam_kernels, points_collision_kernels = (_row_kernels(s) for s in SATELLITES)
+
+
+def generate_sources(out_dir) -> List[str]:
+    """Everything libtrk.so is built from, generated into out_dir (csrc/generated), as file names in link order: the link units, the
+    attached-point units, then every kind of satellite unit (SATELLITES) for the robots of its owner's table that are eligible.  A
+    file is rewritten only when its text changed: make sees no new timestamp.  What csrc/Makefile and _lib.build() call."""
     from pathlib import Path
+    owners = {False: _load_units(SPEC_ROBOTS), True: _load_units(SPEC_POINT_ROBOTS)}
+    units = [(f"spec_{i}.hip", generate_link_kernel_source(k, t, i)) for i, k, t in owners[False]] + \
+            [(f"spec_{i}.hip", generate_points_rollout_source(k, t, i)) for i, k, t in owners[True]]
+    for kind in SATELLITES.values():
+        units += [(f"spec_{i}_{kind.suffix}.hip", kind.source(k, t, i)) for i, k, t in owners[kind.points] if kind.eligible(k, t)]
     out_dir = Path(out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
     for name, src in units:
@@ -3674,39 +3691,3 @@ def _write_units(out_dir, units) -> List[str]:
         if not path.exists() or path.read_text() != src:
             path.write_text(src)
     return [name for name, _ in units]
-
-
-def generate_all(out_dir) -> List[str]:
-    """every ahead-of-time unit of csrc/generated/ itself into out_dir; returns the file names: the main units, then the satellite
-    units of the link units (planning loop with the via-point term, via-point cost) and of the attached-point units (their boolean
-    kernels), which register after the main ones.  (The attached-point units' planning loop: generate_points_adam_units.)"""
-    links, points = _load_units(SPEC_ROBOTS), _load_units(SPEC_POINT_ROBOTS)
-    small = [(ident, kin, tmpl) for ident, kin, tmpl in links if via_cost_ok(kin, tmpl, ident)]
-    return _write_units(out_dir, [(f"spec_{i}.hip", generate_link_kernel_source(k, t, i)) for i, k, t in links] +
-                        [(f"spec_{i}.hip", generate_points_rollout_source(k, t, i)) for i, k, t in points] +
-                        [(f"spec_{i}_vadam.hip", generate_via_adam_source(k, t, i)) for i, k, t in small] +
-                        [(f"spec_{i}_via.hip", generate_via_cost_source(k, t, i)) for i, k, t in small] +
-                        [(f"spec_{i}_coll.hip", generate_points_collision_source(k, t, i)) for i, k, t in points])
-
-
-# The planning-loop units of the attached-point models are generated into a directory of their own below csrc/generated/: what
-# generate_all returns, and which spec_*.hip files csrc/generated/ itself may hold, is pinned unit for unit by the tests of the earlier
-# kernel families (tests/test_arm_traj_via_cpu.py, tests/test_codegen_cpu.py).
-POINTS_ADAM_DIR = "padam"
-
-
-def generate_points_adam_units(out_dir) -> List[str]:
-    """spec_<ident>_padam.hip of every bundled attached-point unit that qualifies (points_adam_ok) into out_dir; the file names"""
-    return _write_units(out_dir, [(f"spec_{i}_padam.hip", generate_points_adam_source(k, t, i))
-                                  for i, k, t in _load_units(SPEC_POINT_ROBOTS) if points_adam_ok(k, t)])
-
-
-def generate_sources(out_dir) -> List[str]:
-    """Everything libtrk.so is built from, generated into out_dir (csrc/generated), as paths relative to it and in link order:
-    generate_all's units, with the attached-point units' planning-loop units (POINTS_ADAM_DIR/) after the via units and in front of
-    the boolean units.  What csrc/Makefile and _lib.build() call."""
-    from pathlib import Path
-    names = generate_all(out_dir)
-    padam = [f"{POINTS_ADAM_DIR}/{n}" for n in generate_points_adam_units(Path(out_dir) / POINTS_ADAM_DIR)]
-    first_coll = next(i for i, n in enumerate(names) if n.endswith("_coll.hip"))
-    return names[:first_coll] + padam + names[first_coll:]

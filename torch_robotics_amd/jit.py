@@ -15,7 +15,7 @@ import hashlib
 import os
 import subprocess
 from pathlib import Path
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -42,14 +42,16 @@ def _compile_cmd(src: str, out: str):
             "-Wl,-rpath,$ORIGIN/.." if JIT_DIR == _CSRC / "jit" else f"-Wl,-rpath,{_CSRC}"]
 
 
-def template_hash(tmpl: codegen.CollisionTemplate) -> str:
+def template_hash(t) -> str:
+    """of a CollisionTemplate or a PointsTemplate (whose point set is named by its own hash in the unit's ident)"""
+    points = isinstance(t, codegen.PointsTemplate)
     h = hashlib.sha1()
-    h.update(np.asarray(tmpl.obj_links, np.int32).tobytes())
-    h.update(np.asarray(tmpl.self_pairs, np.int32).reshape(-1).tobytes())
-    h.update(np.asarray([tmpl.ee_link, tmpl.ee2_link], np.int32).tobytes())
-    if tmpl.virtual:
-        h.update(np.asarray([r[:2] for r in tmpl.virtual], np.int32).tobytes())
-        h.update(np.asarray([r[2:] for r in tmpl.virtual], np.float32).tobytes())
+    h.update(np.asarray(t.obj_cols if points else t.obj_links, np.int32).tobytes())
+    h.update(np.asarray(t.self_pairs, np.int32).reshape(-1).tobytes())
+    h.update(np.asarray([t.ee_link, t.ee2_link], np.int32).tobytes())
+    if not points and t.virtual:
+        h.update(np.asarray([r[:2] for r in t.virtual], np.int32).tobytes())
+        h.update(np.asarray([r[2:] for r in t.virtual], np.float32).tobytes())
     return h.hexdigest()[:8]
 
 
@@ -70,20 +72,22 @@ def _generator_stamp() -> str:
     return h.hexdigest()[:12]
 
 
-def _load_unit(so: Path, ident: str) -> C.CDLL:
-    """dlopen a unit and make sure libtrk.so accepted its registration (it refuses another struct layout)."""
+def _load_unit(so: Path, name: str, main: bool = True) -> None:
+    """dlopen spec_<name>.so and record it in _loaded.  A main unit registers with libtrk.so (trk_spec_register), which refuses another
+    struct layout; a satellite unit (name = <ident>_<suffix>) announces its launcher under the ident of its main unit, loaded before it."""
     L = _lib.lib()                                  # libtrk.so first: the unit's initialiser calls into it
     before = L.trk_spec_count()
     handle = C.CDLL(str(so))
-    if L.trk_spec_count() != before + 1:
+    if main and L.trk_spec_count() != before + 1:
         raise _lib.TrkError(f"{so.name}: libtrk.so refused the unit (compiled against another SpecArgs/SpecEntry layout); "
                             f"delete {so} and retry")
-    return handle
+    _loaded[name] = handle
 
 
-def _compile_unit(source: str, ident: str, verbose: bool) -> Path:
-    """source -> csrc/jit/spec_<ident>.so.  Every file appears under its final name by an atomic rename, so several
-    processes (one per GPU) compiling the same unit at the same time cannot hand each other a half-written object."""
+def _cached_unit(ident: str, source: Callable[[], str], verbose: bool = False) -> Path:
+    """csrc/jit/spec_<ident>.so, current under the generator's stamp: from the cache, else source() -- called on a miss only -- is
+    compiled.  Every file appears under its final name by an atomic rename, so several processes (one per GPU) compiling the same
+    unit at the same time cannot hand each other a half-written object."""
     JIT_DIR.mkdir(parents=True, exist_ok=True)
     src, so, stamp = JIT_DIR / f"spec_{ident}.hip", JIT_DIR / f"spec_{ident}.so", JIT_DIR / f"spec_{ident}.stamp"
     want = _generator_stamp()
@@ -94,7 +98,7 @@ def _compile_unit(source: str, ident: str, verbose: bool) -> Path:
     tag = f".tmp{os.getpid()}"
     src_tmp = JIT_DIR / f"spec_{ident}{tag}.hip"
     so_tmp = JIT_DIR / f"spec_{ident}{tag}.so"
-    src_tmp.write_text(source)
+    src_tmp.write_text(source())
     cmd = _compile_cmd(str(src_tmp), str(so_tmp))
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
@@ -276,70 +280,71 @@ def build_unit(kin: KinModel, tmpl: codegen.CollisionTemplate, verbose: bool = F
     """Generate + compile (no GPU needed: hipcc cross-compiles); returns the path of the shared object.
     pipeline: force the per-link pipeline generator (codegen.generate_points_rollout_source in link mode)."""
     ident = unit_ident(kin, tmpl, pipeline)
-    so, stamp = JIT_DIR / f"spec_{ident}.so", JIT_DIR / f"spec_{ident}.stamp"
-    if so.exists() and stamp.exists() and stamp.read_text() == _generator_stamp():
-        return so
     if pipeline:
-        source = codegen.generate_points_rollout_source(kin, codegen.link_points_template(kin, tmpl), ident, link_mode=True)
-    else:
-        source = codegen.generate_link_kernel_source(kin, tmpl, ident)
-    return _compile_unit(source, ident, verbose)
+        return _cached_unit(ident, lambda: codegen.generate_points_rollout_source(kin, codegen.link_points_template(kin, tmpl), ident,
+                                                                                  link_mode=True), verbose)
+    return _cached_unit(ident, lambda: codegen.generate_link_kernel_source(kin, tmpl, ident), verbose)
+
+
+_loaded_templates: Dict[str, tuple] = {}        # the loaded run-time main units of both column kinds: ident -> (model hash, template)
+_pending: Dict[Tuple[str, str], tuple] = {}     # satellite units nobody has asked for yet: (ident, suffix) -> (kin, template)
+
+
+def _load_satellite(ident: str, kind: codegen.SatelliteKind, kin: KinModel, tmpl, verbose: bool) -> None:
+    """spec_<ident>_<suffix>: a unit of its own, cached under the same stamp as the main unit; its initialiser announces the launcher
+    under the main unit's ident"""
+    name = f"{ident}_{kind.suffix}"
+    _load_unit(_cached_unit(name, lambda: kind.source(kin, tmpl, ident), verbose), name, main=False)
+
+
+def _load_satellites(ident: str, kin: KinModel, tmpl, verbose: bool) -> None:
+    """The satellite units (codegen.SATELLITES) of a freshly loaded main unit: each kind of its owner that the unit is eligible for is
+    compiled and loaded now -- a further hipcc run of about the main unit's length on the robot's first use -- or, when the kind is
+    deferred, noted for the first request for it (load_satellite_units)."""
+    for kind in codegen.SATELLITES.values():
+        if kind.points == isinstance(tmpl, codegen.PointsTemplate) and kind.eligible(kin, tmpl):
+            if kind.deferred:
+                _pending[ident, kind.suffix] = (kin, tmpl)
+            else:
+                _load_satellite(ident, kind, kin, tmpl, verbose)
+
+
+def load_satellite_units(kin: KinModel, suffix: str, verbose: bool = False) -> List[str]:
+    """Compile (cached like every unit) and load the deferred satellite units of one kind -- "vadam": the planning loop with the
+    via-point term, "padam": the planning loop of an attached-point model -- of every run-time unit of this robot that qualifies.
+    Called when a plan binds the kind's entry; idempotent, and a no-op for robots served by the bundled units, whose kernels are
+    linked into libtrk.so.  Returns the idents loaded by this call."""
+    h, done = codegen.model_hash(kin), []
+    for (ident, sfx), (k2, tmpl) in list(_pending.items()):
+        if sfx == suffix and codegen.model_hash(k2) == h:
+            _load_satellite(ident, codegen.SATELLITES[suffix], k2, tmpl, verbose)
+            del _pending[ident, sfx]
+            done.append(ident)
+    return done
 
 
 def specialize(kin: KinModel, obj_links: Sequence[int], self_pairs: Sequence[Tuple[int, int]] = (), ee_link: int = -1,
                verbose: bool = False, pipeline: bool = False, ee2_link: int = -1, virtual=()) -> str:
     """Make sure a generated fused kernel for (kin, collision template) is registered with libtrk.so.  Idempotent.
     Returns the unit's identifier.  Robots that already have an ahead-of-time unit with the same template need nothing.
-    With hipcc a whole-row unit of a robot up to 8 DOF gets its via-point cost kernels (codegen.generate_via_cost_source) compiled
-    and loaded next to it -- a second hipcc run of about the main unit's length on the robot's first use, cached like it;
-    TRK_JIT_VIA_UNITS=0 skips it for callers that never ask for the via-point cost (they keep the two-step route).  The hipRTC
-    fall-back carries none: such a robot keeps the two-step via-point cost.  The planning-loop kernels with the via-point term
-    (codegen.generate_via_adam_source) are a third unit under the same rule and the same switch, compiled and loaded on the first
-    request for the term (load_via_adam_units: ops.ArmAdamPlan(..., w_via=, num_interpolation=)), not here: a robot that never asks
-    for the fused via loop keeps its first-use cost."""
+    With hipcc the unit gets the satellite units of a link unit it is eligible for (codegen.SATELLITES: a whole-row unit of a robot
+    up to 8 DOF) -- the via-point cost kernels next to it, the planning loop with the via-point term on the first request
+    (load_satellite_units: ops.ArmAdamPlan(..., w_via=, num_interpolation=)), so a robot that never asks for the fused via loop keeps
+    its first-use cost.  TRK_JIT_VIA_UNITS=0 skips them all for callers that never ask for the via-point cost (they keep the two-step
+    route).  The hipRTC fall-back carries none: such a robot keeps the two-step via-point cost."""
     tmpl = codegen.CollisionTemplate(obj_links=[int(i) for i in obj_links],
                                      self_pairs=[(int(a), int(b)) for a, b in self_pairs], ee_link=int(ee_link),
                                      ee2_link=int(ee2_link), virtual=[tuple(r) for r in virtual])
     ident = unit_ident(kin, tmpl, pipeline)
     if ident not in _loaded:
         if hipcc_available() or pipeline:
-            _loaded[ident] = _load_unit(build_unit(kin, tmpl, verbose, pipeline), ident)
-            if not pipeline and os.environ.get("TRK_JIT_VIA_UNITS", "1") != "0" and codegen.via_cost_ok(kin, tmpl, ident):
-                # the unit's via-point cost kernels (k_via_cost: ops.rollout_via_cost_grad): a unit of their own, spec_<ident>_via, cached
-                # under the same stamp; its initialiser announces the launcher under the main unit's ident (trk_spec_register_via_cost)
-                vso, vstamp = JIT_DIR / f"spec_{ident}_via.so", JIT_DIR / f"spec_{ident}_via.stamp"
-                if not (vso.exists() and vstamp.exists() and vstamp.read_text() == _generator_stamp()):
-                    vso = _compile_unit(codegen.generate_via_cost_source(kin, tmpl, ident), f"{ident}_via", verbose)
-                _loaded[f"{ident}_via"] = C.CDLL(str(vso))
-                if codegen.via_adam_ok(kin, tmpl, ident):
-                    # its planning-loop kernels with the via-point term (k_traj_via_adam) are a third unit, compiled only when a plan
-                    # first asks for the term: load_via_adam_units
-                    _pending_via_adam[ident] = (kin, tmpl)
+            _load_unit(build_unit(kin, tmpl, verbose, pipeline), ident)
+            if not pipeline and os.environ.get("TRK_JIT_VIA_UNITS", "1") != "0":
+                _load_satellites(ident, kin, tmpl, verbose)
         else:                               # no compiler driver on this box: the in-process fall-back
             _loaded[ident] = _load_unit_rtc(kin, tmpl, ident)
         _loaded_templates[ident] = (codegen.model_hash(kin), tmpl)
     return ident
-
-
-_pending_via_adam: Dict[str, tuple] = {}       # run-time units whose spec_<ident>_vadam unit has not been asked for yet: ident -> (kin, tmpl)
-
-
-def load_via_adam_units(kin: KinModel, verbose: bool = False) -> List[str]:
-    """Compile (cached under the generator's stamp, like every unit) and load the planning-loop kernels with the via-point term of
-    every run-time unit of this robot that qualifies for them; each unit's initialiser announces its launcher under the main unit's
-    ident (trk_spec_register_via_adam).  Called when a plan binds trk_rollout_gp_via_adam_steps; idempotent, and a no-op for robots
-    served by the bundled units, whose kernels are linked into libtrk.so.  Returns the idents loaded by this call."""
-    h, done = codegen.model_hash(kin), []
-    for ident, (k2, tmpl) in list(_pending_via_adam.items()):
-        if codegen.model_hash(k2) != h:
-            continue
-        aso, astamp = JIT_DIR / f"spec_{ident}_vadam.so", JIT_DIR / f"spec_{ident}_vadam.stamp"
-        if not (aso.exists() and astamp.exists() and astamp.read_text() == _generator_stamp()):
-            aso = _compile_unit(codegen.generate_via_adam_source(k2, tmpl, ident), f"{ident}_vadam", verbose)
-        _loaded[f"{ident}_vadam"] = C.CDLL(str(aso))
-        del _pending_via_adam[ident]
-        done.append(ident)
-    return done
 
 
 def _virtual_rows(spec):
@@ -369,45 +374,6 @@ def _template_of(kin: KinModel, spec) -> Optional[codegen.CollisionTemplate]:
                                      ee_link=int(spec.ee_link), ee2_link=int(spec.ee2_link), virtual=_virtual_rows(spec))
 
 
-def _serves(unit: codegen.CollisionTemplate, want: codegen.CollisionTemplate) -> bool:
-    """the dispatcher's rule (trk_capi.hip: spec_matches) for a caller that may use every weight"""
-    if list(unit.obj_links) != list(want.obj_links) or [tuple(p) for p in unit.self_pairs] != [tuple(p) for p in want.self_pairs]:
-        return False
-    if [tuple(np.float32(v) for v in r) for r in unit.virtual] != [tuple(np.float32(v) for v in r) for r in want.virtual]:
-        return False
-    return want.ee_link < 0 or (unit.ee_link == want.ee_link and unit.ee2_link == want.ee2_link)
-
-
-_loaded_templates: Dict[str, Tuple[int, codegen.CollisionTemplate]] = {}
-
-
-def has_matching_unit(kin: KinModel, spec) -> bool:
-    """True if an ahead-of-time unit (codegen.SPEC_ROBOTS) or an already loaded run-time unit serves this robot and
-    collision model."""
-    want = _template_of(kin, spec)
-    if want is None:
-        return False
-    h = codegen.model_hash(kin)
-    for mh, tm in _loaded_templates.values():
-        if mh == h and _serves(tm, want):
-            return True
-    for _ident, mh, t2 in codegen.aot_units():
-        if mh == h and _serves(t2, want):
-            return True
-    return False
-
-
-def specialize_for_cost_spec(kin: KinModel, spec, verbose: bool = False) -> Optional[str]:
-    """Template from a CostModelSpec whose columns are the links (no attached points)."""
-    tmpl = _template_of(kin, spec)
-    if tmpl is None:
-        return None
-    return specialize(kin, tmpl.obj_links, tmpl.self_pairs, tmpl.ee_link, verbose, ee2_link=tmpl.ee2_link, virtual=tmpl.virtual)
-
-
-# ----------------------------------------------------------------------------------------------------------------------
-# attached-point units (link spheres, grasped-object points): same mechanism, codegen.generate_points_rollout_source
-# ----------------------------------------------------------------------------------------------------------------------
 def _points_template_of(kin: KinModel, point_link, point_offset, spec) -> Optional[codegen.PointsTemplate]:
     pl = np.ascontiguousarray(point_link, np.int32).reshape(-1)
     po = np.ascontiguousarray(point_offset, np.float32).reshape(-1, 3)
@@ -420,92 +386,63 @@ def _points_template_of(kin: KinModel, point_link, point_offset, spec) -> Option
                                   ee_link=int(spec.ee_link), ee2_link=int(spec.ee2_link))
 
 
-def _points_template_hash(pt: codegen.PointsTemplate) -> str:
-    h = hashlib.sha1()
-    h.update(np.asarray(pt.obj_cols, np.int32).tobytes())
-    h.update(np.asarray(pt.self_pairs, np.int32).reshape(-1).tobytes())
-    h.update(np.asarray([pt.ee_link, pt.ee2_link], np.int32).tobytes())
-    return h.hexdigest()[:8]
-
-
-def _points_serves(unit: codegen.PointsTemplate, want: codegen.PointsTemplate) -> bool:
-    if codegen.points_hash(unit.point_link, unit.point_offset) != codegen.points_hash(want.point_link, want.point_offset):
-        return False
-    if list(unit.obj_cols) != list(want.obj_cols) or [tuple(p) for p in unit.self_pairs] != [tuple(p) for p in want.self_pairs]:
+def _serves(unit, want) -> bool:
+    """the dispatcher's rule (trk_capi.hip: spec_matches) for a caller that may use every weight: the same collision columns, pairs
+    and -- where the caller tracks a link -- EE links, and the same key of the column kind: the points' hash, or the virtual rows"""
+    def key(t):
+        if isinstance(t, codegen.PointsTemplate):
+            return list(t.obj_cols), codegen.points_hash(t.point_link, t.point_offset)
+        return list(t.obj_links), [tuple(np.float32(v) for v in r) for r in t.virtual]
+    if key(unit) != key(want) or [tuple(p) for p in unit.self_pairs] != [tuple(p) for p in want.self_pairs]:
         return False
     return want.ee_link < 0 or (unit.ee_link == want.ee_link and unit.ee2_link == want.ee2_link)
 
 
-_loaded_point_templates: Dict[str, Tuple[int, codegen.PointsTemplate]] = {}
-
-
-def has_matching_points_unit(kin: KinModel, point_link, point_offset, spec) -> bool:
-    want = _points_template_of(kin, point_link, point_offset, spec)
+def _has_matching(kin: KinModel, want, bundled: dict) -> bool:
+    """does a loaded run-time unit or an ahead-of-time unit of the table `bundled` serve this robot and template?"""
     if want is None:
         return False
     h = codegen.model_hash(kin)
-    for mh, pt in _loaded_point_templates.values():
-        if mh == h and _points_serves(pt, want):
-            return True
-    from .kinematics import URDF_DIR
-    for ident, (urdf, fn) in codegen.SPEC_POINT_ROBOTS.items():
-        k2 = KinModel.from_urdf(str(URDF_DIR / urdf))
-        if codegen.model_hash(k2) == h and _points_serves(fn(k2), want):
-            return True
-    return False
+    return any(mh == h and _serves(t, want) for mh, t in _loaded_templates.values()) or \
+        any(mh == h and _serves(t, want) for _ident, mh, t in codegen.aot_units(bundled))
 
 
-_pending_points_adam: Dict[str, tuple] = {}    # run-time point units whose spec_<ident>_padam unit has not been asked for yet: ident -> (kin, pt)
+def has_matching_unit(kin: KinModel, spec) -> bool:
+    """True if an ahead-of-time unit (codegen.SPEC_ROBOTS) or an already loaded run-time unit serves this robot and
+    collision model."""
+    return _has_matching(kin, _template_of(kin, spec), codegen.SPEC_ROBOTS)
 
 
-def load_points_adam_units(kin: KinModel, verbose: bool = False) -> List[str]:
-    """Compile (cached under the generator's stamp, like every unit) and load the planning-loop kernels of every run-time
-    attached-point unit of this robot that qualifies for them; each unit's initialiser announces its launcher under the main unit's
-    ident and hashes (trk_spec_register_points_adam).  Called when a plan binds trk_rollout_points_gp_adam_steps; idempotent, and a
-    no-op for the bundled units, whose kernels are linked into libtrk.so.  Returns the idents loaded by this call."""
-    h, done = codegen.model_hash(kin), []
-    for ident, (k2, pt) in list(_pending_points_adam.items()):
-        if codegen.model_hash(k2) != h:
-            continue
-        aso, astamp = JIT_DIR / f"spec_{ident}_padam.so", JIT_DIR / f"spec_{ident}_padam.stamp"
-        if not (aso.exists() and astamp.exists() and astamp.read_text() == _generator_stamp()):
-            aso = _compile_unit(codegen.generate_points_adam_source(k2, pt, ident), f"{ident}_padam", verbose)
-        _loaded[f"{ident}_padam"] = C.CDLL(str(aso))
-        del _pending_points_adam[ident]
-        done.append(ident)
-    return done
+def has_matching_points_unit(kin: KinModel, point_link, point_offset, spec) -> bool:
+    """the same for a robot whose collision columns are attached points (codegen.SPEC_POINT_ROBOTS)"""
+    return _has_matching(kin, _points_template_of(kin, point_link, point_offset, spec), codegen.SPEC_POINT_ROBOTS)
+
+
+def specialize_for_cost_spec(kin: KinModel, spec, verbose: bool = False) -> Optional[str]:
+    """Template from a CostModelSpec whose columns are the links (no attached points)."""
+    tmpl = _template_of(kin, spec)
+    if tmpl is None:
+        return None
+    return specialize(kin, tmpl.obj_links, tmpl.self_pairs, tmpl.ee_link, verbose, ee2_link=tmpl.ee2_link, virtual=tmpl.virtual)
 
 
 def specialize_points(kin: KinModel, point_link, point_offset, spec, verbose: bool = False) -> Optional[str]:
     """Generated fused kernel for a robot whose collision columns are attached points (RobotPanda with another sphere
-    table, another grasped object ...).  Returns None when the column layout is not one the generator handles.
-    With hipcc the unit's boolean kernels (codegen.generate_points_collision_source) are compiled and loaded next to it; the hipRTC
-    fall-back carries none: such a robot keeps the two-step boolean path (fk_points + collision_fields).  The planning-loop kernels
-    (codegen.generate_points_adam_source) are a third unit under the same rule, compiled and loaded on the first request for them
-    (load_points_adam_units: ops.PointsAdamPlan), not here."""
+    table, another grasped object ...): same mechanism, codegen.generate_points_rollout_source.  Returns None when the column
+    layout is not one the generator handles.
+    With hipcc the unit gets the satellite units of an attached-point unit (codegen.SATELLITES): its boolean kernels next to it, the
+    planning-loop kernels -- robots up to 8 DOF -- on the first request for them (load_satellite_units: ops.PointsAdamPlan).  The
+    hipRTC fall-back carries none: such a robot keeps the two-step boolean path (fk_points + collision_fields)."""
     pt = _points_template_of(kin, point_link, point_offset, spec)
     if pt is None:
         return None
-    ident = (f"jitp_{codegen.model_hash(kin):016x}_{codegen.points_hash(pt.point_link, pt.point_offset):016x}_"
-             f"{_points_template_hash(pt)}")
-    if ident in _loaded:
-        return ident
-    if hipcc_available():
-        so, stamp = JIT_DIR / f"spec_{ident}.so", JIT_DIR / f"spec_{ident}.stamp"
-        if not (so.exists() and stamp.exists() and stamp.read_text() == _generator_stamp()):
-            so = _compile_unit(codegen.generate_points_rollout_source(kin, pt, ident), ident, verbose)
-        _loaded[ident] = _load_unit(so, ident)
-        # the unit's boolean kernels (k_pcoll: ops.rollout_points_collision[_via]): a unit of their own, spec_<ident>_coll, cached under
-        # the same stamp; its initialiser announces the launcher under the main unit's ident (trk_spec_register_points_coll)
-        cso, cstamp = JIT_DIR / f"spec_{ident}_coll.so", JIT_DIR / f"spec_{ident}_coll.stamp"
-        if not (cso.exists() and cstamp.exists() and cstamp.read_text() == _generator_stamp()):
-            cso = _compile_unit(codegen.generate_points_collision_source(kin, pt, ident), f"{ident}_coll", verbose)
-        _loaded[f"{ident}_coll"] = C.CDLL(str(cso))
-        if codegen.points_adam_ok(kin, pt):
-            # its planning-loop kernels (k_padam: ops.PointsAdamPlan) are a third unit, compiled only when a plan first binds the entry:
-            # load_points_adam_units
-            _pending_points_adam[ident] = (kin, pt)
-    else:           # no compiler driver on this box: the unit's device half through hipRTC (round 5: attached-point units too)
-        _loaded[ident] = _load_points_unit_rtc(kin, pt, ident)
-    _loaded_point_templates[ident] = (codegen.model_hash(kin), pt)
+    ident = f"jitp_{codegen.model_hash(kin):016x}_{codegen.points_hash(pt.point_link, pt.point_offset):016x}_{template_hash(pt)}"
+    if ident not in _loaded:
+        if hipcc_available():
+            _load_unit(_cached_unit(ident, lambda: codegen.generate_points_rollout_source(kin, pt, ident), verbose), ident)
+            _load_satellites(ident, kin, pt, verbose)
+        else:           # no compiler driver on this box: the unit's device half through hipRTC
+            _loaded[ident] = _load_points_unit_rtc(kin, pt, ident)
+        _loaded_templates[ident] = (codegen.model_hash(kin), pt)
     return ident
+

@@ -340,7 +340,7 @@ class DifferentiableTree(torch.nn.Module):
         h = codegen.model_hash(kin)
         if any(mh == h and t.ee_link == link for _i, mh, t in codegen.aot_units()):
             return
-        if any(mh == h and t.ee_link == link for mh, t in jit._loaded_templates.values()):
+        if any(mh == h and isinstance(t, codegen.CollisionTemplate) and t.ee_link == link for mh, t in jit._loaded_templates.values()):
             return
         tmpl = codegen.default_template(kin)
         jit.specialize(kin, tmpl.obj_links, (), ee_link=link)

@@ -1720,7 +1720,7 @@ class ArmAdamPlan(_AdamLoopPlan):
         head = (self.model._h, self.cm._h, C.byref(self._w), C.byref(self._gp))
         if via:
             from . import jit
-            jit.load_via_adam_units(self.model.kin)      # a run-time unit's k_traj_via_adam is compiled on the first request for it
+            jit.load_satellite_units(self.model.kin, "vadam")      # a run-time unit's k_traj_via_adam is compiled on the first request for it
             self._weights = via_point_weights(self.num_interpolation, self.device)      # kept alive: the struct points into them
             self._via = _abi.TrajVia(self.w_via, self.num_interpolation, self._weights[0].data_ptr(), self._weights[1].data_ptr())
             self._fn = lib().trk_rollout_gp_via_adam_steps
@@ -1762,7 +1762,7 @@ class PointsAdamPlan(_AdamLoopPlan):
     def _bind(self) -> None:
         """the entry point and its arguments"""
         from . import jit
-        jit.load_points_adam_units(self.model.kin)       # a run-time unit's k_padam is compiled on the first request for it
+        jit.load_satellite_units(self.model.kin, "padam")       # a run-time unit's k_padam is compiled on the first request for it
         self._fn = lib().trk_rollout_points_gp_adam_steps
         self._args = (self.model._h, self.ps._h, self.cm._h, C.byref(self._w), C.byref(self._gp), C.byref(self._adam), self.q.data_ptr(),
                       self.qd.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.B, self.H, self.cost.data_ptr())
