@@ -2993,17 +2993,35 @@ class _WrenchWalk:
         cr = E.cross(self.t[i], self.PF)
         return E.dot(z, [E.lincomb([(self.PT[k], ONE), (cr[k], S(-1.0))]) for k in range(3)])
 
+    def _exact(self, value) -> S:
+        """`value()`'s arithmetic in a block of its own that takes back the FP freedoms the unit grants itself.  The functional is
+        evaluated twice per joint, at the entry and at the end of the subtree, and where no link of the subtree carries an adjoint
+        the running wrench has not moved and the difference must be an EXACT zero, as the reference's is (an optimiser that
+        normalises its step turns a 1e-9 residue into a full step; tests/test_gpu_fk_edges.py).  Granted contraction and
+        reassociation, the compiler need not fuse the two copies alike (the end's can fold into the subtraction, the entry's cannot),
+        and UR10 + Allegro's k_posbwd left 1e-8 .. 1e-11 on such joints.  Without the freedoms the two are the same instructions on
+        the same numbers; the fmaf calls written out here stay fused."""
+        E = self.E
+        E._k += 1
+        name = f"v{E._k}"
+        E.raw(f"    float {name};")
+        E.raw("    {")
+        E.raw("#pragma clang fp reassociate(off) contract(off) reciprocal(off)")
+        E.raw(f"    {name} = {E.expr(value())};")
+        E.raw("    }")
+        return S(1.0, name)
+
     def enter(self, i: int) -> None:
         """the walk steps onto link i: its pose, and its joint's sample of the running wrench BEFORE the subtree -- a COPY (pf / pt are
         mutable; the expression may be a bare alias)"""
         u, E = self.u, self.E
         _emit_fk_link(E, u.kin, i, self.R, self.t, self.passv, u.snap)
         if int(u.kin.joint_type[i]) != JOINT_FIXED:
-            self.snap_c[i] = S(1.0, E.tmp(E.expr(self.functional(i))))
+            self.snap_c[i] = self._exact(lambda: self.functional(i))
 
     def difference(self, j: int) -> S:
         """joint j's subtree is complete: its share of the running wrench"""
-        return self.E.lincomb([(self.functional(j), ONE), (self.snap_c[j], S(-1.0))])
+        return self._exact(lambda: self.E.lincomb([(self.functional(j), ONE), (self.snap_c[j], S(-1.0))]))
 
     def colpos(self, i: int, c: int) -> List[S]:
         """world position of column c, a point of link i: R_i off + t_i (a zero offset is the link origin itself)"""

@@ -211,8 +211,9 @@ __device__ __forceinline__ float trk_wave_sum(float v) {
 // sin and cos of x together.  Cody-Waite reduction by pi (two fmas): x = k*pi + r, r in [-pi/2, pi/2], so
 // sin x = (-1)^k sin r and cos x = (-1)^k cos r -- a sign flip (one shift, two xors), no sin/cos swap.
 // sin r = r + r^3 P(r^2), cos r = 1 - r^2/2 + r^4 Q(r^2), P and Q cubic near-minimax fits (Chebyshev nodes).
-// Max abs error 1.5e-7 (sin) / 1.3e-7 (cos) for |x| < 3000 rad against fp64 (tests/test_device_math_cpu.py);
-// joint angles are clamped to URDF limits (a few rad).  20 VALU instructions, 13.5 per angle in the paired form.
+// Max abs error 1.560e-7 (sin) / 1.304e-7 (cos) for |x| <= 1e5 rad against fp64, every fp32 value (tests/test_device_math_cpu.py
+// holds the host side to 3 * 2^-24); beyond that the two-term reduction runs out: 3.4e-7 below 1e6, 1.0e-4 below 1e7.  Limited joints
+// are clamped to URDF limits (a few rad); continuous joints are not.  20 VALU instructions, 13.5 per angle in the paired form.
 #define TRK_INV_PI 0x1.45f306p-2f
 #define TRK_PI_HI 0x1.921fb6p+1f
 #define TRK_PI_LO -0x1.777a5cp-24f
