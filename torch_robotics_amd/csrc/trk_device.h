@@ -181,6 +181,10 @@ __device__ __forceinline__ F4 load_f4_uniform(const float4* p, int i) {      // 
 __device__ __forceinline__ float trk_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }   // v_sqrt_f32, 1 ulp
 __device__ __forceinline__ float trk_rcp(float x) { return __builtin_amdgcn_rcpf(x); }     // v_rcp_f32, 1 ulp
 __device__ __forceinline__ float trk_rsq(float x) { return __builtin_amdgcn_rsqf(x); }     // v_rsq_f32, 1 ulp
+// v_rsq_f32 reads a subnormal input as zero and answers +inf (n2 * rsq(n2) is then inf, or NaN behind a zero weight: measured by
+// tests/test_gpu_term_edges.py at a separation of 2^-67 m).  A guard against a zero norm therefore compares with the smallest normal
+// float, not with 0: a squared distance below it counts as 0 (norm 0, no gradient) -- the same compare, with a literal.
+#define TRK_RSQ_MIN 1.17549435e-38f
 
 // Neighbour exchange along the wavefront as a DPP operand (gfx9 `wave_shl:1` / `wave_shr:1`; tools/microbench/dpp_wave_shift.hip): lane l
 // receives v of lane l + 1 (l - 1); the lane without a source -- 63 (0) -- keeps `edge`.  All 64 lanes must be active.
@@ -1097,7 +1101,11 @@ __device__ __forceinline__ float ws_cost_point(const DevCostHdr& C, float mg, fl
     const bool clamp = (C.clamp_fields & TRK_FIELD_WS) != 0;         // wave-uniform
     // the six signed plane distances are {p_k - min_k, max_k - p_k}; per axis the smaller one is h_k - |p_k - c_k|,
     // so max_planes (margin - sd) = margin - min_k (h_k - |d_k|) and the gradient is sign(d_a) on the arg-min axis
-    // (20 instructions instead of 35; differs from the plane form by fp32 rounding of c and h, ~1e-7)
+    // (20 instructions instead of 35.  Against the plane form in fp64: five roundings per axis -- c and h on the host, p - c, h - |d|,
+    // margin - m --, each at most half an ulp of its own result, i.e. <= 2.5 ulp of the largest of |p_k|, |min_k|, |max_k|, margin, and
+    // none where the result is representable; measured <= 0.5 ulp, tests/test_gpu_term_edges.py.  At an exact tie of two planes the
+    // first arg-min AXIS wins and the side is the sign of p - c, where the plane form takes the first of [x-min .. z-max]: another
+    // valid subgradient.  The booleans evaluate the plane form itself, so hinge and boolean can differ by the rounding of p - c.)
     const float dx = x - C.ws_c[0], dy = y - C.ws_c[1], dz = z - C.ws_c[2];
     const float mx = C.ws_h[0] - __builtin_fabsf(dx), my = C.ws_h[1] - __builtin_fabsf(dy), mz = C.ws_h[2] - __builtin_fabsf(dz);
     const float m = __builtin_fminf(__builtin_fminf(mx, my), mz);
@@ -1121,7 +1129,7 @@ __device__ __forceinline__ float ee_cost_eval(const float* R, const float* t, co
         for (int c = 0; c < 3; ++c) tr = fmaf(R[3 * r + c], Ht[4 * r + c], tr);
     const float dx = t[0] - Ht[3], dy = t[1] - Ht[7], dz = t[2] - Ht[11];
     const float n2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
-    const float rs = n2 > 0.0f ? trk_rsq(n2) : 0.0f;
+    const float rs = n2 >= TRK_RSQ_MIN ? trk_rsq(n2) : 0.0f;
     const float nrm = n2 * rs;
     float d = 0.0f;
     if (w_rot > 0.0f) d = fmaf(w_rot, 1.0f - (tr - 1.0f) * 0.5f, d);

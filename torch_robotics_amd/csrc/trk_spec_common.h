@@ -1535,7 +1535,7 @@ __device__ __forceinline__ float spec_self_pair_s(float w, float margin, float a
                                                   bool clamp, float& cost) {
     const float dx = ax - bx, dy = ay - by, dz = az - bz;
     const float n2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
-    const float rs = n2 > 0.0f ? trk_rsq(n2) : 0.0f;
+    const float rs = n2 >= TRK_RSQ_MIN ? trk_rsq(n2) : 0.0f;
     const float nrm = n2 * rs;
     if (clamp) w = margin - nrm > 0.0f ? w : 0.0f;
     cost = fmaf(w, margin - nrm, cost);
@@ -1550,7 +1550,7 @@ __device__ __forceinline__ float spec_self_pair_sd(float w, float margin, float 
                                                    bool clamp, float& cost, float& dx, float& dy, float& dz) {
     dx = ax - bx; dy = ay - by; dz = az - bz;
     const float n2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
-    const float rs = n2 > 0.0f ? trk_rsq(n2) : 0.0f;
+    const float rs = n2 >= TRK_RSQ_MIN ? trk_rsq(n2) : 0.0f;
     const float nrm = n2 * rs;
     if (clamp) w = margin - nrm > 0.0f ? w : 0.0f;
     cost = fmaf(w, margin - nrm, cost);
@@ -1578,7 +1578,7 @@ __device__ __forceinline__ float spec_self_pair(float w, float margin, float ax,
                                                 float& gbz, bool clamp = false) {
     const float dx = ax - bx, dy = ay - by, dz = az - bz;
     const float n2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
-    const float rs = n2 > 0.0f ? trk_rsq(n2) : 0.0f;              // one transcendental: 1/||d|| (0 at d = 0, like torch.norm's backward)
+    const float rs = n2 >= TRK_RSQ_MIN ? trk_rsq(n2) : 0.0f;              // one transcendental: 1/||d|| (0 at d = 0, like torch.norm's backward; TRK_RSQ_MIN: below the smallest normal too)
     const float nrm = n2 * rs;
     if (clamp) w = margin - nrm > 0.0f ? w : 0.0f;                // relu(margin - d): value and gradient vanish at or below zero
     const float inv = w * rs;
