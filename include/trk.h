@@ -994,6 +994,55 @@ int trk_rollout_points_gp_adam_steps(const TrkModel* model, const TrkPointSet* p
                                      const TrkRolloutWeights* weights, const TrkGpPrior* gp, const TrkTrajAdam* adam, float* q, float* qd,
                                      float* adam_m, float* adam_v, int64_t batch, int32_t horizon, float* cost, trk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * 3-D point mass (RobotPointMass3D in EnvSpheres3D, EnvTableShelf, EnvMazeBoxes3D or a voxel grid): the trajectory objective and the
+ * planning loop, the 3-D siblings of trk_scene2d_traj_via_cost_grad / trk_scene2d_traj_via_adam_steps.  The sample IS the collision
+ * point, so there is no TrkModel: `cm` is a cost model with exactly one position column (n_links_in = 1, one object-collision column,
+ * no virtual columns), as PlanningTask builds it for the robot.  BUILD-DEFINED like the prior.
+ *   q, qd [batch, horizon, 3] fp32, the samples of a trajectory consecutive; adam_m, adam_v [batch, horizon, 6] = [q part | qd part]
+ *   per sample; everything contiguous and 4-byte aligned.  1 <= horizon <= TRK_POINT3D_MAX_HORIZON (one lane per sample, a workgroup
+ *   of 256 lanes owns whole trajectories): TRK_ERR_UNSUPPORTED above.
+ * With h, g the hinge at a point and its gradient -- w_obj * (objects) + w_ws * (workspace box) at the margin of the column, each
+ * under the cost model's clamp_fields, the arithmetic of trk_cost_fields (bit for bit at w_obj = w_ws = 1; a zero weight skips the
+ * term; w_self and w_ee must be zero where the cost model has self pairs / a tracked link) -- the objective of sample t is
+ *   C = h(q[b,t]);  L[d] = g(q[b,t])[d];  U[d] = 0                 and, with a via term, TrkTrajVia's fold (above) on the segment t -> t+1:
+ *       C = fma(w_via, h(v[b,t,a]), C);  L[d] = fma(w_via * alpha[a], g(v[b,t,a])[d], L[d]);  U[d] = fma(w_via * beta[a], g(v[b,t,a])[d], U[d])
+ *       in ascending a, v[b,t,a] = q[b,t] * alpha[a] + q[b,t+1] * beta[a] with each product and the sum rounded once;
+ *   cost[b,t] = fma(gp.weight, P[b,t], C),   P[b,t] = 1/2 e_t^T Q^-1 e_t summed over the coordinates, the factor t -> t+1 attributed
+ *       to sample t and 0 at t = horizon-1 (the expressions of trk_scene2d_traj_cost_grad's prior);
+ *   gq[b,t]   = (L[b,t] + U[b,t-1]) + gp.weight * d P / d q[b,t]   (U[b,-1] = 0; without a via term just L),
+ *   gqd[b,t]  = gp.weight * d P / d qd[b,t].
+ * A sample without a segment or without a predecessor leaves the sums by a select, never by a zero weight: a non-finite trajectory
+ * does not reach another trajectory's rows.  via = NULL: no via term (then cost and gq are the plain objective's).
+ * trk_point3d_traj_cost_grad: one evaluation.  cost [batch, horizon]; gq, gqd [batch, horizon, 3] nullable TOGETHER (cost only).
+ * trk_point3d_traj_adam_steps: n_steps iterations of Adam on that objective with (q, qd, m, v) of a sample in its lane's registers,
+ * read once and written once per launch -- the arithmetic, the bias terms (formed in double on the host), pin, first_step and the
+ * 32 iterations per launch of trk_scene2d_traj_adam_steps; more iterations = several launches inside the call, and the result does
+ * not depend on how iterations are grouped into launches or calls.  cost (nullable) [batch, horizon]: the objective of the state as
+ * passed in.  lr = 0 (or n_steps = 0) only evaluates: nothing but cost is written.
+ * Validation, before any device work (also with batch = 0).  TRK_ERR_INVALID_ARG: null cm / weights / prior / adam, null buffers
+ * (batch > 0), non-finite weights, dt, sigma (or dt, sigma <= 0), lr or w_via, pin outside 0 .. 15, first_step < 1, n_steps < 0, a
+ * via with null alpha / beta or n_interp < 1, only one of gq / gqd.  TRK_ERR_UNSUPPORTED, with the reason: horizon above
+ * TRK_POINT3D_MAX_HORIZON (trk_cost_fields + trk_gp_prior_cost_grad serve any horizon); a cost model whose columns are not exactly
+ * one point; self pairs with w_self != 0 or a tracked link with w_ee != 0.  batch = 0: TRK_OK without a launch.
+ * No atomics, no host synchronisation: capturable.  TRK_POINT3D_LDS64=1 in the environment (read per call) sends horizon 64 -- a
+ * wavefront is a trajectory there and neighbours in time come by DPP shifts -- through the LDS exchange of the other horizons: the
+ * same arithmetic, for comparing the two.
+ * --------------------------------------------------------------------------------- */
+#define TRK_POINT3D_MAX_HORIZON 256
+int trk_point3d_traj_cost_grad(const TrkCostModel* cm, const TrkRolloutWeights* w, const TrkGpPrior* gp,
+                               const TrkTrajVia* via /* NULL: no via term */, const float* q, const float* qd,
+                               int64_t batch, int32_t horizon, float* cost, float* gq, float* gqd, trk_stream_t stream);
+int trk_point3d_traj_adam_steps(const TrkCostModel* cm, const TrkRolloutWeights* w, const TrkGpPrior* gp,
+                                const TrkTrajVia* via /* NULL: no via term */, const TrkTrajAdam* adam, float* q, float* qd,
+                                float* adam_m, float* adam_v, int64_t batch, int32_t horizon, float* cost, trk_stream_t stream);
+
+/* Which exchange the CALLING THREAD's latest launch of the two entries above used for the neighbours in time: the DPP wavefront shifts
+ * (horizon 64) or the LDS exchange (every other horizon, and horizon 64 under TRK_POINT3D_LDS64=1); NONE before the first launch (a
+ * call that returned without one -- a refusal, batch = 0 -- leaves the answer as it was).  Both compute the same bits. */
+enum { TRK_POINT3D_FORM_NONE = 0, TRK_POINT3D_FORM_DPP = 1, TRK_POINT3D_FORM_LDS = 2 };
+int trk_point3d_last_form(void);
+
 #ifdef __cplusplus
 }
 #endif

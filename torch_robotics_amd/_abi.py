@@ -147,6 +147,10 @@ class TrajVia(C.Structure):             # TrkTrajVia
     _fields_ = [("w_via", C.c_float), ("n_interp", C.c_int32), ("alpha", C.c_void_p), ("beta", C.c_void_p)]
 
 
+TRK_POINT3D_MAX_HORIZON = 256          # trk_point3d_traj_cost_grad, trk_point3d_traj_adam_steps
+TRK_POINT3D_FORM_NONE, TRK_POINT3D_FORM_DPP, TRK_POINT3D_FORM_LDS = 0, 1, 2      # trk_point3d_last_form
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 

@@ -43,6 +43,7 @@ EXPORTS = [
     "trk_scene2d_traj_via_cost_grad", "trk_scene2d_traj_via_adam_steps",
     "trk_rollout_gp_via_adam_steps",
     "trk_rollout_points_gp_adam_steps",
+    "trk_point3d_traj_cost_grad", "trk_point3d_traj_adam_steps", "trk_point3d_last_form",
 ]
 
 
@@ -211,6 +212,11 @@ def lib():
                                                 C.POINTER(_abi.TrajAdam), vp, vp, vp, vp, i64, i32, vp, vp]
     L.trk_rollout_points_gp_adam_steps.argtypes = [vp, vp, vp, C.POINTER(_abi.RolloutWeights), C.POINTER(_abi.GpPrior),
                                                    C.POINTER(_abi.TrajAdam), vp, vp, vp, vp, i64, i32, vp, vp]
+    L.trk_point3d_traj_cost_grad.argtypes = [vp, C.POINTER(_abi.RolloutWeights), C.POINTER(_abi.GpPrior), C.POINTER(_abi.TrajVia), vp, vp, i64,
+                                             i32, vp, vp, vp, vp]
+    L.trk_point3d_traj_adam_steps.argtypes = [vp, C.POINTER(_abi.RolloutWeights), C.POINTER(_abi.GpPrior), C.POINTER(_abi.TrajVia),
+                                              C.POINTER(_abi.TrajAdam), vp, vp, vp, vp, i64, i32, vp, vp]
+    L.trk_point3d_last_form.argtypes = []
     for name in EXPORTS:
         fn = getattr(L, name)        # AttributeError here = the library does not export the ABI
         if name not in ("trk_last_error", "trk_model_destroy", "trk_cost_model_destroy", "trk_point_set_destroy",

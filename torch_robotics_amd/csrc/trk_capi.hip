@@ -1932,6 +1932,110 @@ int trk_rollout_points_gp_adam_steps(const TrkModel* m, const TrkPointSet* ps, c
     return served_generated(traj_adam_launches(a, ad, cost, [&] { return spec_launch(without_self(fn), e, a, m, stream); }));
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// The 3-D point mass (trk_point3d_traj_cost_grad, trk_point3d_traj_adam_steps): no TrkModel, the sample is the cost model's one
+// column; one hand-written kernel (trk_point3d.hip) serves every scene, so there is no unit search.
+// ------------------------------------------------------------------------------------------------------------------------------
+// What both entries check alike, in this order, before any device work (ad == nullptr: the evaluation, which has gq / gqd instead of
+// the optimiser's state).  Only the header of *cm is read.
+static int check_point3d_call(const std::string& who, const TrkCostModel* cm, const TrkRolloutWeights* w, const TrkGpPrior* gp,
+                              const TrkTrajVia* via, const TrkTrajAdam* ad, bool with_adam, const float* q, const float* qd,
+                              const float* adam_m, const float* adam_v, int64_t batch, int32_t horizon) {
+    if (!cm) return fail(TRK_ERR_INVALID_ARG, who + ": null cost model");
+    if (!w || !gp || (with_adam && !ad)) return fail(TRK_ERR_INVALID_ARG, who + (with_adam ? ": null weights / prior / TrkTrajAdam" : ": null weights / prior"));
+    if (batch < 0 || horizon < 1) return fail(TRK_ERR_INVALID_ARG, who + ": bad batch/horizon");
+    if (via) {
+        if (!via->alpha || !via->beta) return fail(TRK_ERR_INVALID_ARG, who + ": null alpha / beta in TrkTrajVia");
+        if (via->n_interp < 1 || !std::isfinite(via->w_via))
+            return fail(TRK_ERR_INVALID_ARG, who + ": n_interp must be >= 1 and w_via finite");
+    }
+    if (!std::isfinite(w->w_self) || !std::isfinite(w->w_obj) || !std::isfinite(w->w_ws) || !std::isfinite(w->w_ee) ||
+        !std::isfinite(gp->weight) || !std::isfinite(gp->dt) || !std::isfinite(gp->sigma) || !(gp->dt > 0.0f) || !(gp->sigma > 0.0f))
+        return fail(TRK_ERR_INVALID_ARG, who + ": the weights must be finite, the prior needs finite dt > 0 and sigma > 0");
+    if (with_adam) {
+        if (ad->n_steps < 0 || ad->first_step < 1 || !std::isfinite(ad->lr) || ad->pin < 0 || ad->pin > 15)
+            return fail(TRK_ERR_INVALID_ARG, who + ": n_steps >= 0, first_step >= 1, lr finite and pin in 0 .. 15");
+        if (batch > 0 && (!q || !qd || (traj_adam_updates(ad) && (!adam_m || !adam_v))))
+            return fail(TRK_ERR_INVALID_ARG, who + ": null q / qd / adam_m / adam_v");
+    }
+    return TRK_OK;
+}
+// ... and what they refuse as unsupported, after every argument check of their own
+static int check_point3d_served(const std::string& who, const TrkCostModel* cm, const TrkRolloutWeights* w, int64_t batch, int32_t horizon) {
+    if (horizon > TRK_POINT3D_MAX_HORIZON)
+        return fail(TRK_ERR_UNSUPPORTED, who + ": horizon above TRK_POINT3D_MAX_HORIZON (256): a workgroup owns whole trajectories; "
+                                               "trk_cost_fields + trk_gp_prior_cost_grad serve any horizon");
+    if (batch > 0x7fffffff) return fail(TRK_ERR_UNSUPPORTED, who + ": batch too large");
+    const DevCostHdr& h = cm->hdr;
+    if (h.n_links_in != 1 || h.n_virtual != 0 || h.n_obj_links != 1)
+        return fail(TRK_ERR_UNSUPPORTED, who + ": the cost model's columns must be exactly one point (n_links_in = 1, one object-collision "
+                                               "column, no virtual columns): the sample is the collision point");
+    if ((h.n_self_pairs > 0 && w->w_self != 0.0f) || ((h.ee_link >= 0 || h.ee2_link >= 0) && w->w_ee != 0.0f))
+        return fail(TRK_ERR_UNSUPPORTED, who + ": a point has no self-collision and no end-effector term: w_self / w_ee must be zero "
+                                               "where the cost model has self pairs / a tracked link");
+    return TRK_OK;
+}
+// TRK_POINT3D_LDS64=1 (read per call): horizon 64 through the LDS exchange instead of the DPP shifts
+static thread_local int g_point3d_last_form = TRK_POINT3D_FORM_NONE;      // trk_point3d_last_form: this thread's latest launch
+static bool point3d_wave_form(int32_t horizon) {
+    const char* v = getenv("TRK_POINT3D_LDS64");
+    return horizon == 64 && !(v && v[0] == '1');
+}
+// The launches of a call: at most TRK_POINT3D_MAX_STEPS iterations each with their slice of the bias schedule; cost (and gq, gqd)
+// come from the first launch.  Without an update it is one evaluation.
+static int point3d_launches(const TrkCostModel* cm, const TrkRolloutWeights* w, const TrkGpPrior* gp, const TrkTrajVia* via,
+                            const TrkTrajAdam& ad, float* q, float* qd, float* adam_m, float* adam_v, int64_t batch, int32_t horizon,
+                            float* cost, float* gq, float* gqd, trk_stream_t stream) {
+    Point3DPar P{};
+    const float dt = gp->dt, s2 = 1.0f / (gp->sigma * gp->sigma);                     // as trk_launch_gp_prior forms them
+    P.w_obj = w->w_obj; P.w_ws = w->w_ws;
+    P.dt = dt; P.a = 12.0f * s2 / (dt * dt * dt); P.b = -6.0f * s2 / (dt * dt); P.c = 4.0f * s2 / dt; P.w = gp->weight;
+    if (via) { P.w_via = via->w_via; P.via_n = via->n_interp; P.alpha = via->alpha; P.beta = via->beta; }
+    const bool update = traj_adam_updates(&ad);
+    P.lr = ad.lr; P.pin = ad.pin; P.update = update ? 1 : 0;
+    const bool wave = point3d_wave_form(horizon);
+    const int32_t total = update ? ad.n_steps : 1;
+    for (int32_t done = 0; done < total; done += TRK_POINT3D_MAX_STEPS) {
+        P.n_steps = std::min<int32_t>(TRK_POINT3D_MAX_STEPS, total - done);
+        trk_adam_bias_schedule(P.bc1, P.rsqrt_bc2, (int64_t)ad.first_step + done, P.n_steps);
+        const bool first = done == 0;
+        trk_launch_point3d_traj(cm->hdr, P, wave, q, qd, adam_m, adam_v, batch, horizon, first ? cost : nullptr, first ? gq : nullptr,
+                                first ? gqd : nullptr, (hipStream_t)stream);
+        if (int rc = launched()) return rc;
+        g_point3d_last_form = wave ? TRK_POINT3D_FORM_DPP : TRK_POINT3D_FORM_LDS;
+    }
+    return TRK_OK;
+}
+
+int trk_point3d_last_form(void) { return g_point3d_last_form; }
+
+int trk_point3d_traj_cost_grad(const TrkCostModel* cm, const TrkRolloutWeights* w, const TrkGpPrior* gp, const TrkTrajVia* via,
+                               const float* q, const float* qd, int64_t batch, int32_t horizon, float* cost, float* gq, float* gqd,
+                               trk_stream_t stream) {
+    const std::string who = "trk_point3d_traj_cost_grad";
+    int rc = check_point3d_call(who, cm, w, gp, via, nullptr, false, q, qd, nullptr, nullptr, batch, horizon);
+    if (rc) return rc;
+    if ((batch > 0 && (!q || !qd || !cost)) || (gq == nullptr) != (gqd == nullptr))
+        return fail(TRK_ERR_INVALID_ARG, who + ": null q / qd / cost, or only one of gq / gqd");
+    if ((rc = check_point3d_served(who, cm, w, batch, horizon))) return rc;
+    if (batch == 0) return TRK_OK;
+    // one evaluation: no update, nothing but cost, gq and gqd is written (q, qd are read only)
+    const TrkTrajAdam once{0.0f, 0, 1, 1};
+    return point3d_launches(cm, w, gp, via, once, const_cast<float*>(q), const_cast<float*>(qd), nullptr, nullptr, batch, horizon, cost,
+                            gq, gqd, stream);
+}
+
+int trk_point3d_traj_adam_steps(const TrkCostModel* cm, const TrkRolloutWeights* w, const TrkGpPrior* gp, const TrkTrajVia* via,
+                                const TrkTrajAdam* ad, float* q, float* qd, float* adam_m, float* adam_v, int64_t batch, int32_t horizon,
+                                float* cost, trk_stream_t stream) {
+    const std::string who = "trk_point3d_traj_adam_steps";
+    int rc = check_point3d_call(who, cm, w, gp, via, ad, true, q, qd, adam_m, adam_v, batch, horizon);
+    if (!rc) rc = check_point3d_served(who, cm, w, batch, horizon);
+    if (rc) return rc;
+    if (batch == 0 || (!traj_adam_updates(ad) && !cost)) return TRK_OK;
+    return point3d_launches(cm, w, gp, via, *ad, q, qd, adam_m, adam_v, batch, horizon, cost, nullptr, nullptr, stream);
+}
+
 int trk_rollout_via_cost_grad(const TrkModel* m, const TrkCostModel* cm, const TrkRolloutWeights* w, const float* x, int64_t n_traj,
                               int32_t horizon, int32_t n_interp, const float* alpha, const float* beta, const float* seed, float* cost,
                               float* gq, trk_stream_t stream) {

@@ -111,6 +111,19 @@ inline void trk_adam_bias_schedule(float* bc1, float* rsqrt_bc2, int64_t first, 
         rsqrt_bc2[i] = (float)(1.0 / std::sqrt(1.0 - std::pow(0.999, k)));
     }
 }
+// One launch of the 3-D point mass's trajectory kernel (trk_point3d.hip: k_point3d_traj), everything by value.  a, b, c: the entries
+// of Q^-1 as trk_launch_gp_prior forms them; via_n == 0: no via term; update == 0: one evaluation, which also stores gq, gqd where given.
+constexpr int TRK_POINT3D_MAX_STEPS = 32;
+struct Point3DPar {
+    float w_obj, w_ws;
+    float dt, a, b, c, w;
+    float w_via; int32_t via_n; const float* alpha; const float* beta;
+    float lr; int32_t pin, n_steps, update;
+    float bc1[TRK_POINT3D_MAX_STEPS], rsqrt_bc2[TRK_POINT3D_MAX_STEPS];
+};
+// wave: horizon 64 with a wavefront per trajectory (DPP shifts); otherwise the LDS exchange
+void trk_launch_point3d_traj(const DevCostHdr& C, const Point3DPar& P, bool wave, float* q, float* qd, float* adam_m, float* adam_v,
+                             int64_t batch, int horizon, float* cost, float* gq, float* gqd, hipStream_t st);
 // raises the dynamic-LDS ceiling of every kernel once (gfx950: 160 KiB per workgroup)
 int trk_kernels_init(void);
 // trk_capi.hip's error string / initialisation, for the other translation units of the library

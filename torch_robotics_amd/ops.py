@@ -1630,7 +1630,7 @@ def planar_adam_bias_terms(step: int):
 
 
 class _AdamLoopPlan(_Plan):
-    """What PlanarAdamPlan, ArmAdamPlan and PointsAdamPlan share: the state the plan owns, the pin mask, the rule that binds the via loop, and step().
+    """What PlanarAdamPlan, ArmAdamPlan, PointsAdamPlan and Point3DAdamPlan share: the state the plan owns, the pin mask, the rule that binds the via loop, and step().
     A subclass checks its own arguments, calls _own_state with its state width and TrkPlanarAdam / TrkTrajAdam, and binds in _bind."""
 
     def _own_state(self, q, qd, B, H, width, adam_struct, lr, pins, w_via, num_interpolation) -> None:
@@ -1766,6 +1766,80 @@ class PointsAdamPlan(_AdamLoopPlan):
         self._fn = lib().trk_rollout_points_gp_adam_steps
         self._args = (self.model._h, self.ps._h, self.cm._h, C.byref(self._w), C.byref(self._gp), C.byref(self._adam), self.q.data_ptr(),
                       self.qd.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.B, self.H, self.cost.data_ptr())
+
+
+def _point3d_traj_args(cm: CostHandle, q: torch.Tensor, qd: torch.Tensor, who: str):
+    """q, qd: contiguous fp32 (batch, horizon, 3) on one GPU, as the kernel reads them in place -> (B, H)"""
+    if not isinstance(cm, CostHandle):
+        raise TypeError(f"{who}: cm must be a CostHandle")
+    if not (isinstance(q, torch.Tensor) and isinstance(qd, torch.Tensor)) or q.device.type != "cuda" or qd.device != q.device:
+        raise ValueError(f"{who}: q and qd must be tensors on the same GPU (there is no CPU path)")
+    if q.dim() != 3 or q.shape[-1] != 3 or qd.shape != q.shape or q.dtype != torch.float32 or qd.dtype != torch.float32 or \
+            not (q.is_contiguous() and qd.is_contiguous()):
+        raise ValueError(f"{who}: q, qd must be contiguous float32 (batch, horizon, 3) tensors")
+    return int(q.shape[0]), int(q.shape[1])
+
+
+def _point3d_via(w_via, num_interpolation, device):
+    """-> (TrkTrajVia or None, what keeps its device weights alive): the via term only where num_interpolation > 0 and w_via != 0"""
+    n = int(num_interpolation)
+    if n < 0:
+        raise ValueError(f"num_interpolation must be >= 0, got {n}")
+    if n == 0 or float(w_via) == 0.0:
+        return None, None
+    ab = via_point_weights(n, device)
+    return _abi.TrajVia(float(w_via), n, ab[0].data_ptr(), ab[1].data_ptr()), ab
+
+
+def point3d_traj_cost_grad(cm: CostHandle, weights, q: torch.Tensor, qd: torch.Tensor, dt: float, sigma: float, gp_weight: float = 1.0,
+                           w_via: float = 0.0, num_interpolation: int = 0, want_grad: bool = True):
+    """The 3-D point mass's trajectory objective in one launch (include/trk.h: trk_point3d_traj_cost_grad): the hinge of cost_fields at
+    the sample under `weights` (w_self, w_obj, w_ws, w_ee; cm has one position column, the point itself) + the constant-velocity GP
+    prior on q, qd (B,H,3), H <= 256; with num_interpolation > 0 and w_via != 0 also w_via x the hinge at the via points of every
+    segment -> (cost (B,H) with the factor / segment t -> t+1 at sample t, gq, gqd), the gradients None without want_grad."""
+    B, H = _point3d_traj_args(cm, q, qd, "point3d_traj_cost_grad")
+    via, _keep = _point3d_via(w_via, num_interpolation, q.device)
+    cost = torch.empty((B, H), device=q.device, dtype=torch.float32)
+    gq, gqd = (torch.empty_like(q), torch.empty_like(q)) if want_grad else (None, None)
+    gp = _abi.GpPrior(float(dt), float(sigma), float(gp_weight))
+    _call("trk_point3d_traj_cost_grad", q.device, cm._h, C.byref(_weights_struct(weights)), C.byref(gp), None if via is None else C.byref(via),
+          q.data_ptr(), qd.data_ptr(), B, H, cost.data_ptr(), _ptr(gq), _ptr(gqd))
+    return cost, gq, gqd
+
+
+def point3d_last_form() -> str:
+    """Which exchange this thread's latest launch of point3d_traj_cost_grad / Point3DAdamPlan.step used for the neighbours in time
+    (`trk_point3d_last_form`): 'dpp' (horizon 64), 'lds' (other horizons, and horizon 64 under TRK_POINT3D_LDS64=1), 'none' before one."""
+    return ("none", "dpp", "lds")[int(lib().trk_point3d_last_form())]
+
+
+class Point3DAdamPlan(_AdamLoopPlan):
+    """Adam on point3d_traj_cost_grad's objective with the trajectories and the optimiser's state on the chip (include/trk.h:
+    trk_point3d_traj_adam_steps; kernel k_point3d_traj).  Pre-bound: `step(n)` runs the next n iterations on the caller's q, qd (B,H,3)
+    fp32 IN PLACE -- one launch per 32 iterations -- and returns the (B,H) cost of the state it started from.  The plan owns `m`, `v`
+    (B,H,6) = [q part | qd part], `cost` and the iteration counter `t`.  H <= 256.  pin_*: the start / goal position (velocity) keeps
+    its value.  lr = 0 only evaluates.  With num_interpolation > 0 and w_via != 0 the objective also holds w_via x the hinge at the
+    num_interpolation via points of every segment -- the points trajectory validation tests; otherwise the plan is exactly the plain loop."""
+
+    def __init__(self, cm: CostHandle, weights, q: torch.Tensor, qd: torch.Tensor, dt: float, sigma: float, gp_weight: float = 1.0,
+                 lr: float = 5e-3, pin_start: bool = True, pin_goal: bool = True, pin_start_vel: bool = False, pin_goal_vel: bool = False,
+                 w_via: float = 0.0, num_interpolation: int = 0):
+        B, H = _point3d_traj_args(cm, q, qd, "Point3DAdamPlan")
+        if H > _abi.TRK_POINT3D_MAX_HORIZON:
+            raise NotImplementedError(f"Point3DAdamPlan: horizon {H} is above the {_abi.TRK_POINT3D_MAX_HORIZON} samples a workgroup of the "
+                                      f"persistent kernel holds (cost_fields + gp_prior_cost_grad serve any horizon)")
+        self._own_state(q, qd, B, H, 6, _abi.TrajAdam, lr, (pin_start, pin_goal, pin_start_vel, pin_goal_vel), w_via, num_interpolation)
+        self.cm = cm
+        self._w = _weights_struct(weights)
+        self._gp = _abi.GpPrior(float(dt), float(sigma), float(gp_weight))
+        self._bind(via=self._via_on())
+
+    def _bind(self, via: bool) -> None:
+        """the entry point and its arguments: a TrkTrajVia only where the via term is on, otherwise exactly the plain loop"""
+        self._via, self._weights = _point3d_via(self.w_via, self.num_interpolation, self.device) if via else (None, None)
+        self._fn = lib().trk_point3d_traj_adam_steps
+        self._args = (self.cm._h, C.byref(self._w), C.byref(self._gp), None if self._via is None else C.byref(self._via), C.byref(self._adam),
+                      self.q.data_ptr(), self.qd.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.B, self.H, self.cost.data_ptr())
 
 
 def reduce_sum(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

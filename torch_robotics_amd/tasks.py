@@ -321,6 +321,29 @@ class PlanningTask(Task):
         return ops.PlanarAdamPlan(scene, q, qd, dt, sigma_gp, gp_weight, w_obj, clamp, lr, w_via=w_via, num_interpolation=num_interpolation,
                                   **pins)
 
+    def point_mass_3d_optimizer(self, q, qd, dt, sigma_gp, gp_weight=1.0, w_obj=1.0, w_ws=1.0, lr=5e-3, w_via=0.0, num_interpolation=0,
+                                **pins) -> "ops.Point3DAdamPlan":
+        """The 3-D point mass's planning loop on the chip (`trk_point3d_traj_adam_steps`): Adam on w_obj x this task's object hinge +
+        w_ws x its workspace hinge (its cost model, its margins, its clamp_sdf) + the constant-velocity GP prior.  `plan.step(n)`
+        improves q, qd (B,H,3) fp32 in place and returns the (B,H) cost they started from; pins: pin_start / pin_goal (default True),
+        pin_start_vel / pin_goal_vel (default False).  Horizons up to 256.  With num_interpolation > 0 and w_via != 0 the objective
+        also carries w_via x the same hinge at the num_interpolation via points of every segment, the points
+        `get_trajs_collision_and_free` tests."""
+        if getattr(self.robot, "has_extra_points", False):
+            raise NotImplementedError("point_mass_3d_optimizer serves the 3-D point mass (RobotPointMass3D); points_adam_plan is the "
+                                      "planning loop of the attached-point models")
+        if self._has_tree:
+            raise NotImplementedError("point_mass_3d_optimizer serves the 3-D point mass (RobotPointMass3D); rollout_adam_plan is the "
+                                      "planning loop of a robot with a kinematic tree")
+        if self._planar:
+            raise NotImplementedError("point_mass_3d_optimizer serves the 3-D point mass (RobotPointMass3D); trajectory_optimizer is the "
+                                      "planning loop of the 2-D point mass")
+        if self.df_collision_self is not None:
+            raise NotImplementedError("3-D point mass: a self-collision field is outside the point-mass kernel")
+        _model, cm = self._fused_handles(q.device)
+        return ops.Point3DAdamPlan(cm, (0.0, w_obj, w_ws, 0.0), q, qd, dt, sigma_gp, gp_weight, lr, w_via=w_via,
+                                   num_interpolation=num_interpolation, **pins)
+
     def capture_cost_backward(self, x, reduce=torch.sum, warmup: int = 3) -> "GraphedCostBackward":
         """`reduce(task.compute_collision_cost(x)).backward()` captured ONCE as a hipGraph (a planner's inner loop calls it with
         the same shapes thousands of times; eagerly the autograd engine's hand-offs cost ~10x the kernels).
