@@ -1043,6 +1043,59 @@ int trk_point3d_traj_adam_steps(const TrkCostModel* cm, const TrkRolloutWeights*
 enum { TRK_POINT3D_FORM_NONE = 0, TRK_POINT3D_FORM_DPP = 1, TRK_POINT3D_FORM_LDS = 2 };
 int trk_point3d_last_form(void);
 
+/* ---------------------------------------------------------------------------------
+ * Multi-particle planning: GP-prior sampling and best-particle pick.  What goes INTO the planning loops above (several particles per
+ * problem, drawn from the prior the loops carry as a cost) and what comes OUT of them (one winner per problem).  BUILD-DEFINED like
+ * the prior: the reference has no sampler, the arithmetic is specified below and checked against an fp64 restatement.
+ *
+ * trk_gp_prior_sample: n_particles trajectories per problem from the constant-velocity GP prior of trk_gp_prior_cost_grad,
+ * conditioned on the problem's start and goal, in ONE launch.  The noise is an input -- eps, unit normals made by the caller -- so
+ * the call is a pure function of its arguments; nothing is drawn inside.
+ *   start, goal [n_problems, dof]; start_vel, goal_vel [n_problems, dof], required iff pin_vel and ignored otherwise;
+ *   eps [n_problems * n_particles, horizon - 1, dof, 2]; q_min, q_max [dof], nullable TOGETHER; q, qd [n_problems * n_particles,
+ *   horizon, dof], particle k of problem p is row p * n_particles + k.  All fp32, contiguous, 4-byte aligned.
+ * Per trajectory j and coordinate d, independent of every other (j, d); T = horizon - 1, theta = T dt, s = t / T:
+ *   noise   w^p_t = l00 e0,  w^v_t = l10 e0 + l11 e1,  (e0, e1) = eps[j, t, d, :],  l00 = sigma dt^1.5 / sqrt(3),
+ *           l10 = sigma (sqrt(3) / 2) sqrt(dt),  l11 = sigma sqrt(dt) / 2: the Cholesky factor of Q = sigma^2 [[dt^3/3, dt^2/2],
+ *           [dt^2/2, dt]], formed in double on the host and rounded once (like theta);
+ *   walk    p_0 = start, v_0 = pin_vel ? start_vel : 0;  p_{t+1} = p_t + dt v_t + w^p_t,  v_{t+1} = v_t + w^v_t;
+ *   pin_vel = 1, r_p = goal - p_T, r_v = goal_vel - v_T (the cubic Hermite weights):
+ *           q_t = p_t + (3 s^2 - 2 s^3) r_p + theta (s^3 - s^2) r_v,   qd_t = v_t + ((6 s - 6 s^2) / theta) r_p + (3 s^2 - 2 s) r_v;
+ *   pin_vel = 0, v* = (goal - p_T) / theta:   q_t = p_t + t dt v*,   qd_t = v_t + v*.
+ * Both are exact draws of the Gaussian  exp(-sum_t 1/2 e_t^T Q^-1 e_t)  of trk_gp_prior_cost_grad given the pinned components (the
+ * loops' pin mask 15 and 3); at eps = 0, pin_vel = 0 gives the straight line at constant velocity.
+ * The two sums along t are scans across the lanes of the trajectory's workgroup with an association that depends on t alone: a
+ * trajectory's bits depend only on its own inputs -- not on its place in the batch, on n_particles, or on how a batch is split into
+ * calls -- and a non-finite eps row stays in its trajectory.  Any association of the sums is within (2 horizon + 16) 2^-24 of the
+ * same expressions with every term replaced by its absolute value.
+ * Endpoints by select: q[j, 0] and q[j, T] are the bits of start and goal; with pin_vel, qd[j, 0] and qd[j, T] those of the
+ * velocities.  With limits, the way points 0 < t < T are clamped to [q_min[d], q_max[d]] after conditioning by comparisons (a NaN
+ * stays a NaN); endpoints and qd are not touched.
+ * 2 <= horizon <= TRK_GP_SAMPLE_MAX_HORIZON (a workgroup owns floor(256 / horizon) whole trajectories),
+ * 1 <= dof <= TRK_GP_SAMPLE_MAX_DOF.
+ * Validation, before any device work (also with n_problems = 0).  TRK_ERR_INVALID_ARG: null s; dt or sigma non-finite or <= 0;
+ * n_particles < 1; pin_vel outside {0, 1}; n_problems < 0, horizon < 2, dof < 1; n_problems * n_particles > 0x3fffffff; null start,
+ * goal, eps, q or qd (n_problems > 0); pin_vel with a null velocity; only one of q_min / q_max.  TRK_ERR_UNSUPPORTED, the limit
+ * named: horizon above TRK_GP_SAMPLE_MAX_HORIZON, dof above TRK_GP_SAMPLE_MAX_DOF.  n_problems = 0: TRK_OK without a launch.
+ * No atomics, no host synchronisation: capturable.
+ *
+ * trk_traj_select_best: per problem, the particle with the smallest score among the candidates.  A particle is a candidate iff
+ * is_free is NULL or non-zero there and its score is not NaN (+-inf are candidates).  Smallest by <; among equal scores (-0.0 equals
+ * 0.0) the smallest k.  score [n_problems * n_particles]; is_free [n_problems * n_particles] bytes, NULL = all free;
+ * best [n_problems] = the winner's row p * n_particles + k, -1 without a candidate; best_score (nullable) its score, +inf without
+ * one; n_free (nullable) the number of non-zero flags, whatever the scores (n_particles with is_free = NULL).  Any n_particles >= 1;
+ * the result does not depend on how problems are batched.  TRK_ERR_INVALID_ARG: n_problems < 0, n_particles < 1, their product above
+ * 0x3fffffff, null score or best (n_problems > 0).  n_problems = 0: TRK_OK without a launch.  One launch, no atomics: capturable.
+ * --------------------------------------------------------------------------------- */
+#define TRK_GP_SAMPLE_MAX_HORIZON 256
+#define TRK_GP_SAMPLE_MAX_DOF 32
+typedef struct TrkGpSample { float dt, sigma; int32_t n_particles; int32_t pin_vel; } TrkGpSample;
+int trk_gp_prior_sample(const TrkGpSample* s, const float* start, const float* goal, const float* start_vel, const float* goal_vel,
+                        const float* eps, const float* q_min, const float* q_max, int64_t n_problems, int32_t horizon, int32_t dof,
+                        float* q, float* qd, trk_stream_t stream);
+int trk_traj_select_best(const float* score, const uint8_t* is_free /* NULL: all free */, int64_t n_problems, int32_t n_particles,
+                         int64_t* best, float* best_score /* nullable */, int32_t* n_free /* nullable */, trk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,13 @@ class TrajVia(C.Structure):             # TrkTrajVia
 TRK_POINT3D_MAX_HORIZON = 256          # trk_point3d_traj_cost_grad, trk_point3d_traj_adam_steps
 TRK_POINT3D_FORM_NONE, TRK_POINT3D_FORM_DPP, TRK_POINT3D_FORM_LDS = 0, 1, 2      # trk_point3d_last_form
 
+TRK_GP_SAMPLE_MAX_HORIZON = 256        # trk_gp_prior_sample
+TRK_GP_SAMPLE_MAX_DOF = 32
+
+
+class GpSample(C.Structure):            # TrkGpSample
+    _fields_ = [("dt", C.c_float), ("sigma", C.c_float), ("n_particles", C.c_int32), ("pin_vel", C.c_int32)]
+
 
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)

@@ -44,6 +44,7 @@ EXPORTS = [
     "trk_rollout_gp_via_adam_steps",
     "trk_rollout_points_gp_adam_steps",
     "trk_point3d_traj_cost_grad", "trk_point3d_traj_adam_steps", "trk_point3d_last_form",
+    "trk_gp_prior_sample", "trk_traj_select_best",
 ]
 
 
@@ -217,6 +218,8 @@ def lib():
     L.trk_point3d_traj_adam_steps.argtypes = [vp, C.POINTER(_abi.RolloutWeights), C.POINTER(_abi.GpPrior), C.POINTER(_abi.TrajVia),
                                               C.POINTER(_abi.TrajAdam), vp, vp, vp, vp, i64, i32, vp, vp]
     L.trk_point3d_last_form.argtypes = []
+    L.trk_gp_prior_sample.argtypes = [C.POINTER(_abi.GpSample), vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp]
+    L.trk_traj_select_best.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)        # AttributeError here = the library does not export the ABI
         if name not in ("trk_last_error", "trk_model_destroy", "trk_cost_model_destroy", "trk_point_set_destroy",

@@ -1842,6 +1842,83 @@ class Point3DAdamPlan(_AdamLoopPlan):
                       self.q.data_ptr(), self.qd.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.B, self.H, self.cost.data_ptr())
 
 
+def _gp_sample_rows(t, shape, what: str, who: str, device=None):
+    """a contiguous fp32 tensor of `shape` on one GPU (the kernel reads it in place)"""
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or (device is not None and t.device != device):
+        raise ValueError(f"{who}: {what} must be a tensor on the same GPU as start (there is no CPU path)")
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{who}: {what} must be a contiguous float32 tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def gp_prior_sample(start: torch.Tensor, goal: torch.Tensor, horizon: int, dt: float, sigma: float, n_particles: int = 1,
+                    start_vel: Optional[torch.Tensor] = None, goal_vel: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
+                    generator=None, q_min: Optional[torch.Tensor] = None, q_max: Optional[torch.Tensor] = None):
+    """`n_particles` trajectories per problem from the constant-velocity GP prior (the prior of gp_prior_cost_grad) conditioned on the
+    problem's start and goal, in one launch (include/trk.h: trk_gp_prior_sample).  start, goal (P,D) fp32 on a GPU; with start_vel AND
+    goal_vel (P,D) the velocities of both ends are pinned too, otherwise only the positions.  eps (P*n_particles, horizon-1, D, 2):
+    the unit normals the draw is made from; None draws them with torch.randn and `generator`.  q_min, q_max (D,), together: the
+    interior way points are clamped.  2 <= horizon <= 256, D <= 32.  -> (q, qd), each (P*n_particles, horizon, D); particle k of
+    problem p is row p*n_particles + k, q[:, 0] and q[:, -1] are start's and goal's bits."""
+    who = "gp_prior_sample"
+    if not isinstance(start, torch.Tensor) or start.dim() != 2:
+        raise ValueError(f"{who}: start must be a (problems, dof) tensor")
+    P, D = (int(v) for v in start.shape)
+    H, K = int(horizon), int(n_particles)
+    _gp_sample_rows(start, (P, D), "start", who)
+    dev = start.device
+    _gp_sample_rows(goal, (P, D), "goal", who, dev)
+    if (start_vel is None) != (goal_vel is None):
+        raise ValueError(f"{who}: start_vel and goal_vel come together (both pin the velocities, neither leaves them free)")
+    pin_vel = start_vel is not None
+    if pin_vel:
+        _gp_sample_rows(start_vel, (P, D), "start_vel", who, dev)
+        _gp_sample_rows(goal_vel, (P, D), "goal_vel", who, dev)
+    if (q_min is None) != (q_max is None):
+        raise ValueError(f"{who}: q_min and q_max come together")
+    if q_min is not None:
+        _gp_sample_rows(q_min, (D,), "q_min", who, dev)
+        _gp_sample_rows(q_max, (D,), "q_max", who, dev)
+    if K < 1 or H < 2:
+        raise ValueError(f"{who}: n_particles must be >= 1 and horizon >= 2")
+    if eps is None:
+        eps = torch.randn((P * K, H - 1, D, 2), generator=generator, device=dev, dtype=torch.float32)
+    else:
+        _gp_sample_rows(eps, (P * K, H - 1, D, 2), "eps", who, dev)
+    q = torch.empty((P * K, H, D), device=dev, dtype=torch.float32)
+    qd = torch.empty_like(q)
+    s = _abi.GpSample(float(dt), float(sigma), K, int(pin_vel))
+    _call("trk_gp_prior_sample", dev, C.byref(s), start.data_ptr(), goal.data_ptr(), _ptr(start_vel), _ptr(goal_vel), eps.data_ptr(),
+          _ptr(q_min), _ptr(q_max), P, H, D, q.data_ptr(), qd.data_ptr())
+    return q, qd
+
+
+def traj_select_best(score: torch.Tensor, is_free: Optional[torch.Tensor] = None, n_particles: int = 1):
+    """One winner per problem (include/trk.h: trk_traj_select_best): score (P*n_particles,) fp32 on a GPU, is_free the same length
+    (bool or uint8; None = all free) -> (best (P,) int64: the row p*n_particles + k of the smallest score among the free particles
+    whose score is not NaN, the smallest k among equals, -1 without one; best_score (P,) fp32, +inf without one; n_free (P,) int32)."""
+    who = "traj_select_best"
+    K = int(n_particles)
+    if not isinstance(score, torch.Tensor) or score.device.type != "cuda" or score.dim() != 1 or score.dtype != torch.float32 or \
+            not score.is_contiguous():
+        raise ValueError(f"{who}: score must be a contiguous float32 vector on a GPU (there is no CPU path)")
+    if K < 1 or score.numel() % K:
+        raise ValueError(f"{who}: the length of score ({score.numel()}) is not a multiple of n_particles ({K})")
+    P = score.numel() // K
+    if is_free is not None:
+        if not isinstance(is_free, torch.Tensor) or is_free.device != score.device or is_free.shape != score.shape or \
+                is_free.dtype not in (torch.bool, torch.uint8) or not is_free.is_contiguous():
+            raise ValueError(f"{who}: is_free must be a contiguous bool / uint8 vector of score's length on its GPU")
+        if is_free.dtype == torch.bool:
+            is_free = is_free.view(torch.uint8)
+    best = torch.empty((P,), device=score.device, dtype=torch.int64)
+    best_score = torch.empty((P,), device=score.device, dtype=torch.float32)
+    n_free = torch.empty((P,), device=score.device, dtype=torch.int32)
+    _call("trk_traj_select_best", score.device, score.data_ptr(), _ptr(is_free), P, K, best.data_ptr(), best_score.data_ptr(),
+          n_free.data_ptr())
+    return best, best_score, n_free
+
+
 def reduce_sum(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Deterministic sum of a float32 device vector (fixed association order)."""
     x = _dev_f32(x, "reduce_sum(x)").reshape(-1)

@@ -524,6 +524,58 @@ class PlanningTask(Task):
             return trajs_coll, coll_idxs, trajs_free, free_idxs, wp.reshape(lead + (wp.shape[-1],))
         return trajs_coll, trajs_free
 
+    # ---------------------------------------------------------------------------------------------
+    # multi-particle planning: several particles per problem from the GP prior go into a planning loop, one winner per problem
+    # comes out (ops.gp_prior_sample, ops.traj_select_best)
+    # ---------------------------------------------------------------------------------------------
+    def sample_gp_trajs(self, q_start, q_goal, n_particles, horizon, dt, sigma_gp, pin_vel=False, clamp_to_limits=True, generator=None,
+                        eps=None):
+        """`n_particles` initial trajectories per problem from the constant-velocity GP prior the planning loops carry as a cost,
+        conditioned on q_start, q_goal (P, q_dim) or (q_dim,): -> (q, qd), each (P*n_particles, horizon, q_dim), particle k of problem
+        p in row p*n_particles + k -- what rollout_adam_plan / points_adam_plan / trajectory_optimizer / point_mass_3d_optimizer take.
+        pin_vel: zero velocity at both ends (the loops' pin_start_vel / pin_goal_vel), otherwise only the positions are pinned.
+        clamp_to_limits: interior way points are clamped to the robot's q_min / q_max.  eps (P*n_particles, horizon-1, q_dim, 2):
+        the unit normals to draw from; None draws them with `generator`."""
+        D = int(self.robot.q_dim)
+        dev = ops.compute_device(q_start.device if isinstance(q_start, torch.Tensor) else None)
+        rows = lambda t: torch.as_tensor(t).to(dev, torch.float32).reshape(-1, D).contiguous()
+        start, goal = rows(q_start), rows(q_goal)
+        if start.shape != goal.shape:
+            raise ValueError(f"sample_gp_trajs: q_start {tuple(start.shape)} and q_goal {tuple(goal.shape)} differ")
+        vel = (torch.zeros_like(start), torch.zeros_like(start)) if pin_vel else (None, None)
+        lim = (None, None)
+        if clamp_to_limits:
+            lim = tuple(l.to(dev, torch.float32).reshape(D).contiguous() for l in (self.robot.q_min, self.robot.q_max))
+        return ops.gp_prior_sample(start, goal, horizon, dt, sigma_gp, n_particles, vel[0], vel[1], eps=eps, generator=generator,
+                                   q_min=lim[0], q_max=lim[1])
+
+    def select_best_trajs(self, trajs, n_particles, num_interpolation=5, score=None):
+        """The best collision-free particle of every problem: trajs (P*n_particles, H, S), particle k of problem p in row
+        p*n_particles + k -> (best_trajs (P, H, S), best (P,) int64 rows of trajs, solved (P,) bool).  Free are the trajectories
+        `get_trajs_collision_and_free` calls free (its one host read is the only one here); score (P*n_particles,), smaller is
+        better, None = the path length over the first q_dim columns (ops.traj_diff_norm_sum).  A problem without a free particle
+        has solved False and returns its lowest-score particle of all (particle 0 if every score is NaN)."""
+        K = int(n_particles)
+        if trajs.ndim != 3 or K < 1 or trajs.shape[0] % K:
+            raise ValueError(f"select_best_trajs: trajs must be (problems * n_particles, horizon, state), got {tuple(trajs.shape)} "
+                             f"for n_particles = {K}")
+        dev = ops.compute_device(trajs.device)
+        flat = trajs.detach().to(dev, torch.float32).contiguous()
+        N = int(flat.shape[0])
+        _, _, _, free_idxs, _ = self.get_trajs_collision_and_free(flat, return_indices=True, num_interpolation=num_interpolation)
+        is_free = torch.zeros((N,), device=dev, dtype=torch.uint8)
+        is_free[free_idxs.reshape(-1).to(torch.int64)] = 1
+        if score is None:
+            score = ops.traj_diff_norm_sum(flat, 0, int(self.robot.q_dim))
+        score = score.detach().to(dev, torch.float32).reshape(N).contiguous()
+        best, _, _ = ops.traj_select_best(score, is_free, K)
+        solved = best >= 0
+        of_all, _, _ = ops.traj_select_best(score, None, K)
+        first = torch.arange(0, N, K, device=dev, dtype=torch.int64)
+        pick = torch.where(solved, best, torch.where(of_all >= 0, of_all, first))
+        out = (flat.index_select(0, pick), pick, solved)
+        return out if trajs.device == dev else tuple(t.to(trajs.device) for t in out)
+
     def compute_fraction_free_trajs(self, trajs, **kwargs):
         _, coll_idxs, _, free_idxs, _ = self.get_trajs_collision_and_free(trajs, return_indices=True)
         n_free, n_coll = free_idxs.nelement(), coll_idxs.nelement()
