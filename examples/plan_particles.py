@@ -11,9 +11,13 @@ with `--spread` (default 0.3 rad for the arm, 0.15 m for the point mass) as the 
 Needs the MI355X: there is no CPU path.
 
     python examples/plan_particles.py [--problems 64] [--particles 8] [--horizon 64] [--iters 200] [--model links|point3d] [--spread S]
+                                      [--resample S]
 
 --model links: the Panda in EnvSpheres3D through `task.rollout_adam_plan` (horizons 2, 4, ..., 64);
 --model point3d: the 3-D point mass in EnvSpheres3D through `task.point_mass_3d_optimizer` (horizons up to 256).
+--resample S: the winners are resampled to S points by the clamped cubic spline through their way points (`tra.smoothen_trajectory`,
+`trk_traj_spline_resample`) and validated again; both free counts and the winners' way-point variance
+(`tra.compute_variance_waypoints`, `trk_traj_waypoint_variance`) are printed.  Off by default: the output is unchanged without it.
 """
 import argparse
 import sys
@@ -41,14 +45,23 @@ def _setup(model, ta):
     raise ValueError(f"model must be 'links' or 'point3d', got {model!r}")
 
 
-def _plan_and_pick(task, make_plan, q, qd, dt, iters, particles):
-    """the planning loop on (q, qd) in place, then the winner of every problem -> number of problems solved"""
+def _plan_and_pick(task, make_plan, q, qd, dt, iters, particles, winners=False):
+    """the planning loop on (q, qd) in place, then the winner of every problem -> number of problems solved (and the winners)"""
     make_plan(q, qd, dt).step(iters)
-    _, _, solved = task.select_best_trajs(torch.cat([q, qd], -1), particles)
-    return int(solved.sum())
+    best, _, solved = task.select_best_trajs(torch.cat([q, qd], -1), particles)
+    return (int(solved.sum()), best) if winners else int(solved.sum())
 
 
-def main(problems=64, particles=8, horizon=64, iters=200, model="links", device="cuda:0", seed=0, verbose=True, spread=None):
+def _resample_and_validate(task, best, n_points):
+    """the winners (P, H, 2 D) resampled to n_points way points -> (free before, free after, the way-point variance of the winners)"""
+    D = task.robot.q_dim
+    free = lambda trajs: int(task.get_trajs_collision_and_free(trajs, return_indices=True)[3].numel())
+    pos, vel = tra.smoothen_trajectory(best[..., :D].contiguous(), n_support_points=n_points, set_average_velocity=False)
+    dense = torch.cat([pos, vel], -1)
+    return free(best), free(dense), float(tra.compute_variance_waypoints(best, task.robot))
+
+
+def main(problems=64, particles=8, horizon=64, iters=200, model="links", device="cuda:0", seed=0, verbose=True, spread=None, resample=0):
     torch.manual_seed(seed)
     ta = dict(device=torch.device(device), dtype=torch.float32)
     task, make_plan, default_spread = _setup(model, ta)
@@ -67,11 +80,17 @@ def main(problems=64, particles=8, horizon=64, iters=200, model="links", device=
     eps = torch.randn((problems * particles, horizon - 1, D, 2), generator=gen, **ta)
     eps[::particles] = 0.0
     qp, qdp = task.sample_gp_trajs(start, goal, particles, horizon, dt, sigma_init, eps=eps)
-    solved_particles = _plan_and_pick(task, make_plan, qp, qdp, dt, iters, particles)
+    solved_particles, best = _plan_and_pick(task, make_plan, qp, qdp, dt, iters, particles, winners=True)
     if verbose:
         print(f"{model}, EnvSpheres3D, {problems} problems x {horizon} steps, {iters} Adam iterations: solved {solved_line}/{problems} "
               f"from one straight line each, {solved_particles}/{problems} from {particles} GP-prior particles each (sigma_init "
               f"{sigma_init:.3f})")
+    if resample:
+        free_before, free_after, variance = _resample_and_validate(task, best, resample)
+        if verbose:
+            print(f"winners resampled {horizon} -> {resample} points by the clamped cubic spline: {free_before}/{problems} free before, "
+                  f"{free_after}/{problems} after; way-point variance of the winners {variance:.4f}")
+        return solved_line, solved_particles, free_before, free_after, variance
     return solved_line, solved_particles
 
 
@@ -84,5 +103,6 @@ if __name__ == "__main__":
     ap.add_argument("--model", choices=("links", "point3d"), default="links")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--spread", type=float, default=None, help="standard deviation of the particles half way (rad / m)")
+    ap.add_argument("--resample", type=int, default=0, help="resample the winners to this many points and validate them again")
     a = ap.parse_args()
-    main(a.problems, a.particles, a.horizon, a.iters, a.model, seed=a.seed, spread=a.spread)
+    main(a.problems, a.particles, a.horizon, a.iters, a.model, seed=a.seed, spread=a.spread, resample=a.resample)

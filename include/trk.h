@@ -1096,6 +1096,68 @@ int trk_gp_prior_sample(const TrkGpSample* s, const float* start, const float* g
 int trk_traj_select_best(const float* score, const uint8_t* is_free /* NULL: all free */, int64_t n_problems, int32_t n_particles,
                          int64_t* best, float* best_score /* nullable */, int32_t* n_free /* nullable */, trk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Trajectory post-processing: spline resampling and way-point variance.  What happens to trajectories AFTER the loops and the pick: a
+ * coarse path becomes the dense (q, qd) a loop or a controller takes, and a set of particles gets its diversity metric.
+ *
+ * trk_traj_spline_resample (reference: smoothen_trajectory trajectory/utils.py:8-34, there one trajectory at a time on the host
+ * through scipy): the clamped cubic interpolating spline through every column of y, resampled to n_out positions and velocities, in
+ * ONE launch.  y [n_traj, n_points, dim]; pos, vel [n_traj, n_out, dim]; fp32, contiguous, 4-byte aligned; vel may be NULL with
+ * vel_mode 0.  Per (trajectory, coordinate) column, independent of every other; N = n_points, S = n_out, h = 1 / (N - 1):
+ *   spline  the complete cubic spline through y_0 .. y_{N-1} at the uniform knots i h with zero end slopes -- unique, and scipy's
+ *           make_interp_spline(linspace(0, 1, N), y, k=3, bc_type='clamped');
+ *   slopes  s_0 = s_{N-1} = 0;  s_{i-1} + 4 s_i + s_{i+1} = 3 (N - 1) (y_{i+1} - y_{i-1}) for 0 < i < N - 1, by the Thomas recurrence
+ *           down and up the column:  m_1 = 1/4, m_i = 1 / (4 - m_{i-1}) (formed in double, rounded once; they depend on i alone),
+ *           g_i = (3 (N - 1) (y_{i+1} - y_{i-1}) - g_{i-1}) m_i with g_0 = 0,  s_i = g_i - m_i s_{i+1}.  A column is solved
+ *           sequentially by one lane: its bits depend only on its own inputs, not on its place in the batch or on how a batch is split;
+ *   sample  k of S from integers, never a float comparison: a = k (N - 1), i = a / (S - 1), r = a % (S - 1), tau = r / (S - 1); the
+ *           last sample is i = N - 2, tau = 1;
+ *   pos     (y_i + (tau^2 (3 - 2 tau)) (y_{i+1} - y_i)) + ((h tau) (1 - tau)) ((1 - tau) s_i - tau s_{i+1}), without contraction.  A
+ *           constant column comes back bit-exact; at r = 0 the result is the bits of y_i by select, so the endpoints always equal
+ *           the input and, when (S - 1) % (N - 1) == 0, every knot does;
+ *   vel     vel_mode 0: zeros.  1: the reference's set_average_velocity as it is: rows 1 .. S-2 are (y_1 - y_0) / (S dt), the two
+ *           end rows 0; S dt is formed in double and rounded once.  2: the spline's derivative with respect to its parameter u in
+ *           [0, 1] (not time; what the reference returns):  (((6 (N - 1) tau) (1 - tau)) (y_{i+1} - y_i) + ((1 - tau) (1 - 3 tau)) s_i)
+ *           + (tau (3 tau - 2)) s_{i+1};  the two end rows are exactly 0 by select.
+ * A non-finite value poisons its own column and nothing else.
+ * 2 <= n_points <= TRK_SPLINE_MAX_POINTS, 2 <= n_out <= TRK_SPLINE_MAX_OUT, 1 <= dim <= TRK_SPLINE_MAX_DIM.
+ * Validation, before any device work (also with n_traj = 0).  TRK_ERR_INVALID_ARG: n_traj < 0, n_points < 2, n_out < 2, dim < 1;
+ * n_traj * max(n_points, n_out) > 0x3fffffff; vel_mode outside {0, 1, 2}; vel_mode 1 with dt non-finite or <= 0; vel_mode != 0 with
+ * a null vel; null y or pos (n_traj > 0).  TRK_ERR_UNSUPPORTED, the limit named: a value above its maximum.  n_traj = 0: TRK_OK
+ * without a launch.  No atomics, no host synchronisation: capturable.
+ *
+ * trk_traj_waypoint_variance (reference: compute_variance_waypoints trajectory/metrics.py:14-24, there for one set of trajectories):
+ * per problem p, the sum over the way points of the variance of the particles' pairwise distances.  x [n_problems * n_particles,
+ * horizon, state_dim], particle k of problem p is row p * n_particles + k; the positions are columns c0 .. c0 + dim - 1 (as in
+ * trk_traj_diff_norm_sum); out [n_problems].  With K = n_particles and n = K^2 (the reference takes the unbiased variance over the
+ * whole triu matrix, zeros included), per way point t:
+ *   S1 = sum_{i<j} d_ij,  S2 = sum_{i<j} d_ij^2,  var_t = (S2 - S1^2 / n) / (n - 1),  out[p] = sum_t var_t.
+ * d_ij is the Euclidean distance, formed in fp32 from the coordinate differences (sum in ascending coordinate, then the square
+ * root) -- not by |a|^2 + |b|^2 - 2 a.b, which loses clustered particles.  S1, S2, the subtraction, the division and the sum over t
+ * are fp64, rounded once to fp32.  K = 1 gives NaN like the reference (0 / 0); a non-finite input stays in its own problem.
+ * Two launches, no atomics: the particles are cut into tiles of 64, a wavefront sums one (way point, tile pair) and stores its two
+ * fp64 sums in the workspace, and the second kernel adds a way point's tile pairs in ascending order, the way points of a lane in
+ * ascending order, and the lanes by a fixed tree.  The result is bit-reproducible and does not depend on how problems are batched.
+ * workspace: trk_traj_waypoint_variance_workspace_bytes(n_problems, n_particles, horizon) bytes (host-only query; -1 for arguments
+ * the entry refuses), 8-byte aligned, the caller's; nothing in it needs zeroing.
+ * 1 <= n_particles <= TRK_WAYPOINT_VAR_MAX_PARTICLES, horizon >= 1, 1 <= dim <= TRK_WAYPOINT_VAR_MAX_DIM.
+ * Validation, before any device work (also with n_problems = 0).  TRK_ERR_INVALID_ARG: n_problems < 0, n_particles < 1, horizon < 1;
+ * n_problems * n_particles * horizon > 0x3fffffff; dim < 1, c0 < 0, c0 + dim > state_dim; null x or out (n_problems > 0).
+ * TRK_ERR_UNSUPPORTED, the limit named: n_particles or dim above its maximum.  Then TRK_ERR_INVALID_ARG for a workspace that is
+ * null, misaligned or too small (n_problems > 0).  n_problems = 0: TRK_OK without a launch.  Capturable.
+ * --------------------------------------------------------------------------------- */
+#define TRK_SPLINE_MAX_POINTS 256
+#define TRK_SPLINE_MAX_OUT 1024
+#define TRK_SPLINE_MAX_DIM 32
+#define TRK_WAYPOINT_VAR_MAX_PARTICLES 4096
+#define TRK_WAYPOINT_VAR_MAX_DIM 32
+int trk_traj_spline_resample(const float* y, int64_t n_traj, int32_t n_points, int32_t dim, int32_t n_out, int32_t vel_mode, float dt,
+                             float* pos, float* vel /* nullable */, trk_stream_t stream);
+int64_t trk_traj_waypoint_variance_workspace_bytes(int64_t n_problems, int32_t n_particles, int32_t horizon);
+int trk_traj_waypoint_variance(const float* x, int64_t n_problems, int32_t n_particles, int32_t horizon, int32_t state_dim, int32_t c0,
+                               int32_t dim, float* out /* [n_problems] */, void* workspace, int64_t workspace_bytes,
+                               trk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,8 @@ from .environments import (MultiSphereField, MultiBoxField, MultiSharpBoxField, 
                            EnvSimple2DExtraObjects, EnvDense2DExtraObjects, EnvNarrowPassageDense2DExtraObjects)
 from .fields import (DistanceField, CollisionSelfField, CollisionObjectDistanceField,  # noqa: F401
                      CollisionWorkspaceBoundariesDistanceField, EESE3DistanceField, SE3_distance)
-from .robots import RobotBase, RobotPanda, RobotPointMass, RobotPointMass3D, compute_path_length, compute_smoothness, finite_difference_vector  # noqa: F401
+from .robots import RobotBase, RobotPanda, RobotPointMass, RobotPointMass3D, compute_path_length, compute_smoothness, finite_difference_vector, \
+    compute_variance_waypoints, smoothen_trajectory  # noqa: F401
 from .tasks import PlanningTask, GraphedCostBackward  # noqa: F401
 
 __version__ = "0.1.0"

@@ -152,6 +152,8 @@ TRK_POINT3D_FORM_NONE, TRK_POINT3D_FORM_DPP, TRK_POINT3D_FORM_LDS = 0, 1, 2     
 
 TRK_GP_SAMPLE_MAX_HORIZON = 256        # trk_gp_prior_sample
 TRK_GP_SAMPLE_MAX_DOF = 32
+TRK_SPLINE_MAX_POINTS, TRK_SPLINE_MAX_OUT, TRK_SPLINE_MAX_DIM = 256, 1024, 32      # trk_traj_spline_resample
+TRK_WAYPOINT_VAR_MAX_PARTICLES, TRK_WAYPOINT_VAR_MAX_DIM = 4096, 32               # trk_traj_waypoint_variance
 
 
 class GpSample(C.Structure):            # TrkGpSample

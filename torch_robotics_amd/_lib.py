@@ -45,6 +45,7 @@ EXPORTS = [
     "trk_rollout_points_gp_adam_steps",
     "trk_point3d_traj_cost_grad", "trk_point3d_traj_adam_steps", "trk_point3d_last_form",
     "trk_gp_prior_sample", "trk_traj_select_best",
+    "trk_traj_spline_resample", "trk_traj_waypoint_variance", "trk_traj_waypoint_variance_workspace_bytes",
 ]
 
 
@@ -220,11 +221,15 @@ def lib():
     L.trk_point3d_last_form.argtypes = []
     L.trk_gp_prior_sample.argtypes = [C.POINTER(_abi.GpSample), vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp]
     L.trk_traj_select_best.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
+    L.trk_traj_spline_resample.argtypes = [vp, i64, i32, i32, i32, i32, f32, vp, vp, vp]
+    L.trk_traj_waypoint_variance_workspace_bytes.argtypes = [i64, i32, i32]
+    L.trk_traj_waypoint_variance_workspace_bytes.restype = C.c_int64
+    L.trk_traj_waypoint_variance.argtypes = [vp, i64, i32, i32, i32, i32, i32, vp, vp, i64, vp]
     for name in EXPORTS:
         fn = getattr(L, name)        # AttributeError here = the library does not export the ABI
         if name not in ("trk_last_error", "trk_model_destroy", "trk_cost_model_destroy", "trk_point_set_destroy",
                         "trk_pack_sums_scratch_bytes", "trk_mailbox_destroy", "trk_via_partial_flags_bytes",
-                        "trk_scene2d_destroy"):
+                        "trk_scene2d_destroy", "trk_traj_waypoint_variance_workspace_bytes"):
             fn.restype = C.c_int
     if L.trk_abi_version() != _abi.TRK_ABI_VERSION:
         raise TrkError("libtrk.so ABI version mismatch; rebuild it")

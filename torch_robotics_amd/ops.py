@@ -1919,6 +1919,52 @@ def traj_select_best(score: torch.Tensor, is_free: Optional[torch.Tensor] = None
     return best, best_score, n_free
 
 
+SPLINE_VEL_MODES = {"zero": 0, "average": 1, "spline": 2}
+
+
+def traj_spline_resample(y: torch.Tensor, n_out: int, vel_mode: str = "average", dt: float = 0.02):
+    """The clamped cubic spline through every column of y (..., N, D), resampled to n_out rows in one launch (include/trk.h:
+    trk_traj_spline_resample; reference smoothen_trajectory trajectory/utils.py:8-34) -> (pos, vel), each (..., n_out, D) fp32.
+    vel_mode "average": the reference's set_average_velocity rows (y[1] - y[0]) / (n_out dt) with zero end rows; "zero": zeros;
+    "spline": the spline's derivative with respect to its parameter in [0, 1].  y is a contiguous fp32 tensor on a GPU;
+    2 <= N <= 256, 2 <= n_out <= 1024, D <= 32.  No autograd."""
+    who = "traj_spline_resample"
+    if vel_mode not in SPLINE_VEL_MODES:
+        raise ValueError(f"{who}: vel_mode must be one of {sorted(SPLINE_VEL_MODES)}, got {vel_mode!r}")
+    if not isinstance(y, torch.Tensor) or y.device.type != "cuda" or y.dim() < 2:
+        raise ValueError(f"{who}: y must be a (..., points, dim) tensor on a GPU (there is no CPU path)")
+    if y.dtype != torch.float32 or not y.is_contiguous():
+        raise ValueError(f"{who}: y must be a contiguous float32 tensor, got {y.dtype} {tuple(y.shape)}")
+    N, D, S = int(y.shape[-2]), int(y.shape[-1]), int(n_out)
+    lead = tuple(y.shape[:-2])
+    n_traj = 1
+    for v in lead:
+        n_traj *= int(v)
+    pos = torch.empty(lead + (max(S, 0), D), device=y.device, dtype=torch.float32)
+    vel = torch.empty_like(pos)
+    _call("trk_traj_spline_resample", y.device, y.data_ptr(), n_traj, N, D, S, SPLINE_VEL_MODES[vel_mode], float(dt), pos.data_ptr(),
+          vel.data_ptr())
+    return pos, vel
+
+
+def traj_waypoint_variance(trajs: torch.Tensor, c0: int, dim: int) -> torch.Tensor:
+    """Per problem, the sum over the way points of the variance of the particles' pairwise distances (include/trk.h:
+    trk_traj_waypoint_variance; reference compute_variance_waypoints trajectory/metrics.py:14-24): trajs (P, K, H, S) contiguous fp32
+    on a GPU, the positions its columns c0 .. c0+dim-1 -> (P,) fp32.  K <= 4096, dim <= 32; K = 1 gives NaN like the reference."""
+    who = "traj_waypoint_variance"
+    if not isinstance(trajs, torch.Tensor) or trajs.device.type != "cuda" or trajs.dim() != 4:
+        raise ValueError(f"{who}: trajs must be a (problems, particles, horizon, state_dim) tensor on a GPU (there is no CPU path)")
+    if trajs.dtype != torch.float32 or not trajs.is_contiguous():
+        raise ValueError(f"{who}: trajs must be a contiguous float32 tensor, got {trajs.dtype} {tuple(trajs.shape)}")
+    P, K, H, S = (int(v) for v in trajs.shape)
+    out = torch.empty((P,), device=trajs.device, dtype=torch.float32)
+    nbytes = int(lib().trk_traj_waypoint_variance_workspace_bytes(P, max(K, 1), max(H, 1))) if 1 <= K <= _abi.TRK_WAYPOINT_VAR_MAX_PARTICLES else 0
+    work = torch.empty((max(nbytes, 8) // 8,), device=trajs.device, dtype=torch.float64)
+    _call("trk_traj_waypoint_variance", trajs.device, trajs.data_ptr(), P, K, H, S, int(c0), int(dim), out.data_ptr(), work.data_ptr(),
+          nbytes)
+    return out
+
+
 def reduce_sum(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Deterministic sum of a float32 device vector (fixed association order)."""
     x = _dev_f32(x, "reduce_sum(x)").reshape(-1)

@@ -40,6 +40,50 @@ def compute_smoothness(trajs, robot, trajs_vel=None):
     return ops.traj_diff_norm_sum(trajs_vel, 0, trajs_vel.shape[-1])
 
 
+def compute_variance_waypoints(trajs, robot):
+    """trajectory/metrics.py:14-24: the sum over the way points of the variance of the trajectories' pairwise joint-space distances
+    (the diversity metric), (B, H, S) -> a 0-dim tensor: ops.traj_waypoint_variance on one problem of B particles.  One trajectory
+    gives NaN, as in the reference."""
+    assert trajs.ndim == 3
+    return _waypoint_variance_one(trajs, robot.q_dim)
+
+
+@ops.host_round_trip
+def _waypoint_variance_one(trajs, q_dim):
+    trajs = ops._dev_f32(trajs.detach(), "compute_variance_waypoints(trajs)")
+    return ops.traj_waypoint_variance(trajs[None], 0, q_dim)[0]
+
+
+def smoothen_trajectory(traj_pos, n_support_points=30, dt=0.02, set_average_velocity=True, zero_velocity=False, tensor_args=None):
+    """trajectory/utils.py:8-34: the clamped cubic spline (zero velocity at both ends) through the path traj_pos (N, D), resampled to
+    n_support_points positions and velocities in one launch (ops.traj_spline_resample); (..., N, D) resamples a batch of paths at
+    once.  -> (pos, vel), each (..., n_support_points, D), on the input's device (moved and cast by tensor_args when given).
+    Velocities as in the reference: set_average_velocity -> (traj_pos[1] - traj_pos[0]) / (n_support_points dt) in the interior rows
+    and 0 at the ends; zero_velocity -> zeros; neither -> the spline's derivative with respect to its parameter in [0, 1].
+    The input is detached: there is no autograd through the resampling.  N = 1 raises IndexError as the reference does (through
+    scipy); its random-noise retry cannot be reached for N >= 2 and is not built."""
+    assert not (set_average_velocity and zero_velocity), "Either sets the average velocity or zero velocity"
+    y = torch.as_tensor(traj_pos).detach()
+    if y.dim() < 2:
+        raise ValueError("smoothen_trajectory: traj_pos must be (N, D) or (..., N, D)")
+    if y.shape[-2] < 2:
+        raise IndexError("smoothen_trajectory: a path of one point has no segment to interpolate (index 1 is out of bounds)")
+    home = y.device
+    if y.device.type != "cuda":
+        y = y.to(ops.compute_device(y.device))
+    y = y.to(torch.float32).contiguous()
+    S = int(n_support_points)
+    if S == 1:                                                   # linspace(0, 1, 1) = [0]: the first point, and no interior row
+        pos = y[..., :1, :].clone()
+        vel = torch.zeros_like(pos)
+    else:
+        mode = "zero" if zero_velocity else ("average" if set_average_velocity else "spline")
+        pos, vel = ops.traj_spline_resample(y, S, mode, dt)
+    if tensor_args is not None:
+        return pos.to(**tensor_args), vel.to(**tensor_args)
+    return pos.to(home), vel.to(home)
+
+
 class RobotBase:
     def __init__(self, name="RobotBase", q_limits=None, grasped_object=None,
                  margin_for_grasped_object_collision_checking=0.001,
