@@ -1158,6 +1158,74 @@ int trk_traj_waypoint_variance(const float* x, int64_t n_problems, int32_t n_par
                                int32_t dim, float* out /* [n_problems] */, void* workspace, int64_t workspace_bytes,
                                trk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Sampling-based trajectory update: soft-min weights and the weighted particle mean.  The optimiser of STOMP / MPPI for every robot
+ * and horizon a cost can be evaluated at: perturb the mean with smooth noise (trk_gp_prior_sample with zero start and goal), evaluate
+ * every particle, weight the particles by a soft-min of their costs, move the mean to the weighted particle mean.  These two entries
+ * are the last two steps.  BUILD-DEFINED like the sampler: the arithmetic is specified below and checked against restatements.
+ * Particle k of problem p is row p * n_particles + k everywhere; K = n_particles, H = horizon.  fp32, contiguous, 4-byte aligned.
+ *
+ * trk_traj_softmin_weights: cost [n_problems * K, H] (H = 1: the scores are already summed); valid [n_problems * K] bytes, NULL =
+ * all valid, 0 = rejected; lambda = s->temperature.  Everything between reading cost and the final rounding is fp64.
+ *   TRK_SOFTMIN_TRAJECTORY (MPPI), w [n_problems * K], ess (nullable) [n_problems]:
+ *     S_k = sum_t cost[k, t];  a particle is a candidate iff it is valid and S_k is finite;  m = min over the candidates;
+ *     a_k = exp(-(S_k - m) / lambda),  Z = sum_k a_k over the candidates;
+ *     w_k = (float)(a_k / Z), exactly 0 for a non-candidate;  ess = (float)(Z^2 / sum_k a_k^2).
+ *   TRK_SOFTMIN_WAYPOINT (STOMP's probabilities), w [n_problems * K, H], ess (nullable) [n_problems, H], per way point t:
+ *     the candidates are the valid particles with finite cost[k, t];  lo, hi their min and max;
+ *     a_k = hi > lo ? exp(-(cost[k, t] - lo) / ((hi - lo) lambda)) : 1;  Z, w_k and ess as above.  STOMP's h = 10 is lambda = 0.1.
+ *   A problem (or way point) without a candidate gets all weights 0 and ess 0.
+ * The association is fixed and a function of H and K alone, so a problem's bits do not depend on its place in the batch or on how
+ * the batch is split into calls.  S_k: with G = the power of two >= min(H, 64), G partial sums s_j = cost[k, j] + cost[k, j + G] +
+ * ... in ascending t, folded by the xor tree j ^ G/2, .., j ^ 1.  Z and sum a^2: one workgroup of 1024 lanes owns a problem (way-point
+ * mode: 16 consecutive way points of it, NG = 64 lanes a way point; trajectory mode NG = 1024); lane g adds the candidates k = g,
+ * g + NG, ... in ascending k, and the NG sums fold by the tree sum[g] += sum[g + m] for g < m, m = NG/2, .., 1.  One launch; the trajectory mode with
+ * K > 256 and H > 1 takes two: S_k of all rows is formed across the chip first (the same arithmetic, the same bits) and passes
+ * through the workspace, so one problem with thousands of particles is not summed by a single workgroup.
+ * workspace: trk_traj_softmin_weights_workspace_bytes(n_problems, K, H, mode) bytes (host-only query; 0 where one launch serves,
+ * and workspace may then be NULL; -1 for arguments the entry refuses), 8-byte aligned, the caller's; nothing in it needs zeroing.
+ *
+ * trk_traj_weighted_update: out = mean + step * sum_k w_k (x_k - mean).  x [n_problems * K, H, dim]; mean, out [n_problems, H, dim]
+ * (out == mean is allowed); w [n_problems * K], or [n_problems * K, H] with w_per_waypoint = 1; lo, hi [dim], nullable TOGETHER.
+ * Per element, in fp32, every operation rounded once (no contraction):  d = x_k - mean,  acc = acc + w_k * d,  out = mean + step * acc.
+ *   A particle whose weight is exactly 0 (+-0) leaves the sum by a select, not by its zero product: a NaN row of a rejected particle
+ *   does not reach the mean.
+ *   Order of the K terms: chunks of 64 particles (the last one shorter); a chunk's sum starts from +0 and adds its terms in ascending
+ *   k; the result is chunk 0's sum, then + chunk 1's, .. in ascending chunk order.  A function of k and K alone: a problem's bits
+ *   do not depend on the batch.
+ *   step = 0: mean + step * acc is replaced by mean's bits by select.
+ *   pin: bit 0 keeps the first way point, bit 1 the last -- the output is mean's bits by select, whatever the limits say.
+ *   With limits the unpinned result r is clamped by comparisons, r < lo[d] ? lo[d] : r, then r > hi[d] ? hi[d] : r: a NaN stays a NaN.
+ * x is read exactly once; a wavefront's loads cover 64 consecutive floats of a particle's H * dim row.  K <= 64: one launch, a
+ * wavefront per (problem, 64 elements).  K > 64: a wavefront per (problem, chunk, 64 elements) stores the chunk's sum in the
+ * workspace [n_problems, ceil(K / 64), H * dim] fp32, and a second launch adds the chunks and finishes: one problem with thousands of
+ * particles fills the chip as many problems with few do.
+ * workspace: trk_traj_weighted_update_workspace_bytes(n_problems, K, H, dim) bytes (host-only query; 0 for K <= 64, where workspace
+ * may be NULL; -1 for arguments the entry refuses), 4-byte aligned, the caller's; nothing in it needs zeroing.
+ * Any association of the K terms is within (K + 3) 2^-24 of  |mean| + |step| sum_k |w_k| |x_k - mean|  (each term's difference,
+ * product and addition, then the step and the final addition).
+ *
+ * 1 <= n_particles <= TRK_SOFTMIN_MAX_PARTICLES, horizon >= 1, dim >= 1.
+ * Validation, before any device work (also with n_problems = 0).  TRK_ERR_INVALID_ARG: a null struct; temperature non-finite or
+ * <= 0; step non-finite; mode outside {0, 1}, pin outside 0 .. 3, w_per_waypoint outside {0, 1}; n_problems < 0, n_particles < 1,
+ * horizon < 1, dim < 1; n_problems * n_particles or horizon * dim above 0x3fffffff, more than 0x7fffffff workgroups; only one of
+ * lo / hi; null cost, w, x, mean or out (n_problems > 0).  TRK_ERR_UNSUPPORTED, the limit named: n_particles above the maximum.  Then
+ * TRK_ERR_INVALID_ARG for a workspace that is null, misaligned or too small (n_problems > 0 and the query above 0).  n_problems = 0: TRK_OK
+ * without a launch.  No atomics, no host synchronisation: capturable.
+ * --------------------------------------------------------------------------------- */
+#define TRK_SOFTMIN_MAX_PARTICLES 4096
+enum { TRK_SOFTMIN_TRAJECTORY = 0, TRK_SOFTMIN_WAYPOINT = 1 };
+typedef struct TrkSoftmin { float temperature; int32_t mode; int32_t n_particles; } TrkSoftmin;
+typedef struct TrkWeightedUpdate { float step; int32_t pin; int32_t n_particles; int32_t w_per_waypoint; } TrkWeightedUpdate;
+int trk_traj_softmin_weights(const TrkSoftmin* s, const float* cost, const uint8_t* valid /* NULL: all valid */, int64_t n_problems,
+                             int32_t horizon, float* w, float* ess /* nullable */, void* workspace, int64_t workspace_bytes,
+                             trk_stream_t stream);
+int64_t trk_traj_softmin_weights_workspace_bytes(int64_t n_problems, int32_t n_particles, int32_t horizon, int32_t mode);
+int64_t trk_traj_weighted_update_workspace_bytes(int64_t n_problems, int32_t n_particles, int32_t horizon, int32_t dim);
+int trk_traj_weighted_update(const TrkWeightedUpdate* u, const float* x, const float* mean, const float* w, const float* lo,
+                             const float* hi, int64_t n_problems, int32_t horizon, int32_t dim, float* out, void* workspace,
+                             int64_t workspace_bytes, trk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

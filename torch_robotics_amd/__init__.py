@@ -22,6 +22,6 @@ from .fields import (DistanceField, CollisionSelfField, CollisionObjectDistanceF
                      CollisionWorkspaceBoundariesDistanceField, EESE3DistanceField, SE3_distance)
 from .robots import RobotBase, RobotPanda, RobotPointMass, RobotPointMass3D, compute_path_length, compute_smoothness, finite_difference_vector, \
     compute_variance_waypoints, smoothen_trajectory  # noqa: F401
-from .tasks import PlanningTask, GraphedCostBackward  # noqa: F401
+from .tasks import PlanningTask, GraphedCostBackward, SamplingPlan  # noqa: F401
 
 __version__ = "0.1.0"

@@ -160,6 +160,18 @@ class GpSample(C.Structure):            # TrkGpSample
     _fields_ = [("dt", C.c_float), ("sigma", C.c_float), ("n_particles", C.c_int32), ("pin_vel", C.c_int32)]
 
 
+TRK_SOFTMIN_MAX_PARTICLES = 4096        # trk_traj_softmin_weights, trk_traj_weighted_update
+TRK_SOFTMIN_TRAJECTORY, TRK_SOFTMIN_WAYPOINT = 0, 1
+
+
+class Softmin(C.Structure):             # TrkSoftmin
+    _fields_ = [("temperature", C.c_float), ("mode", C.c_int32), ("n_particles", C.c_int32)]
+
+
+class WeightedUpdate(C.Structure):      # TrkWeightedUpdate
+    _fields_ = [("step", C.c_float), ("pin", C.c_int32), ("n_particles", C.c_int32), ("w_per_waypoint", C.c_int32)]
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 

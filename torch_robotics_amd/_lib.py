@@ -46,6 +46,8 @@ EXPORTS = [
     "trk_point3d_traj_cost_grad", "trk_point3d_traj_adam_steps", "trk_point3d_last_form",
     "trk_gp_prior_sample", "trk_traj_select_best",
     "trk_traj_spline_resample", "trk_traj_waypoint_variance", "trk_traj_waypoint_variance_workspace_bytes",
+    "trk_traj_softmin_weights", "trk_traj_weighted_update", "trk_traj_weighted_update_workspace_bytes",
+    "trk_traj_softmin_weights_workspace_bytes",
 ]
 
 
@@ -225,11 +227,18 @@ def lib():
     L.trk_traj_waypoint_variance_workspace_bytes.argtypes = [i64, i32, i32]
     L.trk_traj_waypoint_variance_workspace_bytes.restype = C.c_int64
     L.trk_traj_waypoint_variance.argtypes = [vp, i64, i32, i32, i32, i32, i32, vp, vp, i64, vp]
+    L.trk_traj_softmin_weights.argtypes = [C.POINTER(_abi.Softmin), vp, vp, i64, i32, vp, vp, vp, i64, vp]
+    L.trk_traj_softmin_weights_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    L.trk_traj_softmin_weights_workspace_bytes.restype = C.c_int64
+    L.trk_traj_weighted_update_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    L.trk_traj_weighted_update_workspace_bytes.restype = C.c_int64
+    L.trk_traj_weighted_update.argtypes = [C.POINTER(_abi.WeightedUpdate), vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, i64, vp]
     for name in EXPORTS:
         fn = getattr(L, name)        # AttributeError here = the library does not export the ABI
         if name not in ("trk_last_error", "trk_model_destroy", "trk_cost_model_destroy", "trk_point_set_destroy",
                         "trk_pack_sums_scratch_bytes", "trk_mailbox_destroy", "trk_via_partial_flags_bytes",
-                        "trk_scene2d_destroy", "trk_traj_waypoint_variance_workspace_bytes"):
+                        "trk_scene2d_destroy", "trk_traj_waypoint_variance_workspace_bytes",
+                        "trk_traj_weighted_update_workspace_bytes", "trk_traj_softmin_weights_workspace_bytes"):
             fn.restype = C.c_int
     if L.trk_abi_version() != _abi.TRK_ABI_VERSION:
         raise TrkError("libtrk.so ABI version mismatch; rebuild it")

@@ -1965,6 +1965,101 @@ def traj_waypoint_variance(trajs: torch.Tensor, c0: int, dim: int) -> torch.Tens
     return out
 
 
+SOFTMIN_MODES = {"trajectory": _abi.TRK_SOFTMIN_TRAJECTORY, "waypoint": _abi.TRK_SOFTMIN_WAYPOINT}
+
+
+def traj_softmin_weights(cost: torch.Tensor, n_particles: int, temperature: float, mode: str = "trajectory",
+                         valid: Optional[torch.Tensor] = None):
+    """Soft-min weights of every problem's particles from their costs, in one launch (include/trk.h: trk_traj_softmin_weights).
+    cost (P*n_particles, H) or (P*n_particles,) (the scores already summed) contiguous fp32 on a GPU, particle k of problem p in
+    row p*n_particles + k; valid (P*n_particles,) bool / uint8, None = all valid.  mode "trajectory" (MPPI): weights
+    (P*n_particles,) from exp(-(S_k - min S) / temperature) of the summed scores, ess (P,).  mode "waypoint" (STOMP's
+    probabilities; its h = 10 is temperature 0.1): weights (P*n_particles, H) from exp(-(c - lo) / ((hi - lo) temperature)) per
+    way point, ess (P, H).  A particle that is not valid or whose score is not finite gets exactly 0; a problem without a candidate
+    gets all weights 0 and ess 0.  fp64 inside, rounded once; one launch, two in the trajectory mode beyond 256 particles.  n_particles <= 4096.  -> (weights, ess)."""
+    who = "traj_softmin_weights"
+    if mode not in SOFTMIN_MODES:
+        raise ValueError(f"{who}: mode must be one of {sorted(SOFTMIN_MODES)}, got {mode!r}")
+    K = int(n_particles)
+    if not isinstance(cost, torch.Tensor) or cost.device.type != "cuda" or cost.dim() not in (1, 2):
+        raise ValueError(f"{who}: cost must be a (problems * n_particles, horizon) or (problems * n_particles,) tensor on a GPU "
+                         f"(there is no CPU path)")
+    if cost.dtype != torch.float32 or not cost.is_contiguous():
+        raise ValueError(f"{who}: cost must be a contiguous float32 tensor, got {cost.dtype} {tuple(cost.shape)}")
+    N = int(cost.shape[0])
+    H = int(cost.shape[1]) if cost.dim() == 2 else 1
+    if K < 1 or N % K:
+        raise ValueError(f"{who}: the rows of cost ({N}) are not a multiple of n_particles ({K})")
+    P = N // K
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.device != cost.device or tuple(valid.shape) != (N,) or \
+                valid.dtype not in (torch.bool, torch.uint8) or not valid.is_contiguous():
+            raise ValueError(f"{who}: valid must be a contiguous bool / uint8 vector of shape ({N},) on cost's GPU")
+        if valid.dtype == torch.bool:
+            valid = valid.view(torch.uint8)
+    per_wp = mode == "waypoint"
+    w = torch.empty((N, H) if per_wp else (N,), device=cost.device, dtype=torch.float32)
+    ess = torch.empty((P, H) if per_wp else (P,), device=cost.device, dtype=torch.float32)
+    s = _abi.Softmin(float(temperature), SOFTMIN_MODES[mode], K)
+    nbytes = max(int(lib().trk_traj_softmin_weights_workspace_bytes(P, K, H, s.mode)), 0)
+    work = torch.empty((nbytes // 8,), device=cost.device, dtype=torch.float64) if nbytes else None
+    _call("trk_traj_softmin_weights", cost.device, C.byref(s), cost.data_ptr(), _ptr(valid), P, H, w.data_ptr(), ess.data_ptr(),
+          _ptr(work), nbytes)
+    return w, ess
+
+
+def _softmin_rows(t, shape, what: str, who: str, device=None):
+    """a contiguous fp32 tensor of `shape` on one GPU (the kernels read and write it in place)"""
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or (device is not None and t.device != device):
+        raise ValueError(f"{who}: {what} must be a tensor on the same GPU as mean (there is no CPU path)")
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{who}: {what} must be a contiguous float32 tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def traj_weighted_update(mean: torch.Tensor, x: torch.Tensor, weights: torch.Tensor, step: float = 1.0, pin: int = 3,
+                         q_min: Optional[torch.Tensor] = None, q_max: Optional[torch.Tensor] = None,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = mean + step * sum_k w_k (x_k - mean) per problem (include/trk.h: trk_traj_weighted_update).  mean (P, H, D), x
+    (P*n_particles, H, D), weights (P*n_particles,) or per way point (P*n_particles, H): contiguous fp32 on one GPU; particle k of
+    problem p is row p*n_particles + k.  A particle whose weight is exactly 0 is skipped (its row may hold NaN).  pin: bit 0 keeps
+    the first way point, bit 1 the last (mean's bits).  q_min, q_max (D,), together: the unpinned result is clamped.  out (P, H, D),
+    None = a new tensor; out may be mean.  fp32, a fixed order of the particles: chunks of 64 in ascending k, then the chunks in
+    ascending order.  n_particles <= 4096.  -> out."""
+    who = "traj_weighted_update"
+    if not isinstance(mean, torch.Tensor) or mean.device.type != "cuda" or mean.dim() != 3:
+        raise ValueError(f"{who}: mean must be a (problems, horizon, dim) tensor on a GPU (there is no CPU path)")
+    P, H, D = (int(v) for v in mean.shape)
+    dev = mean.device
+    _softmin_rows(mean, (P, H, D), "mean", who)
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or tuple(x.shape[1:]) != (H, D) or P == 0 or int(x.shape[0]) % P or \
+            int(x.shape[0]) == 0:
+        raise ValueError(f"{who}: x must be a (problems * n_particles, {H}, {D}) tensor with a whole number (>= 1) of particles for "
+                         f"each of mean's {P} problems, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
+    N = int(x.shape[0])
+    K = N // P
+    _softmin_rows(x, (N, H, D), "x", who, dev)
+    if not isinstance(weights, torch.Tensor) or weights.dim() not in (1, 2):
+        raise ValueError(f"{who}: weights must be a tensor of shape ({N},) or ({N}, {H})")
+    per_wp = weights.dim() == 2
+    _softmin_rows(weights, (N, H) if per_wp else (N,), "weights", who, dev)
+    if (q_min is None) != (q_max is None):
+        raise ValueError(f"{who}: q_min and q_max come together")
+    if q_min is not None:
+        _softmin_rows(q_min, (D,), "q_min", who, dev)
+        _softmin_rows(q_max, (D,), "q_max", who, dev)
+    if out is None:
+        out = torch.empty_like(mean)
+    else:
+        _softmin_rows(out, (P, H, D), "out", who, dev)
+    nbytes = int(lib().trk_traj_weighted_update_workspace_bytes(P, K, H, D)) if K <= _abi.TRK_SOFTMIN_MAX_PARTICLES else 0
+    work = torch.empty((max(nbytes, 0) // 4,), device=dev, dtype=torch.float32) if nbytes > 0 else None
+    u = _abi.WeightedUpdate(float(step), int(pin), K, int(per_wp))
+    _call("trk_traj_weighted_update", dev, C.byref(u), x.data_ptr(), mean.data_ptr(), weights.data_ptr(), _ptr(q_min), _ptr(q_max),
+          P, H, D, out.data_ptr(), _ptr(work), max(nbytes, 0))
+    return out
+
+
 def reduce_sum(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Deterministic sum of a float32 device vector (fixed association order)."""
     x = _dev_f32(x, "reduce_sum(x)").reshape(-1)

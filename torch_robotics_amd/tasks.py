@@ -576,6 +576,23 @@ class PlanningTask(Task):
         out = (flat.index_select(0, pick), pick, solved)
         return out if trajs.device == dev else tuple(t.to(trajs.device) for t in out)
 
+    def sampling_optimizer(self, q, qd, dt, sigma_gp, n_particles, sigma_noise, temperature, mode="trajectory", w_coll=1.0,
+                           gp_weight=1.0, step=1.0, pin_vel=False, clamp_to_limits=True, generator=None) -> "SamplingPlan":
+        """The sampling-based optimiser (STOMP / MPPI style) for every robot and horizon `compute_collision_cost` serves -- link
+        columns of any DOF, attached points, both point masses, horizons 2 .. 256, up to 32 DOF: no gradient, no planning-loop
+        kernel.  `plan.step(n)` runs n iterations, improves the means q, qd (P, H, D) fp32 in place and returns the (P,) summed cost
+        of the mean it started from.  One iteration: n_particles perturbations of every mean by zero-mean, end-pinned, GP-smooth
+        noise (`ops.gp_prior_sample` with zero start and goal at sigma_noise; with pin_vel also zero end velocities) -- particle 0
+        is the mean itself -- clamped to the joint limits in the interior (clamp_to_limits); the (P n_particles, H) cost
+        w_coll * compute_collision_cost(q) + (gp_weight / H) * ops.gp_prior_cost(q, qd, dt, sigma_gp) (the trajectory's prior
+        cost spread evenly over its way points, so a row sums to the trajectory's objective); the soft-min weights
+        (`ops.traj_softmin_weights`: mode "trajectory" is MPPI's, "waypoint" STOMP's per-way-point probabilities, whose h = 10 is
+        temperature 0.1); and the step of both means towards the weighted particle means (`ops.traj_weighted_update`, the same
+        weights for q and qd).  Start and goal are always kept; qd's ends with pin_vel.  Build the task with clamp_sdf=True, as for
+        the other optimisers: the plain cost decreases without bound."""
+        return SamplingPlan(self, q, qd, dt, sigma_gp, n_particles, sigma_noise, temperature, mode, w_coll, gp_weight, step, pin_vel,
+                            clamp_to_limits, generator)
+
     def compute_fraction_free_trajs(self, trajs, **kwargs):
         _, coll_idxs, _, free_idxs, _ = self.get_trajs_collision_and_free(trajs, return_indices=True)
         n_free, n_coll = free_idxs.nelement(), coll_idxs.nelement()
@@ -588,6 +605,92 @@ class PlanningTask(Task):
     def compute_success_free_trajs(self, trajs, **kwargs):
         _, trajs_free = self.get_trajs_collision_and_free(trajs)
         return 1 if (trajs_free is not None and trajs_free.nelement() >= 1) else 0
+
+
+class SamplingPlan:
+    """`PlanningTask.sampling_optimizer`: the state of the sampling-based optimiser.  `step(n)` runs n iterations on q, qd in place."""
+
+    def __init__(self, task, q, qd, dt, sigma_gp, n_particles, sigma_noise, temperature, mode, w_coll, gp_weight, step, pin_vel,
+                 clamp_to_limits, generator):
+        who = "sampling_optimizer"
+        for name, t in (("q", q), ("qd", qd)):
+            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dim() != 3 or t.dtype != torch.float32 or \
+                    not t.is_contiguous():
+                raise ValueError(f"{who}: {name} must be a contiguous float32 (problems, horizon, q_dim) tensor on a GPU (there is no "
+                                 f"CPU path)")
+        if q.shape != qd.shape or q.device != qd.device or int(q.shape[2]) != int(task.robot.q_dim):
+            raise ValueError(f"{who}: q {tuple(q.shape)} and qd {tuple(qd.shape)} must both be (problems, horizon, {task.robot.q_dim}) "
+                             f"on one GPU")
+        if mode not in ops.SOFTMIN_MODES:
+            raise ValueError(f"{who}: mode must be one of {sorted(ops.SOFTMIN_MODES)}, got {mode!r}")
+        self.task, self.q, self.qd = task, q, qd
+        self.P, self.H, self.D = (int(v) for v in q.shape)
+        self.K = int(n_particles)
+        if not 1 <= self.K <= _abi.TRK_SOFTMIN_MAX_PARTICLES:
+            raise ValueError(f"{who}: n_particles must be 1 .. {_abi.TRK_SOFTMIN_MAX_PARTICLES}, got {self.K}")
+        if not 2 <= self.H <= _abi.TRK_GP_SAMPLE_MAX_HORIZON or self.D > _abi.TRK_GP_SAMPLE_MAX_DOF:
+            raise NotImplementedError(f"{who}: the noise comes from ops.gp_prior_sample: horizons 2 .. {_abi.TRK_GP_SAMPLE_MAX_HORIZON} "
+                                      f"and up to {_abi.TRK_GP_SAMPLE_MAX_DOF} DOF, got horizon {self.H} and {self.D} DOF")
+        self.dt, self.sigma_gp, self.sigma_noise = float(dt), float(sigma_gp), float(sigma_noise)
+        self.temperature, self.mode = float(temperature), mode
+        self.w_coll, self.gp_weight, self.step_size = float(w_coll), float(gp_weight), float(step)
+        self.pin_vel, self.generator = bool(pin_vel), generator
+        dev = q.device
+        self._zero = torch.zeros((self.P, self.D), device=dev, dtype=torch.float32)
+        self._lim = (None, None)
+        if clamp_to_limits:
+            self._lim = tuple(l.to(dev, torch.float32).reshape(self.D).contiguous() for l in (task.robot.q_min, task.robot.q_max))
+        self.ess = None                                    # the effective sample sizes of the latest iteration
+        # particle 0 is the mean itself: zero noise rows must come back as exact zeros
+        nq, nqd = self._noise(torch.zeros((self.P, self.H - 1, self.D, 2), device=dev, dtype=torch.float32), 1)
+        if bool((nq != 0).any()) or bool((nqd != 0).any()):
+            raise RuntimeError(f"{who}: ops.gp_prior_sample does not return exact zeros for zero noise rows")
+
+    def _noise(self, eps, K):
+        vel = (self._zero, self._zero) if self.pin_vel else (None, None)
+        return ops.gp_prior_sample(self._zero, self._zero, self.H, self.dt, self.sigma_noise, K, vel[0], vel[1], eps=eps)
+
+    def particles(self, eps=None):
+        """-> (xq, xqd), each (P K, H, D): the means plus one draw of the noise, the interior clamped to the limits; eps
+        (P K, H - 1, D, 2): the unit normals to draw from (the rows of particle 0 are taken as zero), None draws them"""
+        P, K, H, D = self.P, self.K, self.H, self.D
+        if eps is None:
+            eps = torch.randn((P * K, H - 1, D, 2), generator=self.generator, device=self.q.device, dtype=torch.float32)
+        else:
+            eps = eps.clone()
+        eps.view(P, K, H - 1, D, 2)[:, 0] = 0.0
+        nq, nqd = self._noise(eps, K)
+        xq = (self.q[:, None] + nq.view(P, K, H, D)).reshape(P * K, H, D)
+        xqd = (self.qd[:, None] + nqd.view(P, K, H, D)).reshape(P * K, H, D)
+        if self._lim[0] is not None and H > 2:
+            xq[:, 1:-1] = torch.minimum(torch.maximum(xq[:, 1:-1], self._lim[0]), self._lim[1])
+        return xq, xqd
+
+    def cost(self, xq, xqd):
+        """(B, H): w_coll x the collision cost per way point + the trajectory's GP-prior cost spread evenly over its way points"""
+        with torch.no_grad():
+            coll = self.task.compute_collision_cost(xq)
+            gp = ops.gp_prior_cost(xq, xqd, self.dt, self.sigma_gp)
+            return (self.w_coll * coll + (self.gp_weight / self.H) * gp[:, None]).contiguous()
+
+    def step(self, n=1, eps=None):
+        """n iterations on q, qd in place -> the (P,) summed cost of the mean they started from.  eps: the unit normals of a single
+        iteration (n = 1), for reproducing it."""
+        n = int(n)
+        if n < 1:
+            raise ValueError("SamplingPlan.step: n must be >= 1")
+        if eps is not None and n != 1:
+            raise ValueError("SamplingPlan.step: eps is the noise of one iteration (n = 1)")
+        first = None
+        for _ in range(n):
+            xq, xqd = self.particles(eps)
+            c = self.cost(xq, xqd)
+            if first is None:
+                first = c.view(self.P, self.K, self.H)[:, 0].sum(1)
+            w, self.ess = ops.traj_softmin_weights(c, self.K, self.temperature, self.mode)
+            ops.traj_weighted_update(self.q, xq, w, self.step_size, 3, self._lim[0], self._lim[1], out=self.q)
+            ops.traj_weighted_update(self.qd, xqd, w, self.step_size, 3 if self.pin_vel else 0, out=self.qd)
+        return first
 
 
 # (columns of the point set, call) for which the fused boolean kernel did NOT beat the two-step routing by more than the spread of the
